@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — UNet denoise steps/sec of the MI355X-native Kandinsky sampling engine.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--size 768] [--bs 1] [--dtype bf16]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--size 768] [--bs 1] [--dtype bf16] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -13,8 +13,12 @@ percentile, posterior mean, ancestral noise).  Inputs are resident in HBM before
 Multi-GPU: every rank denoises its own image (weak scaling), weights arrive by ONE RCCL broadcast of the
 packed arena before the timed region; value = images-steps per second over all ranks.
 
-Extra objects on the JSON line: "roofline" (dominant kernel = implicit-GEMM conv3x3, MFMA-bound; measured
-with HIP events around every engine op on the launch stream), "cpu_baseline" (the CPU oracle, i.e. the
+A plain run sets up, warms up, times the K steps and prints the line; `--dump-outputs DIR` also writes the final latent of the
+timed steps (what a caller of the timed path receives) as DIR/latent.npy (float32; DIR/latent_rank<r>.npy per rank at N > 1).
+
+Extra objects on the JSON line, measured only with `--full` (null otherwise): "gate_holding", "two_chains", "box",
+"roofline" (dominant kernel = implicit-GEMM conv3x3, MFMA-bound; measured with HIP events around every engine op on the
+launch stream), "cpu_baseline" (the CPU oracle, i.e. the
 restated reference algorithm in PyTorch fp32, timed on this box's host cores on a bounded sample; N = 1 only),
 "parity_paths" (N = 1, default workload: steps/s of the fp16 and fp32 engines next to the timed dtype, each with the
 distance of ITS 50-step final latent from the committed reference golden tests/golden/c2_text2img.pt - the number that is
@@ -52,12 +56,18 @@ def main(argv=None):
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp16", "fp32", "f16x3", "f16x2"],
                     help="engine storage / MFMA operand type: bf16 (BASELINE's), fp16 (the reference's own use_fp16 mode), fp32 (parity path), "
                          "f16x3 (split precision: three fp16 MFMAs per product), f16x2 (asymmetric split with a per-op precision plan: the gate-holding "
-                         "mode that is also printed as `gate_holding` in the default line)")
+                         "mode that is also printed as `gate_holding` in the --full line)")
+    ap.add_argument("--full", action="store_true",
+                    help="also take every side measurement of the line (gate_holding, two_chains, box, roofline + PMC traffic, cpu_baseline, "
+                         "parity_paths, e2e; each can still be turned off by its --no-* option); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the final latent they computed to DIR/latent.npy (float32), for output-for-output "
+                         "comparison of two builds on the same seeded inputs")
     ap.add_argument("--sched-steps", type=int, default=50, help="decoder_steps of the schedule being sampled")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--no-loop-graph", action="store_true",
                     help="time the per-step path (one UNet graph + sampler launch per step from the host) instead of the whole denoising loop "
-                         "replayed as ONE hipGraph (k22_unet_sample_loop); the loop graph needs --steps to be a multiple of --sched-steps")
+                         "replayed as hipGraphs (k22_unet_sample_loop); a captured loop holds at most --sched-steps steps, --steps of them are replayed")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity", action="store_true", help="skip the parity_paths object (fp16 / fp32 engines + final-latent distances)")
     ap.add_argument("--parity-timed-only", action="store_true", help="parity_paths for the timed engine only (A/B runs)")
@@ -69,7 +79,7 @@ def main(argv=None):
                     help="2 = the CFG pair as two half-batch engines side by side on two streams (Text2ImUNetHIP(chains=2): per step two graph replays "
                          "+ the sampler step, driven from the host); 1 = one engine, whole loop as one hipGraph; 0 (default) = 1: the headline stays on one "
                          "chain so that the per-class roofline can be attributed; the two-chain rate of the same workload is reported beside it as "
-                         "`two_chains` (+2.6 % at C2, profiles/r06_chains.txt; C4 measured -5 % in round 4)")
+                         "`two_chains` under --full (+2.6 %% at C2, profiles/r06_chains.txt; C4 measured -5 %% in round 4)")
     ap.add_argument("--no-traffic", action="store_true",
                     help="skip the two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) that fill roofline.traffic: bench.py re-runs itself for 2 steps "
                          "under the profiler, ~1 minute each; skipped anyway when rocprofv3 is not on PATH, at N > 1 and for non-default workloads")
@@ -82,6 +92,11 @@ def main(argv=None):
                          "2.2 = diffusers UNet2DConditionModel of the 2.2 decoder (32 image tokens, DDPMScheduler step per SCHEDULER_CONFIG_2_2; parity unpinned)")
     ap.add_argument("--controlnet", action="store_true", help="2.2 ControlNet-depth UNet (hint conv stack, in_channels 8): config C5")
     a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not a.full:
+        # a plain run: set-up, warm-up, the K timed steps, the outputs and the line - no side measurement
+        a.no_e2e = a.no_profile = a.no_traffic = a.no_cpu_baseline = a.no_parity = a.no_box = True
     if a.gpus > 1 and "RANK" not in os.environ:
         # plain `python bench.py --gpus N`: start the N ranks here (what torch.distributed.run would do) - never a quiet 1-rank run
         from kandinsky2_amd.parallel import launch_ranks
@@ -207,11 +222,13 @@ def run(a):
 
     # the whole loop as one graph: K timed steps = K / T replays of the T-step loop (same kernels, same bits as the per-step path)
     # (round 5: whatever K is - the driver's line uses --steps 20 - the timed region is graph replays: K a multiple of the schedule length
-    # T = K / T replays of the whole T-step loop; any other K = ONE replay of a K-step loop over the first K steps of the schedule)
+    # T = K / T replays of the whole T-step loop; K < T = ONE replay of a K-step loop over the first K steps of the schedule; any other K =
+    # K / Lp replays of an Lp-step loop, Lp the largest divisor of K not above T).  A captured loop never holds more than T steps (~400
+    # nodes per step): one graph of all K steps for a K of a few hundred is far larger than anything else captures and crashed the runtime.
     use_loop = not (a.no_loop_graph or a.no_graph or v22)
     Lp = n_loops = warm_loops = 0
     if use_loop:
-        Lp = T if a.steps % T == 0 else a.steps                 # steps per captured loop
+        Lp = next(d for d in range(min(a.steps, T), 0, -1) if a.steps % d == 0)   # steps per captured loop
         n_loops, warm_loops = a.steps // Lp, max(1, -(-a.warmup // Lp))
         order = [(T - 1 - (j % T)) for j in range(Lp)]
         ts_exec = ts_rows[torch.as_tensor(order, device=dev)].contiguous()
@@ -272,6 +289,8 @@ def run(a):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         el = tt.item()
     finite = bool(torch.isfinite(x).all().item())
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, x, "latent" if world == 1 else f"latent_rank{rank}", world)
 
     # ---- end-to-end images/sec: every rank generates its own images (weak scaling, no collective inside) --------------------
     e2e = None
@@ -397,6 +416,24 @@ def run(a):
     if dist_on:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_CAP_BYTES = 64 << 20   # all files of one --dump-outputs run together
+
+
+def dump_outputs(out_dir, x, name, world):
+    """x (the final latent of the timed steps) -> out_dir/<name>.npy as float32.  Above this rank's share of DUMP_CAP_BYTES a fixed,
+    seeded sample of its elements is written instead (flat indices in ascending order, the same on every run)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    flat = x.detach().float().cpu().reshape(-1)
+    cap = DUMP_CAP_BYTES // 4 // world
+    if flat.numel() > cap:
+        idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(0))[:cap].sort().values
+        arr = flat[idx].numpy()
+    else:
+        arr = flat.reshape(x.shape).numpy()
+    np.save(os.path.join(out_dir, name + ".npy"), arr)
 
 
 def _seeded_pipeline(a, arch, sd, dev, tdt):

@@ -3,7 +3,7 @@
 cd "$GRAFT_REPO_ROOT" 2>/dev/null || cd /root/repo
 TAG=${1:-prof}
 STEPS=${2:-10}
-EXTRA=${3:-}          # extra bench.py flags, e.g. "--dtype f16x3"
+EXTRA="--full ${3:-}"  # --full keeps the per-op profile pass in the trace; $3 = extra bench.py flags, e.g. "--dtype f16x3"
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 OUT=$PWD/gpurun_out/rocprof_$TAG
