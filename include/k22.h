@@ -36,8 +36,9 @@ extern "C" {
                       16-bit MFMA rate: tensors stay fp32, every MFMA operand x is carried as the fp16 pair hi = rne(x), lo = rne(x - hi)
                       and every product as three v_mfma_f32_32x32x16_f16 (hi.hi + hi.lo + lo.hi) into one fp32 accumulator: ~23
                       significand bits per operand at 3/16 of the exact-fp32 MFMA cost.  Operand format ("x3 chunks"): 4 bytes per
-                      element, every aligned group of 4 consecutive K elements stored as [hi x4 | lo x4] fp16 (csrc/common.h);
-                      weights are packed so (pre-multiplied by 2^8) by pack.py / k22_x3_pack, activations by their producers. */
+                      element, every aligned group of 8 consecutive K elements (32 bytes) stored as [hi0..hi7 | lo0..lo7] fp16
+                      (csrc/common.h; round 6 - rounds 4-5 used groups of 4, [hi x4 | lo x4]); weights are packed so (pre-multiplied
+                      by 2^8) by pack.py / k22_x3_pack, activations by their producers. */
 #define K22_F16X2 4 /* UNet engine only - the ASYMMETRIC SPLIT (round 5): the tensors, the arena and the operand formats of K22_F16X3, with
                       the precision of every MFMA op a property of the PLAN: weights always as (hi, lo) pairs (their rounding is the
                       systematic error of a 16-bit engine), the activation operand at fp16 precision - two MFMAs per product,
@@ -45,8 +46,8 @@ extern "C" {
                       drift_ablation_x2.json) prices it as cheap: the 3x3 convolutions below the top resolution level and the qkv
                       projections; ONE MFMA (fp16 tiles, fp32 softmax) in the attention; all three where it is not: 1x1 skip
                       connections, the out head, proj_out / encoder_kv, and (default plan; env K22_X2_PLAN bits 0 / 1 release its
-                      in_layers / out_layers convolutions) the top level.  C2 final latent 2.7e-4 from the reference p_sampler
-                      (gate 1e-3) at 1.17x the K22_F16X3 engine's speed.  The kernel-level entries accept it: k22_conv3x3* / k22_gemm* /
+                      in_layers / out_layers convolutions) the top level.  C2 final latent 2.2e-4 from the reference p_sampler
+                      (gate 1e-3; round 6) at 1.20x the K22_F16X3 engine's speed.  The kernel-level entries accept it: k22_conv3x3* / k22_gemm* /
                       k22_qkv_project = two MFMAs, activation operand rounded to fp16 (a fused skip keeps three); k22_attention = fp16
                       tiles on fp32 tensors. */
 
@@ -244,7 +245,8 @@ int k22_sampler_step(const float* x, const float* model_out, const float* noise,
 int k22_gemm(const void* A0, const void* A1, const void* Wp, const float* bias, const void* residual, void* out,
              void* partial, int M, int N, int Npad, int K0, int K1, long lda0, long lda1, int ldo, int ldr,
              int out_f32, int act, int splitk, int bm, int bn, int dtype, void* stream);
-/* fp32 -> x3 chunks (K22_F16X3 operand format): dst[n] (4 bytes per element) from src[n] * scale, n % 4 == 0, 16-byte aligned.
+/* fp32 -> x3 chunks (K22_F16X3 operand format): dst[n] (4 bytes per element) from src[n] * scale, n % 8 == 0, src 16-byte and
+ * dst 32-byte aligned (K22_EINVAL otherwise).
  * scale = 256 for weights (what pack.py writes and the epilogues undo), 1 for activations.  With dtype == K22_F16X3 the kernel-level
  * entries take: k22_gemm / k22_gemm_gnstats / k22_qkv_project - A as plain fp32 rows (split at fragment-read time), W in x3 chunks;
  * k22_conv3x3* - x_padded AND W in x3 chunks (in the engine the GroupNorm-apply kernel writes the input so: k22_groupnorm with
@@ -304,6 +306,11 @@ int k22_qkv_project_stream(const void* x, const void* Wp, const float* bias, voi
                            int B, int H, int T, int S, int K, int bm, int splitk, int dtype, void* stream);
 int k22_linear_smallm(const float* x, const void* W, const float* bias, const float* add, float* out, int M, int N,
                       int K, int act_in, int act_out, int wdtype, void* stream);
+/* Direct fp32 3x3 convolution, pad 1, stride 1 or 2, optional SiLU (act 0 / 1): one layer of the ControlNet-depth hint stack of the 2.2
+ * UNet (diffusers ImageHintTimeEmbedding.input_hint_block; the engine runs eight of them through the same launcher).  x [B][Cin][Hin][Win],
+ * w [Cout][Cin][3][3], bias [Cout], y [B][Cout][Ho][Wo] with Ho = (Hin - 1) / stride + 1, Wo likewise; all fp32 NCHW. */
+int k22_conv3x3_direct(const float* x, const float* w, const float* bias, float* y, int B, int Cin, int Cout, int Hin, int Win,
+                       int stride, int act, void* stream);
 
 /* ---- skinny-M weight-streaming GEMM family (round 6; csrc/skinny.hip) - unit-parity surface of the kernels the prior engine's
  * 16-bit path is made of.  Replaces nn.Linear c_qkv / c_proj / c_fc / mlp.c_proj (kandinsky2/model/prior.py:57-83), the LayerNorm in

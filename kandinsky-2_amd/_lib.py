@@ -140,6 +140,7 @@ SIGNATURES = {
     "k22_qkv_project": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "k22_qkv_project_stream": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "k22_linear_smallm": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "k22_conv3x3_direct": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "k22_debug_counter": (_L, [C.c_char_p]),
     "k22_stream_frag_bytes": (C.c_size_t, [_I, _I, _I, _I]),
     "k22_stream_repack": (_I, [_P, _P, _I, _I, _I, _I, _P]),

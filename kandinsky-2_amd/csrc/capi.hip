@@ -383,6 +383,17 @@ int k22_linear_smallm(const float* x, const void* W, const float* bias, const fl
   return launch_linear_smallm(lp, wdtype, reinterpret_cast<hipStream_t>(stream));
 }
 
+int k22_conv3x3_direct(const float* x, const float* w, const float* bias, float* y, int B, int Cin, int Cout, int Hin, int Win,
+                       int stride, int act, void* stream) {
+  if (!x || !w || !bias || !y) return k22_set_error(K22_EINVAL, "conv3x3_direct: null argument");
+  if (B < 1 || Cin < 1 || Cout < 1 || Hin < 1 || Win < 1) return k22_set_error(K22_EINVAL, "conv3x3_direct: empty shape");
+  if (act != K22_ACT_NONE && act != K22_ACT_SILU) return k22_set_error(K22_EINVAL, "conv3x3_direct: act must be 0 (none) or 1 (SiLU)");
+  ConvDirectParams p = {};
+  p.x = x; p.w = w; p.bias = bias; p.y = y;
+  p.B = B; p.Cin = Cin; p.Cout = Cout; p.Hin = Hin; p.Win = Win; p.stride = stride; p.act = act;
+  return launch_conv3x3_direct(p, reinterpret_cast<hipStream_t>(stream));
+}
+
 int k22_ddim_step(const float* x, const float* model_out, const float* noise, const float* table_row, float guidance, int use_cfg,
                   float* x_out, float* x0_out, int N, int HW, void* stream) {
   if (!x || !model_out || !table_row || !x_out) return k22_set_error(K22_EINVAL, "ddim_step: null argument");

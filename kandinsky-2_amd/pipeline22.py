@@ -72,22 +72,21 @@ class KandinskyV22DecoderHIP:
         after_step(k, latents [bs,4,h,w]) -> latents"""
         bs = x.shape[0]
         x = torch.cat([x, x], 0).contiguous()
-        self.unet.del_cache()
         ack = {"image_embeds": emb} if hint2 is None else {"image_embeds": emb, "hint": hint2}
-        for k, t in enumerate(timesteps):
-            half = x[:bs]
-            inp = torch.cat([half, half], 0)
-            if extra is not None:
-                inp = torch.cat([inp, extra], 1)
-            out = self.unet(inp, t, encoder_hidden_states=None, added_cond_kwargs=ack, return_dict=False)[0]
-            nz = None
-            if noise_seq is not None:
-                nz = torch.cat([noise_seq[k], noise_seq[k]], 0).to(x.device)
-            x = self.scheduler.step(out, t, x, noise=nz, generator=generator, guidance_scale=guidance_scale).prev_sample
-            if after_step is not None:
-                h = after_step(k, x[:bs])
-                x = torch.cat([h, h], 0)
-        self.unet.del_cache()
+        with self.unet.fixed_conditioning():          # emb / hint2 are this call's own and do not change during the loop
+            for k, t in enumerate(timesteps):
+                half = x[:bs]
+                inp = torch.cat([half, half], 0)
+                if extra is not None:
+                    inp = torch.cat([inp, extra], 1)
+                out = self.unet(inp, t, encoder_hidden_states=None, added_cond_kwargs=ack, return_dict=False)[0]
+                nz = None
+                if noise_seq is not None:
+                    nz = torch.cat([noise_seq[k], noise_seq[k]], 0).to(x.device)
+                x = self.scheduler.step(out, t, x, noise=nz, generator=generator, guidance_scale=guidance_scale).prev_sample
+                if after_step is not None:
+                    h = after_step(k, x[:bs])
+                    x = torch.cat([h, h], 0)
         self.last_latent = x[:bs]
         return self.last_latent
 

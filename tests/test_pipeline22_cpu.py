@@ -124,3 +124,25 @@ def test_aux_engine_dtypes_one_rule_for_both_drivers():
     # both drivers go through it (no second copy of the rule)
     assert "aux_engine_dtypes" in inspect.getsource(pipeline22.Kandinsky2_2HIP.__init__)
     assert "aux_engine_dtypes" in inspect.getsource(pipeline.Kandinsky2_1HIP.__init__)
+
+
+def test_c5_fixture_hint_latent_matches_the_oracle(golden_dir):
+    """tests/golden/c5_forward.pt against the oracle it was made from: unet22_ref.hint_block on the fixture's re-drawn hint and weights
+    (oracle/make_golden_unet22.py) reproduces the stored hint latent, so a fixture that drifted from the oracle, the seeds or the weight
+    initialisation is caught without a GPU."""
+    import os
+    from oracle import make_golden_unet22 as mg, unet22_ref
+    fx = torch.load(os.path.join(golden_dir, "c5_forward.pt"), weights_only=False)
+    assert (fx["seed"], fx["bs"], fx["lat"]) == (mg.SEED, mg.BS, mg.LAT)
+    _, _, sd = mg.c5_weights()
+    hint = mg.c5_inputs(fx["seed"])["hint"]
+    n = torch.get_num_threads()
+    torch.set_num_threads(mg.CPU_THREADS)     # the thread count the fixture was written at: the same reduction order on any host
+    try:
+        with torch.no_grad():
+            got = unet22_ref.hint_block(sd, hint)
+    finally:
+        torch.set_num_threads(n)
+    assert got.shape == fx["hint_latent"].shape == (2, 4, 96, 96)
+    assert (got - fx["hint_latent"]).abs().max().item() <= 1e-6
+    assert fx["forward_compact"]["sub"].shape == (4, 8, 48, 48)

@@ -296,3 +296,40 @@ def test_kandinsky2_2_builds_itself_from_a_cache_dir(tmp_path):
     assert not torch.equal(outs["learned"], want)
     with pytest.raises(ValueError, match="conditioner"):
         k22.get_kandinsky2("cuda", task_type="text2img", cache_dir=str(tmp_path), model_version="2.2")
+
+
+def test_unet22_conditioning_follows_content_not_tensor_identity():
+    """The drop-in module caches the 2.2 head and the hint latent; it must never compute from conditioning other than what it is
+    given.  Writes through .data (like NumPy / DLPack aliases and foreign kernels) do not bump _version, so a cache keyed on
+    (data_ptr, _version, shape) would reuse the stale conditioning: the outputs must equal those of a fresh module, bit for bit."""
+    cfg, sd, m = _unet(True, torch.float32)
+    _, _, fresh = _unet(True, torch.float32)
+    B, h, w = 4, 16, 24
+    x, emb1, hint1 = _inputs(B, h, w, seed=4, hint=True)
+    _, emb2, hint2 = _inputs(B, h, w, seed=13, hint=True)
+    x, t = x.cuda(), torch.tensor([980.0, 500.0, 20.0, 0.0]).cuda()
+
+    def want(e, hh):
+        fresh.del_cache()
+        return fresh(x, t, added_cond_kwargs={"image_embeds": e.cuda(), "hint": hh.cuda()}, return_dict=False)[0]
+
+    e, hh = emb1.cuda(), hint1.cuda()
+    ack = {"image_embeds": e, "hint": hh}
+    assert torch.equal(m(x, t, added_cond_kwargs=ack, return_dict=False)[0], want(emb1, hint1))
+    key = lambda z: (z.data_ptr(), z._version, tuple(z.shape))  # noqa: E731
+    k0 = (key(e), key(hh))
+    hh.data.copy_(hint2.cuda())                                   # the hint alone changes
+    assert (key(e), key(hh)) == k0
+    assert torch.equal(m(x, t, added_cond_kwargs=ack, return_dict=False)[0], want(emb1, hint2))
+    e.data.copy_(emb2.cuda())                                     # the image embeds alone change
+    assert (key(e), key(hh)) == k0
+    assert torch.equal(m(x, t, added_cond_kwargs=ack, return_dict=False)[0], want(emb2, hint2))
+    # new tensors (the caching allocator may hand out the freed blocks again, at _version 0)
+    del ack, e, hh
+    e, hh = emb1.cuda(), hint1.cuda()
+    assert torch.equal(m(x, t, added_cond_kwargs={"image_embeds": e, "hint": hh}, return_dict=False)[0], want(emb1, hint1))
+    # inside fixed_conditioning() the caller owns the tensors: the first call computes, the cache is dropped on exit
+    with m.fixed_conditioning():
+        a = m(x, t, added_cond_kwargs={"image_embeds": e, "hint": hh}, return_dict=False)[0]
+        b = m(x, t, added_cond_kwargs={"image_embeds": e, "hint": hh}, return_dict=False)[0]
+    assert torch.equal(a, b) and torch.equal(a, want(emb1, hint1)) and m._cond_key is None

@@ -269,3 +269,29 @@ def test_qkv_projection_x3_writes_attention_operands(B, H, T, S, K, bm, gemm8):
     close64(vtall[:, :, :, S:S + T], ref[:, :, 2].permute(0, 2, 3, 1), "v^T")
     assert (kall[:, :, :S] == 7).all() and (kall[:, :, S + T:] == 7).all()
     assert (vtall[:, :, :, :S] == 7).all() and (vtall[:, :, :, S + T:] == 7).all()
+
+
+def test_x3_pack_is_the_layout_the_header_documents():
+    """k22_x3_pack against include/k22.h's description of the x3 chunk format, restated here in NumPy (not through pack.to_x3): every
+    aligned group of EIGHT consecutive elements is stored as [hi0..hi7 | lo0..lo7] in fp16, hi = rne(x * scale), lo = rne(x * scale - hi),
+    bit for bit - including fp16 subnormal lo halves, values that round hi up across a power of two, signed zeros and a scale of 1."""
+    n = 8 * 1031
+    g = np.random.default_rng(3)
+    x = (g.standard_normal(n) * np.exp2(g.integers(-20, 5, n))).astype(np.float32)   # |x * 256| stays below the fp16 range
+    x[:16] = [0.0, -0.0, 1.0, -1.0, 65504.0 / 256, 2.0 ** -24, -(2.0 ** -30), 1.0 + 2.0 ** -11, 1.0 + 3 * 2.0 ** -12, 0.1, 1 / 3, -7.75,
+              2.0 ** -14, 3e-5, -1e-8, 0.5 - 2.0 ** -13]
+    src = torch.from_numpy(x).cuda()
+    for scale in (256.0, 1.0):
+        dst = torch.empty(n, dtype=torch.float32, device="cuda")
+        _lib.check(_lib.lib().k22_x3_pack(src.data_ptr(), dst.data_ptr(), n, scale, _lib.current_stream()))
+        got = dst.cpu().numpy().view(np.uint16)                                  # 2n fp16 halves, memory order
+        xs = x * np.float32(scale)                                               # scale is a power of two: exact
+        hi = xs.astype(np.float16)                                               # round to nearest even
+        lo = (xs - hi.astype(np.float32)).astype(np.float16)                     # x - hi is exact in fp32
+        want = np.empty((n // 8, 2, 8), dtype=np.float16)
+        want[:, 0, :], want[:, 1, :] = hi.reshape(-1, 8), lo.reshape(-1, 8)
+        assert np.array_equal(got, want.reshape(-1).view(np.uint16)), f"scale {scale}: x3 chunks differ from [hi x8 | lo x8]"
+    # the alignment contract the header states: n % 8 == 0, dst 32-byte aligned
+    dst = torch.empty(n + 8, dtype=torch.float32, device="cuda")
+    assert _lib.lib().k22_x3_pack(src.data_ptr(), dst.data_ptr(), 12, 256.0, _lib.current_stream()) == -1
+    assert _lib.lib().k22_x3_pack(src.data_ptr(), dst.data_ptr() + 16, 8, 256.0, _lib.current_stream()) == -1
