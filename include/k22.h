@@ -275,6 +275,44 @@ int k22_conv3x3_gnstats(const void* x_padded, const void* Wp, const float* bias,
 int k22_gemm_gnstats(const void* A, const void* Wp, const float* bias, const void* residual, void* out, void* partial,
                      int B, int H, int W, int N, int Npad, int K, int splitk, int bm, float* stats,
                      int stats_capacity_rows, int* rows_per_image, int dtype, void* stream);
+/* One launch_igemm problem in full, as the engines hand it to the tile table (csrc/tuning.h), plus one explicit tile configuration: the
+ * unit-parity surface of the SHIPPED table (tiles_gfx950.txt), whose every line is `dtype taps M N Kc K0 H W outmode stats | algo bm bn
+ * splitk stages`.  Key fields as the table spells them, with the packed ones taken apart: K0 is the width of A0 alone (the table adds
+ * 100000 * (SK0 + SK1) for a fused skip), out_mode is 0 = T rows, 1 = fp32 rows, 2 = NCHW fp32, 3 = the qkv projection of
+ * k22_qkv_project (the table adds 16 * res_f32 + 32 * act + 256 * a_raw).
+ * H = W = 0: a GEMM whose rows are not image shaped.  ldo / ldr = 0: the engines' defaults (N; N / 3 for the q rows of out_mode 3).
+ * has_frag: the owner of the weights holds their fragment-major copy (k22_stream_repack) - the UNet engine's 16-bit 3x3 convolutions
+ * with M <= 1152 only; it decides whether algo 20 is a candidate. */
+typedef struct K22IgemmProblem {
+  int dtype, taps, M, N, Kc, K0, H, W;
+  int out_mode, res_f32, act, a_raw, want_stats;
+  int SK0, SK1;                 /* fused 1x1 skip connection: channels of S0 / S1 (0, 0 = none) */
+  int att_T, att_S, att_Tkp;    /* out_mode 3: tokens per image, context keys, padded key count */
+  int ldo, ldr;
+  int has_frag;
+  int algo, bm, bn, splitk, stages;   /* the configuration (columns 11-15 of a table line) */
+} K22IgemmProblem;
+/* Device operands of k22_igemm_cfg, in the formats the engine of `dtype` holds them (k22_x3_pack's comment for the split arithmetics:
+ * A0 / A1 in x3 chunks unless a_raw, S0 / S1 plain fp32 rows, weights in x3 chunks).  Null = absent (bias, residual, A1, S1, stats).
+ * Wfrag / Wsfrag: fragment-major weights, required by algo 20 (Wsfrag when a skip is fused).  kall / vtall: out_mode 3 only. */
+typedef struct K22IgemmOperands {
+  const void *A0, *A1, *Wp, *bias, *residual;
+  void *out, *partial;          /* partial: fp32 [splitk][M][N] (splitk > 1, and always for algo 20) */
+  const void *S0, *S1, *Ws, *bias2;
+  void *kall, *vtall;
+  const void *Wfrag, *Wsfrag;
+  float* stats;                 /* want_stats: [stats_capacity_rows][N][2] fp32 */
+  int stats_capacity_rows;
+} K22IgemmOperands;
+/* Host only (no GPU call): does THIS build accept the configuration for the problem?  Builds the launch descriptor the engines build,
+ * lists its candidates (tuned_make_candidates) and answers tuned_is_candidate: 1 = a table line with this key and configuration is
+ * used as it stands, 0 = it is dropped silently and the problem is measured again on every start.  Negative: K22_EINVAL. */
+int k22_igemm_cfg_accepted(const K22IgemmProblem* pr);
+/* Runs the problem ONCE with exactly that configuration, the way an engine's launch closure does (IgemmParams from the problem,
+ * tuned_apply_cfg, launch_igemm); it needs and sets no process-wide option (k22_set_option).  A configuration k22_igemm_cfg_accepted rejects
+ * is an error (K22_EINVAL), never a quiet run of another kernel.  With want_stats the GroupNorm partial sums land in ops->stats as in
+ * k22_conv3x3_gnstats: image b owns rows [b * rpi, (b + 1) * rpi), *rows_per_image receives rpi (0 without want_stats). */
+int k22_igemm_cfg(const K22IgemmProblem* pr, const K22IgemmOperands* ops, int* rows_per_image, void* stream);
 /* Developer tool: runs the 256-row bf16 halo kernel once with s_memtime stamps; trace = device u64 [2][1024][4]
  * (wave 0 / wave 5 of workgroup 0; per tap: before the counted vmcnt wait, after it, after the barrier, after the last
  * MFMA was issued).  tools/conv_trace.py prints the per-phase cycle budget. */

@@ -36,7 +36,7 @@ def dtype_code(backend_dtype) -> int:
     except KeyError:
         raise ValueError('backend_dtype must be torch.bfloat16, torch.float16, torch.float32 "f16x3" or "f16x2"') from None
 ACT_NONE, ACT_SILU, ACT_GELU = 0, 1, 2
-OUT_ROWMAJOR, OUT_ROWMAJOR_F32, OUT_NCHW_F32 = 0, 1, 2
+OUT_ROWMAJOR, OUT_ROWMAJOR_F32, OUT_NCHW_F32, OUT_QKV = 0, 1, 2, 3
 
 
 class K22UNetConfig(C.Structure):
@@ -47,6 +47,19 @@ class K22UNetConfig(C.Structure):
         ("ctx_dim", C.c_int), ("ctx_len", C.c_int), ("n_image_embs", C.c_int), ("text_dim1", C.c_int),
         ("text_dim2", C.c_int), ("image_dim", C.c_int), ("head_type", C.c_int), ("hint_channels", C.c_int),
     ]
+
+
+class K22IgemmProblem(C.Structure):
+    """one launch_igemm problem + tile configuration (include/k22.h: k22_igemm_cfg / k22_igemm_cfg_accepted)"""
+    _fields_ = [(n, C.c_int) for n in (
+        "dtype", "taps", "M", "N", "Kc", "K0", "H", "W", "out_mode", "res_f32", "act", "a_raw", "want_stats", "SK0", "SK1",
+        "att_T", "att_S", "att_Tkp", "ldo", "ldr", "has_frag", "algo", "bm", "bn", "splitk", "stages")]
+
+
+class K22IgemmOperands(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in (
+        "A0", "A1", "Wp", "bias", "residual", "out", "partial", "S0", "S1", "Ws", "bias2", "kall", "vtall", "Wfrag", "Wsfrag",
+        "stats")] + [("stats_capacity_rows", C.c_int)]
 
 
 class K22MoVQConfig(C.Structure):
@@ -132,6 +145,8 @@ SIGNATURES = {
     "k22_conv3x3_skip": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "k22_gemm_gnstats": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, C.POINTER(_I), _I, _P]),
     "k22_conv3x3_gnstats": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, C.POINTER(_I), _I, _P]),
+    "k22_igemm_cfg_accepted": (_I, [C.POINTER(K22IgemmProblem)]),
+    "k22_igemm_cfg": (_I, [C.POINTER(K22IgemmProblem), C.POINTER(K22IgemmOperands), C.POINTER(_I), _P]),
     "k22_conv3x3_gn": (_I, [_P, _P, _I, _I, _P, _P, _P, _L, _F, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "k22_debug_conv_trace": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "k22_groupnorm": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _L, _F, _I, _I, _I, _P, _P, _I, _P]),

@@ -234,6 +234,80 @@ int k22_conv3x3_skip(const void* x_padded, const void* Wp, const float* bias, co
   return launch_igemm(p, dtype, reinterpret_cast<hipStream_t>(stream));
 }
 
+// ---- one table line, as the engine runs it (tests/test_tile_table_*.py) ---------------------------------------------------------
+// The launch descriptor an engine builds for the problem (engine.hip: op_conv / op_gemm; movq.hip, prior.hip, encoder.hip: the same
+// fields): device pointers are non-null MARKERS, as there, because the candidate list only asks whether an operand exists.
+static int igemm_problem_tuned(const K22IgemmProblem& d, Tuned& t) {
+  if (d.dtype < K22_BF16 || d.dtype > K22_F16X2) return k22_set_error(K22_EINVAL, "igemm_cfg: bad dtype");
+  if ((d.taps != 1 && d.taps != 9) || d.M <= 0 || d.N <= 0 || d.Kc <= 0 || d.K0 <= 0 || d.K0 > d.Kc)
+    return k22_set_error(K22_EINVAL, "igemm_cfg: bad problem (taps 1 / 9, M, N > 0, 0 < K0 <= Kc)");
+  if (d.out_mode < IG_OUT_ROWMAJOR || d.out_mode > IG_OUT_QKV || d.SK0 < 0 || d.SK1 < 0 || (d.SK1 > 0 && d.SK0 == 0))
+    return k22_set_error(K22_EINVAL, "igemm_cfg: bad output mode / skip widths");
+  if (d.taps == 9 && (d.H <= 0 || d.W <= 0 || d.M % (d.H * d.W))) return k22_set_error(K22_EINVAL, "igemm_cfg: a convolution needs M = B * H * W");
+  const void* mark = reinterpret_cast<const void*>(1);
+  IgemmParams& p = t.p;
+  p = IgemmParams{};
+  p.stages = -1;
+  p.M = d.M; p.N = d.N; p.Npad = (d.N + 63) / 64 * 64; p.Kc = d.Kc; p.K0 = d.K0; p.taps = d.taps; p.H = d.H; p.W = d.W;
+  p.lda0 = d.K0; p.lda1 = d.Kc - d.K0;
+  p.ldo = d.ldo > 0 ? d.ldo : (d.out_mode == IG_OUT_QKV ? d.N / 3 : d.N);
+  p.ldr = d.ldr > 0 ? d.ldr : (d.res_f32 ? p.ldo : d.N);
+  p.out_mode = d.out_mode; p.act = d.act; p.res_f32 = d.res_f32 ? 1 : 0; p.a_raw = d.a_raw ? 1 : 0;
+  p.Wp = mark; p.bias = reinterpret_cast<const float*>(mark);
+  if (d.SK0 > 0) { p.S0 = mark; p.S1 = d.SK1 > 0 ? mark : nullptr; p.SK0 = d.SK0; p.SK1 = d.SK1; p.Ws = mark; p.bias2 = reinterpret_cast<const float*>(mark); }
+  if (d.out_mode == IG_OUT_QKV) { p.att_T = d.att_T; p.att_S = d.att_S; p.att_Tkp = d.att_Tkp; }
+  if (d.has_frag) { p.Wfrag = mark; if (d.SK0 > 0) p.Wsfrag = mark; }
+  t.want_stats = d.want_stats != 0;
+  t.dt = d.dtype;
+  tuned_make_candidates(t, d.dtype);
+  return K22_OK;
+}
+static Cfg igemm_problem_cfg(const K22IgemmProblem& d) {
+  Cfg c; c.algo = d.algo; c.bm = d.bm; c.bn = d.bn; c.splitk = d.splitk; c.stages = d.stages;
+  return c;
+}
+
+int k22_igemm_cfg_accepted(const K22IgemmProblem* pr) {
+  if (!pr) return k22_set_error(K22_EINVAL, "igemm_cfg_accepted: null problem");
+  Tuned t;
+  if (int rc = igemm_problem_tuned(*pr, t)) return rc;
+  return tuned_is_candidate(t, igemm_problem_cfg(*pr)) ? 1 : 0;
+}
+
+int k22_igemm_cfg(const K22IgemmProblem* pr, const K22IgemmOperands* ops, int* rows_per_image, void* stream) {
+  if (rows_per_image) *rows_per_image = 0;
+  if (!pr || !ops) return k22_set_error(K22_EINVAL, "igemm_cfg: null problem / operands");
+  const K22IgemmProblem& d = *pr;
+  const K22IgemmOperands& o = *ops;
+  Tuned t;
+  if (int rc = igemm_problem_tuned(d, t)) return rc;
+  const Cfg c = igemm_problem_cfg(d);
+  if (!tuned_is_candidate(t, c)) return k22_set_error(K22_EINVAL, "igemm_cfg: this build does not generate the configuration for the problem");
+  if (!o.A0 || !o.Wp || !o.out) return k22_set_error(K22_EINVAL, "igemm_cfg: A0, Wp and out are required");
+  if (d.K0 < d.Kc && !o.A1) return k22_set_error(K22_EINVAL, "igemm_cfg: A1 missing for the concat operand");
+  if (d.SK0 > 0 && (!o.S0 || !o.Ws || (d.SK1 > 0 && !o.S1))) return k22_set_error(K22_EINVAL, "igemm_cfg: fused-skip operands missing");
+  if (d.out_mode == IG_OUT_QKV && (!o.kall || !o.vtall)) return k22_set_error(K22_EINVAL, "igemm_cfg: kall / vtall missing");
+  if ((c.splitk > 1 || c.algo == 20) && !o.partial) return k22_set_error(K22_EINVAL, "igemm_cfg: the configuration needs the fp32 partial buffer");
+  if (c.algo == 20 && (!o.Wfrag || (d.SK0 > 0 && !o.Wsfrag))) return k22_set_error(K22_EINVAL, "igemm_cfg: algo 20 needs the fragment-major weights");
+  IgemmParams q = t.p;
+  tuned_apply_cfg(q, c);
+  q.A0 = o.A0; q.A1 = o.A1; q.Wp = o.Wp; q.bias = reinterpret_cast<const float*>(o.bias); q.residual = o.residual; q.out = o.out;
+  q.partial = reinterpret_cast<float*>(o.partial);
+  q.S0 = d.SK0 > 0 ? o.S0 : nullptr; q.S1 = d.SK1 > 0 ? o.S1 : nullptr; q.Ws = d.SK0 > 0 ? o.Ws : nullptr;
+  q.bias2 = d.SK0 > 0 ? reinterpret_cast<const float*>(o.bias2) : nullptr;
+  q.kall = o.kall; q.vtall = o.vtall;
+  q.Wfrag = c.algo == 20 ? o.Wfrag : nullptr; q.Wsfrag = (c.algo == 20 && d.SK0 > 0) ? o.Wsfrag : nullptr;
+  if (t.want_stats) {
+    const int rpi = igemm_stats_rows_per_image(q, d.dtype);
+    const int B = d.H > 0 ? d.M / (d.H * d.W) : 1;
+    if (rpi <= 0) return k22_set_error(K22_EINVAL, "igemm_cfg: this configuration cannot produce GroupNorm partial sums");
+    if (!o.stats || (long)rpi * B > o.stats_capacity_rows) return k22_set_error(K22_ENOMEM, "igemm_cfg: stats buffer missing / too small");
+    if (rows_per_image) *rows_per_image = rpi;
+    q.stats = o.stats;
+  }
+  return launch_igemm(q, d.dtype, reinterpret_cast<hipStream_t>(stream));
+}
+
 int k22_debug_conv_trace(const void* x_padded, const void* Wp, const float* bias, void* out, int B, int H, int W, int Cin, int Cout,
                          int Npad, unsigned long long* trace, void* stream) {
   IgemmParams p = {};
