@@ -134,6 +134,15 @@ typedef struct K22UNet K22UNet; /* opaque */
 int k22_unet_create(const K22UNetConfig* cfg, const K22Weight* weights, int n_weights, K22UNet** out);
 void k22_unet_destroy(K22UNet* u);
 
+/* Life cycle of every engine handle (K22UNet, K22MoVQ, K22Prior, K22Encoder):  create -> plan -> bind -> run.
+ * k22_*_plan sizes the workspace for one shape and returns its size.  Arguments it rejects leave the previous plan (and its
+ * binding) in place; a plan that fails later (a weight name missing from the table) leaves the handle WITHOUT a plan: bind
+ * then answers "plan first" and the run entries "bind a workspace first".  A successful plan drops the previous binding.
+ * k22_*_bind attaches a caller-owned workspace of at least that size, 256-byte aligned; it may be called again to move the
+ * same plan to another workspace.  Binding invalidates what was cached for the previous workspace (captured graphs, the
+ * UNet's conditioning / hint, per-binding weight copies).  The workspace stays the caller's: it must outlive its use and
+ * may be freed after a re-plan or re-bind once the stream has drained. */
+
 /* Plans a forward for batch B (= 2*bs with classifier-free guidance) and latent H x W; returns the
  * workspace size the caller must provide to k22_unet_bind().  Re-planning invalidates the binding. */
 int k22_unet_plan(K22UNet* u, int B, int H, int W, size_t* workspace_bytes);

@@ -329,22 +329,13 @@ int k22_groupnorm(const void* x0, const void* x1, int C0, int C1, int B, int H, 
   const int C = C0 + C1, HW = H * W;
   const int out_x3 = k22_is_split(dtype) ? 1 : 0;   // split-precision engine: fp32 in, x3 chunks out (what its convolutions read)
   dtype = k22_storage_dtype(dtype);
-  const int nsplit = gn_nsplit(B, HW);
   float* partial = reinterpret_cast<float*>(scratch);
   float* coeff = partial + (size_t)B * 128 * C * 2;
-  GnStatsParams sp;
-  sp.x0 = x0; sp.x1 = x1; sp.C0 = C0; sp.C1 = C1; sp.HW = HW; sp.B = B; sp.groups = 32; sp.nsplit = nsplit; sp.partial = partial;
-  int rc = launch_gn_stats(sp, dtype, st);
+  const int rc = launch_gn_stats_coeff(x0, x1, C0, C1, B, HW, eps, gamma, beta, film, film_ld, partial, coeff, dtype, st);
   if (rc) return rc;
-  GnCoeffParams cp = {};
-  cp.src[0].st = partial; cp.src[0].rpi = nsplit; cp.src[0].C = C; cp.src[1].st = nullptr; cp.src[1].rpi = 0; cp.src[1].C = 0;
-  cp.HW = HW; cp.C = C; cp.groups = 32; cp.eps = eps; cp.gamma = gamma; cp.beta = beta;
-  cp.film = film; cp.film_ld = film_ld; cp.coeff = coeff;
   GnApplyParams ap = {};
   ap.x0 = x0; ap.x1 = x1; ap.C0 = C0; ap.C1 = C1; ap.B = B; ap.H = H; ap.W = W; ap.mode = mode; ap.pad = pad; ap.act = act;
   ap.coeff = coeff; ap.out = out; ap.out_x3 = out_x3;
-  rc = launch_gn_coeff(cp, B, st);
-  if (rc) return rc;
   return launch_gn_apply(ap, dtype, st);
 }
 
@@ -357,17 +348,9 @@ int k22_conv3x3_gn(const void* x0, const void* x1, int C0, int C1, const float* 
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int C = C0 + C1, HW = H * W;
   const int sdt = k22_storage_dtype(dtype);
-  const int nsplit = gn_nsplit(B, HW);
   float* part = reinterpret_cast<float*>(scratch);
   float* coeff = part + (size_t)B * 128 * C * 2;
-  GnStatsParams sp;
-  sp.x0 = x0; sp.x1 = x1; sp.C0 = C0; sp.C1 = C1; sp.HW = HW; sp.B = B; sp.groups = 32; sp.nsplit = nsplit; sp.partial = part;
-  int rc = launch_gn_stats(sp, sdt, st);
-  if (rc) return rc;
-  GnCoeffParams cp = {};
-  cp.src[0].st = part; cp.src[0].rpi = nsplit; cp.src[0].C = C;
-  cp.HW = HW; cp.C = C; cp.groups = 32; cp.eps = eps; cp.gamma = gamma; cp.beta = beta; cp.film = film; cp.film_ld = film_ld; cp.coeff = coeff;
-  rc = launch_gn_coeff(cp, B, st);
+  const int rc = launch_gn_stats_coeff(x0, x1, C0, C1, B, HW, eps, gamma, beta, film, film_ld, part, coeff, sdt, st);
   if (rc) return rc;
   IgemmParams p = {};
   p.stages = -1;

@@ -102,6 +102,20 @@ int launch_x3_pack(const float* in, void* out, int64_t n, float scale, hipStream
 int gn_nsplit(int B, int HW);
 int launch_gn_stats(const GnStatsParams& p, int dtype, hipStream_t s);
 int launch_gn_coeff(const GnCoeffParams& p, int B, hipStream_t s);
+// The launch pair of a GroupNorm (32 groups) whose producer delivered no partial sums: statistics of the virtual concat x0 | x1 into `partial`
+// ([B][gn_nsplit(B, HW)][C0 + C1][2]), then the per-channel coefficients (gamma / beta, optional FiLM) into `coeff`.
+inline int launch_gn_stats_coeff(const void* x0, const void* x1, int C0, int C1, int B, int HW, float eps, const float* gamma, const float* beta,
+                                 const float* film, int64_t film_ld, float* partial, float* coeff, int dtype, hipStream_t s) {
+  const int nsplit = gn_nsplit(B, HW), C = C0 + C1;
+  GnStatsParams sp = {};
+  sp.x0 = x0; sp.x1 = x1; sp.C0 = C0; sp.C1 = C1; sp.HW = HW; sp.B = B; sp.groups = 32; sp.nsplit = nsplit; sp.partial = partial;
+  const int rc = launch_gn_stats(sp, dtype, s);
+  if (rc) return rc;
+  GnCoeffParams cp = {};
+  cp.src[0].st = partial; cp.src[0].rpi = nsplit; cp.src[0].C = C;
+  cp.HW = HW; cp.C = C; cp.groups = 32; cp.eps = eps; cp.gamma = gamma; cp.beta = beta; cp.film = film; cp.film_ld = film_ld; cp.coeff = coeff;
+  return launch_gn_coeff(cp, B, s);
+}
 int launch_gn_apply(const GnApplyParams& p, int dtype, hipStream_t s);
 int launch_resample(const void* x, void* y, int B, int H, int W, int C, int mode, int dtype, hipStream_t s);
 int launch_conv_in(const ConvInParams& p, int dtype, hipStream_t s);

@@ -22,6 +22,7 @@
 #include "elementwise.h"
 #include "../../include/k22.h"
 #include "tuning.h"
+#include "plan.h"
 
 #include <deque>
 #include <functional>
@@ -220,66 +221,28 @@ __global__ __launch_bounds__(256) void enc_attention_generic_kernel(const T* __r
   }
 }
 
-struct ESlot { size_t bytes = 0, off = 0; };
 typedef std::function<int(hipStream_t)> EOp;
 }  // namespace
 
-struct K22Encoder {
+struct K22Encoder : GraphPlan {   // tuned: every transformer Linear; graph: the 150-300 launches of one tower pass
   K22EncoderConfig cfg;
-  int dtype; size_t esz;
-  std::unordered_map<std::string, const void*> w;
   int B = 0;
-  std::deque<ESlot> slots;
   std::vector<EOp> ops;
-  std::deque<Tuned> tuned;   // every transformer Linear: its tile configuration (table / measurement at the first pass)
-  bool tuned_done = false;
-  int autotune = 1;
-  size_t ws_bytes = 0;
-  char* ws = nullptr;
-  std::string err;
-  hipGraphExec_t graph_exec = nullptr;   // the 150-300 launches of one tower pass, replayed as one graph
-  hipStream_t cap_stream = nullptr;
-  ~K22Encoder() {
-    if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
-    if (cap_stream) (void)hipStreamDestroy(cap_stream);
-  }
-  ESlot *s_tok, *s_valid, *s_img, *s_patch, *s_pout, *s_inp, *s_ln, *s_qkv, *s_att, *s_fc, *s_fc32, *s_seq, *s_pool_in, *s_pooled, *s_splitk,
+  Slot *s_tok, *s_valid, *s_img, *s_patch, *s_pout, *s_inp, *s_ln, *s_qkv, *s_att, *s_fc, *s_fc32, *s_seq, *s_pool_in, *s_pooled, *s_splitk,
       *s_kall, *s_vtall, *s_flush;
 
-  ESlot* new_slot(size_t bytes = 0) { slots.emplace_back(); slots.back().bytes = bytes; return &slots.back(); }
-  static void need(ESlot* s, size_t bytes) { if (bytes > s->bytes) s->bytes = bytes; }
-  template <typename T = char> T* ptr(const ESlot* s) const { return reinterpret_cast<T*>(ws + s->off); }
-  const void* W_(const std::string& name) {
-    auto it = w.find(name);
-    if (it == w.end()) { if (err.empty()) err = "missing weight: " + name; return nullptr; }
-    return it->second;
+  int run_ops(hipStream_t st) const {
+    for (auto& op : ops) { int rc = op(st); if (rc) return rc; }
+    return K22_OK;
   }
-  const float* Wf(const std::string& name) { return reinterpret_cast<const float*>(W_(name)); }
 
   // out = A[M][K] . W[N][K]^T + bias:  mode 0 -> T rows; 1 -> fp32 rows; 2 -> fp32 rows += (in-place residual stream)
-  void op_linear(ESlot* a, int M, int N, int K, const std::string& pfx, int act, ESlot* dst, int ldo, int mode) {
-    tuned.emplace_back();
-    Tuned* t = &tuned.back();
-    IgemmParams& p = t->p;
-    p.stages = -1;
-    p.M = M; p.N = N; p.Npad = (N + 63) / 64 * 64; p.Kc = K; p.K0 = K; p.taps = 1; p.lda0 = K; p.ldo = ldo; p.ldr = ldo;
-    p.out_mode = mode == 0 ? IG_OUT_ROWMAJOR : IG_OUT_ROWMAJOR_F32; p.act = act; p.res_f32 = mode == 2 ? 1 : 0;
-    p.Wp = W_(pfx + ".weight"); p.bias = Wf(pfx + ".bias");
-    tuned_make_candidates(*t, dtype);
-    tuned_default_cfg(*t, dtype);
-    need(s_splitk, tuned_max_splitk_bytes(*t, autotune != 0));
-    const int dt = dtype;
-    t->run = [=](hipStream_t st) {
-      IgemmParams q = t->p;
-      tuned_apply_cfg(q, t->cfg);
-      q.A0 = ptr(a); q.out = ptr(dst); q.partial = ptr<float>(s_splitk);
-      q.residual = mode == 2 ? ptr(dst) : nullptr;
-      return launch_igemm(q, dt, st);
-    };
+  void op_linear(Slot* a, int M, int N, int K, const std::string& pfx, int act, Slot* dst, int ldo, int mode) {
+    Tuned* t = tuned_linear(a, 0, M, N, K, pfx, act, dst, 0, ldo, mode, s_splitk);
     ops.push_back([=](hipStream_t st) { return t->run(st); });
   }
   // LayerNorm of `rows` fp32 rows of x (stride ldx): fp32 copy into yf (may be x itself) and / or T copy into yt
-  void op_ln(ESlot* x, size_t x_off, int64_t ldx, int rows, const std::string& pfx, ESlot* yf, int64_t ldyf, ESlot* yt) {
+  void op_ln(Slot* x, size_t x_off, int64_t ldx, int rows, const std::string& pfx, Slot* yf, int64_t ldyf, Slot* yt) {
     const float* g = Wf(pfx + ".weight"); const float* b = Wf(pfx + ".bias");
     const int D = cfg.width, dt = dtype;
     const float eps = cfg.ln_eps;
@@ -318,9 +281,9 @@ struct K22Encoder {
     if (vision && (cfg.image_size % cfg.patch || P + 1 != n)) return k22_set_error(K22_EINVAL, "encoder: n_ctx must be (image_size/patch)^2 + 1");
     if (!vision && cfg.vocab < 1) return k22_set_error(K22_EINVAL, "encoder: vocab");
     // validated: only now drop the previous plan
+    begin_plan();
     B = nB;
-    slots.clear(); ops.clear(); err.clear(); ws = nullptr; tuned.clear(); tuned_done = false;
-    if (graph_exec) { (void)hipGraphExecDestroy(graph_exec); graph_exec = nullptr; }
+    ops.clear();
     s_tok = new_slot((size_t)M * 4); s_valid = new_slot((size_t)M * 4);
     s_img = new_slot(vision ? (size_t)B * 3 * cfg.image_size * cfg.image_size * 4 : 0);
     s_patch = new_slot(vision ? (size_t)B * P * Kp * esz : 0); s_pout = new_slot(vision ? (size_t)B * P * D * 4 : 0);
@@ -463,11 +426,7 @@ struct K22Encoder {
       lp.M = Bn; lp.N = od; lp.K = D; lp.act_in = K22_ACT_NONE; lp.act_out = K22_ACT_NONE;
       return launch_linear_smallm(lp, K22_F32, st);
     });
-    if (!err.empty()) return k22_set_error(K22_EINVAL, err.c_str());
-    size_t off = 0;
-    for (auto& s : slots) { s.off = off; off += (s.bytes + 255) / 256 * 256; }
-    ws_bytes = off + 256;
-    return K22_OK;
+    return finish_plan();
   }
 };
 
@@ -477,12 +436,8 @@ int k22_encoder_create(const K22EncoderConfig* cfg, const K22Weight* weights, in
   if (!cfg || !out || (!weights && n_weights > 0)) return k22_set_error(K22_EINVAL, "encoder_create: null argument");
   if (!k22_dtype_ok(cfg->dtype)) return k22_set_error(K22_EINVAL, "encoder_create: dtype");
   K22Encoder* m = new K22Encoder();
-  m->cfg = *cfg; m->dtype = cfg->dtype; m->esz = cfg->dtype == K22_F32 ? 4 : 2;
-  for (int i = 0; i < n_weights; ++i) m->w[weights[i].name] = weights[i].ptr;
-  {
-    const char* e = getenv("K22_AUTOTUNE");
-    m->autotune = e ? (atoi(e) != 0) : 1;
-  }
+  m->cfg = *cfg; m->set_dtype(cfg->dtype);
+  m->set_weights(weights, n_weights);
   *out = m;
   return K22_OK;
 }
@@ -491,18 +446,13 @@ void k22_encoder_destroy(K22Encoder* m) { delete m; }
 int k22_encoder_plan(K22Encoder* m, int B, size_t* workspace_bytes) {
   if (!m || !workspace_bytes) return k22_set_error(K22_EINVAL, "encoder_plan: null argument");
   int rc = m->plan(B);
-  if (rc) { if (!m->err.empty()) { m->ops.clear(); m->ws = nullptr; } return rc; }   // a missing weight is found after the old plan was dropped
+  if (rc) return rc;
   *workspace_bytes = m->ws_bytes;
   return K22_OK;
 }
 int k22_encoder_bind(K22Encoder* m, void* workspace, size_t workspace_bytes) {
-  if (!m || !workspace) return k22_set_error(K22_EINVAL, "encoder_bind: null argument");
-  if (m->ops.empty()) return k22_set_error(K22_EINVAL, "encoder_bind: plan first");
-  if (workspace_bytes < m->ws_bytes) return k22_set_error(K22_ENOMEM, "encoder_bind: workspace too small");
-  if ((uintptr_t)workspace % 256) return k22_set_error(K22_EINVAL, "encoder_bind: workspace must be 256-byte aligned");
-  m->ws = reinterpret_cast<char*>(workspace);
-  if (m->graph_exec) { (void)hipGraphExecDestroy(m->graph_exec); m->graph_exec = nullptr; }
-  return K22_OK;
+  if (!m) return k22_set_error(K22_EINVAL, "encoder_bind: null argument");
+  return m->bind(workspace, workspace_bytes, "encoder_bind");
 }
 
 int k22_encoder_forward(K22Encoder* m, const int* tokens, const float* key_valid, const float* image, float* seq_out, float* pooled_out,
@@ -515,46 +465,14 @@ int k22_encoder_forward(K22Encoder* m, const int* tokens, const float* key_valid
   if (vision && seq_out) return k22_set_error(K22_EINVAL, "encoder_forward: the vision tower has no sequence output");
   if (!pooled_out) return k22_set_error(K22_EINVAL, "encoder_forward: pooled_out is null");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipError_t e;
-#define K22_CPY(dst, src, bytes)                                                   \
-  e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st);                \
-  if (e != hipSuccess) return k22_set_error_hip(e, __FILE__, __LINE__);
   const size_t M = (size_t)m->B * c.n_ctx;
-  if (vision) { K22_CPY(m->ptr(m->s_img), image, (size_t)m->B * 3 * c.image_size * c.image_size * 4); }
-  else { K22_CPY(m->ptr(m->s_tok), tokens, M * 4); }
-  if (xlmr) { K22_CPY(m->ptr(m->s_valid), key_valid, M * 4); }
-  if (m->autotune && !m->tuned_done) {
-    // problems the tile table does not know are measured here (the in-place residual GEMMs accumulate garbage into the sequence
-    // buffer meanwhile: the real pass below rebuilds it from the inputs)
-    int rc = tune_igemm_ops(m->tuned, m->dtype, m->s_flush->bytes ? m->ptr(m->s_flush) : nullptr, m->s_flush->bytes, st);
-    if (rc) return rc;
-    m->tuned_done = true;
-  }
-  if (!m->graph_exec) {
-    // first pass on this plan: run eagerly once (function attributes, code load), then capture the launch list
-    for (auto& op : m->ops) { int rc = op(st); if (rc) return rc; }
-    if (!m->cap_stream) {
-      e = hipStreamCreateWithFlags(&m->cap_stream, hipStreamNonBlocking);
-      if (e != hipSuccess) return k22_set_error_hip(e, __FILE__, __LINE__);
-    }
-    hipGraph_t g = nullptr;
-    e = hipStreamBeginCapture(m->cap_stream, hipStreamCaptureModeThreadLocal);
-    if (e != hipSuccess) return k22_set_error_hip(e, __FILE__, __LINE__);
-    int rc = K22_OK;
-    for (auto& op : m->ops) { rc = op(m->cap_stream); if (rc) break; }
-    e = hipStreamEndCapture(m->cap_stream, &g);
-    if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
-    if (e != hipSuccess) return k22_set_error_hip(e, __FILE__, __LINE__);
-    e = hipGraphInstantiate(&m->graph_exec, g, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(g);
-    if (e != hipSuccess) { m->graph_exec = nullptr; return k22_set_error_hip(e, __FILE__, __LINE__); }
-  }
-  e = hipGraphLaunch(m->graph_exec, st);
-  if (e != hipSuccess) return k22_set_error_hip(e, __FILE__, __LINE__);
-  if (seq_out) { K22_CPY(seq_out, m->ptr(m->s_seq), M * c.width * 4); }
-  K22_CPY(pooled_out, m->ptr(m->s_pooled), (size_t)m->B * c.out_dim * 4);
-#undef K22_CPY
-  return K22_OK;
+  if (vision) { if (int rc = copy_d2d(m->ptr(m->s_img), image, (size_t)m->B * 3 * c.image_size * c.image_size * 4, st)) return rc; }
+  else { if (int rc = copy_d2d(m->ptr(m->s_tok), tokens, M * 4, st)) return rc; }
+  if (xlmr) { if (int rc = copy_d2d(m->ptr(m->s_valid), key_valid, M * 4, st)) return rc; }
+  if (int rc = m->tune_once(m->s_flush, st)) return rc;
+  if (int rc = m->replay(m->graph, st, [m](hipStream_t s) { return m->run_ops(s); })) return rc;
+  if (seq_out) { if (int rc = copy_d2d(seq_out, m->ptr(m->s_seq), M * c.width * 4, st)) return rc; }
+  return copy_d2d(pooled_out, m->ptr(m->s_pooled), (size_t)m->B * c.out_dim * 4, st);
 }
 
 }  // extern "C"

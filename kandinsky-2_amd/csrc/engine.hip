@@ -13,6 +13,7 @@
 #include "elementwise.h"
 #include "../../include/k22.h"
 #include "tuning.h"
+#include "plan.h"
 
 #include <deque>
 #include <functional>
@@ -29,8 +30,6 @@
 int launch_step_advance(int* step, int delta, hipStream_t s);
 
 namespace {
-
-struct Slot { size_t bytes = 0, off = 0; };
 
 enum OpKind { OP_CONV3 = 0, OP_GEMM = 1, OP_GN = 2, OP_ATTN = 3, OP_MISC = 4, OP_NKINDS = 5 };
 
@@ -59,23 +58,16 @@ struct Act {  // unpadded NHWC activation, optionally a virtual channel concat o
 
 }  // namespace
 
-struct K22UNet {
+struct K22UNet : GraphPlan {   // dtype: arithmetic type of the MFMA kernels (K22DType; K22_F16X3 = split precision)
   K22UNetConfig cfg;
-  int dtype;   // arithmetic type of the MFMA kernels (K22DType; K22_F16X3 = split precision)
   int sdt;     // type of everything the data-movement kernels touch: dtype, except fp32 for the split-precision arithmetic
-  size_t esz;
-  std::unordered_map<std::string, const void*> w;
 
   // ---- plan state ----
   int B = 0, H = 0, W = 0;
-  std::deque<Slot> slots;
   OpList ops;       // one UNet forward
   OpList cond_ops;  // conditioning head
   OpList hint_ops;  // 2.2 ControlNet-depth: input_hint_block over the hint image (once per generation)
   bool hint_set = false;
-  std::deque<Tuned> tuned;  // stable addresses: op closures and Act descriptors point into it
-  bool tuned_done = false;
-  int autotune = 1;
   int fuse_skip = 1;
   // GroupNorm-apply (+FiLM, +SiLU, zero border) fused into the consuming 3x3 convolution's halo fill (conv3_halo_spec_kernel producers)
   // wherever the convolution's tile configuration is one of the specialised kernels; the stand-alone gn_apply stays for the rest.
@@ -100,16 +92,10 @@ struct K22UNet {
     frag_done = true;
     return K22_OK;
   }
-  size_t ws_bytes = 0;
-  char* ws = nullptr;
   bool cond_set = false;
-  bool warmed = false;   // one eager pass of the op list has run on this plan (function attributes set, code loaded): capture may start
-  hipGraphExec_t graph_exec = nullptr;
-  hipStream_t cap_stream = nullptr;  // private stream used only to CAPTURE (the caller's may be the legacy default stream)
   // the whole denoising loop as ONE graph (k22_unet_sample_loop): valid for exactly the buffers / scalars it was captured with
-  hipGraphExec_t loop_exec = nullptr;
+  GraphCache loop;
   std::vector<unsigned long long> loop_key;
-  std::string err;
 
   // persistent slots
   Slot *s_xin, *s_img, *s_mask, *s_t, *s_out;
@@ -152,43 +138,20 @@ struct K22UNet {
     return launch_linear_smallm(le, tw.dt, st);
   }
 
-  Slot* new_slot(size_t bytes = 0) { slots.emplace_back(); slots.back().bytes = bytes; return &slots.back(); }
-  static void need(Slot* s, size_t bytes) { if (bytes > s->bytes) s->bytes = bytes; }
-  template <typename T = char> T* ptr(const Slot* s) const { return reinterpret_cast<T*>(ws + s->off); }
-
-  const void* W_(const std::string& name) {
-    auto it = w.find(name);
-    if (it == w.end()) { if (err.empty()) err = "missing weight: " + name; return nullptr; }
-    return it->second;
-  }
-  const float* Wf(const std::string& name) { return reinterpret_cast<const float*>(W_(name)); }
-
   // (Round 4's "two half-batch chains" mode - the CFG pair as two engines on two streams, +3.9 % - is gone: it rested on a work-around for
   // a kernel pair whose co-resident victim returned wrong elements.  Round 5 narrowed that to the victim's packed-fp32 instructions
   // (profiles/r05_two_stream_probe.txt; `make NOPK=1` builds the library without them): INTEGRATION.md G.)
   // the [B][out_channels][HW] model output
   float* model_out() { return ptr<float>(s_out); }
   int exec(hipStream_t st) { return run_ops(st); }
-  int exec_eager(hipStream_t st) { const int rc = exec(st); if (rc == K22_OK) warmed = true; return rc; }
+  int exec_eager(hipStream_t st) { return run_eager(st, [this](hipStream_t s) { return exec(s); }); }
   // first forward of a plan / binding: fragment-major weight copies, tile configurations the table does not know
   int prepare_run(hipStream_t st) {
     if (!frag_done) { int rc = repack_frags(st); if (rc) return rc; }
-    if (autotune && !tuned_done) {
-      int rc = tune_all(st);
-      if (rc) return rc;
-      tuned_done = true;
-    }
-    return K22_OK;
-  }
-  void drop_graphs() {
-    if (graph_exec) { (void)hipGraphExecDestroy(graph_exec); graph_exec = nullptr; }
-    if (loop_exec) { (void)hipGraphExecDestroy(loop_exec); loop_exec = nullptr; }
+    return tune_once(s_flush, st);
   }
 
   ~K22UNet() {
-    if (loop_exec) (void)hipGraphExecDestroy(loop_exec);
-    if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
-    if (cap_stream) (void)hipStreamDestroy(cap_stream);
     if (film_all) (void)hipFree(film_all);
   }
 
@@ -201,7 +164,6 @@ struct K22UNet {
     return K22_OK;
   }
   int run_ops(hipStream_t st) { return run_ops_range(st, 0, ops.size()); }
-  int run_ops_eager(hipStream_t st) { const int rc = run_ops(st); if (rc == K22_OK) warmed = true; return rc; }
 
   // ------------------------------------------------------------------------------------------
   void op_gn(OpList& L, const Act& in, const std::string& pfx, int64_t film_off,
@@ -403,8 +365,6 @@ struct K22UNet {
     return t;
   }
 
-  int tune_all(hipStream_t st) { return tune_igemm_ops(tuned, dtype, s_flush->bytes ? ptr(s_flush) : nullptr, s_flush->bytes, st); }
-
   // ResBlock (unet.py:110-220) with use_scale_shift_norm=True; updown: 0 none, 1 down, 2 up.
   Act resblock(const std::string& pfx, const Act& in, int Cout, int updown, int64_t& film_cursor, Slot* dst, Slot* dst_stats) {
     const int Cin = in.C();
@@ -521,13 +481,12 @@ struct K22UNet {
     if (nB < 1 || nH < 1 || nW < 1) return k22_set_error(K22_EINVAL, "unet: B, H, W must be positive");
     if (nH % (1 << n_down) || nW % (1 << n_down)) return k22_set_error(K22_EINVAL, "unet: H, W must be divisible by 2^(levels-1)");
     if (nB > 8) return k22_set_error(K22_EINVAL, "unet: batch (2*bs) must be <= 8 per engine call");
+    begin_plan();
     B = nB; H = nH; W = nW;
     gn_links.clear();
-    slots.clear(); ops.clear(); cond_ops.clear(); hint_ops.clear(); s_ctxkv.clear(); frag_jobs.clear(); frag_done = false; n_attn = 0; err.clear();
-    tuned.clear(); tuned_done = false; warmed = false;
-    ws = nullptr; cond_set = false; hint_set = false;
-    if (graph_exec) { (void)hipGraphExecDestroy(graph_exec); graph_exec = nullptr; }
-    if (loop_exec) { (void)hipGraphExecDestroy(loop_exec); loop_exec = nullptr; }
+    ops.clear(); cond_ops.clear(); hint_ops.clear(); s_ctxkv.clear(); frag_jobs.clear(); frag_done = false; n_attn = 0;
+    cond_set = false; hint_set = false;
+    loop.drop();
     const int mc = cfg.model_channels, ted = 4 * mc;
 
     // total FiLM width = sum over ResBlocks of 2*Cout, in module order
@@ -670,12 +629,7 @@ struct K22UNet {
     op_gn(ops, h, "out.0", -1, K22_ACT_SILU, 0, 1, s_P1);
     op_conv(ops, CONV_HEAD, s_P1, H, W, ch, cfg.out_channels, "out.2", nullptr, s_out, IG_OUT_NCHW_F32);
 
-    if (!err.empty()) return k22_set_error(K22_EINVAL, err.c_str());
-    // ---- lay the slots out -----------------------------------------------------------------------
-    size_t off = 0;
-    for (auto& s : slots) { s.off = off; off += (s.bytes + 255) / 256 * 256; }
-    ws_bytes = off + 256;
-    return K22_OK;
+    return finish_plan();
   }
 
   // Kandinsky 2.2 conditioning head (the UNet2DConditionModel injected at kandinsky2_2_model.py:26-41; arithmetic of diffusers'
@@ -807,22 +761,14 @@ int k22_unet_create(const K22UNetConfig* cfg, const K22Weight* weights, int n_we
     return k22_set_error(K22_EINVAL, "unet_create: hint_channels = 3 goes with in_channels = 8 (latent + hint latent), else 0");
   if (cfg->head_type == 1 && cfg->n_image_embs != cfg->ctx_len) return k22_set_error(K22_EINVAL, "unet_create: the 2.2 head has image tokens only (n_image_embs == ctx_len)");
   K22UNet* u = new K22UNet();
-  u->cfg = *cfg; u->dtype = cfg->dtype; u->sdt = k22_storage_dtype(cfg->dtype); u->esz = k22_esz(cfg->dtype);
-  {
-    const char* e = getenv("K22_AUTOTUNE");  // 0 = heuristics only (no measurement at the first forward)
-    u->autotune = e ? (atoi(e) != 0) : 1;
-    const char* sf = getenv("K22_STREAM");   // 0 = no fragment-major weight copies, no weight-streaming kernel
-    u->stream_frag = sf ? (atoi(sf) != 0) : 1;
-    const char* fg = getenv("K22_FUSE_GN");   // 0 = every GroupNorm through the stand-alone gn_apply kernel
-    u->fuse_gn = fg ? (atoi(fg) != 0) : 0;
-    const char* f = getenv("K22_FUSE_SKIP");  // 0 = 1x1 skip connections as separate GEMMs
-    u->fuse_skip = f ? (atoi(f) != 0) : 1;
-    const char* xp = getenv("K22_X2_PLAN");   // K22_F16X2 only: which of the top level's convolutions run with two MFMAs (K22UNet::x2_plan)
-    u->x2_plan = xp ? (atoi(xp) & 3) : 0;
-    const char* ht = getenv("K22_HOIST_TIME");   // 0 (measurement only) = k22_unet_sample_loop keeps the per-step time-embedding / FiLM launches
-    u->hoist_time = ht ? (atoi(ht) != 0) : 1;
-  }
-  for (int i = 0; i < n_weights; ++i) u->w[weights[i].name] = weights[i].ptr;
+  u->cfg = *cfg; u->set_dtype(cfg->dtype); u->sdt = k22_storage_dtype(cfg->dtype);
+  u->stream_frag = env_flag("K22_STREAM", 1);     // 0 = no fragment-major weight copies, no weight-streaming kernel
+  u->fuse_gn = env_flag("K22_FUSE_GN", 0);        // 0 = every GroupNorm through the stand-alone gn_apply kernel
+  u->fuse_skip = env_flag("K22_FUSE_SKIP", 1);    // 0 = 1x1 skip connections as separate GEMMs
+  u->hoist_time = env_flag("K22_HOIST_TIME", 1);  // 0 (measurement only) = k22_unet_sample_loop keeps the per-step time-embedding / FiLM launches
+  const char* xp = getenv("K22_X2_PLAN");         // K22_F16X2 only: which of the top level's convolutions run with two MFMAs (K22UNet::x2_plan)
+  u->x2_plan = xp ? (atoi(xp) & 3) : 0;
+  u->set_weights(weights, n_weights);
   *out = u;
   return K22_OK;
 }
@@ -838,13 +784,10 @@ int k22_unet_plan(K22UNet* u, int B, int H, int W, size_t* workspace_bytes) {
 }
 
 int k22_unet_bind(K22UNet* u, void* workspace, size_t workspace_bytes) {
-  if (!u || !workspace) return k22_set_error(K22_EINVAL, "unet_bind: null argument");
-  if (u->ops.empty()) return k22_set_error(K22_EINVAL, "unet_bind: plan first");
-  if (workspace_bytes < u->ws_bytes) return k22_set_error(K22_ENOMEM, "unet_bind: workspace too small");
-  if ((uintptr_t)workspace % 256) return k22_set_error(K22_EINVAL, "unet_bind: workspace must be 256-byte aligned");
-  u->ws = reinterpret_cast<char*>(workspace);
+  if (!u) return k22_set_error(K22_EINVAL, "unet_bind: null argument");
+  if (int rc = u->bind(workspace, workspace_bytes, "unet_bind")) return rc;
   u->cond_set = false; u->hint_set = false; u->frag_done = false;
-  u->drop_graphs();
+  u->loop.drop();
   return K22_OK;
 }
 
@@ -855,16 +798,12 @@ int k22_unet_set_condition(K22UNet* u, const float* full_emb, const float* poole
   const int ntext = c.ctx_len - c.n_image_embs;
   if (!image_emb) return k22_set_error(K22_EINVAL, "unet_set_condition: image_emb is required");
   if (c.head_type == 0 && (!full_emb || !pooled_emb)) return k22_set_error(K22_EINVAL, "unet_set_condition: the 2.1 head needs full_emb and pooled_emb");
-  hipError_t e;
   const size_t pb = (size_t)u->B;
   if (c.head_type == 0) {
-    e = hipMemcpyAsync(u->ptr(u->s_full), full_emb, pb * ntext * c.text_dim1 * 4, hipMemcpyDeviceToDevice, st);
-    if (e != hipSuccess) return k22_set_error_hip(e, __FILE__, __LINE__);
-    e = hipMemcpyAsync(u->ptr(u->s_pool), pooled_emb, pb * c.text_dim2 * 4, hipMemcpyDeviceToDevice, st);
-    if (e != hipSuccess) return k22_set_error_hip(e, __FILE__, __LINE__);
+    if (int rc = copy_d2d(u->ptr(u->s_full), full_emb, pb * ntext * c.text_dim1 * 4, st)) return rc;
+    if (int rc = copy_d2d(u->ptr(u->s_pool), pooled_emb, pb * c.text_dim2 * 4, st)) return rc;
   }
-  e = hipMemcpyAsync(u->ptr(u->s_imgemb), image_emb, pb * c.image_dim * 4, hipMemcpyDeviceToDevice, st);
-  if (e != hipSuccess) return k22_set_error_hip(e, __FILE__, __LINE__);
+  if (int rc = copy_d2d(u->ptr(u->s_imgemb), image_emb, pb * c.image_dim * 4, st)) return rc;
   for (auto& op : u->cond_ops) { int rc = op(st); if (rc) return rc; }
   u->cond_set = true;
   return K22_OK;
@@ -876,8 +815,7 @@ int k22_unet_set_hint(K22UNet* u, const float* hint, void* stream) {
   if (!hint) return k22_set_error(K22_EINVAL, "unet_set_hint: null hint");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const size_t per = (size_t)u->B * u->cfg.hint_channels * 64 * u->H * u->W;
-  hipError_t e = hipMemcpyAsync(u->ptr(u->s_hintin), hint, per * 4, hipMemcpyDeviceToDevice, st);
-  if (e != hipSuccess) return k22_set_error_hip(e, __FILE__, __LINE__);
+  if (int rc = copy_d2d(u->ptr(u->s_hintin), hint, per * 4, st)) return rc;
   for (auto& op : u->hint_ops) { int rc = op(st); if (rc) return rc; }
   u->hint_set = true;
   return K22_OK;
@@ -891,47 +829,19 @@ int k22_unet_forward(K22UNet* u, const float* x, const float* timesteps, const f
   if (u->cfg.hint_channels && !u->hint_set) return k22_set_error(K22_EINVAL, "unet_forward: call k22_unet_set_hint first");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const size_t hw = (size_t)u->H * u->W;
-  hipError_t e;
-#define K22_CPY(dst, src, bytes)                                                   \
-  e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st);                \
-  if (e != hipSuccess) return k22_set_error_hip(e, __FILE__, __LINE__);
   const size_t pb = (size_t)u->B;
-  K22_CPY(u->ptr(u->s_xin), x, pb * 4 * hw * 4);
-  K22_CPY(u->ptr(u->s_t), timesteps, pb * 4);
+  if (int rc = copy_d2d(u->ptr(u->s_xin), x, pb * 4 * hw * 4, st)) return rc;
+  if (int rc = copy_d2d(u->ptr(u->s_t), timesteps, pb * 4, st)) return rc;
   if (u->cfg.in_channels == 9) {
-    K22_CPY(u->ptr(u->s_img), inpaint_image, pb * 4 * hw * 4);
-    K22_CPY(u->ptr(u->s_mask), inpaint_mask, pb * hw * 4);
+    if (int rc = copy_d2d(u->ptr(u->s_img), inpaint_image, pb * 4 * hw * 4, st)) return rc;
+    if (int rc = copy_d2d(u->ptr(u->s_mask), inpaint_mask, pb * hw * 4, st)) return rc;
   }
   // first forward on this plan: fragment-major weight copies; conv / GEMM problems the tile table does not know are measured on the device
   { int rc = u->prepare_run(st); if (rc) return rc; }
-  if (use_graph) {
-    if (!u->graph_exec) {
-      // warm-up eagerly once (sets function attributes), then capture
-      if (!u->warmed) { int rc = u->exec_eager(st); if (rc) return rc; }
-      hipGraph_t g = nullptr;
-      if (!u->cap_stream) {
-        e = hipStreamCreateWithFlags(&u->cap_stream, hipStreamNonBlocking);
-        if (e != hipSuccess) return k22_set_error_hip(e, __FILE__, __LINE__);
-      }
-      e = hipStreamBeginCapture(u->cap_stream, hipStreamCaptureModeThreadLocal);
-      if (e != hipSuccess) return k22_set_error_hip(e, __FILE__, __LINE__);
-      const int rc = u->exec(u->cap_stream);
-      e = hipStreamEndCapture(u->cap_stream, &g);
-      if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
-      if (e != hipSuccess) return k22_set_error_hip(e, __FILE__, __LINE__);
-      e = hipGraphInstantiate(&u->graph_exec, g, nullptr, nullptr, 0);
-      (void)hipGraphDestroy(g);
-      if (e != hipSuccess) { u->graph_exec = nullptr; return k22_set_error_hip(e, __FILE__, __LINE__); }
-    }
-    e = hipGraphLaunch(u->graph_exec, st);
-    if (e != hipSuccess) return k22_set_error_hip(e, __FILE__, __LINE__);
-  } else {
-    int rc = u->exec_eager(st);
-    if (rc) return rc;
-  }
-  K22_CPY(out, u->ptr(u->s_out), pb * u->cfg.out_channels * hw * 4);
-#undef K22_CPY
-  return K22_OK;
+  // graph: warm-up eagerly once per plan (sets function attributes), then capture and replay
+  const int rc = use_graph ? u->replay(u->graph, st, [u](hipStream_t s) { return u->exec(s); }) : u->exec_eager(st);
+  if (rc) return rc;
+  return copy_d2d(out, u->ptr(u->s_out), pb * u->cfg.out_channels * hw * 4, st);
 }
 
 // The whole classifier-free-guided p_sampler loop of Kandinsky2_1.generate_img (kandinsky2_1_model.py:222-257 ->
@@ -967,7 +877,7 @@ int k22_unet_sample_loop(K22UNet* u, float* x, float* x_tmp, const float* timest
   if (hoist) {
     const size_t need = (size_t)rows_all * (size_t)(u->film_total + u->tw.mc + 2 * u->tw.ted) * sizeof(float);
     if (need > u->film_all_bytes) {
-      u->drop_graphs();   // captured loops hold the old buffer's addresses
+      u->loop.drop();   // captured loops hold the old buffer's addresses (a captured forward does not: it reads s_film)
       if (u->film_all) { (void)hipStreamSynchronize(st); (void)hipFree(u->film_all); u->film_all = nullptr; u->film_all_bytes = 0; }
       e = hipMalloc(reinterpret_cast<void**>(&u->film_all), need);
       if (e != hipSuccess) { u->film_all = nullptr; return k22_set_error_hip(e, __FILE__, __LINE__); }
@@ -980,7 +890,6 @@ int k22_unet_sample_loop(K22UNet* u, float* x, float* x_tmp, const float* timest
   }
   // one pass over the loop on `s`: what is captured is exactly what an eager call runs
   auto run_loop_body = [&](hipStream_t s) -> int {
-    hipError_t er;
     if (hoist) {
       const int spl = 8 / B;   // steps per batched launch
       for (int k0 = 0; k0 < n_steps; k0 += spl) {
@@ -991,23 +900,18 @@ int k22_unet_sample_loop(K22UNet* u, float* x, float* x_tmp, const float* timest
       }
     }
     if (u->cfg.in_channels == 9) {
-      er = hipMemcpyAsync(u->ptr(u->s_img), inpaint_image, pb * 4 * HW * 4, hipMemcpyDeviceToDevice, s);
-      if (er != hipSuccess) return k22_set_error_hip(er, __FILE__, __LINE__);
-      er = hipMemcpyAsync(u->ptr(u->s_mask), inpaint_mask, pb * HW * 4, hipMemcpyDeviceToDevice, s);
-      if (er != hipSuccess) return k22_set_error_hip(er, __FILE__, __LINE__);
+      if (int rc = copy_d2d(u->ptr(u->s_img), inpaint_image, pb * 4 * HW * 4, s)) return rc;
+      if (int rc = copy_d2d(u->ptr(u->s_mask), inpaint_mask, pb * HW * 4, s)) return rc;
     }
     float* cur = x; float* nxt = x_tmp;
     for (int k = 0; k < n_steps; ++k) {
       // model_fn: the UNet sees the first half twice (kandinsky2_1_model.py:223-225)
-      er = hipMemcpyAsync(u->ptr(u->s_xin), cur, half, hipMemcpyDeviceToDevice, s);
-      if (er != hipSuccess) return k22_set_error_hip(er, __FILE__, __LINE__);
-      er = hipMemcpyAsync(u->ptr(u->s_xin) + half, cur, half, hipMemcpyDeviceToDevice, s);
-      if (er != hipSuccess) return k22_set_error_hip(er, __FILE__, __LINE__);
+      if (int rc = copy_d2d(u->ptr(u->s_xin), cur, half, s)) return rc;
+      if (int rc = copy_d2d(u->ptr(u->s_xin) + half, cur, half, s)) return rc;
       if (hoist) {
         u->film_cur = fa_film + (int64_t)k * B * u->film_total;
       } else {
-        er = hipMemcpyAsync(u->ptr(u->s_t), timesteps + (size_t)k * B, (size_t)B * 4, hipMemcpyDeviceToDevice, s);
-        if (er != hipSuccess) return k22_set_error_hip(er, __FILE__, __LINE__);
+        if (int rc = copy_d2d(u->ptr(u->s_t), timesteps + (size_t)k * B, (size_t)B * 4, s)) return rc;
       }
       int rc = u->exec(s);
       if (rc) return rc;
@@ -1021,10 +925,7 @@ int k22_unet_sample_loop(K22UNet* u, float* x, float* x_tmp, const float* timest
       if (rc) return rc;
       float* t_ = cur; cur = nxt; nxt = t_;
     }
-    if (cur != x) {
-      er = hipMemcpyAsync(x, cur, (size_t)B * 4 * HW * sizeof(float), hipMemcpyDeviceToDevice, s);
-      if (er != hipSuccess) return k22_set_error_hip(er, __FILE__, __LINE__);
-    }
+    if (cur != x) return copy_d2d(x, cur, (size_t)B * 4 * HW * sizeof(float), s);
     return K22_OK;
   };
   auto run_loop = [&](hipStream_t s) -> int { const int rc = run_loop_body(s); u->film_cur = nullptr; return rc; };
@@ -1037,53 +938,34 @@ int k22_unet_sample_loop(K22UNet* u, float* x, float* x_tmp, const float* timest
   auto bits = [](double v) { unsigned long long b; memcpy(&b, &v, 8); return b; };
   key.push_back(bits(guidance)); key.push_back(bits(clamp_lo)); key.push_back(bits(clamp_hi)); key.push_back(bits(pct_gamma));
   for (int k = 0; k < n_steps; ++k) key.push_back((unsigned long long)table_rows[k]);
-  if (!u->loop_exec || key != u->loop_key) {
-    if (u->loop_exec) { (void)hipGraphExecDestroy(u->loop_exec); u->loop_exec = nullptr; }
+  if (!u->loop || key != u->loop_key) {
     if (!u->warmed) {   // first forward of this plan: run one step's ops eagerly (function attributes, code load) on a scratch input; a re-capture
                         // for other scalars / buffers (guidance, step count: they are baked into the graph's nodes) does not repeat it
       e = hipMemsetAsync(u->ptr(u->s_xin), 0, pb * 4 * HW * 4, st);
       if (e != hipSuccess) return k22_set_error_hip(e, __FILE__, __LINE__);
-      e = hipMemcpyAsync(u->ptr(u->s_t), timesteps, pb * 4, hipMemcpyDeviceToDevice, st);
-      if (e != hipSuccess) return k22_set_error_hip(e, __FILE__, __LINE__);
+      if (int rc = copy_d2d(u->ptr(u->s_t), timesteps, pb * 4, st)) return rc;
       if (u->cfg.in_channels == 9) {
-        e = hipMemcpyAsync(u->ptr(u->s_img), inpaint_image, pb * 4 * HW * 4, hipMemcpyDeviceToDevice, st);
-        if (e != hipSuccess) return k22_set_error_hip(e, __FILE__, __LINE__);
-        e = hipMemcpyAsync(u->ptr(u->s_mask), inpaint_mask, pb * HW * 4, hipMemcpyDeviceToDevice, st);
-        if (e != hipSuccess) return k22_set_error_hip(e, __FILE__, __LINE__);
+        if (int rc = copy_d2d(u->ptr(u->s_img), inpaint_image, pb * 4 * HW * 4, st)) return rc;
+        if (int rc = copy_d2d(u->ptr(u->s_mask), inpaint_mask, pb * HW * 4, st)) return rc;
       }
       int rc = u->exec_eager(st);
       if (rc) return rc;
       e = hipStreamSynchronize(st);
       if (e != hipSuccess) return k22_set_error_hip(e, __FILE__, __LINE__);
     }
-    if (!u->cap_stream) {
-      e = hipStreamCreateWithFlags(&u->cap_stream, hipStreamNonBlocking);
-      if (e != hipSuccess) return k22_set_error_hip(e, __FILE__, __LINE__);
-    }
-    hipGraph_t g = nullptr;
-    e = hipStreamBeginCapture(u->cap_stream, hipStreamCaptureModeThreadLocal);
-    if (e != hipSuccess) return k22_set_error_hip(e, __FILE__, __LINE__);
-    const int rc = run_loop(u->cap_stream);
-    e = hipStreamEndCapture(u->cap_stream, &g);
-    if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
-    if (e != hipSuccess) return k22_set_error_hip(e, __FILE__, __LINE__);
-    e = hipGraphInstantiate(&u->loop_exec, g, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(g);
-    if (e != hipSuccess) { u->loop_exec = nullptr; return k22_set_error_hip(e, __FILE__, __LINE__); }
+    if (int rc = u->loop.capture(u->cap, run_loop)) return rc;
     u->loop_key = key;
   }
-  e = hipGraphLaunch(u->loop_exec, st);
-  if (e != hipSuccess) return k22_set_error_hip(e, __FILE__, __LINE__);
-  return K22_OK;
+  return u->loop.launch(st);
 }
 
 int k22_unet_num_ops(const K22UNet* u) {
-  return u ? (int)u->ops.size() : 0;
+  return u && u->planned ? (int)u->ops.size() : 0;
 }
 
 int k22_unet_set_autotune(K22UNet* u, int on) {
   if (!u) return k22_set_error(K22_EINVAL, "unet_set_autotune: null handle");
-  if (!u->ops.empty() && (on != 0) != (u->autotune != 0)) return k22_set_error(K22_EINVAL, "unet_set_autotune: call before k22_unet_plan");
+  if (u->planned && (on != 0) != (u->autotune != 0)) return k22_set_error(K22_EINVAL, "unet_set_autotune: call before k22_unet_plan");
   u->autotune = on ? 1 : 0;
   return K22_OK;
 }

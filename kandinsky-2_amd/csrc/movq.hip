@@ -16,6 +16,7 @@
 #include "kernels.h"
 #include "elementwise.h"
 #include "../../include/k22.h"
+#include "plan.h"
 
 #include <deque>
 #include <functional>
@@ -24,38 +25,22 @@
 #include <vector>
 
 namespace {
-struct MSlot { size_t bytes = 0, off = 0; };
 typedef std::function<int(hipStream_t)> MOp;
-struct MAct { MSlot* s = nullptr; int C = 0, H = 0, W = 0; };
+struct MAct { Slot* s = nullptr; int C = 0, H = 0, W = 0; };
 }  // namespace
 
-struct K22MoVQ {
+struct K22MoVQ : PlanBase {
   K22MoVQConfig cfg;
-  int dtype; size_t esz;
-  std::unordered_map<std::string, const void*> w;
   int B = 0, h0 = 0, w0 = 0;
-  std::deque<MSlot> slots;
   std::vector<MOp> ops;
-  size_t ws_bytes = 0;
-  char* ws = nullptr;
-  std::string err;
-  MSlot *s_zq, *s_xin, *s_part, *s_coeff, *s_P, *s_U, *s_S, *s_N, *s_Q, *s_K, *s_VT, *s_SC, *s_O, *s_splitk, *s_out, *s_z;
-  MSlot *s_img = nullptr, *s_lat = nullptr;   // encoder plan: fp32 NCHW image in, fp32 NCHW latent out
+  Slot *s_zq, *s_xin, *s_part, *s_coeff, *s_P, *s_U, *s_S, *s_N, *s_Q, *s_K, *s_VT, *s_SC, *s_O, *s_splitk, *s_out, *s_z;
+  Slot *s_img = nullptr, *s_lat = nullptr;   // encoder plan: fp32 NCHW image in, fp32 NCHW latent out
   bool enc = false;                           // the current plan is the encoder (plain GroupNorm instead of SpatialNorm)
   int encH = 0, encW = 0;
-  MSlot* s_h[3];
+  Slot* s_h[3];
   int hrot = 0;
 
-  MSlot* new_slot(size_t bytes = 0) { slots.emplace_back(); slots.back().bytes = bytes; return &slots.back(); }
-  static void need(MSlot* s, size_t bytes) { if (bytes > s->bytes) s->bytes = bytes; }
-  template <typename T = char> T* ptr(const MSlot* s) const { return reinterpret_cast<T*>(ws + s->off); }
-  MSlot* next_h() { MSlot* s = s_h[hrot]; hrot = (hrot + 1) % 3; return s; }
-  const void* W_(const std::string& name) {
-    auto it = w.find(name);
-    if (it == w.end()) { if (err.empty()) err = "missing weight: " + name; return nullptr; }
-    return it->second;
-  }
-  const float* Wf(const std::string& name) { return reinterpret_cast<const float*>(W_(name)); }
+  Slot* next_h() { Slot* s = s_h[hrot]; hrot = (hrot + 1) % 3; return s; }
   static int ilog2(int v) { int s = 0; while ((1 << s) < v) ++s; return s; }
 
   // generic launch of one igemm problem with the library's heuristics
@@ -73,10 +58,9 @@ struct K22MoVQ {
   }
 
   // SpatialNorm (+act) -> dst (zero-bordered when pad)
-  void op_sn(const MAct& in, const std::string& pfx, int act, int pad, MSlot* dst) {
+  void op_sn(const MAct& in, const std::string& pfx, int act, int pad, Slot* dst) {
     const int Bn = B, C = in.C, HW = in.H * in.W;
-    const int nsplit = gn_nsplit(Bn, HW);
-    need(s_part, (size_t)Bn * nsplit * C * 2 * sizeof(float));
+    need(s_part, (size_t)Bn * gn_nsplit(Bn, HW) * C * 2 * sizeof(float));
     need(s_coeff, (size_t)Bn * C * 2 * sizeof(float));
     need(dst, (size_t)Bn * (in.H + 2 * pad) * (in.W + 2 * pad) * C * esz);
     const float* gamma = Wf(pfx + ".norm_layer.weight"); const float* beta = Wf(pfx + ".norm_layer.bias");
@@ -85,16 +69,7 @@ struct K22MoVQ {
     const MAct a = in;
     const int dt = dtype, shift = ilog2(in.H / h0), hh = h0, ww = w0;
     ops.push_back([=](hipStream_t st) {
-      GnStatsParams sp;
-      sp.x0 = ptr(a.s); sp.x1 = nullptr; sp.C0 = C; sp.C1 = 0; sp.HW = HW; sp.B = Bn; sp.groups = 32; sp.nsplit = nsplit;
-      sp.partial = ptr<float>(s_part);
-      int rc = launch_gn_stats(sp, dt, st);
-      if (rc) return rc;
-      GnCoeffParams cp = {};
-      cp.src[0].st = ptr<float>(s_part); cp.src[0].rpi = nsplit; cp.src[0].C = C;
-      cp.HW = HW; cp.C = C; cp.groups = 32; cp.eps = 1e-6f; cp.gamma = gamma; cp.beta = beta; cp.film = nullptr; cp.film_ld = 0;
-      cp.coeff = ptr<float>(s_coeff);
-      rc = launch_gn_coeff(cp, Bn, st);
+      int rc = launch_gn_stats_coeff(ptr(a.s), nullptr, C, 0, Bn, HW, 1e-6f, gamma, beta, nullptr, 0, ptr<float>(s_part), ptr<float>(s_coeff), dt, st);
       if (rc) return rc;
       SpatialNormParams np;
       np.x = ptr(a.s); np.coeff = ptr<float>(s_coeff); np.zq = ptr<float>(s_zq); np.wy = wy; np.by = by; np.wb = wb; np.bb = bb;
@@ -104,26 +79,16 @@ struct K22MoVQ {
   }
 
   // plain GroupNorm (vqgan_blocks.Normalize: 32 groups, eps 1e-6, affine) (+act) -> dst (zero-bordered when pad)
-  void op_gn(const MAct& in, const std::string& pfx, int act, int pad, MSlot* dst) {
+  void op_gn(const MAct& in, const std::string& pfx, int act, int pad, Slot* dst) {
     const int Bn = B, C = in.C, HW = in.H * in.W;
-    const int nsplit = gn_nsplit(Bn, HW);
-    need(s_part, (size_t)Bn * nsplit * C * 2 * sizeof(float));
+    need(s_part, (size_t)Bn * gn_nsplit(Bn, HW) * C * 2 * sizeof(float));
     need(s_coeff, (size_t)Bn * C * 2 * sizeof(float));
     need(dst, (size_t)Bn * (in.H + 2 * pad) * (in.W + 2 * pad) * C * esz);
     const float* gamma = Wf(pfx + ".weight"); const float* beta = Wf(pfx + ".bias");
     const MAct a = in;
     const int dt = dtype;
     ops.push_back([=](hipStream_t st) {
-      GnStatsParams sp = {};
-      sp.x0 = ptr(a.s); sp.x1 = nullptr; sp.C0 = C; sp.C1 = 0; sp.HW = HW; sp.B = Bn; sp.groups = 32; sp.nsplit = nsplit;
-      sp.partial = ptr<float>(s_part);
-      int rc = launch_gn_stats(sp, dt, st);
-      if (rc) return rc;
-      GnCoeffParams cp = {};
-      cp.src[0].st = ptr<float>(s_part); cp.src[0].rpi = nsplit; cp.src[0].C = C;
-      cp.HW = HW; cp.C = C; cp.groups = 32; cp.eps = 1e-6f; cp.gamma = gamma; cp.beta = beta; cp.film = nullptr; cp.film_ld = 0;
-      cp.coeff = ptr<float>(s_coeff);
-      rc = launch_gn_coeff(cp, Bn, st);
+      int rc = launch_gn_stats_coeff(ptr(a.s), nullptr, C, 0, Bn, HW, 1e-6f, gamma, beta, nullptr, 0, ptr<float>(s_part), ptr<float>(s_coeff), dt, st);
       if (rc) return rc;
       GnApplyParams ap = {};
       ap.x0 = ptr(a.s); ap.x1 = nullptr; ap.C0 = C; ap.C1 = 0; ap.B = Bn; ap.H = a.H; ap.W = a.W; ap.mode = 0; ap.pad = pad; ap.act = act;
@@ -131,12 +96,12 @@ struct K22MoVQ {
       return launch_gn_apply(ap, dt, st);
     });
   }
-  void op_norm(const MAct& in, const std::string& pfx, int act, int pad, MSlot* dst) {
+  void op_norm(const MAct& in, const std::string& pfx, int act, int pad, Slot* dst) {
     if (enc) op_gn(in, pfx, act, pad, dst);
     else op_sn(in, pfx, act, pad, dst);
   }
 
-  void op_conv3(MSlot* src, int H, int W, int Cin, int Cout, const std::string& pfx, MSlot* residual, MSlot* dst, int out_mode) {
+  void op_conv3(Slot* src, int H, int W, int Cin, int Cout, const std::string& pfx, Slot* residual, Slot* dst, int out_mode) {
     IgemmParams p = {};
     p.M = B * H * W; p.N = Cout; p.Npad = (Cout + 63) / 64 * 64; p.Kc = Cin; p.K0 = Cin; p.taps = 9; p.H = H; p.W = W;
     p.ldo = Cout; p.ldr = Cout; p.out_mode = out_mode; p.act = K22_ACT_NONE;
@@ -145,7 +110,7 @@ struct K22MoVQ {
     push_igemm(p, [=](IgemmParams& q) { q.A0 = ptr(src); q.residual = residual ? ptr(residual) : nullptr; q.out = ptr(dst); });
   }
 
-  void op_gemm(MSlot* a, int M, int N, int K, const std::string& pfx, MSlot* residual, MSlot* dst) {
+  void op_gemm(Slot* a, int M, int N, int K, const std::string& pfx, Slot* residual, Slot* dst) {
     IgemmParams p = {};
     p.M = M; p.N = N; p.Npad = (N + 63) / 64 * 64; p.Kc = K; p.K0 = K; p.taps = 1; p.lda0 = K; p.ldo = N; p.ldr = N;
     p.out_mode = IG_OUT_ROWMAJOR; p.act = K22_ACT_NONE;
@@ -161,12 +126,12 @@ struct K22MoVQ {
     op_conv3(s_P, H, W, Cin, Cout, pfx + ".conv1", nullptr, s_U, IG_OUT_ROWMAJOR);
     MAct u; u.s = s_U; u.C = Cout; u.H = H; u.W = W;
     op_norm(u, pfx + ".norm2", K22_ACT_SILU, 1, s_P);
-    MSlot* skip = in.s;
+    Slot* skip = in.s;
     if (Cin != Cout) {
       op_gemm(in.s, B * H * W, Cout, Cin, pfx + ".nin_shortcut", nullptr, s_S);
       skip = s_S;
     }
-    MSlot* d = next_h();
+    Slot* d = next_h();
     if (d == in.s) d = next_h();
     op_conv3(s_P, H, W, Cout, Cout, pfx + ".conv2", skip, d, IG_OUT_ROWMAJOR);
     MAct out; out.s = d; out.C = Cout; out.H = H; out.W = W;
@@ -208,7 +173,7 @@ struct K22MoVQ {
       push_igemm(p, [=](IgemmParams& q) { q.A0 = ptr(s_SC) + (size_t)b * T * T * es; q.Wp = ptr(s_VT) + (size_t)b * C * T * es; q.bias = bv;
                                           q.out = ptr(s_O) + (size_t)b * T * C * es; });
     }
-    MSlot* d = next_h();
+    Slot* d = next_h();
     if (d == in.s) d = next_h();
     op_gemm(s_O, B * T, C, C, pfx + ".proj_out", in.s, d);
     MAct out; out.s = d; out.C = C; out.H = in.H; out.W = in.W;
@@ -216,10 +181,12 @@ struct K22MoVQ {
   }
 
   int plan(int nB, int nh, int nw) {
+    // validate before touching the current plan: rejected arguments leave the engine usable as it was
+    if (nB < 1 || nh < 1 || nw < 1) return k22_set_error(K22_EINVAL, "movq: empty input");
+    begin_plan();
     B = nB; h0 = nh; w0 = nw; enc = false;
-    slots.clear(); ops.clear(); err.clear(); ws = nullptr; hrot = 0;
+    ops.clear(); hrot = 0;
     const int nres = cfg.n_levels;
-    if (B < 1 || h0 < 1 || w0 < 1) return k22_set_error(K22_EINVAL, "movq: empty input");
     s_z = new_slot((size_t)B * 4 * h0 * w0 * 4);
     s_zq = new_slot((size_t)B * h0 * w0 * 4 * 4);
     s_xin = new_slot((size_t)B * (h0 + 2) * (w0 + 2) * 64 * esz);
@@ -238,7 +205,7 @@ struct K22MoVQ {
     int block_in = cfg.ch * cfg.ch_mult[nres - 1];
     MAct hcur;
     {
-      MSlot* d = next_h();
+      Slot* d = next_h();
       op_conv3(s_xin, h0, w0, 64, block_in, "decoder.conv_in", nullptr, d, IG_OUT_ROWMAJOR);
       hcur.s = d; hcur.C = block_in; hcur.H = h0; hcur.W = w0;
     }
@@ -260,7 +227,7 @@ struct K22MoVQ {
         const int Bn = B, dt = dtype, C = hcur.C;
         need(s_P, (size_t)B * (2 * a.H + 2) * (2 * a.W + 2) * C * esz);
         ops.push_back([=](hipStream_t st) { return launch_upsample2_pad(ptr(a.s), ptr(s_P), Bn, a.H, a.W, C, dt, st); });
-        MSlot* d = next_h();
+        Slot* d = next_h();
         if (d == a.s) d = next_h();
         op_conv3(s_P, 2 * a.H, 2 * a.W, C, C, "decoder.up." + std::to_string(lvl) + ".upsample.conv", nullptr, d, IG_OUT_ROWMAJOR);
         hcur.s = d; hcur.H = 2 * a.H; hcur.W = 2 * a.W;
@@ -268,20 +235,17 @@ struct K22MoVQ {
     }
     op_sn(hcur, "decoder.norm_out", K22_ACT_SILU, 1, s_P);
     op_conv3(s_P, hcur.H, hcur.W, hcur.C, cfg.out_ch, "decoder.conv_out", nullptr, s_out, IG_OUT_NCHW_F32);
-    if (!err.empty()) return k22_set_error(K22_EINVAL, err.c_str());
-    size_t off = 0;
-    for (auto& s : slots) { s.off = off; off += (s.bytes + 255) / 256 * 256; }
-    ws_bytes = off + 256;
-    return K22_OK;
+    return finish_plan();
   }
 
   // Encoder.forward + quant_conv.  H, W: image size (multiples of 2^(levels-1); (H/8)*(W/8) a multiple of 64 for the
   // attention GEMMs).
   int plan_enc(int nB, int H, int W) {
     const int nres = cfg.n_levels;
+    if (nB < 1 || H < 1 || W < 1 || H % (1 << (nres - 1)) || W % (1 << (nres - 1))) return k22_set_error(K22_EINVAL, "movq encoder: H, W must be positive multiples of 2^(levels-1)");
+    begin_plan();
     B = nB; enc = true; encH = H; encW = W;
-    slots.clear(); ops.clear(); err.clear(); ws = nullptr; hrot = 0;
-    if (B < 1 || H < 1 || W < 1 || H % (1 << (nres - 1)) || W % (1 << (nres - 1))) return k22_set_error(K22_EINVAL, "movq encoder: H, W must be positive multiples of 2^(levels-1)");
+    ops.clear(); hrot = 0;
     h0 = H >> (nres - 1); w0 = W >> (nres - 1);
     s_img = new_slot((size_t)B * 3 * H * W * 4);
     s_xin = new_slot((size_t)B * (H + 2) * (W + 2) * 64 * esz);
@@ -295,7 +259,7 @@ struct K22MoVQ {
     ops.push_back([=](hipStream_t st) { return launch_movq_enc_prepare(ptr<float>(s_img), ptr(s_xin), Bn, H, W, 64, dt, st); });
     MAct hcur;
     {
-      MSlot* d = next_h();
+      Slot* d = next_h();
       op_conv3(s_xin, H, W, 64, cfg.ch, "encoder.conv_in", nullptr, d, IG_OUT_ROWMAJOR);
       hcur.s = d; hcur.C = cfg.ch; hcur.H = H; hcur.W = W;
     }
@@ -314,7 +278,7 @@ struct K22MoVQ {
         need(s_P, (size_t)B * (a.H + 2) * (a.W + 2) * C * esz);
         ops.push_back([=](hipStream_t st) { return launch_pad_copy(ptr(a.s), ptr(s_P), Bn, a.H, a.W, C, dt, st); });
         op_conv3(s_P, a.H, a.W, C, C, pfx + ".downsample.conv", nullptr, s_U, IG_OUT_ROWMAJOR);
-        MSlot* d = next_h();
+        Slot* d = next_h();
         if (d == a.s) d = next_h();
         need(d, (size_t)B * (a.H / 2) * (a.W / 2) * C * esz);
         ops.push_back([=](hipStream_t st) { return launch_subsample_odd(ptr(s_U), ptr(d), Bn, a.H, a.W, C, dt, st); });
@@ -331,11 +295,7 @@ struct K22MoVQ {
       const int hw = h0 * w0;
       ops.push_back([=](hipStream_t st) { return launch_movq_quant_conv(ptr<float>(s_out), wq, bq, ptr<float>(s_lat), Bn, hw, st); });
     }
-    if (!err.empty()) return k22_set_error(K22_EINVAL, err.c_str());
-    size_t off = 0;
-    for (auto& s : slots) { s.off = off; off += (s.bytes + 255) / 256 * 256; }
-    ws_bytes = off + 256;
-    return K22_OK;
+    return finish_plan();
   }
 };
 
@@ -346,8 +306,8 @@ int k22_movq_create(const K22MoVQConfig* cfg, const K22Weight* weights, int n_we
   if (!k22_dtype_ok(cfg->dtype)) return k22_set_error(K22_EINVAL, "movq_create: dtype");
   if (cfg->n_levels < 1 || cfg->n_levels > 8 || cfg->z_channels != 4 || cfg->ch % 128) return k22_set_error(K22_EINVAL, "movq_create: unsupported configuration (z_channels == 4, ch % 128 == 0)");
   K22MoVQ* m = new K22MoVQ();
-  m->cfg = *cfg; m->dtype = cfg->dtype; m->esz = cfg->dtype == K22_F32 ? 4 : 2;
-  for (int i = 0; i < n_weights; ++i) m->w[weights[i].name] = weights[i].ptr;
+  m->cfg = *cfg; m->set_dtype(cfg->dtype);
+  m->set_weights(weights, n_weights);
   *out = m;
   return K22_OK;
 }
@@ -361,25 +321,17 @@ int k22_movq_plan(K22MoVQ* m, int B, int h, int w, size_t* workspace_bytes) {
   return K22_OK;
 }
 int k22_movq_bind(K22MoVQ* m, void* workspace, size_t workspace_bytes) {
-  if (!m || !workspace) return k22_set_error(K22_EINVAL, "movq_bind: null argument");
-  if (m->ops.empty()) return k22_set_error(K22_EINVAL, "movq_bind: plan first");
-  if (workspace_bytes < m->ws_bytes) return k22_set_error(K22_ENOMEM, "movq_bind: workspace too small");
-  if ((uintptr_t)workspace % 256) return k22_set_error(K22_EINVAL, "movq_bind: workspace must be 256-byte aligned");
-  m->ws = reinterpret_cast<char*>(workspace);
-  return K22_OK;
+  if (!m) return k22_set_error(K22_EINVAL, "movq_bind: null argument");
+  return m->bind(workspace, workspace_bytes, "movq_bind");
 }
 int k22_movq_decode(K22MoVQ* m, const float* z, float* out, unsigned char* out_u8, void* stream) {
   if (!m || !m->ws || m->enc) return k22_set_error(K22_EINVAL, "movq_decode: plan the decoder and bind a workspace first");
   if (!z || (!out && !out_u8)) return k22_set_error(K22_EINVAL, "movq_decode: null argument");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipError_t e = hipMemcpyAsync(m->ptr(m->s_z), z, (size_t)m->B * 4 * m->h0 * m->w0 * 4, hipMemcpyDeviceToDevice, st);
-  if (e != hipSuccess) return k22_set_error_hip(e, __FILE__, __LINE__);
+  if (int rc = copy_d2d(m->ptr(m->s_z), z, (size_t)m->B * 4 * m->h0 * m->w0 * 4, st)) return rc;
   for (auto& op : m->ops) { int rc = op(st); if (rc) return rc; }
   const int H8 = m->h0 << (m->cfg.n_levels - 1), W8 = m->w0 << (m->cfg.n_levels - 1);
-  if (out) {
-    e = hipMemcpyAsync(out, m->ptr(m->s_out), (size_t)m->B * m->cfg.out_ch * H8 * W8 * 4, hipMemcpyDeviceToDevice, st);
-    if (e != hipSuccess) return k22_set_error_hip(e, __FILE__, __LINE__);
-  }
+  if (out) { if (int rc = copy_d2d(out, m->ptr(m->s_out), (size_t)m->B * m->cfg.out_ch * H8 * W8 * 4, st)) return rc; }
   if (out_u8) return launch_to_uint8_nhwc(m->ptr<float>(m->s_out), out_u8, m->B, m->cfg.out_ch, H8, W8, st);
   return K22_OK;
 }
@@ -394,13 +346,10 @@ int k22_movq_encode(K22MoVQ* m, const float* image, float* latent, void* stream)
   if (!m || !m->ws || !m->enc) return k22_set_error(K22_EINVAL, "movq_encode: plan the encoder and bind a workspace first");
   if (!image || !latent) return k22_set_error(K22_EINVAL, "movq_encode: null argument");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipError_t e = hipMemcpyAsync(m->ptr(m->s_img), image, (size_t)m->B * 3 * m->encH * m->encW * 4, hipMemcpyDeviceToDevice, st);
-  if (e != hipSuccess) return k22_set_error_hip(e, __FILE__, __LINE__);
+  if (int rc = copy_d2d(m->ptr(m->s_img), image, (size_t)m->B * 3 * m->encH * m->encW * 4, st)) return rc;
   for (auto& op : m->ops) { int rc = op(st); if (rc) return rc; }
-  e = hipMemcpyAsync(latent, m->ptr(m->s_lat), (size_t)m->B * 4 * m->h0 * m->w0 * 4, hipMemcpyDeviceToDevice, st);
-  if (e != hipSuccess) return k22_set_error_hip(e, __FILE__, __LINE__);
-  return K22_OK;
+  return copy_d2d(latent, m->ptr(m->s_lat), (size_t)m->B * 4 * m->h0 * m->w0 * 4, st);
 }
-int k22_movq_num_ops(const K22MoVQ* m) { return m ? (int)m->ops.size() : 0; }
+int k22_movq_num_ops(const K22MoVQ* m) { return m && m->planned ? (int)m->ops.size() : 0; }
 
 }  // extern "C"

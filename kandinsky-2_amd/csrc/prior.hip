@@ -14,6 +14,7 @@
 #include "elementwise.h"
 #include "../../include/k22.h"
 #include "tuning.h"
+#include "plan.h"
 #include "skinny.h"
 
 #include <algorithm>
@@ -71,72 +72,34 @@ __global__ void prior_sampler_step_kernel(const float* x, const float* model_out
 }
 
 namespace {
-struct PSlot { size_t bytes = 0, off = 0; };
 typedef std::function<int(hipStream_t)> POp;
 }  // namespace
 
-struct K22Prior {
+struct K22Prior : GraphPlan {   // tuned: every transformer Linear; graph: the ~250 launches of one forward
   K22PriorConfig cfg;
-  int dtype; size_t esz;
-  std::unordered_map<std::string, const void*> w;
   int B = 0;
-  std::deque<PSlot> slots;
   std::vector<POp> ops;
-  std::deque<Tuned> tuned;   // every transformer Linear: tile configuration picked by measurement at the first forward
-  bool tuned_done = false;
-  int autotune = 1;
-  hipGraphExec_t graph_exec = nullptr;   // the ~250 launches of one forward, replayed as one graph
-  hipStream_t cap_stream = nullptr;
-  ~K22Prior() {
-    if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
-    if (cap_stream) (void)hipStreamDestroy(cap_stream);
-  }
-  size_t ws_bytes = 0;
-  char* ws = nullptr;
-  std::string err;
-  PSlot *s_x, *s_t, *s_temb, *s_te1, *s_txtemb, *s_txtenc, *s_txtencT, *s_valid, *s_mask, *s_inp, *s_ln, *s_qkv, *s_att, *s_fc,
+  Slot *s_x, *s_t, *s_temb, *s_te1, *s_txtemb, *s_txtenc, *s_txtencT, *s_valid, *s_mask, *s_inp, *s_ln, *s_qkv, *s_att, *s_fc,
       *s_lnlast, *s_out, *s_splitk, *s_flush, *s_kall, *s_vtall;
   // skinny path (round 6; skinny.hip): 16-bit engines run the transformer through the fragment-major weight-streaming GEMM, the fused
   // split-K finish + LayerNorm and the small-T attention: 7 launches per layer instead of 12.  K22_PRIOR_SKINNY=0 keeps the old path.
   bool skinny = false;
   bool wfrag_done = false;
-  struct WFrag { const void* src; PSlot* dst; int Npad, K; };
+  struct WFrag { const void* src; Slot* dst; int Npad, K; };
   std::vector<WFrag> wfrags;   // fragment-major copies of the transformer weights, written into the workspace once per bind
 
-  PSlot* new_slot(size_t bytes = 0) { slots.emplace_back(); slots.back().bytes = bytes; return &slots.back(); }
-  static void need(PSlot* s, size_t bytes) { if (bytes > s->bytes) s->bytes = bytes; }
-  template <typename T = char> T* ptr(const PSlot* s) const { return reinterpret_cast<T*>(ws + s->off); }
-  const void* W_(const std::string& name) {
-    auto it = w.find(name);
-    if (it == w.end()) { if (err.empty()) err = "missing weight: " + name; return nullptr; }
-    return it->second;
+  int run_ops(hipStream_t st) const {
+    for (auto& op : ops) { int rc = op(st); if (rc) return rc; }
+    return K22_OK;
   }
-  const float* Wf(const std::string& name) { return reinterpret_cast<const float*>(W_(name)); }
 
   // out (+)= A[M][K] . W[N][K]^T + bias; A is T; out T, or fp32 with an fp32 residual (in-place residual stream)
-  void op_linear(PSlot* a, size_t a_off, int M, int N, int K, const std::string& pfx, int act, PSlot* dst, size_t dst_off, int ldo,
+  void op_linear(Slot* a, size_t a_off, int M, int N, int K, const std::string& pfx, int act, Slot* dst, size_t dst_off, int ldo,
                  bool f32_out_residual) {
-    tuned.emplace_back();
-    Tuned* t = &tuned.back();
-    IgemmParams& p = t->p;
-    p.stages = -1;
-    p.M = M; p.N = N; p.Npad = (N + 63) / 64 * 64; p.Kc = K; p.K0 = K; p.taps = 1; p.lda0 = K; p.ldo = ldo; p.ldr = ldo;
-    p.out_mode = f32_out_residual ? IG_OUT_ROWMAJOR_F32 : IG_OUT_ROWMAJOR; p.act = act; p.res_f32 = f32_out_residual ? 1 : 0;
-    p.Wp = W_(pfx + ".weight"); p.bias = Wf(pfx + ".bias");
-    tuned_make_candidates(*t, dtype);
-    tuned_default_cfg(*t, dtype);
-    need(s_splitk, tuned_max_splitk_bytes(*t, autotune != 0));
-    const int dt = dtype;
-    t->run = [=](hipStream_t st) {
-      IgemmParams q = t->p;
-      tuned_apply_cfg(q, t->cfg);
-      q.A0 = ptr(a) + a_off; q.out = ptr(dst) + dst_off; q.partial = ptr<float>(s_splitk);
-      q.residual = f32_out_residual ? (ptr(dst) + dst_off) : nullptr;
-      return launch_igemm(q, dt, st);
-    };
+    Tuned* t = tuned_linear(a, a_off, M, N, K, pfx, act, dst, dst_off, ldo, f32_out_residual ? 2 : 0, s_splitk);
     ops.push_back([=](hipStream_t st) { return t->run(st); });
   }
-  void op_ln(PSlot* x, size_t x_off, int64_t ldx, int rows, const std::string& pfx, PSlot* y, bool to_f32) {
+  void op_ln(Slot* x, size_t x_off, int64_t ldx, int rows, const std::string& pfx, Slot* y, bool to_f32) {
     const float* g = Wf(pfx + ".weight"); const float* b = Wf(pfx + ".bias");
     const int D = cfg.xf_width, dt = dtype;
     ops.push_back([=](hipStream_t st) {
@@ -151,15 +114,15 @@ struct K22Prior {
   }
 
   // fragment-major copy of a transformer weight [Npad][K] (slot in the workspace, repacked at the first forward after a bind)
-  PSlot* wfrag_of(const std::string& name, int N, int K) {
+  Slot* wfrag_of(const std::string& name, int N, int K) {
     const int Npad = (N + 63) / 64 * 64;
-    PSlot* s = new_slot((size_t)Npad * K * esz);
+    Slot* s = new_slot((size_t)Npad * K * esz);
     wfrags.push_back(WFrag{W_(name), s, Npad, K});
     return s;
   }
   // out = act(A . W^T + bias) through the skinny kernel; epi: SkinnyEpi; partial launches leave [splitk][M][N] in s_splitk
-  void op_skinny(PSlot* a, int M, int N, int K, const std::string& pfx, int act, int epi, int splitk, PSlot* dst, int ldo) {
-    PSlot* wf = wfrag_of(pfx + ".weight", N, K);
+  void op_skinny(Slot* a, int M, int N, int K, const std::string& pfx, int act, int epi, int splitk, Slot* dst, int ldo) {
+    Slot* wf = wfrag_of(pfx + ".weight", N, K);
     const float* bias = Wf(pfx + ".bias");
     if (epi == SK_EPI_PARTIAL) need(s_splitk, (size_t)splitk * M * N * 4);
     const int dt = dtype;
@@ -185,20 +148,18 @@ struct K22Prior {
   }
 
   int plan(int nB) {
-    B = nB;
-    slots.clear(); ops.clear(); err.clear(); ws = nullptr; tuned.clear(); tuned_done = false; wfrags.clear(); wfrag_done = false;
-    if (graph_exec) { (void)hipGraphExecDestroy(graph_exec); graph_exec = nullptr; }
-    const int D = cfg.xf_width, nt = cfg.text_ctx, nc = nt + 4, cd = cfg.clip_dim, cw = cfg.clip_xf_width, M = B * nc;
-    if (B < 1 || B > 8) return k22_set_error(K22_EINVAL, "prior: batch (2*bs) must be in 1..8 per engine call");
+    // validate before touching the current plan: rejected arguments leave the engine usable as it was
+    const int D = cfg.xf_width, nt = cfg.text_ctx, nc = nt + 4, cd = cfg.clip_dim, cw = cfg.clip_xf_width, M = nB * nc;
+    if (nB < 1 || nB > 8) return k22_set_error(K22_EINVAL, "prior: batch (2*bs) must be in 1..8 per engine call");
     if (D % 64 || D / cfg.xf_heads != 64) return k22_set_error(K22_EINVAL, "prior: 64 channels per head");
+    begin_plan();
+    B = nB;
+    ops.clear(); wfrags.clear(); wfrag_done = false;
     s_x = new_slot((size_t)B * cd * 4); s_t = new_slot((size_t)B * 4 + 64);
     s_temb = new_slot((size_t)B * D * 4); s_te1 = new_slot((size_t)B * D * 4);
     s_txtemb = new_slot((size_t)B * cd * 4); s_txtenc = new_slot((size_t)B * nt * cw * 4); s_txtencT = new_slot((size_t)B * nt * cw * esz);
     s_valid = new_slot((size_t)B * nt * 4); s_mask = new_slot((size_t)B * nc * nc * 4);
-    {
-      const char* e = getenv("K22_PRIOR_SKINNY");
-      skinny = (!e || atoi(e) != 0) && esz == 2 && D <= 2048 && nc <= 128;
-    }
+    skinny = env_flag("K22_PRIOR_SKINNY", 1) && esz == 2 && D <= 2048 && nc <= 128;
     const size_t Mp = (size_t)(M + 31) / 32 * 32;   // the fragment-major tensors hold whole 32-row atoms
     s_inp = new_slot((size_t)M * D * 4); s_ln = new_slot(Mp * D * esz); s_qkv = new_slot((size_t)M * 3 * D * esz);
     s_att = new_slot(Mp * D * esz); s_fc = new_slot(Mp * 4 * D * esz);
@@ -330,11 +291,7 @@ struct K22Prior {
         return launch_linear_smallm(lp, K22_F32, st);
       });
     }
-    if (!err.empty()) return k22_set_error(K22_EINVAL, err.c_str());
-    size_t off = 0;
-    for (auto& s : slots) { s.off = off; off += (s.bytes + 255) / 256 * 256; }
-    ws_bytes = off + 256;
-    return K22_OK;
+    return finish_plan();
   }
 };
 
@@ -344,12 +301,8 @@ int k22_prior_create(const K22PriorConfig* cfg, const K22Weight* weights, int n_
   if (!cfg || !out) return k22_set_error(K22_EINVAL, "prior_create: null argument");
   if (!k22_dtype_ok(cfg->dtype)) return k22_set_error(K22_EINVAL, "prior_create: dtype");
   K22Prior* m = new K22Prior();
-  m->cfg = *cfg; m->dtype = cfg->dtype; m->esz = cfg->dtype == K22_F32 ? 4 : 2;
-  for (int i = 0; i < n_weights; ++i) m->w[weights[i].name] = weights[i].ptr;
-  {
-    const char* e = getenv("K22_AUTOTUNE");
-    m->autotune = e ? (atoi(e) != 0) : 1;
-  }
+  m->cfg = *cfg; m->set_dtype(cfg->dtype);
+  m->set_weights(weights, n_weights);
   *out = m;
   return K22_OK;
 }
@@ -368,13 +321,9 @@ int k22_prior_plan(K22Prior* m, int B, size_t* workspace_bytes) {
   return K22_OK;
 }
 int k22_prior_bind(K22Prior* m, void* workspace, size_t workspace_bytes) {
-  if (!m || !workspace) return k22_set_error(K22_EINVAL, "prior_bind: null argument");
-  if (m->ops.empty()) return k22_set_error(K22_EINVAL, "prior_bind: plan first");
-  if (workspace_bytes < m->ws_bytes) return k22_set_error(K22_ENOMEM, "prior_bind: workspace too small");
-  if ((uintptr_t)workspace % 256) return k22_set_error(K22_EINVAL, "prior_bind: workspace must be 256-byte aligned");
-  m->ws = reinterpret_cast<char*>(workspace);
+  if (!m) return k22_set_error(K22_EINVAL, "prior_bind: null argument");
+  if (int rc = m->bind(workspace, workspace_bytes, "prior_bind")) return rc;
   m->wfrag_done = false;
-  if (m->graph_exec) { (void)hipGraphExecDestroy(m->graph_exec); m->graph_exec = nullptr; }
   return K22_OK;
 }
 int k22_prior_forward(K22Prior* m, const float* x, const float* timesteps, const float* text_emb, const float* text_enc,
@@ -383,15 +332,11 @@ int k22_prior_forward(K22Prior* m, const float* x, const float* timesteps, const
   if (!x || !timesteps || !text_emb || !text_enc || !key_valid || !out) return k22_set_error(K22_EINVAL, "prior_forward: null argument");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const K22PriorConfig& c = m->cfg;
-  hipError_t e;
-#define K22_CPY(dst, src, bytes)                                                   \
-  e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st);                \
-  if (e != hipSuccess) return k22_set_error_hip(e, __FILE__, __LINE__);
-  K22_CPY(m->ptr(m->s_x), x, (size_t)m->B * c.clip_dim * 4);
-  K22_CPY(m->ptr(m->s_t), timesteps, (size_t)m->B * 4);
-  K22_CPY(m->ptr(m->s_txtemb), text_emb, (size_t)m->B * c.clip_dim * 4);
-  K22_CPY(m->ptr(m->s_txtenc), text_enc, (size_t)m->B * c.text_ctx * c.clip_xf_width * 4);
-  K22_CPY(m->ptr(m->s_valid), key_valid, (size_t)m->B * c.text_ctx * 4);
+  if (int rc = copy_d2d(m->ptr(m->s_x), x, (size_t)m->B * c.clip_dim * 4, st)) return rc;
+  if (int rc = copy_d2d(m->ptr(m->s_t), timesteps, (size_t)m->B * 4, st)) return rc;
+  if (int rc = copy_d2d(m->ptr(m->s_txtemb), text_emb, (size_t)m->B * c.clip_dim * 4, st)) return rc;
+  if (int rc = copy_d2d(m->ptr(m->s_txtenc), text_enc, (size_t)m->B * c.text_ctx * c.clip_xf_width * 4, st)) return rc;
+  if (int rc = copy_d2d(m->ptr(m->s_valid), key_valid, (size_t)m->B * c.text_ctx * 4, st)) return rc;
   if (m->skinny && !m->wfrag_done) {
     for (auto& wf : m->wfrags) {
       int rc = launch_stream_repack(wf.src, m->ptr(wf.dst), wf.Npad, 1, wf.K, m->dtype, st);
@@ -399,37 +344,9 @@ int k22_prior_forward(K22Prior* m, const float* x, const float* timesteps, const
     }
     m->wfrag_done = true;
   }
-  if (m->autotune && !m->tuned_done) {
-    // the in-place residual GEMMs make the tuning runs accumulate garbage into the sequence buffer: harmless, the
-    // real forward below rebuilds it from the inputs
-    int rc = tune_igemm_ops(m->tuned, m->dtype, m->s_flush->bytes ? m->ptr(m->s_flush) : nullptr, m->s_flush->bytes, st);
-    if (rc) return rc;
-    m->tuned_done = true;
-  }
-  if (!m->graph_exec) {
-    // first forward: run eagerly once (function attributes, code load), then capture the launch list
-    for (auto& op : m->ops) { int rc = op(st); if (rc) return rc; }
-    if (!m->cap_stream) {
-      e = hipStreamCreateWithFlags(&m->cap_stream, hipStreamNonBlocking);
-      if (e != hipSuccess) return k22_set_error_hip(e, __FILE__, __LINE__);
-    }
-    hipGraph_t g = nullptr;
-    e = hipStreamBeginCapture(m->cap_stream, hipStreamCaptureModeThreadLocal);
-    if (e != hipSuccess) return k22_set_error_hip(e, __FILE__, __LINE__);
-    int rc = K22_OK;
-    for (auto& op : m->ops) { rc = op(m->cap_stream); if (rc) break; }
-    e = hipStreamEndCapture(m->cap_stream, &g);
-    if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
-    if (e != hipSuccess) return k22_set_error_hip(e, __FILE__, __LINE__);
-    e = hipGraphInstantiate(&m->graph_exec, g, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(g);
-    if (e != hipSuccess) { m->graph_exec = nullptr; return k22_set_error_hip(e, __FILE__, __LINE__); }
-  }
-  e = hipGraphLaunch(m->graph_exec, st);
-  if (e != hipSuccess) return k22_set_error_hip(e, __FILE__, __LINE__);
-  K22_CPY(out, m->ptr(m->s_out), (size_t)m->B * c.clip_dim * 4);
-#undef K22_CPY
-  return K22_OK;
+  if (int rc = m->tune_once(m->s_flush, st)) return rc;
+  if (int rc = m->replay(m->graph, st, [m](hipStream_t s) { return m->run_ops(s); })) return rc;
+  return copy_d2d(out, m->ptr(m->s_out), (size_t)m->B * c.clip_dim * 4, st);
 }
 
 int k22_prior_sampler_step(const float* x, const float* model_out, const float* noise, const float* scales, const float* table_row,

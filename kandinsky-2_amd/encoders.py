@@ -312,14 +312,7 @@ class _Engine:
         c.dtype = _lib.dtype_code(backend_dtype)
         for k, v in ecfg.items():
             setattr(c, k, v)
-        base = arena.data_ptr()
-        arr = (_lib.K22Weight * len(table))()
-        self._names = []
-        for i, (name, (off, _n)) in enumerate(table.items()):
-            nb = name.encode()
-            self._names.append(nb)
-            arr[i].name = nb
-            arr[i].ptr = base + off
+        arr, self._names = _lib.weight_array(arena, table)
         h = C.c_void_p()
         _lib.check(_lib.lib().k22_encoder_create(C.byref(c), arr, len(table), C.byref(h)))
         self.handle, self._plan_B, self._ws = h, None, None
@@ -338,11 +331,8 @@ class _Engine:
     def _plan(self, B):
         if self._plan_B != B:
             self._plan_B = None
-            nbytes = C.c_size_t()
-            _lib.check(_lib.lib().k22_encoder_plan(self.handle, B, C.byref(nbytes)))
-            self._ws = torch.empty(nbytes.value + 256, dtype=torch.uint8, device=self.arena.device)
-            al = (self._ws.data_ptr() + 255) // 256 * 256
-            _lib.check(_lib.lib().k22_encoder_bind(self.handle, al, nbytes.value))
+            L = _lib.lib()
+            self._ws = _lib.plan_and_bind(L.k22_encoder_plan, L.k22_encoder_bind, self.handle, self.arena.device, B)
             self._plan_B = B
 
     def run(self, tokens=None, key_valid=None, image=None, want_seq=True):

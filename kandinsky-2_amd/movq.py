@@ -218,14 +218,7 @@ class MoVQDecoderHIP(nn.Module):
         cfg.attn_levels = sum(1 << i for i in a.attn_levels)
         cfg.z_channels = a.z_channels
         cfg.out_ch = a.out_ch
-        base = self._arena.data_ptr()
-        arr = (_lib.K22Weight * len(table))()
-        self._names = []
-        for i, (name, (off, _n)) in enumerate(table.items()):
-            nb = name.encode()
-            self._names.append(nb)
-            arr[i].name = nb
-            arr[i].ptr = base + off
+        arr, self._names = _lib.weight_array(self._arena, table)
         h = C.c_void_p()
         _lib.check(L.k22_movq_create(C.byref(cfg), arr, len(table), C.byref(h)))
         self._handle = h
@@ -236,11 +229,8 @@ class MoVQDecoderHIP(nn.Module):
             self.prepare()
         if self._plan_key != (B, h, w):
             self._plan_key = None   # a failed plan / bind leaves the native engine without a plan: never skip re-planning after it
-            nbytes = C.c_size_t()
-            _lib.check(_lib.lib().k22_movq_plan(self._handle, B, h, w, C.byref(nbytes)))
-            self._ws = torch.empty(nbytes.value + 256, dtype=torch.uint8, device=self._arena.device)
-            al = (self._ws.data_ptr() + 255) // 256 * 256
-            _lib.check(_lib.lib().k22_movq_bind(self._handle, al, nbytes.value))
+            L = _lib.lib()
+            self._ws = _lib.plan_and_bind(L.k22_movq_plan, L.k22_movq_bind, self._handle, self._arena.device, B, h, w)
             self._plan_key = (B, h, w)
 
     @torch.no_grad()
@@ -428,14 +418,7 @@ class MoVQEncoderHIP(nn.Module):
         cfg.attn_levels = sum(1 << i for i in a.attn_levels)
         cfg.z_channels = a.z_channels
         cfg.out_ch = a.out_ch
-        base = self._arena.data_ptr()
-        arr = (_lib.K22Weight * len(table))()
-        self._names = []
-        for i, (name, (off, _n)) in enumerate(table.items()):
-            nb = name.encode()
-            self._names.append(nb)
-            arr[i].name = nb
-            arr[i].ptr = base + off
+        arr, self._names = _lib.weight_array(self._arena, table)
         h = C.c_void_p()
         _lib.check(L.k22_movq_create(C.byref(cfg), arr, len(table), C.byref(h)))
         self._handle = h
@@ -452,11 +435,8 @@ class MoVQEncoderHIP(nn.Module):
             self.prepare()
         if self._plan_key != (B, H, W):
             self._plan_key = None   # a failed plan / bind leaves the native engine without a plan: never skip re-planning after it
-            nbytes = C.c_size_t()
-            _lib.check(_lib.lib().k22_movq_plan_encoder(self._handle, B, H, W, C.byref(nbytes)))
-            self._ws = torch.empty(nbytes.value + 256, dtype=torch.uint8, device=self._arena.device)
-            al = (self._ws.data_ptr() + 255) // 256 * 256
-            _lib.check(_lib.lib().k22_movq_bind(self._handle, al, nbytes.value))
+            L = _lib.lib()
+            self._ws = _lib.plan_and_bind(L.k22_movq_plan_encoder, L.k22_movq_bind, self._handle, self._arena.device, B, H, W)
             self._plan_key = (B, H, W)
         x = image.detach().float().contiguous()
         down = 1 << (len(self.arch.ch_mult) - 1)

@@ -218,14 +218,7 @@ class PriorDiffusionModelHIP(nn.Module):
         for k in ("text_ctx", "xf_width", "xf_layers", "xf_heads", "clip_dim", "clip_xf_width"):
             setattr(cfg, k, int(self.hp[k]))
         cfg.xf_final_ln = 1 if self.hp["xf_final_ln"] else 0
-        base = self._arena.data_ptr()
-        arr = (_lib.K22Weight * len(table))()
-        self._names = []
-        for i, (name, (off, _n)) in enumerate(table.items()):
-            nb = name.encode()
-            self._names.append(nb)
-            arr[i].name = nb
-            arr[i].ptr = base + off
+        arr, self._names = _lib.weight_array(self._arena, table)
         h = C.c_void_p()
         _lib.check(_lib.lib().k22_prior_create(C.byref(cfg), arr, len(table), C.byref(h)))
         self._handle = h
@@ -236,11 +229,8 @@ class PriorDiffusionModelHIP(nn.Module):
             self.prepare()
         if self._plan_key != B:
             self._plan_key = None   # a failed plan / bind leaves the native engine without a plan: never skip re-planning after it
-            nbytes = C.c_size_t()
-            _lib.check(_lib.lib().k22_prior_plan(self._handle, B, C.byref(nbytes)))
-            self._ws = torch.empty(nbytes.value + 256, dtype=torch.uint8, device=self._arena.device)
-            al = (self._ws.data_ptr() + 255) // 256 * 256
-            _lib.check(_lib.lib().k22_prior_bind(self._handle, al, nbytes.value))
+            L = _lib.lib()
+            self._ws = _lib.plan_and_bind(L.k22_prior_plan, L.k22_prior_bind, self._handle, self._arena.device, B)
             self._plan_key = B
 
     def tuning_report(self) -> str:

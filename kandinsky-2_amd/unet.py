@@ -190,14 +190,7 @@ class Text2ImUNetHIP(nn.Module):
                 raise ValueError("arena does not match this architecture/dtype")
         self._arena = arena
         cfg = self._engine_config()
-        base = arena.data_ptr()
-        arr = (_lib.K22Weight * len(table))()
-        names = []
-        for i, (name, (off, _n)) in enumerate(table.items()):
-            nb = name.encode()
-            names.append(nb)
-            arr[i].name = nb
-            arr[i].ptr = base + off
+        arr, _names = _lib.weight_array(arena, table)
         h = C.c_void_p()
         _lib.check(L.k22_unet_create(C.byref(cfg), arr, len(table), C.byref(h)))
         self._handle = h
@@ -221,17 +214,10 @@ class Text2ImUNetHIP(nn.Module):
             self._plan_key = None   # a failed plan / bind leaves the native engine without a plan: never skip re-planning after it
             self._cond_key = None
             L = _lib.lib()
-            nbytes = C.c_size_t()
             pb = B // 2 if self._chained(B) else B
-            _lib.check(L.k22_unet_plan(self._handle, pb, H, W, C.byref(nbytes)))
-            self._ws = torch.empty(nbytes.value + 256, dtype=torch.uint8, device=self._arena.device)
-            p = self._ws.data_ptr()
-            al = (p + 255) // 256 * 256
-            _lib.check(L.k22_unet_bind(self._handle, al, nbytes.value))
+            self._ws = _lib.plan_and_bind(L.k22_unet_plan, L.k22_unet_bind, self._handle, self._arena.device, pb, H, W)
             if self._chained(B):
-                _lib.check(L.k22_unet_plan(self._handle2, pb, H, W, C.byref(nbytes)))
-                self._ws2 = torch.empty(nbytes.value + 256, dtype=torch.uint8, device=self._arena.device)
-                _lib.check(L.k22_unet_bind(self._handle2, (self._ws2.data_ptr() + 255) // 256 * 256, nbytes.value))
+                self._ws2 = _lib.plan_and_bind(L.k22_unet_plan, L.k22_unet_bind, self._handle2, self._arena.device, pb, H, W)
                 if self._side is None:
                     self._side = torch.cuda.Stream(device=self._arena.device)
             self._plan_key = key

@@ -829,3 +829,59 @@ def test_isa_mix_tool_counts_a_synthetic_loop():
     assert c["valu_mov"] == 1 and cyc["valu"] == 4 and c["s_barrier"] == 1 and c["s_waitcnt"] == 1
     assert im.lds_cycles("ds_write_b128") == 13 and im.lds_cycles("ds_read_b64") == 2 and im.lds_cycles("ds_read_b64_tr_b16") == 2
     assert im.classify("global_load_lds_dwordx4") == "lds_dma" and im.classify("global_load_dwordx4") == "vmem_load"
+
+
+def test_a_plan_that_failed_is_no_plan_for_every_native_engine():
+    """The shared life cycle of csrc/plan.h, host logic only (no weights, nothing bound, nothing launched): a plan that misses a weight reports
+    it, and after it `bind` answers "plan first" and the run entry finds no workspace - for the UNet, the MoVQ decoder and encoder, the prior
+    and a conditioning tower alike.  (The launch list such a plan built holds null weight pointers: it must stay unreachable.)  A UNet plan
+    with a rejected shape (B = 9) is refused as well."""
+    import ctypes as C
+    L = _lib.lib()
+
+    def ints(n, vals):
+        return (C.c_int * n)(*vals)
+
+    def err():
+        return (L.k22_last_error() or b"").decode()
+
+    def failed_plan_then_bind_then_run(name, handle, plan, bind, run, destroy):
+        try:
+            n = C.c_size_t()
+            assert plan(handle, C.byref(n)) != 0 and "missing weight" in err(), (name, err())
+            rc = bind(handle, C.c_void_p(1 << 20), C.c_size_t(1 << 60))
+            assert rc != 0 and "plan first" in err(), (name, rc, err())
+            assert run(handle) != 0, name      # reached only with bind refused: no workspace, nothing is launched
+        finally:
+            destroy(handle)
+
+    uc = _lib.K22UNetConfig(dtype=_lib.K22_BF16, in_channels=4, model_channels=128, out_channels=8, num_res_blocks=1, n_levels=2,
+                            channel_mult=ints(8, (1, 2)), n_attention_ds=1, attention_ds=ints(8, (2,)), num_head_channels=64, ctx_dim=128,
+                            ctx_len=12, n_image_embs=10, text_dim1=64, text_dim2=64, image_dim=64, head_type=0, hint_channels=0)
+    h = C.c_void_p()
+    assert L.k22_unet_create(C.byref(uc), None, 0, C.byref(h)) == 0
+    n = C.c_size_t()
+    assert L.k22_unet_plan(h, 9, 8, 8, C.byref(n)) != 0 and "batch" in err()
+    failed_plan_then_bind_then_run("unet", h, lambda m, n: L.k22_unet_plan(m, 2, 8, 8, n), L.k22_unet_bind,
+                                   lambda m: L.k22_unet_forward(m, None, None, None, None, None, 0, None), L.k22_unet_destroy)
+
+    mc = _lib.K22MoVQConfig(dtype=_lib.K22_BF16, ch=128, n_levels=2, ch_mult=ints(8, (1, 2)), num_res_blocks=1, attn_levels=0, z_channels=4,
+                            out_ch=3)
+    for which, plan, run in (("movq decoder", lambda m, n: L.k22_movq_plan(m, 1, 8, 8, n), lambda m: L.k22_movq_decode(m, None, None, None, None)),
+                             ("movq encoder", lambda m, n: L.k22_movq_plan_encoder(m, 1, 64, 64, n), lambda m: L.k22_movq_encode(m, None, None, None))):
+        h = C.c_void_p()
+        assert L.k22_movq_create(C.byref(mc), None, 0, C.byref(h)) == 0
+        failed_plan_then_bind_then_run(which, h, plan, L.k22_movq_bind, run, L.k22_movq_destroy)
+
+    pc = _lib.K22PriorConfig(dtype=_lib.K22_BF16, text_ctx=77, xf_width=128, xf_layers=2, xf_heads=2, xf_final_ln=1, clip_dim=64, clip_xf_width=64)
+    h = C.c_void_p()
+    assert L.k22_prior_create(C.byref(pc), None, 0, C.byref(h)) == 0
+    failed_plan_then_bind_then_run("prior", h, lambda m, n: L.k22_prior_plan(m, 2, n), L.k22_prior_bind,
+                                   lambda m: L.k22_prior_forward(m, None, None, None, None, None, None, None), L.k22_prior_destroy)
+
+    ec = _lib.K22EncoderConfig(dtype=_lib.K22_BF16, kind=2, width=128, layers=2, heads=2, n_ctx=77, vocab=1000, out_dim=64, image_size=0, patch=0,
+                               max_pos=514, pad_id=1, ln_eps=1e-5)
+    h = C.c_void_p()
+    assert L.k22_encoder_create(C.byref(ec), None, 0, C.byref(h)) == 0
+    failed_plan_then_bind_then_run("encoder", h, lambda m, n: L.k22_encoder_plan(m, 2, n), L.k22_encoder_bind,
+                                   lambda m: L.k22_encoder_forward(m, None, None, None, None, None, None), L.k22_encoder_destroy)
