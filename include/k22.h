@@ -74,8 +74,9 @@ const char* k22_last_error(void);
  * "conv_algo" / "gemm_algo" = 20: the weight-streaming small-M kernel (stream_gemm.hip; bm = 160 / 288 picks 5 / 9 m-blocks
  * per workgroup, needs the fp32 partial buffer also for splitk == 1). */
 int k22_set_option(const char* name, int value);
-/* Launch counters for tests ("stream_launches": launches of the weight-streaming kernel since the library was loaded);
- * -1 for an unknown name. */
+/* Host counters for tests, since the library was loaded: "stream_launches" = launches of the weight-streaming kernel;
+ * "loop_captures" = whole-loop graphs captured by any loop entry (k22_unet_sample_loop, k22_unet_ddim_loop); "loop_launches" = whole-loop
+ * replays or eager loop runs.  -1 for an unknown name. */
 long k22_debug_counter(const char* name);
 /* Fragment-major copy of a 16-bit weight matrix [Npad][taps * Kc] for the weight-streaming kernel (1 KB contiguous per MFMA B
  * fragment; layout in stream_gemm.hip).  k22_stream_frag_bytes = size of the copy (0 for fp32: the kernel is 16-bit only).
@@ -181,6 +182,29 @@ int k22_unet_sample_loop(K22UNet* u, float* x, float* x_tmp, const float* timest
                          const float* mask, const float* inpaint_image, const float* inpaint_mask, const float* table,
                          const int* table_rows, int n_steps, float guidance, float clamp_lo, float clamp_hi, int pct_index,
                          double pct_gamma, void* scratch, int use_graph, void* stream);
+/* The whole classifier-free-guided DDIM or PLMS loop - generate_img's default sampler and its documented alternative - as ONE hipGraph
+ * replay (kandinsky2/kandinsky2_1_model.py:222-233, the non-p_sampler model_fn, driving kandinsky2/model/samplers.py:206-331 for
+ * kind = K22_LOOP_DDIM and samplers.py:475-637 for kind = K22_LOOP_PLMS): per step  UNet([x_half | x_half], t) -> k22_ddim_step or
+ * k22_plms_step on all B rows (use_cfg = 1)  with no host work between steps.  It shares k22_unet_sample_loop's machinery: the time /
+ * FiLM rows of every model call are computed before the first step, the engine keeps ONE captured loop whose key holds the kind and every
+ * pointer / scalar below (a loop of another kind, or other buffers, re-captures), and the result equals the stepwise calls bit for bit -
+ * also with use_graph = 0 (the same launches, eagerly) and under K22_HOIST_TIME=0.
+ * Device buffers, filled by the caller before the call:
+ *   x [B][4][HW]: in x_T, out the final latent;  x_tmp: same-size scratch;  x0_out [B][4][HW] or NULL: the predicted x0 of the last step;
+ *   timesteps [n_calls][B]: the raw DDIM timestep (1 .. 981) of every MODEL CALL in execution order.  n_calls = n_steps for DDIM and
+ *     n_steps + 1 for PLMS, whose first step calls the model twice - the second time at the next step's timestep (at its own when
+ *     n_steps == 1): rows = t_0, t_1 (or t_0), t_1, t_2, ...;
+ *   table [n_steps][4]: the k22_ddim_step rows (a_t, a_prev, sigma_t, sqrt(1 - a_t)) in execution order;
+ *   noise_seq [n_steps][B][4][HW], or NULL for eta = 0; DDIM only (PLMS with noise is K22_EINVAL: the reference asserts eta = 0);
+ *   inpaint_image / inpaint_mask: 9-channel UNet inputs (required for it), else NULL;
+ *   eps_hist: PLMS only, 4 x [B][4][HW] floats - the ring of guided eps tensors.  Its rotation is resolved on the host when the loop is
+ *     captured: orders 0 and 4 are the pseudo improved-Euler start, orders 1, 2, 3 follow (see k22_plms_step).
+ * K22_EINVAL (with a k22_last_error text) for a null argument, an odd B, n_steps < 1, a missing condition / hint or missing inpaint
+ * operands; a refused call leaves the handle and its captured loop as they were. */
+enum { K22_LOOP_DDIM = 0, K22_LOOP_PLMS = 1 };
+int k22_unet_ddim_loop(K22UNet* u, int kind, float* x, float* x_tmp, float* x0_out, const float* timesteps, const float* table,
+                       const float* noise_seq, const float* inpaint_image, const float* inpaint_mask, float* eps_hist, int n_steps,
+                       float guidance, int use_graph, void* stream);
 int k22_unet_num_ops(const K22UNet* u);
 /* Tile configurations of the convolutions / GEMMs are chosen by measurement during the first k22_unet_forward
  * after k22_unet_plan (default on; env K22_AUTOTUNE=0 or k22_unet_set_autotune(u, 0) before planning = heuristics).

@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("K22_LIB_PATH") or os.path.join(_HERE, "libk22hip.so")
 TILE_TABLE_PATH = os.path.join(_HERE, "tiles_gfx950.txt")
 
 K22_BF16, K22_F32, K22_F16, K22_F16X3, K22_F16X2 = 0, 1, 2, 3, 4
+K22_LOOP_DDIM, K22_LOOP_PLMS = 0, 1   # include/k22.h: kind of k22_unet_ddim_loop
 # backend_dtype of the split-precision UNet engine (no torch dtype names it): fp32 tensors, MFMA operands as fp16 (hi, lo) pairs, three
 # fp16 MFMAs per product - the arithmetic that meets the 1e-3 final-latent gate at 16-bit MFMA rate (include/k22.h: K22_F16X3)
 F16X3 = "f16x3"
@@ -104,6 +105,7 @@ SIGNATURES = {
     "k22_unet_set_hint": (_I, [_P, _P, _P]),
     "k22_unet_forward": (_I, [_P, _P, _P, _P, _P, _P, _I, _P]),
     "k22_unet_sample_loop": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(_I), _I, _F, _F, _F, _I, _D, _P, _I, _P]),
+    "k22_unet_ddim_loop": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _F, _I, _P]),
     "k22_unet_num_ops": (_I, [_P]),
     "k22_unet_set_autotune": (_I, [_P, _I]),
     "k22_unet_tuning_report": (_I, [_P, C.c_char_p, _Z]),

@@ -84,6 +84,8 @@ int k22_stream_repack(const void* W, void* out, int Npad, int taps, int Kc, int 
 
 long k22_debug_counter(const char* name) {
   if (name && !strcmp(name, "stream_launches")) return stream_launch_count();
+  if (name && !strcmp(name, "loop_captures")) return loop_capture_count();
+  if (name && !strcmp(name, "loop_launches")) return loop_launch_count();
   return -1;
 }
 

@@ -15,6 +15,7 @@
 #include "tuning.h"
 #include "plan.h"
 
+#include <atomic>
 #include <deque>
 #include <functional>
 #include <map>
@@ -28,6 +29,18 @@
 #include <string.h>
 
 int launch_step_advance(int* step, int delta, hipStream_t s);
+
+// k22_debug_counter("loop_captures" / "loop_launches"): whole-loop graphs captured, and whole-loop replays or eager loop runs, by any loop
+// entry of this process (host counters: a test reads from them that the one-graph path ran and that a second generation replayed)
+static std::atomic<long> g_loop_captures{0}, g_loop_launches{0};
+long loop_capture_count() { return g_loop_captures.load(); }
+long loop_launch_count() { return g_loop_launches.load(); }
+static void loop_count_capture() { g_loop_captures.fetch_add(1); }
+static void loop_count_launch() { g_loop_launches.fetch_add(1); }
+// first word of a captured loop's key: which entry's nodes the graph holds
+enum : unsigned long long { K22_LOOP_KIND_P = 0, K22_LOOP_KIND_DDIM = 1, K22_LOOP_KIND_PLMS = 2 };
+static unsigned long long loop_key_ptr(const void* p) { return (unsigned long long)(uintptr_t)p; }
+static unsigned long long loop_key_bits(double v) { unsigned long long b; memcpy(&b, &v, 8); return b; }
 
 namespace {
 
@@ -153,6 +166,98 @@ struct K22UNet : GraphPlan {   // dtype: arithmetic type of the MFMA kernels (K2
 
   ~K22UNet() {
     if (film_all) (void)hipFree(film_all);
+  }
+
+  // ---- shared body of the whole-loop entries (k22_unet_sample_loop, k22_unet_ddim_loop) -------------------------------------------
+  // A loop is n_calls model calls, each  UNet([x_half | x_half], timesteps[call])  followed by the entry's own sampler kernels.
+  struct LoopRows {   // hoisted time / FiLM rows of all model calls (null members: per-call launches)
+    bool hoist = false;
+    float *film = nullptr, *temb = nullptr, *e1 = nullptr, *emb = nullptr;
+  };
+  // first-run preparation + the [n_calls * B] row buffer; called after validation (it may drop the captured loop)
+  int loop_begin(int n_calls, hipStream_t st, LoopRows* lr) {
+    if (int rc = prepare_run(st)) return rc;
+    // the time / FiLM rows of all calls up front (film_all): 8 / B calls per batched launch; B > 8 keeps the per-call launches
+    lr->hoist = B <= 8 && hoist_time;
+    if (!lr->hoist) return K22_OK;
+    const int64_t rows_all = (int64_t)n_calls * B;
+    const size_t need = (size_t)rows_all * (size_t)(film_total + tw.mc + 2 * tw.ted) * sizeof(float);
+    if (need > film_all_bytes) {
+      loop.drop();   // captured loops hold the old buffer's addresses (a captured forward does not: it reads s_film)
+      if (film_all) { (void)hipStreamSynchronize(st); (void)hipFree(film_all); film_all = nullptr; film_all_bytes = 0; }
+      const hipError_t e = hipMalloc(reinterpret_cast<void**>(&film_all), need);
+      if (e != hipSuccess) { film_all = nullptr; return k22_set_error_hip(e, __FILE__, __LINE__); }
+      film_all_bytes = need;
+    }
+    lr->film = film_all;
+    lr->temb = lr->film + rows_all * film_total;
+    lr->e1 = lr->temb + rows_all * tw.mc;
+    lr->emb = lr->e1 + rows_all * tw.ted;
+    return K22_OK;
+  }
+  // what a loop runs before its first step: the batched time rows, the 9-channel UNet's constant inputs
+  int loop_prologue(const LoopRows& lr, const float* timesteps, int n_calls, const float* inpaint_image, const float* inpaint_mask, hipStream_t s) {
+    if (lr.hoist) {
+      const int spl = 8 / B;   // calls per batched launch
+      for (int k0 = 0; k0 < n_calls; k0 += spl) {
+        const int rows = (n_calls - k0 < spl ? n_calls - k0 : spl) * B;
+        const int64_t r0 = (int64_t)k0 * B;
+        const int rc = time_rows(timesteps + r0, lr.temb + r0 * tw.mc, lr.e1 + r0 * tw.ted, lr.emb + r0 * tw.ted, lr.film + r0 * film_total, rows, s);
+        if (rc) return rc;
+      }
+    }
+    if (cfg.in_channels == 9) {
+      const size_t pb = (size_t)B, hw = (size_t)H * W;
+      if (int rc = copy_d2d(ptr(s_img), inpaint_image, pb * 4 * hw * 4, s)) return rc;
+      if (int rc = copy_d2d(ptr(s_mask), inpaint_mask, pb * hw * 4, s)) return rc;
+    }
+    return K22_OK;
+  }
+  // model call number `call` of the loop on the latent `cur` [B][4][HW]; the output is model_out()
+  int loop_model(const LoopRows& lr, const float* cur, const float* timesteps, int call, hipStream_t s) {
+    // model_fn: the UNet sees the first half twice (kandinsky2_1_model.py:223-225)
+    const size_t half = (size_t)(B / 2) * 4 * H * W * sizeof(float);
+    if (int rc = copy_d2d(ptr(s_xin), cur, half, s)) return rc;
+    if (int rc = copy_d2d(ptr(s_xin) + half, cur, half, s)) return rc;
+    if (lr.hoist) {
+      film_cur = lr.film + (int64_t)call * B * film_total;
+    } else {
+      if (int rc = copy_d2d(ptr(s_t), timesteps + (size_t)call * B, (size_t)B * 4, s)) return rc;
+    }
+    return exec(s);
+  }
+  // `body` (one pass over the whole loop on a stream: what is captured is exactly what an eager call runs) eagerly, or as the ONE captured loop
+  // of this engine, valid for `key`: every pointer and scalar baked into its nodes, the entry's kind first.
+  template <typename F> int loop_run(const std::vector<unsigned long long>& key, const float* timesteps, const float* inpaint_image,
+                                     const float* inpaint_mask, int use_graph, hipStream_t st, F body) {
+    auto run_loop = [&](hipStream_t s) -> int { const int rc = body(s); film_cur = nullptr; return rc; };
+    if (!use_graph) {
+      const int rc = run_loop(st);
+      if (rc == K22_OK) loop_count_launch();
+      return rc;
+    }
+    if (!loop || key != loop_key) {
+      if (!warmed) {   // first forward of this plan: run one step's ops eagerly (function attributes, code load) on a scratch input; a re-capture
+                       // for other scalars / buffers (guidance, step count: they are baked into the graph's nodes) does not repeat it
+        const size_t pb = (size_t)B, hw = (size_t)H * W;
+        hipError_t e = hipMemsetAsync(ptr(s_xin), 0, pb * 4 * hw * 4, st);
+        if (e != hipSuccess) return k22_set_error_hip(e, __FILE__, __LINE__);
+        if (int rc = copy_d2d(ptr(s_t), timesteps, pb * 4, st)) return rc;
+        if (cfg.in_channels == 9) {
+          if (int rc = copy_d2d(ptr(s_img), inpaint_image, pb * 4 * hw * 4, st)) return rc;
+          if (int rc = copy_d2d(ptr(s_mask), inpaint_mask, pb * hw * 4, st)) return rc;
+        }
+        if (int rc = exec_eager(st)) return rc;
+        e = hipStreamSynchronize(st);
+        if (e != hipSuccess) return k22_set_error_hip(e, __FILE__, __LINE__);
+      }
+      if (int rc = loop.capture(cap, run_loop)) return rc;
+      loop_key = key;
+      loop_count_capture();
+    }
+    const int rc = loop.launch(st);
+    if (rc == K22_OK) loop_count_launch();
+    return rc;
   }
 
   // One forward on `st`: the op list in order.  (A variant that forked the time-embedding / FiLM GEMV onto a second stream,
@@ -866,54 +971,13 @@ int k22_unet_sample_loop(K22UNet* u, float* x, float* x_tmp, const float* timest
   const int B = u->B, HW = u->H * u->W;
   if (pct_index >= 4 * HW) return k22_set_error(K22_EINVAL, "unet_sample_loop: percentile index out of range");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipError_t e;
-  { int rc = u->prepare_run(st); if (rc) return rc; }
-  const size_t half = (size_t)(B / 2) * 4 * HW * sizeof(float);
-  const size_t pb = (size_t)B;
-  // the time / FiLM rows of all steps up front (K22UNet::film_all): 8 / B steps per batched launch; B > 8 keeps the per-step launches
-  const bool hoist = B <= 8 && u->hoist_time;
-  const int64_t rows_all = (int64_t)n_steps * B;
-  float *fa_film = nullptr, *fa_temb = nullptr, *fa_e1 = nullptr, *fa_emb = nullptr;
-  if (hoist) {
-    const size_t need = (size_t)rows_all * (size_t)(u->film_total + u->tw.mc + 2 * u->tw.ted) * sizeof(float);
-    if (need > u->film_all_bytes) {
-      u->loop.drop();   // captured loops hold the old buffer's addresses (a captured forward does not: it reads s_film)
-      if (u->film_all) { (void)hipStreamSynchronize(st); (void)hipFree(u->film_all); u->film_all = nullptr; u->film_all_bytes = 0; }
-      e = hipMalloc(reinterpret_cast<void**>(&u->film_all), need);
-      if (e != hipSuccess) { u->film_all = nullptr; return k22_set_error_hip(e, __FILE__, __LINE__); }
-      u->film_all_bytes = need;
-    }
-    fa_film = u->film_all;
-    fa_temb = fa_film + rows_all * u->film_total;
-    fa_e1 = fa_temb + rows_all * u->tw.mc;
-    fa_emb = fa_e1 + rows_all * u->tw.ted;
-  }
-  // one pass over the loop on `s`: what is captured is exactly what an eager call runs
-  auto run_loop_body = [&](hipStream_t s) -> int {
-    if (hoist) {
-      const int spl = 8 / B;   // steps per batched launch
-      for (int k0 = 0; k0 < n_steps; k0 += spl) {
-        const int rows = (n_steps - k0 < spl ? n_steps - k0 : spl) * B;
-        const int64_t r0 = (int64_t)k0 * B;
-        const int rc = u->time_rows(timesteps + r0, fa_temb + r0 * u->tw.mc, fa_e1 + r0 * u->tw.ted, fa_emb + r0 * u->tw.ted, fa_film + r0 * u->film_total, rows, s);
-        if (rc) return rc;
-      }
-    }
-    if (u->cfg.in_channels == 9) {
-      if (int rc = copy_d2d(u->ptr(u->s_img), inpaint_image, pb * 4 * HW * 4, s)) return rc;
-      if (int rc = copy_d2d(u->ptr(u->s_mask), inpaint_mask, pb * HW * 4, s)) return rc;
-    }
+  K22UNet::LoopRows lr;
+  if (int rc = u->loop_begin(n_steps, st, &lr)) return rc;
+  auto body = [&](hipStream_t s) -> int {
+    if (int rc = u->loop_prologue(lr, timesteps, n_steps, inpaint_image, inpaint_mask, s)) return rc;
     float* cur = x; float* nxt = x_tmp;
     for (int k = 0; k < n_steps; ++k) {
-      // model_fn: the UNet sees the first half twice (kandinsky2_1_model.py:223-225)
-      if (int rc = copy_d2d(u->ptr(u->s_xin), cur, half, s)) return rc;
-      if (int rc = copy_d2d(u->ptr(u->s_xin) + half, cur, half, s)) return rc;
-      if (hoist) {
-        u->film_cur = fa_film + (int64_t)k * B * u->film_total;
-      } else {
-        if (int rc = copy_d2d(u->ptr(u->s_t), timesteps + (size_t)k * B, (size_t)B * 4, s)) return rc;
-      }
-      int rc = u->exec(s);
+      int rc = u->loop_model(lr, cur, timesteps, k, s);
       if (rc) return rc;
       SamplerParams p = {};
       p.x = cur; p.model_out = u->model_out(); p.noise = noise_seq + (size_t)k * B * 4 * HW; p.init_img = init_img; p.mask = mask;
@@ -928,35 +992,78 @@ int k22_unet_sample_loop(K22UNet* u, float* x, float* x_tmp, const float* timest
     if (cur != x) return copy_d2d(x, cur, (size_t)B * 4 * HW * sizeof(float), s);
     return K22_OK;
   };
-  auto run_loop = [&](hipStream_t s) -> int { const int rc = run_loop_body(s); u->film_cur = nullptr; return rc; };
-  if (!use_graph) return run_loop(st);
-  // key of the captured loop: every pointer and scalar baked into its nodes
-  std::vector<unsigned long long> key = {(unsigned long long)(uintptr_t)x, (unsigned long long)(uintptr_t)x_tmp, (unsigned long long)(uintptr_t)timesteps,
-      (unsigned long long)(uintptr_t)noise_seq, (unsigned long long)(uintptr_t)init_img, (unsigned long long)(uintptr_t)mask,
-      (unsigned long long)(uintptr_t)inpaint_image, (unsigned long long)(uintptr_t)inpaint_mask, (unsigned long long)(uintptr_t)table,
-      (unsigned long long)(uintptr_t)scratch, (unsigned long long)n_steps, (unsigned long long)pct_index, (unsigned long long)(hoist ? 1 : 0)};
-  auto bits = [](double v) { unsigned long long b; memcpy(&b, &v, 8); return b; };
-  key.push_back(bits(guidance)); key.push_back(bits(clamp_lo)); key.push_back(bits(clamp_hi)); key.push_back(bits(pct_gamma));
+  std::vector<unsigned long long> key = {K22_LOOP_KIND_P, loop_key_ptr(x), loop_key_ptr(x_tmp), loop_key_ptr(timesteps), loop_key_ptr(noise_seq),
+      loop_key_ptr(init_img), loop_key_ptr(mask), loop_key_ptr(inpaint_image), loop_key_ptr(inpaint_mask), loop_key_ptr(table), loop_key_ptr(scratch),
+      (unsigned long long)n_steps, (unsigned long long)pct_index, (unsigned long long)(lr.hoist ? 1 : 0),
+      loop_key_bits(guidance), loop_key_bits(clamp_lo), loop_key_bits(clamp_hi), loop_key_bits(pct_gamma)};
   for (int k = 0; k < n_steps; ++k) key.push_back((unsigned long long)table_rows[k]);
-  if (!u->loop || key != u->loop_key) {
-    if (!u->warmed) {   // first forward of this plan: run one step's ops eagerly (function attributes, code load) on a scratch input; a re-capture
-                        // for other scalars / buffers (guidance, step count: they are baked into the graph's nodes) does not repeat it
-      e = hipMemsetAsync(u->ptr(u->s_xin), 0, pb * 4 * HW * 4, st);
-      if (e != hipSuccess) return k22_set_error_hip(e, __FILE__, __LINE__);
-      if (int rc = copy_d2d(u->ptr(u->s_t), timesteps, pb * 4, st)) return rc;
-      if (u->cfg.in_channels == 9) {
-        if (int rc = copy_d2d(u->ptr(u->s_img), inpaint_image, pb * 4 * HW * 4, st)) return rc;
-        if (int rc = copy_d2d(u->ptr(u->s_mask), inpaint_mask, pb * HW * 4, st)) return rc;
-      }
-      int rc = u->exec_eager(st);
+  return u->loop_run(key, timesteps, inpaint_image, inpaint_mask, use_graph, st, body);
+}
+
+// The whole classifier-free-guided DDIM or PLMS loop of Kandinsky2_1.generate_img (kandinsky2_1_model.py:222-233 -> samplers.py:206-331,
+// 475-637) as ONE hipGraph: the k22_unet_sample_loop machinery with k22_ddim_step / k22_plms_step as the step.  PLMS: the rotation of the
+// eps ring is resolved here, at capture time - every captured plms_step node holds fixed h1 / h2 / h3 / eps_out pointers.
+int k22_unet_ddim_loop(K22UNet* u, int kind, float* x, float* x_tmp, float* x0_out, const float* timesteps, const float* table,
+                       const float* noise_seq, const float* inpaint_image, const float* inpaint_mask, float* eps_hist, int n_steps,
+                       float guidance, int use_graph, void* stream) {
+  if (!u || !u->ws) return k22_set_error(K22_EINVAL, "unet_ddim_loop: bind a workspace first");
+  if (kind != K22_LOOP_DDIM && kind != K22_LOOP_PLMS) return k22_set_error(K22_EINVAL, "unet_ddim_loop: kind must be K22_LOOP_DDIM or K22_LOOP_PLMS");
+  if (!u->cond_set) return k22_set_error(K22_EINVAL, "unet_ddim_loop: call k22_unet_set_condition first");
+  if (!x || !x_tmp || !timesteps || !table) return k22_set_error(K22_EINVAL, "unet_ddim_loop: null argument");
+  if (n_steps < 1) return k22_set_error(K22_EINVAL, "unet_ddim_loop: n_steps must be >= 1");
+  if (kind == K22_LOOP_PLMS && noise_seq) return k22_set_error(K22_EINVAL, "unet_ddim_loop: PLMS is eta = 0 (samplers.py:355-356): noise_seq must be NULL");
+  if (kind == K22_LOOP_PLMS && !eps_hist) return k22_set_error(K22_EINVAL, "unet_ddim_loop: PLMS needs the eps-history workspace (4 x [B][4][HW] floats)");
+  if (u->B % 2) return k22_set_error(K22_EINVAL, "unet_ddim_loop: the batch is the CFG batch [cond | uncond] (even)");
+  if (u->cfg.out_channels != 8) return k22_set_error(K22_EINVAL, "unet_ddim_loop: the UNet must predict eps and variance (8 channels)");
+  if (u->cfg.in_channels == 9 && (!inpaint_image || !inpaint_mask)) return k22_set_error(K22_EINVAL, "unet_ddim_loop: inpainting UNet needs inpaint_image and inpaint_mask");
+  if (u->cfg.hint_channels && !u->hint_set) return k22_set_error(K22_EINVAL, "unet_ddim_loop: call k22_unet_set_hint first");
+  const int B = u->B, HW = u->H * u->W;
+  const int n_calls = kind == K22_LOOP_PLMS ? n_steps + 1 : n_steps;   // PLMS: the pseudo improved-Euler start calls the model twice
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  K22UNet::LoopRows lr;
+  if (int rc = u->loop_begin(n_calls, st, &lr)) return rc;
+  const size_t lat = (size_t)B * 4 * HW;
+  auto body = [&](hipStream_t s) -> int {
+    if (int rc = u->loop_prologue(lr, timesteps, n_calls, inpaint_image, inpaint_mask, s)) return rc;
+    float* cur = x; float* nxt = x_tmp;
+    float* old[3] = {nullptr, nullptr, nullptr};   // PLMS: guided eps of earlier steps, newest first
+    int n_old = 0, call = 0;
+    for (int k = 0; k < n_steps; ++k) {
+      const float* row = table + (size_t)k * 4;
+      int rc = u->loop_model(lr, cur, timesteps, call++, s);
       if (rc) return rc;
-      e = hipStreamSynchronize(st);
-      if (e != hipSuccess) return k22_set_error_hip(e, __FILE__, __LINE__);
+      if (kind == K22_LOOP_DDIM) {
+        rc = launch_ddim_step(cur, u->model_out(), noise_seq ? noise_seq + (size_t)k * lat : nullptr, row, guidance, 1, nxt, x0_out, B, HW, s);
+        if (rc) return rc;
+      } else {
+        float* e_buf = nullptr;   // the slot of the ring of four that holds none of the (at most three) live history tensors
+        for (int j = 0; j < 4 && !e_buf; ++j) {
+          float* c = eps_hist + (size_t)j * lat;
+          if (c != old[0] && c != old[1] && c != old[2]) e_buf = c;
+        }
+        if (n_old == 0) {
+          // stage one: e_t -> e_buf, provisional x_prev -> nxt; stage two: the model on it at the NEXT timestep, e' = (e_t + e_next) / 2
+          rc = launch_plms_step(cur, u->model_out(), nullptr, nullptr, nullptr, 0, row, guidance, 1, nxt, e_buf, nullptr, B, HW, s);
+          if (rc) return rc;
+          rc = u->loop_model(lr, nxt, timesteps, call++, s);
+          if (rc) return rc;
+          rc = launch_plms_step(cur, u->model_out(), e_buf, nullptr, nullptr, 4, row, guidance, 1, nxt, nullptr, x0_out, B, HW, s);
+        } else {
+          rc = launch_plms_step(cur, u->model_out(), old[0], old[1], old[2], n_old, row, guidance, 1, nxt, e_buf, x0_out, B, HW, s);
+        }
+        if (rc) return rc;
+        old[2] = old[1]; old[1] = old[0]; old[0] = e_buf;
+        if (n_old < 3) ++n_old;
+      }
+      float* t_ = cur; cur = nxt; nxt = t_;
     }
-    if (int rc = u->loop.capture(u->cap, run_loop)) return rc;
-    u->loop_key = key;
-  }
-  return u->loop.launch(st);
+    if (cur != x) return copy_d2d(x, cur, lat * sizeof(float), s);
+    return K22_OK;
+  };
+  const std::vector<unsigned long long> key = {kind == K22_LOOP_DDIM ? K22_LOOP_KIND_DDIM : K22_LOOP_KIND_PLMS, loop_key_ptr(x), loop_key_ptr(x_tmp),
+      loop_key_ptr(x0_out), loop_key_ptr(timesteps), loop_key_ptr(table), loop_key_ptr(noise_seq), loop_key_ptr(inpaint_image), loop_key_ptr(inpaint_mask),
+      loop_key_ptr(eps_hist), (unsigned long long)n_steps, (unsigned long long)(lr.hoist ? 1 : 0), loop_key_bits(guidance)};
+  return u->loop_run(key, timesteps, inpaint_image, inpaint_mask, use_graph, st, body);
 }
 
 int k22_unet_num_ops(const K22UNet* u) {

@@ -113,6 +113,9 @@ bool stream_supported(const IgemmParams& p, int dtype, int mb);
 int stream_mtiles(const IgemmParams& p, int mb);
 int launch_stream(const IgemmParams& p, int dtype, int mb, int splitk, hipStream_t stream);
 long stream_launch_count();
+// engine.hip: whole-loop graphs captured / whole-loop replays or eager loop runs since the library was loaded
+long loop_capture_count();
+long loop_launch_count();
 // bytes of the fragment-major copy of a [Npad][taps * Kc] weight matrix, and the one-time repack (any 16-bit dtype)
 size_t stream_frag_bytes(int Npad, int taps, int Kc, int dtype);
 int launch_stream_repack(const void* W, void* out, int Npad, int taps, int Kc, int dtype, hipStream_t stream);

@@ -316,7 +316,19 @@ class DDIMSamplerHIP:
                                             x_out.data_ptr(), x0_out.data_ptr(), N, HW, _lib.current_stream()))
 
     @torch.no_grad()
-    def sample(self, S, batch_size, shape, conditioning=None, eta=0.0, x_T=None, init_step=None, noise_seq=None, device="cuda", **_unused):
+    def _whole_loop(self, kind, x, calls, noise_seq, conditioning):
+        """The loop as ONE hipGraph replay (Text2ImUNetHIP.ddim_loop -> k22_unet_ddim_loop): `calls` = the raw ddim timestep of every model
+        call in execution order, the table rows flipped into execution order."""
+        dev = x.device
+        ts_rows = torch.tensor([float(c) for c in calls], dtype=torch.float32, device=dev)[:, None].expand(-1, x.shape[0]).contiguous()
+        table = torch.from_numpy(self.table[::-1].copy()).to(dev)
+        x, x0 = self.model.ddim_loop(kind, x, ts_rows, table, self.guidance_scale, noise_seq, **(conditioning or {}))
+        return x, {"pred_x0": [x0]}
+
+    @torch.no_grad()
+    def sample(self, S, batch_size, shape, conditioning=None, eta=0.0, x_T=None, init_step=None, noise_seq=None, device="cuda",
+               whole_loop_graph: bool = False, **_unused):
+        """whole_loop_graph=True: the whole loop as one hipGraph (no host work between steps; same kernels, same bits)."""
         self.make_schedule(S, ddim_eta=eta, init_step=init_step)
         C, H, W = shape
         if C != 4 or batch_size % 2:
@@ -327,6 +339,17 @@ class DDIMSamplerHIP:
         x_next, x0 = torch.empty_like(x), torch.empty_like(x)
         table = torch.from_numpy(self.table).to(dev)
         total = len(self.ddim_timesteps)
+        if whole_loop_graph and hasattr(self.model, "ddim_loop") and total > 0:
+            # the noise of every step drawn up front by the same sequence of randn_like calls the per-step path makes (same generator draws)
+            nzs = None
+            if self.eta > 0.0:
+                if noise_seq is not None:
+                    nzs = noise_seq[:total].to(dev).float().contiguous()
+                else:
+                    nzs = torch.empty(total, *x.shape, device=dev)
+                    for k in range(total):
+                        nzs[k] = torch.randn_like(x)
+            return self._whole_loop("ddim", x, np.flip(self.ddim_timesteps), nzs, conditioning)
         for i, step in enumerate(np.flip(self.ddim_timesteps)):
             index = total - i - 1
             ts = torch.full((N,), float(step), device=dev)
@@ -357,7 +380,8 @@ class PLMSSamplerHIP(DDIMSamplerHIP):
                                             _lib.current_stream()))
 
     @torch.no_grad()
-    def sample(self, S, batch_size, shape, conditioning=None, eta=0.0, x_T=None, init_step=None, device="cuda", **_unused):
+    def sample(self, S, batch_size, shape, conditioning=None, eta=0.0, x_T=None, init_step=None, device="cuda",
+               whole_loop_graph: bool = False, **_unused):
         if eta != 0:
             raise ValueError("ddim_eta must be 0 for PLMS")   # samplers.py:355-356
         self.make_schedule(S, ddim_eta=0.0, init_step=init_step)
@@ -367,6 +391,11 @@ class PLMSSamplerHIP(DDIMSamplerHIP):
         dev = torch.device(device)
         N, HW, bs = batch_size, H * W, batch_size // 2
         x = x_T.to(dev).float().contiguous().clone() if x_T is not None else torch.randn(N, C, H, W, device=dev)
+        if whole_loop_graph and hasattr(self.model, "ddim_loop") and len(self.ddim_timesteps) > 0:
+            # model calls in execution order: the first step calls the model twice, the second time at the next step's timestep (its own when
+            # it is the only step)
+            tr = list(np.flip(self.ddim_timesteps))
+            return self._whole_loop("plms", x, [tr[0], tr[min(1, len(tr) - 1)]] + tr[1:], None, conditioning)
         x_next, x0 = torch.empty_like(x), torch.empty_like(x)
         hist = [torch.empty_like(x) for _ in range(4)]   # ring of guided eps tensors: 3 of history + the one being written
         old = []                                          # newest last, like the reference's old_eps

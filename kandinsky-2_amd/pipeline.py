@@ -181,7 +181,8 @@ class Kandinsky2_1HIP:
         self.device = device
         self.task_type = task_type
         self.backend_dtype = backend_dtype
-        # p_sampler: the whole denoising loop as ONE hipGraph replay (k22_unet_sample_loop) - on whenever graphs are
+        # every sampler: the whole denoising loop as ONE hipGraph replay (p_sampler: k22_unet_sample_loop; ddim_sampler / plms_sampler:
+        # k22_unet_ddim_loop) - on whenever graphs are
         self.whole_loop_graph = use_graph if whole_loop_graph is None else bool(whole_loop_graph)
         self.use_fp16 = False                       # public tensors are fp32; engine precision is backend_dtype
         self.model_dtype = torch.float32
@@ -294,7 +295,8 @@ class Kandinsky2_1HIP:
         elif sampler in ("ddim_sampler", "plms_sampler"):
             cls = DDIMSamplerHIP if sampler == "ddim_sampler" else PLMSSamplerHIP
             samples, _ = cls(self.model, diffusion, guidance_scale).sample(
-                num_steps, batch_size * 2, (4, new_h, new_w), conditioning=model_kwargs, x_T=noise, init_step=init_step, device=self.device)
+                num_steps, batch_size * 2, (4, new_h, new_w), conditioning=model_kwargs, x_T=noise, init_step=init_step, device=self.device,
+                whole_loop_graph=self.whole_loop_graph)
             samples = samples[:batch_size]
         else:
             raise ValueError("Only ddim_sampler and plms_sampler is available")

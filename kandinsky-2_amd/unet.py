@@ -119,6 +119,7 @@ class Text2ImUNetHIP(nn.Module):
         self._ws = None
         self._ws2 = None
         self._loop_bufs = None
+        self._ddim_bufs = None
         self._plan_key = None
         self._cond_key = None
 
@@ -286,6 +287,15 @@ class Text2ImUNetHIP(nn.Module):
         self._join(B)
         return self
 
+    def _ensure_condition(self, full_emb, pooled_emb, image_emb):
+        """the reference caches the conditioning after the first call until del_cache() (text2im_model2_1.py:58-59, 82-83)"""
+        if self._cond_key is None or not self.cache_text_emb:
+            if full_emb is None or pooled_emb is None or image_emb is None:
+                raise ValueError("full_emb, pooled_emb and image_emb are required")
+            self.set_condition(full_emb, pooled_emb, image_emb)
+            self._cond_key = True
+            self.cache = {"cached": True}
+
     @torch.no_grad()
     def forward(self, x, timesteps, full_emb=None, pooled_emb=None, image_emb=None, inpaint_image=None, inpaint_mask=None):
         if x.device.type != "cuda":
@@ -294,13 +304,7 @@ class Text2ImUNetHIP(nn.Module):
         if Cx != 4:
             raise ValueError("expected a 4-channel latent")
         self._ensure_plan(B, H, W)
-        # the reference caches the conditioning after the first call until del_cache() (text2im_model2_1.py:58-59, 82-83)
-        if self._cond_key is None or not self.cache_text_emb:
-            if full_emb is None or pooled_emb is None or image_emb is None:
-                raise ValueError("full_emb, pooled_emb and image_emb are required")
-            self.set_condition(full_emb, pooled_emb, image_emb)
-            self._cond_key = True
-            self.cache = {"cached": True}
+        self._ensure_condition(full_emb, pooled_emb, image_emb)
         if timesteps.numel() != B:
             raise ValueError(f"timesteps must hold one value per batch element ({B}); got {tuple(timesteps.shape)}")
         xf = x.detach().float().contiguous()
@@ -339,12 +343,7 @@ class Text2ImUNetHIP(nn.Module):
         if tuple(ts_rows.shape) != (n_steps, B) or tuple(noise_seq.shape) != (n_steps, B, 4, H, W):
             raise ValueError("sample_loop: ts_rows must be [n_steps, N] and noise_seq [n_steps, N, 4, h, w]")
         self._ensure_plan(B, H, W)
-        if self._cond_key is None or not self.cache_text_emb:
-            if full_emb is None or pooled_emb is None or image_emb is None:
-                raise ValueError("full_emb, pooled_emb and image_emb are required")
-            self.set_condition(full_emb, pooled_emb, image_emb)
-            self._cond_key = True
-            self.cache = {"cached": True}
+        self._ensure_condition(full_emb, pooled_emb, image_emb)
         if not self.arch.inpainting and (inpaint_image is not None or inpaint_mask is not None):
             raise ValueError("inpaint_image / inpaint_mask given to a text2img UNet (create it with inpainting=True)")
         dev = x.device
@@ -390,6 +389,88 @@ class Text2ImUNetHIP(nn.Module):
             float(clamp[0]), float(clamp[1]), int(pct[0]), float(pct[1]), bufs["scratch"].data_ptr(), 1 if self.use_graph else 0,
             _lib.current_stream()))
         return bufs["x"].clone()
+
+    @torch.no_grad()
+    def ddim_loop(self, kind, x, ts_rows, table, guidance_scale, noise_seq=None, *, full_emb=None, pooled_emb=None, image_emb=None,
+                  inpaint_image=None, inpaint_mask=None):
+        """The whole guided DDIM (kind "ddim") or PLMS ("plms") loop as ONE hipGraph replay (k22_unet_ddim_loop); returns (final latent,
+        predicted x0 of the last step), both [N,4,h,w].  x = x_T; table [n_steps, 4]: the k22_ddim_step rows in execution order; ts_rows
+        [n_calls, N]: the timestep of every model call in execution order - n_calls = n_steps for DDIM, n_steps + 1 for PLMS (its first step
+        calls the model a second time, at the next step's timestep); noise_seq [n_steps, N,4,h,w]: DDIM with eta > 0 only.  As in sample_loop
+        the operands are copied into buffers this module OWNS: a second generation of the same shape, step count and kind replays the capture."""
+        if kind not in ("ddim", "plms"):
+            raise ValueError('ddim_loop: kind must be "ddim" or "plms"')
+        B, Cx, H, W = x.shape
+        if Cx != 4 or x.device.type != "cuda":
+            raise ValueError("ddim_loop: x must be [N,4,h,w] on the GPU")
+        plms = kind == "plms"
+        n_steps = table.shape[0]
+        n_calls = n_steps + 1 if plms else n_steps
+        if n_steps < 1 or tuple(table.shape) != (n_steps, 4) or tuple(ts_rows.shape) != (n_calls, B):
+            raise ValueError("ddim_loop: table must be [n_steps, 4] and ts_rows [n_calls, N] (n_calls = n_steps, + 1 for PLMS)")
+        if noise_seq is not None and (plms or tuple(noise_seq.shape) != (n_steps, B, 4, H, W)):
+            raise ValueError("ddim_loop: noise_seq is [n_steps, N, 4, h, w], for DDIM only (PLMS is eta = 0)")
+        self._ensure_plan(B, H, W)
+        self._ensure_condition(full_emb, pooled_emb, image_emb)
+        if not self.arch.inpainting and (inpaint_image is not None or inpaint_mask is not None):
+            raise ValueError("inpaint_image / inpaint_mask given to a text2img UNet (create it with inpainting=True)")
+        L, dev = _lib.lib(), x.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        if self._chained(B):
+            # two chains: host-driven, per model call the two half-batch graphs side by side (see sample_loop).  The steps of k22_unet_ddim_loop.
+            cur, nxt, x0 = x.detach().float().clone(), torch.empty(B, 4, H, W, **f32), torch.empty(B, 4, H, W, **f32)
+            tbl, g, st = table.float().contiguous(), float(guidance_scale), _lib.current_stream
+            ring, old, call = [torch.empty(B, 4, H, W, **f32) for _ in range(4)] if plms else [], [], 0
+
+            def model(xx, c):
+                half = xx[: B // 2]
+                return self.forward(torch.cat([half, half], 0), ts_rows[c], inpaint_image=inpaint_image, inpaint_mask=inpaint_mask)
+
+            def plms_step(out, hist, order, row, eps_out, x0_out):
+                h = [t.data_ptr() for t in hist] + [None, None, None]
+                _lib.check(L.k22_plms_step(cur.data_ptr(), out.data_ptr(), h[0], h[1], h[2], order, row.data_ptr(), g, 1, nxt.data_ptr(),
+                                           _lib.ptr(eps_out), _lib.ptr(x0_out), B, H * W, st()))
+
+            for k in range(n_steps):
+                out = model(cur, call)
+                call += 1
+                if not plms:
+                    nz = None if noise_seq is None else noise_seq[k].float().contiguous()
+                    _lib.check(L.k22_ddim_step(cur.data_ptr(), out.data_ptr(), _lib.ptr(nz), tbl[k].data_ptr(), g, 1, nxt.data_ptr(), x0.data_ptr(),
+                                               B, H * W, st()))
+                else:
+                    e_buf = next(b for b in ring if all(b is not o for o in old))
+                    if not old:
+                        plms_step(out, [], 0, tbl[k], e_buf, None)
+                        out = model(nxt, call)
+                        call += 1
+                        plms_step(out, [e_buf], 4, tbl[k], None, x0)
+                    else:
+                        plms_step(out, old, len(old), tbl[k], e_buf, x0)
+                    old = [e_buf] + old[:2]   # newest first
+                cur, nxt = nxt, cur
+            return cur, x0
+        key = (kind, B, H, W, n_steps, noise_seq is not None, str(dev))
+        bufs = getattr(self, "_ddim_bufs", None)
+        if bufs is None or bufs["key"] != key:
+            bufs = {"key": key, "x": torch.empty(B, 4, H, W, **f32), "tmp": torch.empty(B, 4, H, W, **f32), "x0": torch.empty(B, 4, H, W, **f32),
+                    "ts": torch.empty(n_calls, B, **f32), "table": torch.empty(n_steps, 4, **f32),
+                    "noise": torch.empty(n_steps, B, 4, H, W, **f32) if noise_seq is not None else None,
+                    "hist": torch.empty(4, B, 4, H, W, **f32) if plms else None,
+                    "img": torch.zeros(B, 4, H, W, **f32) if self.arch.inpainting else None,
+                    "msk": torch.zeros(B, 1, H, W, **f32) if self.arch.inpainting else None}
+            self._ddim_bufs = bufs
+        bufs["x"].copy_(x); bufs["ts"].copy_(ts_rows); bufs["table"].copy_(table)
+        if noise_seq is not None:
+            bufs["noise"].copy_(noise_seq)
+        if self.arch.inpainting:
+            bufs["img"].zero_() if inpaint_image is None else bufs["img"].copy_(inpaint_image.float().expand(B, 4, H, W))
+            bufs["msk"].zero_() if inpaint_mask is None else bufs["msk"].copy_(inpaint_mask.float().expand(B, 1, H, W))
+        _lib.check(L.k22_unet_ddim_loop(
+            self._handle, _lib.K22_LOOP_PLMS if plms else _lib.K22_LOOP_DDIM, bufs["x"].data_ptr(), bufs["tmp"].data_ptr(), bufs["x0"].data_ptr(),
+            bufs["ts"].data_ptr(), bufs["table"].data_ptr(), _lib.ptr(bufs["noise"]), _lib.ptr(bufs["img"]), _lib.ptr(bufs["msk"]),
+            _lib.ptr(bufs["hist"]), n_steps, float(guidance_scale), 1 if self.use_graph else 0, _lib.current_stream()))
+        return bufs["x"].clone(), bufs["x0"].clone()
 
 
 def create_model(backend_dtype: torch.dtype = torch.bfloat16, use_graph: bool = True, inpainting: bool = False,
