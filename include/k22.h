@@ -538,6 +538,65 @@ int k22_encoder_forward(K22Encoder* m, const int* tokens, const float* key_valid
 int k22_blend_noised(const float* x, const float* init, const float* noise, const float* mask, float sa, float sb, float* out,
                      int N, int C, int HW, int broadcast_first, void* stream);
 
+/* ---- single-kernel entry points for the parity tests; no product code calls them ----------------
+ * The small kernels around the MoVQ, encoder and prior engines (csrc/movq_kernels.hip, encoder.hip, prior.hip), each through the
+ * launcher its engine's plan uses - same grid, same LDS attribute, same admission rule (tests/test_aux_kernels_gpu.py compares every
+ * one with a float64 restatement, tests/aux_ref.py).  Conventions of the other kernel-level entries: enqueue on `stream`, allocate
+ * nothing, return 0 or a K22_E* code; dtype = K22_BF16 | K22_F16 | K22_F32 is the storage type T of the tensors declared void*.
+ *
+ * MoVQ.  NHWC T tensors move one 16-byte channel vector per thread: C % 8 == 0 (16-bit types) / C % 4 == 0 (fp32), else K22_EINVAL.
+ *   spatialnorm_apply  out = act((x * A + Bc) * conv_y(zq) + conv_b(zq)) with coeff [B][C][2] = (A, Bc) GIVEN (the GroupNorm statistics
+ *                      are not run), zq fp32 NHWC [B][h0][w0][4] read at (y >> shift, x >> shift), wy / wb [C][4], by / bb [C];
+ *                      x [B][H][W][C] -> out [B][H + 2 pad][W + 2 pad][C] (zero border); W % 2^shift == 0; act 0 | K22_ACT_SILU
+ *   upsample2_pad      [B][H][W][C] -> zero-bordered nearest x2 [B][2H + 2][2W + 2][C]
+ *   pad_copy           [B][H][W][C] -> zero-bordered [B][H + 2][W + 2][C]
+ *   subsample_odd      [B][H][W][C] (H, W even) -> [B][H/2][W/2][C] = x[2y + 1][2x + 1]
+ *   softmax_rows       in place: row r of `rows` rows of L elements (L % 8 / % 4 == 0) becomes softmax(scale * row), fp32 math
+ *   movq_prepare       z fp32 NCHW [B][4][h][w] -> zq fp32 NHWC [B][h][w][4] (copy) and xin T [B][h + 2][w + 2][Cpad] = zero-bordered
+ *                      post_quant_conv(z) (wpq [4][4], bpq [4]) in channels 0..3, zeros in 4..Cpad-1
+ *   movq_enc_prepare   image fp32 NCHW [B][3][H][W] -> xin T [B][H + 2][W + 2][Cpad], channels 3.. and the border zero
+ *   movq_quant_conv    h fp32 NCHW [B][4][HW] -> out fp32 [B][4][HW] = wq [4][4] . h + bq
+ *   to_uint8_nhwc      x fp32 NCHW [B][C][H][W] -> y uint8 NHWC = ((x + 1) * 127.5).round().clamp(0, 255), ties to even */
+int k22_spatialnorm_apply(const void* x, const float* coeff, const float* zq, const float* wy, const float* by, const float* wb, const float* bb,
+                          void* out, int B, int H, int W, int C, int h0, int w0, int shift, int act, int pad, int dtype, void* stream);
+int k22_upsample2_pad(const void* x, void* y, int B, int H, int W, int C, int dtype, void* stream);
+int k22_pad_copy(const void* x, void* y, int B, int H, int W, int C, int dtype, void* stream);
+int k22_subsample_odd(const void* x, void* y, int B, int H, int W, int C, int dtype, void* stream);
+int k22_softmax_rows(void* x, long rows, int L, float scale, int dtype, void* stream);
+int k22_movq_prepare(const float* z, const float* wpq, const float* bpq, float* zq, void* xin, int B, int h, int w, int Cpad, int dtype, void* stream);
+int k22_movq_enc_prepare(const float* image, void* xin, int B, int H, int W, int Cpad, int dtype, void* stream);
+int k22_movq_quant_conv(const float* h, const float* wq, const float* bq, float* out, int B, int HW, void* stream);
+int k22_to_uint8_nhwc(const float* x, unsigned char* y, int B, int C, int H, int W, void* stream);
+/* Encoder towers.
+ *   enc_layernorm      `rows` fp32 rows x + r * ldx of D <= 2048 values (K22_EINVAL above: 8 x 256 values per row) -> fp32 rows
+ *                      out_f32 + r * ld_out (optional; may be x itself) and / or T rows out_t + r * D (optional)
+ *   enc_embed          x [B][n_ctx][D] = (tok_emb[id] + pos_emb[pos]) + type_emb (type_emb optional), ids clamped into [0, vocab);
+ *                      pos = t, or (xlmr) cumsum(tok != pad_id) * (tok != pad_id) + pad_id clamped to max_pos - 1
+ *   enc_gather_eot     out [B][D] = x[b][argmax_t tokens[b][t]] (first maximum)
+ *   enc_masked_mean    out [B][D] = sum_t x[b][t] * mask[b][t] / sum_t mask[b][t]
+ *   enc_patchify       image fp32 [B][3][S][S] -> T rows [B * (S / patch)^2][Kp], column c * patch^2 + i * patch + j, zeros from 3 * patch^2 on
+ *   enc_vision_assemble x [B][P + 1][D]: row 0 = cls + pos[0], row 1 + p = patch_out[b][p] + pos[1 + p]
+ *   enc_mlp_act        y T [n] = x * sigmoid(1.702 x) (exact == 0) or the erf GELU (exact != 0) of fp32 x [n]
+ *   enc_attention_generic  qkv T [B][n][3 * heads * hd] (columns Q | K | V, heads x hd inside each) -> out T [B][n][heads * hd] =
+ *                      softmax(q k^T hd^-0.5) v per head; admitted as K22Encoder's plan admits it: hd <= 128, n <= 512 and
+ *                      n * (hd + 2) * sizeof(T) * (2 for the 16-bit types) + 10 KB <= 160 KB of LDS, else K22_EINVAL */
+int k22_enc_layernorm(const float* x, long ldx, const float* gain, const float* beta, float* out_f32, long ld_out, void* out_t, int rows,
+                      int D, float eps, int dtype, void* stream);
+int k22_enc_embed(const int* tokens, const float* tok_emb, const float* pos_emb, const float* type_emb, float* x, int B, int n_ctx, int D,
+                  int vocab, int xlmr, int pad_id, int max_pos, void* stream);
+int k22_enc_gather_eot(const int* tokens, const float* x, float* out, int B, int n_ctx, int D, void* stream);
+int k22_enc_masked_mean(const float* x, const float* mask, float* out, int B, int n_ctx, int D, void* stream);
+int k22_enc_patchify(const float* image, void* out, int B, int S, int patch, int Kp, int dtype, void* stream);
+int k22_enc_vision_assemble(const float* patch_out, const float* cls, const float* pos, float* x, int B, int P, int D, void* stream);
+int k22_enc_mlp_act(const float* x, void* y, long n, int exact, int dtype, void* stream);
+int k22_enc_attention_generic(const void* qkv, void* out, int B, int heads, int n, int hd, int dtype, void* stream);
+/* Prior (k22_prior_sampler_step above belongs to the same surface).
+ *   prior_layernorm    `rows` fp32 rows x + r * ldx of D values -> rows y + r * D, fp32 (to_f32 != 0) or T; eps 1e-5
+ *   prior_finish_input inp [B][n_ctx][D] += pos [n_ctx][D], the last row of every sequence = prd [D] + pos[n_ctx - 1] */
+int k22_prior_layernorm(const float* x, long ldx, const float* gain, const float* beta, void* y, int rows, int D, int to_f32, int dtype,
+                        void* stream);
+int k22_prior_finish_input(float* inp, const float* pos, const float* prd, int B, int n_ctx, int D, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -163,6 +163,26 @@ SIGNATURES = {
     "k22_stream_repack": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "k22_debug_set_stream_frag": (_I, [_P, _P]),
     "k22_debug_set_stream_scratch": (_I, [_P, C.c_size_t]),
+    # single-kernel entry points for the parity tests (tests/test_aux_kernels_gpu.py); no product code calls them
+    "k22_spatialnorm_apply": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "k22_upsample2_pad": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
+    "k22_pad_copy": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
+    "k22_subsample_odd": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
+    "k22_softmax_rows": (_I, [_P, _L, _I, _F, _I, _P]),
+    "k22_movq_prepare": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "k22_movq_enc_prepare": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
+    "k22_movq_quant_conv": (_I, [_P, _P, _P, _P, _I, _I, _P]),
+    "k22_to_uint8_nhwc": (_I, [_P, _P, _I, _I, _I, _I, _P]),
+    "k22_enc_layernorm": (_I, [_P, _L, _P, _P, _P, _L, _P, _I, _I, _F, _I, _P]),
+    "k22_enc_embed": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "k22_enc_gather_eot": (_I, [_P, _P, _P, _I, _I, _I, _P]),
+    "k22_enc_masked_mean": (_I, [_P, _P, _P, _I, _I, _I, _P]),
+    "k22_enc_patchify": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
+    "k22_enc_vision_assemble": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
+    "k22_enc_mlp_act": (_I, [_P, _P, _L, _I, _I, _P]),
+    "k22_enc_attention_generic": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
+    "k22_prior_layernorm": (_I, [_P, _L, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "k22_prior_finish_input": (_I, [_P, _P, _P, _I, _I, _I, _P]),
 }
 
 _lib = None

@@ -488,6 +488,49 @@ int k22_sampler_step(const float* x, const float* model_out, const float* noise,
   return launch_sampler_step(p, reinterpret_cast<hipStream_t>(stream));
 }
 
+// ---- single-kernel entry points of the MoVQ helpers for the parity tests (include/k22.h); no product code calls them ---------------
+static bool aux_dtype_ok(int dt) { return dt == K22_BF16 || dt == K22_F16 || dt == K22_F32; }
+
+int k22_spatialnorm_apply(const void* x, const float* coeff, const float* zq, const float* wy, const float* by, const float* wb, const float* bb,
+                          void* out, int B, int H, int W, int C, int h0, int w0, int shift, int act, int pad, int dtype, void* stream) {
+  if (!x || !coeff || !zq || !wy || !by || !wb || !bb || !out || B < 1 || H < 1 || W < 1 || C < 1 || h0 < 1 || w0 < 1 || shift < 0 || shift > 12 || (H & ((1 << shift) - 1)) ||
+      (pad != 0 && pad != 1) || (act != K22_ACT_NONE && act != K22_ACT_SILU) || !aux_dtype_ok(dtype))
+    return k22_set_error(K22_EINVAL, "spatialnorm_apply: bad argument");
+  SpatialNormParams p = {};
+  p.x = x; p.coeff = coeff; p.zq = zq; p.wy = wy; p.by = by; p.wb = wb; p.bb = bb; p.out = out;
+  p.B = B; p.H = H; p.W = W; p.C = C; p.h0 = h0; p.w0 = w0; p.shift = shift; p.act = act; p.pad = pad;
+  return launch_spatialnorm_apply(p, dtype, reinterpret_cast<hipStream_t>(stream));
+}
+#define K22_AUX_NHWC(NAME_)                                                                                                     \
+  int k22_##NAME_(const void* x, void* y, int B, int H, int W, int C, int dtype, void* stream) {                                \
+    if (!x || !y || B < 1 || B > 65535 || H < 1 || W < 1 || C < 1 || !aux_dtype_ok(dtype)) return k22_set_error(K22_EINVAL, #NAME_ ": bad argument"); \
+    return launch_##NAME_(x, y, B, H, W, C, dtype, reinterpret_cast<hipStream_t>(stream));                                      \
+  }
+K22_AUX_NHWC(upsample2_pad)
+K22_AUX_NHWC(pad_copy)
+K22_AUX_NHWC(subsample_odd)
+#undef K22_AUX_NHWC
+int k22_softmax_rows(void* x, long rows, int L, float scale, int dtype, void* stream) {
+  if (!x || L < 1 || !aux_dtype_ok(dtype)) return k22_set_error(K22_EINVAL, "softmax_rows: bad argument");
+  return launch_softmax_rows(x, rows, L, scale, dtype, reinterpret_cast<hipStream_t>(stream));
+}
+int k22_movq_prepare(const float* z, const float* wpq, const float* bpq, float* zq, void* xin, int B, int h, int w, int Cpad, int dtype, void* stream) {
+  if (!z || !wpq || !bpq || !zq || !xin || B < 1 || h < 1 || w < 1 || Cpad < 4 || !aux_dtype_ok(dtype)) return k22_set_error(K22_EINVAL, "movq_prepare: bad argument");
+  return launch_movq_prepare(z, wpq, bpq, zq, xin, B, h, w, Cpad, dtype, reinterpret_cast<hipStream_t>(stream));
+}
+int k22_movq_enc_prepare(const float* image, void* xin, int B, int H, int W, int Cpad, int dtype, void* stream) {
+  if (!image || !xin || B < 1 || H < 1 || W < 1 || Cpad < 3 || !aux_dtype_ok(dtype)) return k22_set_error(K22_EINVAL, "movq_enc_prepare: bad argument");
+  return launch_movq_enc_prepare(image, xin, B, H, W, Cpad, dtype, reinterpret_cast<hipStream_t>(stream));
+}
+int k22_movq_quant_conv(const float* h, const float* wq, const float* bq, float* out, int B, int HW, void* stream) {
+  if (!h || !wq || !bq || !out || B < 1 || HW < 1) return k22_set_error(K22_EINVAL, "movq_quant_conv: bad argument");
+  return launch_movq_quant_conv(h, wq, bq, out, B, HW, reinterpret_cast<hipStream_t>(stream));
+}
+int k22_to_uint8_nhwc(const float* x, unsigned char* y, int B, int C, int H, int W, void* stream) {
+  if (!x || !y || B < 1 || C < 1 || H < 1 || W < 1) return k22_set_error(K22_EINVAL, "to_uint8_nhwc: bad argument");
+  return launch_to_uint8_nhwc(x, y, B, C, H, W, reinterpret_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"
 
 // ---- debug: LDS sentinel (tools/lds_victim_probe.py) -------------------------------------------------------------

@@ -221,6 +221,76 @@ __global__ __launch_bounds__(256) void enc_attention_generic_kernel(const T* __r
   }
 }
 
+// ---- launchers: the plan's ops and the single-kernel entry points (include/k22.h) go through the same code ------------------------------
+int launch_enc_layernorm(const float* x, int64_t ldx, const float* g, const float* b, float* yf, int64_t ldyf, void* yt, int rows, int D,
+                         float eps, int dt, hipStream_t st) {
+  if (yt != nullptr && dt == K22_BF16)
+    hipLaunchKernelGGL(enc_layernorm_kernel<bf16_t>, dim3(rows), dim3(256), 0, st, x, ldx, g, b, yf, ldyf, reinterpret_cast<bf16_t*>(yt), (int64_t)D, D, eps);
+  else if (yt != nullptr && dt == K22_F16)
+    hipLaunchKernelGGL(enc_layernorm_kernel<f16_t>, dim3(rows), dim3(256), 0, st, x, ldx, g, b, yf, ldyf, reinterpret_cast<f16_t*>(yt), (int64_t)D, D, eps);
+  else
+    hipLaunchKernelGGL(enc_layernorm_kernel<float>, dim3(rows), dim3(256), 0, st, x, ldx, g, b, yf, ldyf, reinterpret_cast<float*>(yt), (int64_t)D, D, eps);
+  K22_CHECK_LAUNCH();
+  return K22_OK;
+}
+int launch_enc_embed(const int* tok, const float* te, const float* pe, const float* ty, float* x, int B, int n, int D, int vocab, int xlmr,
+                     int pad, int maxp, hipStream_t st) {
+  hipLaunchKernelGGL(enc_embed_kernel, dim3(n, B), dim3(256), 0, st, tok, te, pe, ty, x, n, D, vocab, xlmr ? 1 : 0, pad, maxp);
+  K22_CHECK_LAUNCH();
+  return K22_OK;
+}
+int launch_enc_gather_eot(const int* tok, const float* x, float* out, int B, int n, int D, hipStream_t st) {
+  hipLaunchKernelGGL(enc_gather_eot_kernel, dim3(B), dim3(256), 0, st, tok, x, out, n, D);
+  K22_CHECK_LAUNCH();
+  return K22_OK;
+}
+int launch_enc_masked_mean(const float* x, const float* mask, float* out, int B, int n, int D, hipStream_t st) {
+  hipLaunchKernelGGL(enc_masked_mean_kernel, dim3(B), dim3(256), 0, st, x, mask, out, n, D);
+  K22_CHECK_LAUNCH();
+  return K22_OK;
+}
+int launch_enc_patchify(const float* img, void* out, int B, int S, int patch, int Kp, int dt, hipStream_t st) {
+  const int g = S / patch, P = g * g;
+  if (dt == K22_BF16) hipLaunchKernelGGL(enc_patchify_kernel<bf16_t>, dim3(B * P), dim3(256), 0, st, img, reinterpret_cast<bf16_t*>(out), S, patch, Kp);
+  else if (dt == K22_F16) hipLaunchKernelGGL(enc_patchify_kernel<f16_t>, dim3(B * P), dim3(256), 0, st, img, reinterpret_cast<f16_t*>(out), S, patch, Kp);
+  else hipLaunchKernelGGL(enc_patchify_kernel<float>, dim3(B * P), dim3(256), 0, st, img, reinterpret_cast<float*>(out), S, patch, Kp);
+  K22_CHECK_LAUNCH();
+  return K22_OK;
+}
+int launch_enc_vision_assemble(const float* patch_out, const float* cls, const float* pos, float* x, int B, int P, int D, hipStream_t st) {
+  hipLaunchKernelGGL(enc_vision_assemble_kernel, dim3(P + 1, B), dim3(256), 0, st, patch_out, cls, pos, x, P, D);
+  K22_CHECK_LAUNCH();
+  return K22_OK;
+}
+int launch_enc_mlp_act(const float* x, void* y, int64_t nel, int exact, int dt, hipStream_t st) {
+  const int nb = (int)((nel + 255) / 256 < 4096 ? (nel + 255) / 256 : 4096);
+  if (dt == K22_BF16) hipLaunchKernelGGL(enc_quickgelu_kernel<bf16_t>, dim3(nb), dim3(256), 0, st, x, reinterpret_cast<bf16_t*>(y), nel, exact);
+  else if (dt == K22_F16) hipLaunchKernelGGL(enc_quickgelu_kernel<f16_t>, dim3(nb), dim3(256), 0, st, x, reinterpret_cast<f16_t*>(y), nel, exact);
+  else hipLaunchKernelGGL(enc_quickgelu_kernel<float>, dim3(nb), dim3(256), 0, st, x, reinterpret_cast<float*>(y), nel, exact);
+  K22_CHECK_LAUNCH();
+  return K22_OK;
+}
+// dynamic LDS of enc_attention_generic_kernel: K (and V for the 16-bit types) rows of hd + 2 elements, then [4 waves][128 + 512] fp32
+size_t enc_ga_smem(int n, int hd, size_t esz) { return ((size_t)n * (hd + 2) * esz * (esz == 2 ? 2 : 1) + 15) / 16 * 16 + 4 * 640 * 4; }
+// what the kernel is built for: q rows of <= 128 channels and <= 512 scores per wave in the LDS, everything within 160 KB
+bool enc_ga_admits(int n, int hd, size_t esz) { return hd <= 128 && n <= 512 && enc_ga_smem(n, hd, esz) <= 160 * 1024; }
+int launch_enc_attention_generic(const void* qkv, void* out, int B, int heads, int n, int hd, int dt, hipStream_t st) {
+  const int D = heads * hd;
+  const size_t smem = enc_ga_smem(n, hd, dt == K22_F32 ? 4 : 2);
+  const float sc = 1.0f / sqrtf((float)hd);
+  dim3 grid((n + 15) / 16, heads, B);
+#define K22_GA(TT_)                                                                                                              \
+  {                                                                                                                      \
+    static LdsAttrGuard guard;                                                                                           \
+    if (int rc_ = k22_ensure_lds_attr(guard, reinterpret_cast<const void*>(&enc_attention_generic_kernel<TT_>), 160 * 1024, __FILE__, __LINE__)) return rc_; \
+    hipLaunchKernelGGL(enc_attention_generic_kernel<TT_>, grid, dim3(256), smem, st, reinterpret_cast<const TT_*>(qkv), reinterpret_cast<TT_*>(out), n, D, hd, sc);  \
+  }
+  if (dt == K22_BF16) K22_GA(bf16_t) else if (dt == K22_F16) K22_GA(f16_t) else K22_GA(float)
+#undef K22_GA
+  K22_CHECK_LAUNCH();
+  return K22_OK;
+}
+
 typedef std::function<int(hipStream_t)> EOp;
 }  // namespace
 
@@ -248,15 +318,7 @@ struct K22Encoder : GraphPlan {   // tuned: every transformer Linear; graph: the
     const float eps = cfg.ln_eps;
     ops.push_back([=](hipStream_t st) {
       const float* xp = reinterpret_cast<const float*>(ptr(x) + x_off);
-      float* f = yf ? ptr<float>(yf) : nullptr;
-      if (yt != nullptr && dt == K22_BF16)
-        hipLaunchKernelGGL(enc_layernorm_kernel<bf16_t>, dim3(rows), dim3(256), 0, st, xp, ldx, g, b, f, ldyf, ptr<bf16_t>(yt), (int64_t)D, D, eps);
-      else if (yt != nullptr && dt == K22_F16)
-        hipLaunchKernelGGL(enc_layernorm_kernel<f16_t>, dim3(rows), dim3(256), 0, st, xp, ldx, g, b, f, ldyf, ptr<f16_t>(yt), (int64_t)D, D, eps);
-      else
-        hipLaunchKernelGGL(enc_layernorm_kernel<float>, dim3(rows), dim3(256), 0, st, xp, ldx, g, b, f, ldyf, yt ? ptr<float>(yt) : nullptr, (int64_t)D, D, eps);
-      K22_CHECK_LAUNCH();
-      return K22_OK;
+      return launch_enc_layernorm(xp, ldx, g, b, yf ? ptr<float>(yf) : nullptr, ldyf, yt ? ptr(yt) : nullptr, rows, D, eps, dt, st);
     });
   }
 
@@ -266,8 +328,7 @@ struct K22Encoder : GraphPlan {   // tuned: every transformer Linear; graph: the
     if (D < 64 || D % 64 || D > 2048 || heads < 1 || D % heads) return k22_set_error(K22_EINVAL, "encoder: width % 64 == 0, width <= 2048, width % heads == 0");
     const int hd = D / heads;
     const bool flash = hd == 64;       // the UNet's flash attention kernel; anything else: enc_attention_generic_kernel (vision tower only)
-    const size_t ga_smem = ((size_t)n * (hd + 2) * esz * (esz == 2 ? 2 : 1) + 15) / 16 * 16 + 4 * 640 * 4;   // enc_attention_generic_kernel
-    if (!flash && (cfg.kind != K22_ENC_CLIP_VISION || hd > 128 || n > 512 || ga_smem > 160 * 1024))
+    if (!flash && (cfg.kind != K22_ENC_CLIP_VISION || !enc_ga_admits(n, hd, esz)))
       return k22_set_error(K22_EINVAL, "encoder: head widths other than 64 are built for the vision tower (<= 128 per head, <= 512 tokens)");
     const int F = cfg.mlp_dim > 0 ? cfg.mlp_dim : 4 * D;
     if (F % 64) return k22_set_error(K22_EINVAL, "encoder: mlp_dim % 64");
@@ -300,13 +361,7 @@ struct K22Encoder : GraphPlan {   // tuned: every transformer Linear; graph: the
       const void* wp = W_("patch.weight");
       const float* cls = Wf("class_embedding"); const float* pos = Wf("positional_embedding");
       const int S = cfg.image_size, patch = cfg.patch;
-      ops.push_back([=](hipStream_t st) {
-        if (dt == K22_BF16) hipLaunchKernelGGL(enc_patchify_kernel<bf16_t>, dim3(Bn * P), dim3(256), 0, st, ptr<float>(s_img), ptr<bf16_t>(s_patch), S, patch, Kp);
-        else if (dt == K22_F16) hipLaunchKernelGGL(enc_patchify_kernel<f16_t>, dim3(Bn * P), dim3(256), 0, st, ptr<float>(s_img), ptr<f16_t>(s_patch), S, patch, Kp);
-        else hipLaunchKernelGGL(enc_patchify_kernel<float>, dim3(Bn * P), dim3(256), 0, st, ptr<float>(s_img), ptr<float>(s_patch), S, patch, Kp);
-        K22_CHECK_LAUNCH();
-        return K22_OK;
-      });
+      ops.push_back([=](hipStream_t st) { return launch_enc_patchify(ptr<float>(s_img), ptr(s_patch), Bn, S, patch, Kp, dt, st); });
       {
         IgemmParams p = {};
         p.stages = -1;
@@ -318,20 +373,14 @@ struct K22Encoder : GraphPlan {   // tuned: every transformer Linear; graph: the
           return launch_igemm(q, dt, st);
         });
       }
-      ops.push_back([=](hipStream_t st) {
-        hipLaunchKernelGGL(enc_vision_assemble_kernel, dim3(P + 1, Bn), dim3(256), 0, st, ptr<float>(s_pout), cls, pos, ptr<float>(s_inp), P, D);
-        K22_CHECK_LAUNCH();
-        return K22_OK;
-      });
+      ops.push_back([=](hipStream_t st) { return launch_enc_vision_assemble(ptr<float>(s_pout), cls, pos, ptr<float>(s_inp), Bn, P, D, st); });
       op_ln(s_inp, 0, D, M, "ln_pre", s_inp, D, nullptr);
     } else {
       const float* te = Wf("token_embedding"); const float* pe = Wf("positional_embedding");
       const float* ty = xlmr ? Wf("token_type_embedding") : nullptr;
       const int vocab = cfg.vocab, pad = cfg.pad_id, maxp = cfg.max_pos;
       ops.push_back([=](hipStream_t st) {
-        hipLaunchKernelGGL(enc_embed_kernel, dim3(n, Bn), dim3(256), 0, st, ptr<int>(s_tok), te, pe, ty, ptr<float>(s_inp), n, D, vocab, xlmr ? 1 : 0, pad, maxp);
-        K22_CHECK_LAUNCH();
-        return K22_OK;
+        return launch_enc_embed(ptr<int>(s_tok), te, pe, ty, ptr<float>(s_inp), Bn, n, D, vocab, xlmr ? 1 : 0, pad, maxp, st);
       });
       if (xlmr) op_ln(s_inp, 0, D, M, "embeddings_ln", s_inp, D, s_ln);
     }
@@ -347,21 +396,7 @@ struct K22Encoder : GraphPlan {   // tuned: every transformer Linear; graph: the
       op_linear(s_ln, M, 3 * D, D, pfx + ".qkv", K22_ACT_NONE, s_qkv, 3 * D, 0);
       const int causal = kind == K22_ENC_CLIP_TEXT ? 1 : 0;
       if (!flash) {
-        const size_t smem = ga_smem;
-        const float sc = 1.0f / sqrtf((float)hd);
-        ops.push_back([=](hipStream_t st) {
-          dim3 grid((n + 15) / 16, heads, Bn);
-#define K22_GA(TT_)                                                                                                              \
-          {                                                                                                                      \
-            static LdsAttrGuard guard;                                                                                           \
-            if (int rc_ = k22_ensure_lds_attr(guard, reinterpret_cast<const void*>(&enc_attention_generic_kernel<TT_>), 160 * 1024, __FILE__, __LINE__)) return rc_; \
-            hipLaunchKernelGGL(enc_attention_generic_kernel<TT_>, grid, dim3(256), smem, st, ptr<TT_>(s_qkv), ptr<TT_>(s_att), n, D, hd, sc);  \
-          }
-          if (dt == K22_BF16) K22_GA(bf16_t) else if (dt == K22_F16) K22_GA(f16_t) else K22_GA(float)
-#undef K22_GA
-          K22_CHECK_LAUNCH();
-          return K22_OK;
-        });
+        ops.push_back([=](hipStream_t st) { return launch_enc_attention_generic(ptr(s_qkv), ptr(s_att), Bn, heads, n, hd, dt, st); });
       } else
       ops.push_back([=](hipStream_t st) {
         KvPackParams kp;
@@ -388,14 +423,7 @@ struct K22Encoder : GraphPlan {   // tuned: every transformer Linear; graph: the
         op_linear(s_ln, M, F, D, pfx + ".fc", K22_ACT_NONE, s_fc32, F, 1);
         const int64_t nel = (int64_t)M * F;
         const int exact = cfg.hidden_act == 1 ? 1 : 0;
-        ops.push_back([=](hipStream_t st) {
-          const int nb = (int)((nel + 255) / 256 < 4096 ? (nel + 255) / 256 : 4096);
-          if (dt == K22_BF16) hipLaunchKernelGGL(enc_quickgelu_kernel<bf16_t>, dim3(nb), dim3(256), 0, st, ptr<float>(s_fc32), ptr<bf16_t>(s_fc), nel, exact);
-          else if (dt == K22_F16) hipLaunchKernelGGL(enc_quickgelu_kernel<f16_t>, dim3(nb), dim3(256), 0, st, ptr<float>(s_fc32), ptr<f16_t>(s_fc), nel, exact);
-          else hipLaunchKernelGGL(enc_quickgelu_kernel<float>, dim3(nb), dim3(256), 0, st, ptr<float>(s_fc32), ptr<float>(s_fc), nel, exact);
-          K22_CHECK_LAUNCH();
-          return K22_OK;
-        });
+        ops.push_back([=](hipStream_t st) { return launch_enc_mlp_act(ptr<float>(s_fc32), ptr(s_fc), nel, exact, dt, st); });
         op_linear(s_fc, M, D, F, pfx + ".out", K22_ACT_NONE, s_inp, D, 2);
       }
     }
@@ -404,20 +432,14 @@ struct K22Encoder : GraphPlan {   // tuned: every transformer Linear; graph: the
     const float* hb = xlmr ? Wf("head.bias") : nullptr;
     if (kind == K22_ENC_CLIP_TEXT) {
       op_ln(s_inp, 0, D, M, "ln_final", s_seq, D, nullptr);
-      ops.push_back([=](hipStream_t st) {
-        hipLaunchKernelGGL(enc_gather_eot_kernel, dim3(Bn), dim3(256), 0, st, ptr<int>(s_tok), ptr<float>(s_seq), ptr<float>(s_pool_in), n, D);
-        K22_CHECK_LAUNCH();
-        return K22_OK;
-      });
+      ops.push_back([=](hipStream_t st) { return launch_enc_gather_eot(ptr<int>(s_tok), ptr<float>(s_seq), ptr<float>(s_pool_in), Bn, n, D, st); });
     } else if (vision) {
       op_ln(s_inp, 0, (int64_t)n * D, B, "ln_post", s_pool_in, D, nullptr);      // class-token rows only
     } else {
       ops.push_back([=](hipStream_t st) {
         hipError_t e = hipMemcpyAsync(ptr(s_seq), ptr(s_inp), (size_t)M * D * 4, hipMemcpyDeviceToDevice, st);
         if (e != hipSuccess) return k22_set_error_hip(e, __FILE__, __LINE__);
-        hipLaunchKernelGGL(enc_masked_mean_kernel, dim3(Bn), dim3(256), 0, st, ptr<float>(s_inp), ptr<float>(s_valid), ptr<float>(s_pool_in), n, D);
-        K22_CHECK_LAUNCH();
-        return K22_OK;
+        return launch_enc_masked_mean(ptr<float>(s_inp), ptr<float>(s_valid), ptr<float>(s_pool_in), Bn, n, D, st);
       });
     }
     ops.push_back([=](hipStream_t st) {
@@ -473,6 +495,51 @@ int k22_encoder_forward(K22Encoder* m, const int* tokens, const float* key_valid
   if (int rc = m->replay(m->graph, st, [m](hipStream_t s) { return m->run_ops(s); })) return rc;
   if (seq_out) { if (int rc = copy_d2d(seq_out, m->ptr(m->s_seq), M * c.width * 4, st)) return rc; }
   return copy_d2d(pooled_out, m->ptr(m->s_pooled), (size_t)m->B * c.out_dim * 4, st);
+}
+
+// ---- single-kernel entry points for the parity tests (include/k22.h); no product code calls them -------------------------------------
+static bool aux_dtype_ok(int dt) { return dt == K22_BF16 || dt == K22_F16 || dt == K22_F32; }
+
+int k22_enc_layernorm(const float* x, long ldx, const float* gain, const float* beta, float* out_f32, long ld_out, void* out_t, int rows,
+                      int D, float eps, int dtype, void* stream) {
+  if (!x || !gain || !beta || (!out_f32 && !out_t) || rows < 1 || D < 1 || ldx < D || (out_f32 && ld_out < D) || !aux_dtype_ok(dtype))
+    return k22_set_error(K22_EINVAL, "enc_layernorm: bad argument");
+  if (D > 2048) return k22_set_error(K22_EINVAL, "enc_layernorm: D <= 2048 (8 x 256 values per row)");
+  return launch_enc_layernorm(x, ldx, gain, beta, out_f32, ld_out, out_t, rows, D, eps, dtype, reinterpret_cast<hipStream_t>(stream));
+}
+int k22_enc_embed(const int* tokens, const float* tok_emb, const float* pos_emb, const float* type_emb, float* x, int B, int n_ctx, int D,
+                  int vocab, int xlmr, int pad_id, int max_pos, void* stream) {
+  if (!tokens || !tok_emb || !pos_emb || !x || B < 1 || B > 65535 || n_ctx < 1 || D < 1 || vocab < 1)
+    return k22_set_error(K22_EINVAL, "enc_embed: bad argument");
+  if (xlmr && (max_pos < 2 || pad_id < 0 || pad_id >= max_pos)) return k22_set_error(K22_EINVAL, "enc_embed: max_pos / pad_id");
+  return launch_enc_embed(tokens, tok_emb, pos_emb, type_emb, x, B, n_ctx, D, vocab, xlmr, pad_id, max_pos, reinterpret_cast<hipStream_t>(stream));
+}
+int k22_enc_gather_eot(const int* tokens, const float* x, float* out, int B, int n_ctx, int D, void* stream) {
+  if (!tokens || !x || !out || B < 1 || n_ctx < 1 || D < 1) return k22_set_error(K22_EINVAL, "enc_gather_eot: bad argument");
+  return launch_enc_gather_eot(tokens, x, out, B, n_ctx, D, reinterpret_cast<hipStream_t>(stream));
+}
+int k22_enc_masked_mean(const float* x, const float* mask, float* out, int B, int n_ctx, int D, void* stream) {
+  if (!x || !mask || !out || B < 1 || n_ctx < 1 || D < 1) return k22_set_error(K22_EINVAL, "enc_masked_mean: bad argument");
+  return launch_enc_masked_mean(x, mask, out, B, n_ctx, D, reinterpret_cast<hipStream_t>(stream));
+}
+int k22_enc_patchify(const float* image, void* out, int B, int S, int patch, int Kp, int dtype, void* stream) {
+  if (!image || !out || B < 1 || patch < 1 || S < patch || S % patch || Kp < 3 * patch * patch || !aux_dtype_ok(dtype))
+    return k22_set_error(K22_EINVAL, "enc_patchify: bad argument");
+  return launch_enc_patchify(image, out, B, S, patch, Kp, dtype, reinterpret_cast<hipStream_t>(stream));
+}
+int k22_enc_vision_assemble(const float* patch_out, const float* cls, const float* pos, float* x, int B, int P, int D, void* stream) {
+  if (!patch_out || !cls || !pos || !x || B < 1 || B > 65535 || P < 1 || D < 1) return k22_set_error(K22_EINVAL, "enc_vision_assemble: bad argument");
+  return launch_enc_vision_assemble(patch_out, cls, pos, x, B, P, D, reinterpret_cast<hipStream_t>(stream));
+}
+int k22_enc_mlp_act(const float* x, void* y, long n, int exact, int dtype, void* stream) {
+  if (!x || !y || n < 1 || !aux_dtype_ok(dtype)) return k22_set_error(K22_EINVAL, "enc_mlp_act: bad argument");
+  return launch_enc_mlp_act(x, y, n, exact ? 1 : 0, dtype, reinterpret_cast<hipStream_t>(stream));
+}
+int k22_enc_attention_generic(const void* qkv, void* out, int B, int heads, int n, int hd, int dtype, void* stream) {
+  if (!qkv || !out || B < 1 || B > 65535 || heads < 1 || heads > 65535 || !aux_dtype_ok(dtype)) return k22_set_error(K22_EINVAL, "enc_attention_generic: bad argument");
+  if (n < 1 || hd < 1 || !enc_ga_admits(n, hd, dtype == K22_F32 ? 4 : 2))
+    return k22_set_error(K22_EINVAL, "enc_attention_generic: <= 128 channels per head, <= 512 tokens, <= 160 KB of LDS");
+  return launch_enc_attention_generic(qkv, out, B, heads, n, hd, dtype, reinterpret_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -71,6 +71,28 @@ __global__ void prior_sampler_step_kernel(const float* x, const float* model_out
   x_out[i] = mean + tab[3] * expf(0.5f * tab[2]) * noise[i];
 }
 
+// ---- launchers: the plan's ops and the single-kernel entry points (include/k22.h) go through the same code ------------------
+static int launch_prior_layernorm(const float* x, int64_t ldx, const float* g, const float* b, void* y, int rows, int D, bool to_f32, int dt,
+                                  hipStream_t st) {
+  if (to_f32) hipLaunchKernelGGL(prior_layernorm_kernel<float>, dim3(rows), dim3(256), 0, st, x, ldx, g, b, reinterpret_cast<float*>(y), (int64_t)D, D, 1e-5f);
+  else if (dt == K22_BF16) hipLaunchKernelGGL(prior_layernorm_kernel<bf16_t>, dim3(rows), dim3(256), 0, st, x, ldx, g, b, reinterpret_cast<bf16_t*>(y), (int64_t)D, D, 1e-5f);
+  else if (dt == K22_F16) hipLaunchKernelGGL(prior_layernorm_kernel<f16_t>, dim3(rows), dim3(256), 0, st, x, ldx, g, b, reinterpret_cast<f16_t*>(y), (int64_t)D, D, 1e-5f);
+  else hipLaunchKernelGGL(prior_layernorm_kernel<float>, dim3(rows), dim3(256), 0, st, x, ldx, g, b, reinterpret_cast<float*>(y), (int64_t)D, D, 1e-5f);
+  K22_CHECK_LAUNCH();
+  return K22_OK;
+}
+static int launch_prior_finish_input(float* inp, const float* pos, const float* prd, int B, int n_ctx, int D, hipStream_t st) {
+  hipLaunchKernelGGL(prior_finish_input_kernel, dim3(256), dim3(256), 0, st, inp, pos, prd, B, n_ctx, D);
+  K22_CHECK_LAUNCH();
+  return K22_OK;
+}
+static int launch_prior_sampler_step(const float* x, const float* model_out, const float* noise, const float* scales, const float* tab, float clamp,
+                                     float* x_out, int bs, int D, hipStream_t st) {
+  hipLaunchKernelGGL(prior_sampler_step_kernel, dim3((2 * bs * D + 255) / 256), dim3(256), 0, st, x, model_out, noise, scales, tab, clamp, x_out, bs, D);
+  K22_CHECK_LAUNCH();
+  return K22_OK;
+}
+
 namespace {
 typedef std::function<int(hipStream_t)> POp;
 }  // namespace
@@ -104,12 +126,7 @@ struct K22Prior : GraphPlan {   // tuned: every transformer Linear; graph: the ~
     const int D = cfg.xf_width, dt = dtype;
     ops.push_back([=](hipStream_t st) {
       const float* xp = reinterpret_cast<const float*>(ptr(x) + x_off);
-      if (to_f32) hipLaunchKernelGGL(prior_layernorm_kernel<float>, dim3(rows), dim3(256), 0, st, xp, ldx, g, b, ptr<float>(y), (int64_t)D, D, 1e-5f);
-      else if (dt == K22_BF16) hipLaunchKernelGGL(prior_layernorm_kernel<bf16_t>, dim3(rows), dim3(256), 0, st, xp, ldx, g, b, ptr<bf16_t>(y), (int64_t)D, D, 1e-5f);
-      else if (dt == K22_F16) hipLaunchKernelGGL(prior_layernorm_kernel<f16_t>, dim3(rows), dim3(256), 0, st, xp, ldx, g, b, ptr<f16_t>(y), (int64_t)D, D, 1e-5f);
-      else hipLaunchKernelGGL(prior_layernorm_kernel<float>, dim3(rows), dim3(256), 0, st, xp, ldx, g, b, ptr<float>(y), (int64_t)D, D, 1e-5f);
-      K22_CHECK_LAUNCH();
-      return K22_OK;
+      return launch_prior_layernorm(xp, ldx, g, b, ptr(y), rows, D, to_f32, dt, st);
     });
   }
 
@@ -210,11 +227,7 @@ struct K22Prior : GraphPlan {   // tuned: every transformer Linear; graph: the ~
         });
       }
       const float* pos = Wf("positional_embedding"); const float* prd = Wf("prd_emb");
-      ops.push_back([=](hipStream_t st) {
-        hipLaunchKernelGGL(prior_finish_input_kernel, dim3(256), dim3(256), 0, st, ptr<float>(s_inp), pos, prd, Bn, nc, D);
-        K22_CHECK_LAUNCH();
-        return K22_OK;
-      });
+      ops.push_back([=](hipStream_t st) { return launch_prior_finish_input(ptr<float>(s_inp), pos, prd, Bn, nc, D, st); });
     }
     // ---- transformer (prior.py:105-155) ------------------------------------------------------------------
     if (skinny) {
@@ -352,10 +365,19 @@ int k22_prior_forward(K22Prior* m, const float* x, const float* timesteps, const
 int k22_prior_sampler_step(const float* x, const float* model_out, const float* noise, const float* scales, const float* table_row,
                            float clamp, float* x_out, int bs, int D, void* stream) {
   if (!x || !model_out || !noise || !scales || !table_row || !x_out || bs < 1 || D < 1) return k22_set_error(K22_EINVAL, "prior_sampler_step: bad argument");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(prior_sampler_step_kernel, dim3((2 * bs * D + 255) / 256), dim3(256), 0, st, x, model_out, noise, scales, table_row, clamp, x_out, bs, D);
-  K22_CHECK_LAUNCH();
-  return K22_OK;
+  return launch_prior_sampler_step(x, model_out, noise, scales, table_row, clamp, x_out, bs, D, reinterpret_cast<hipStream_t>(stream));
+}
+
+// ---- single-kernel entry points for the parity tests (include/k22.h); no product code calls them -------------------------
+int k22_prior_layernorm(const float* x, long ldx, const float* gain, const float* beta, void* y, int rows, int D, int to_f32, int dtype,
+                        void* stream) {
+  if (!x || !gain || !beta || !y || rows < 1 || D < 1 || ldx < D || (dtype != K22_BF16 && dtype != K22_F16 && dtype != K22_F32))
+    return k22_set_error(K22_EINVAL, "prior_layernorm: bad argument");
+  return launch_prior_layernorm(x, ldx, gain, beta, y, rows, D, to_f32 != 0, dtype, reinterpret_cast<hipStream_t>(stream));
+}
+int k22_prior_finish_input(float* inp, const float* pos, const float* prd, int B, int n_ctx, int D, void* stream) {
+  if (!inp || !pos || !prd || B < 1 || n_ctx < 1 || D < 1) return k22_set_error(K22_EINVAL, "prior_finish_input: bad argument");
+  return launch_prior_finish_input(inp, pos, prd, B, n_ctx, D, reinterpret_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"
