@@ -72,7 +72,8 @@ const char* k22_last_error(void);
  * 2 LDS-resident halo kernel for the 3x3 convolutions (3-7: its variants, see conv3_halo.hip; 8-9: measurement only);
  * "gemm_algo" = 0 generic implicit-GEMM kernel, 10 = 8-wave BM x 128 tile kernel where it applies;
  * "conv_algo" / "gemm_algo" = 20: the weight-streaming small-M kernel (stream_gemm.hip; bm = 160 / 288 picks 5 / 9 m-blocks
- * per workgroup, needs the fp32 partial buffer also for splitk == 1). */
+ * per workgroup, needs the fp32 partial buffer also for splitk == 1);
+ * "att_pipe" = -1 as K22_ATT_PIPE says (default), 0 / 1: the unmasked 16-bit attention through attention_kernel / attention_pipe_kernel. */
 int k22_set_option(const char* name, int value);
 /* Host counters for tests, since the library was loaded: "stream_launches" = launches of the weight-streaming kernel;
  * "loop_captures" = whole-loop graphs captured by any loop entry (k22_unet_sample_loop, k22_unet_ddim_loop); "loop_launches" = whole-loop
@@ -596,6 +597,17 @@ int k22_enc_attention_generic(const void* qkv, void* out, int B, int heads, int 
 int k22_prior_layernorm(const float* x, long ldx, const float* gain, const float* beta, void* y, int rows, int D, int to_f32, int dtype,
                         void* stream);
 int k22_prior_finish_input(float* inp, const float* pos, const float* prd, int B, int n_ctx, int D, void* stream);
+/* Flash attention with the mask and output-format fields the engines set (csrc/attention.hip; tests/test_attention_parity_gpu.py,
+ * tests/attention_ref.py).  k22_attention's sequence - kv_pack, then launch_attention - and its tensors (ctxkv may be null when S == 0;
+ * dtype: all five arithmetics, fp32 tensors for the split ones), plus
+ *   causal     key j is dead for query t when j > t (the CLIP text tower, the prior); compares key index with query index: S must be 0
+ *   key_valid  optional fp32 [B][kv_n]: 0 = key dead for every query of the image; keys >= kv_n are alive (the prior's appended tokens)
+ *   out_x3     split dtypes only: `out` is written as x3 chunks (what the proj_out GEMM of the split engines reads)
+ * K22_EINVAL with nothing launched for causal && S != 0, kv_n > S + T, out_x3 with a non-split dtype.
+ * PRECONDITION, met by every engine: each query keeps at least one alive key, i.e. key 0 is valid (causal keeps key 0 for query 0).  A row
+ * without one is 0 * inf. */
+int k22_attention_masked(const void* qkv, const void* ctxkv, void* kall, void* vtall, void* out, int B, int H, int T, int S, int causal,
+                         const float* key_valid, int kv_n, int out_x3, int dtype, void* stream);
 
 #ifdef __cplusplus
 }

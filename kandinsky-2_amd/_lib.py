@@ -183,6 +183,7 @@ SIGNATURES = {
     "k22_enc_attention_generic": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
     "k22_prior_layernorm": (_I, [_P, _L, _P, _P, _P, _I, _I, _I, _I, _P]),
     "k22_prior_finish_input": (_I, [_P, _P, _P, _I, _I, _I, _P]),
+    "k22_attention_masked": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _P]),
 }
 
 _lib = None

@@ -13,6 +13,7 @@
 // K_all / V^T_all are produced by kv_pack_kernel (elementwise.hip), zero padded to 64 keys.
 #include "kernels.h"
 #include "elementwise.h"
+#include <atomic>
 #include <type_traits>
 #include <stdlib.h>
 
@@ -57,8 +58,14 @@ __device__ __forceinline__ void ld_frag_split(Frag<x3_t>& f, const char* tile, i
   f.hi = u32x4_t{h0.x, h0.y, h1.x, h1.y};
   f.lo = u32x4_t{l0.x, l0.y, l1.x, l1.y};
 }
+// P (<= 1) is split as 2^10 P: the lo half of an unscaled probability under 2^-3 is a fp16 subnormal, i.e. P carried to 2^-25 ABSOLUTE
+// (common.h, "x3 chunk") where the arithmetic promises 2^-22 relative - on a row whose heavy keys have a small V element the many light
+// keys then decide the error (tests/test_attention_parity_gpu.py: 1.03 of the float64 bound at T = 81, causal, before).  The exact power
+// of two comes out of the accumulators with 1 / l (K22_ATT_X3_PSCALE_INV below); 2^10 P <= 1024 is far inside fp16's range.
+constexpr float K22_ATT_X3_PSCALE = 1024.f, K22_ATT_X3_PSCALE_INV = 1.f / 1024.f;
 __device__ __forceinline__ void make_pfrag(Frag<x3_t>& f, const float* p) {
-  x3_frag_from_f32(f, make_float4(p[0], p[1], p[2], p[3]), make_float4(p[4], p[5], p[6], p[7]));
+  constexpr float c = K22_ATT_X3_PSCALE;
+  x3_frag_from_f32(f, make_float4(c * p[0], c * p[1], c * p[2], c * p[3]), make_float4(c * p[4], c * p[5], c * p[6], c * p[7]));
 }
 __device__ __forceinline__ void ld_qfrag(Frag<x3_t>& f, const x3_t* p) {
   x3_frag_from_f32(f, *reinterpret_cast<const float4*>(p), *reinterpret_cast<const float4*>(p + 4));
@@ -289,7 +296,7 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(AttentionParams p) {
   }
 
   const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-  const float inv = 1.f / l_tot;
+  const float inv = (std::is_same<T, x3_t>::value ? K22_ATT_X3_PSCALE_INV : 1.f) / l_tot;   // x3: the accumulators hold 2^10 P V (make_pfrag)
   if (t < p.T) {
     TG* orow = reinterpret_cast<TG*>(p.out) + (int64_t)(b * p.T + t) * p.ldo + hd * 64;
 #pragma unroll
@@ -732,11 +739,18 @@ int launch_small_attention(const SmallAttnParams& p, int dtype, hipStream_t s) {
   return K22_OK;
 }
 
+// kernel choice of the unmasked 16-bit attention: -1 = as K22_ATT_PIPE says (the default), 0 = attention_kernel, 1 = attention_pipe_kernel
+// (k22_set_option "att_pipe": the parity tests run both in one process)
+static std::atomic<int> g_att_pipe{-1};
+void attention_set_pipe(int v) { g_att_pipe.store((v == 0 || v == 1) ? v : -1, std::memory_order_relaxed); }
+
 int launch_attention(const AttentionParams& p, int dtype, hipStream_t s) {
   if (p.Tkp % 64 || p.Tkp < p.Tk) return k22_set_error(K22_EINVAL, "attention: Tkp must be roundup(Tk,64)");
   dim3 grid((p.T + 127) / 128, p.H, p.B);
   // the UNet's / MoVQ-free unmasked attention on 16-bit tiles: the software-pipelined kernel (K22_ATT_PIPE=0: attention_kernel, for A/B runs)
-  static const bool pipe = [] { const char* e = getenv("K22_ATT_PIPE"); return !(e && e[0] == '0'); }();
+  static const bool env_pipe = [] { const char* e = getenv("K22_ATT_PIPE"); return !(e && e[0] == '0'); }();
+  const int knob = g_att_pipe.load(std::memory_order_relaxed);
+  const bool pipe = knob < 0 ? env_pipe : knob != 0;
   if (pipe && !p.causal && p.key_valid == nullptr && (dtype == K22_BF16 || dtype == K22_F16 || dtype == K22_F16X2)) {
     const dim3 g1(grid.x * grid.y * grid.z);   // 1-D: the kernel maps workgroups to (image, head, query block) itself (XCD-aware)
     if (dtype == K22_BF16) hipLaunchKernelGGL(attention_pipe_kernel<bf16_t>, g1, dim3(256), 0, s, p);

@@ -38,6 +38,7 @@ int k22_set_option(const char* name, int value) {
   if (name && !strcmp(name, "igemm_xcd_remap")) { igemm_set_xcd_remap(value); return K22_OK; }
   if (name && !strcmp(name, "conv_algo")) { igemm_set_conv_algo(value); return K22_OK; }
   if (name && !strcmp(name, "gemm_algo")) { igemm_set_gemm_algo(value); return K22_OK; }
+  if (name && !strcmp(name, "att_pipe")) { attention_set_pipe(value); return K22_OK; }
   return k22_set_error(K22_EINVAL, "k22_set_option: unknown option");
 }
 const char* k22_last_error(void) { return g_err; }
@@ -529,6 +530,26 @@ int k22_movq_quant_conv(const float* h, const float* wq, const float* bq, float*
 int k22_to_uint8_nhwc(const float* x, unsigned char* y, int B, int C, int H, int W, void* stream) {
   if (!x || !y || B < 1 || C < 1 || H < 1 || W < 1) return k22_set_error(K22_EINVAL, "to_uint8_nhwc: bad argument");
   return launch_to_uint8_nhwc(x, y, B, C, H, W, reinterpret_cast<hipStream_t>(stream));
+}
+// k22_attention's sequence (kv_pack, then attention) with the mask and output-format fields of AttentionParams the engines set
+int k22_attention_masked(const void* qkv, const void* ctxkv, void* kall, void* vtall, void* out, int B, int H, int T, int S, int causal,
+                         const float* key_valid, int kv_n, int out_x3, int dtype, void* stream) {
+  if (!qkv || !kall || !vtall || !out || B < 1 || H < 1 || T < 1 || S < 0 || kv_n < 0 || (S > 0 && !ctxkv) || !(aux_dtype_ok(dtype) || k22_is_split(dtype)))
+    return k22_set_error(K22_EINVAL, "attention_masked: bad argument");
+  if (causal && S != 0) return k22_set_error(K22_EINVAL, "attention_masked: causal needs S == 0 (key index against query index)");
+  if (kv_n > S + T) return k22_set_error(K22_EINVAL, "attention_masked: kv_n > S + T");
+  if (out_x3 && !k22_is_split(dtype)) return k22_set_error(K22_EINVAL, "attention_masked: out_x3 needs a split dtype");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int C = H * 64, Tk = S + T, Tkp = (Tk + 63) / 64 * 64;
+  KvPackParams kp;
+  kp.qkv = qkv; kp.ctxkv = ctxkv; kp.kall = kall; kp.vtall = vtall; kp.B = B; kp.H = H; kp.T = T; kp.S = S; kp.Tkp = Tkp;
+  int rc = launch_kv_pack(kp, k22_storage_dtype(dtype), st);
+  if (rc) return rc;
+  AttentionParams ap = {};
+  ap.q = qkv; ap.ldq = 3 * C; ap.kall = kall; ap.vtall = vtall; ap.out = out; ap.ldo = C;
+  ap.B = B; ap.H = H; ap.T = T; ap.Tk = Tk; ap.Tkp = Tkp; ap.scale = 0.125f;
+  ap.causal = causal ? 1 : 0; ap.key_valid = key_valid; ap.kv_ld = kv_n; ap.kv_n = kv_n; ap.out_x3 = out_x3 ? 1 : 0;
+  return launch_attention(ap, dtype, st);
 }
 
 }  // extern "C"

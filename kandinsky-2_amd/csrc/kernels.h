@@ -123,4 +123,5 @@ void igemm_set_gemm_algo(int v);
 void igemm_set_conv_algo(int v);       // tuning knob: 0 auto, 1 generic, 2 halo
 void igemm_set_default_stages(int v);  // tuning knob: 2..4 LDS-DMA stages, -1 env/default
 void igemm_set_xcd_remap(int v);       // tuning knob: XCD-aware block renumbering (default on)
+void attention_set_pipe(int v);        // test knob: -1 K22_ATT_PIPE / default, 0 attention_kernel, 1 attention_pipe_kernel (unmasked 16-bit attention)
 int igemm_choose_splitk(const IgemmParams& p, int dtype);  // split-K factor the heuristic picks (scratch = splitk*M*N*4 B)
