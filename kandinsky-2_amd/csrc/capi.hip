@@ -153,12 +153,10 @@ void k22_tile_table_clear(void) {
 int k22_gemm(const void* A0, const void* A1, const void* Wp, const float* bias, const void* residual, void* out,
              void* partial, int M, int N, int Npad, int K0, int K1, long lda0, long lda1, int ldo, int ldr,
              int out_f32, int act, int splitk, int bm, int bn, int dtype, void* stream) {
-  IgemmParams p = {};
-    p.stages = -1;
+  IgemmParams p = igemm_gemm_problem(M, N, K0, K1, out_f32 ? IG_OUT_ROWMAJOR_F32 : IG_OUT_ROWMAJOR, act);
   p.A0 = A0; p.A1 = A1; p.Wp = Wp; p.bias = bias; p.residual = residual; p.out = out;
   p.partial = reinterpret_cast<float*>(partial);
-  p.M = M; p.N = N; p.Npad = Npad; p.Kc = K0 + K1; p.K0 = K0; p.taps = 1; p.lda0 = lda0; p.lda1 = lda1;
-  p.ldo = ldo; p.ldr = ldr; p.out_mode = out_f32 ? IG_OUT_ROWMAJOR_F32 : IG_OUT_ROWMAJOR; p.act = act;
+  p.Npad = Npad; p.lda0 = lda0; p.lda1 = lda1; p.ldo = ldo; p.ldr = ldr;   // the caller's own padding and strides
   p.splitk = splitk; p.force_bm = bm; p.force_bn = bn;
   p.a_raw = k22_is_split(dtype) ? 1 : 0;   // unit entry: A0 / A1 are plain fp32 rows (the engine feeds x3 chunks where its own kernels produce A)
   if (p.splitk == 0) p.splitk = partial ? igemm_choose_splitk(p, dtype) : 1;
@@ -174,12 +172,10 @@ int k22_x3_pack(const float* src, void* dst, long n, float scale, void* stream) 
 int k22_conv3x3(const void* x_padded, const void* Wp, const float* bias, const void* residual, void* out,
                 void* partial, int B, int H, int W, int Cin, int Cout, int Npad, int out_mode, int act, int splitk,
                 int bm, int bn, int dtype, void* stream) {
-  IgemmParams p = {};
-    p.stages = -1;
+  IgemmParams p = igemm_conv3_problem(B, H, W, Cin, Cout, out_mode, act);
   p.A0 = x_padded; p.Wp = Wp; p.bias = bias; p.residual = residual; p.out = out;
   p.partial = reinterpret_cast<float*>(partial);
-  p.M = B * H * W; p.N = Cout; p.Npad = Npad; p.Kc = Cin; p.K0 = Cin; p.taps = 9; p.H = H; p.W = W;
-  p.ldo = Cout; p.ldr = Cout; p.out_mode = out_mode; p.act = act; p.splitk = splitk; p.force_bm = bm; p.force_bn = bn;
+  p.Npad = Npad; p.splitk = splitk; p.force_bm = bm; p.force_bn = bn;
   if (p.splitk == 0) p.splitk = partial ? igemm_choose_splitk(p, dtype) : 1;
   K22_DBG_FRAG(p);
   return launch_igemm(p, dtype, reinterpret_cast<hipStream_t>(stream));
@@ -188,12 +184,10 @@ int k22_conv3x3(const void* x_padded, const void* Wp, const float* bias, const v
 int k22_conv3x3_gnstats(const void* x_padded, const void* Wp, const float* bias, const void* residual, void* out,
                         void* partial, int B, int H, int W, int Cin, int Cout, int Npad, int splitk, int bm, int bn,
                         float* stats, int stats_capacity_rows, int* rows_per_image, int dtype, void* stream) {
-  IgemmParams p = {};
-  p.stages = -1;
+  IgemmParams p = igemm_conv3_problem(B, H, W, Cin, Cout);
   p.A0 = x_padded; p.Wp = Wp; p.bias = bias; p.residual = residual; p.out = out;
   p.partial = reinterpret_cast<float*>(partial);
-  p.M = B * H * W; p.N = Cout; p.Npad = Npad; p.Kc = Cin; p.K0 = Cin; p.taps = 9; p.H = H; p.W = W;
-  p.ldo = Cout; p.ldr = Cout; p.out_mode = IG_OUT_ROWMAJOR; p.act = K22_ACT_NONE; p.splitk = splitk; p.force_bm = bm; p.force_bn = bn;
+  p.Npad = Npad; p.splitk = splitk; p.force_bm = bm; p.force_bn = bn;
   if (p.splitk == 0) p.splitk = partial ? igemm_choose_splitk(p, dtype) : 1;
   const int rpi = igemm_stats_rows_per_image(p, dtype);
   if (rows_per_image) *rows_per_image = rpi;
@@ -207,12 +201,11 @@ int k22_conv3x3_gnstats(const void* x_padded, const void* Wp, const float* bias,
 int k22_gemm_gnstats(const void* A, const void* Wp, const float* bias, const void* residual, void* out, void* partial,
                      int B, int H, int W, int N, int Npad, int K, int splitk, int bm, float* stats,
                      int stats_capacity_rows, int* rows_per_image, int dtype, void* stream) {
-  IgemmParams p = {};
-  p.stages = -1;
+  IgemmParams p = igemm_gemm_problem(B * H * W, N, K, 0);
   p.A0 = A; p.Wp = Wp; p.bias = bias; p.residual = residual; p.out = out; p.partial = reinterpret_cast<float*>(partial);
-  p.M = B * H * W; p.N = N; p.Npad = Npad; p.Kc = K; p.K0 = K; p.taps = 1; p.H = H; p.W = W; p.lda0 = K;
-  p.ldo = N; p.ldr = N; p.out_mode = IG_OUT_ROWMAJOR; p.act = K22_ACT_NONE; p.splitk = splitk > 0 ? splitk : 1;
-  p.force_bm = bm; p.algo = (bm == 160 || bm == 288) ? 20 : 10;
+  p.Npad = Npad; p.H = H; p.W = W;   // rows per image
+  p.splitk = splitk > 0 ? splitk : 1;
+  p.force_bm = bm; p.algo = (bm == 160 || bm == 288) ? IG_ALGO_STREAM : IG_ALGO_GEMM8;
   p.a_raw = k22_is_split(dtype) ? 1 : 0;
   const int rpi = igemm_stats_rows_per_image(p, dtype);
   if (rows_per_image) *rows_per_image = rpi;
@@ -226,12 +219,10 @@ int k22_gemm_gnstats(const void* A, const void* Wp, const float* bias, const voi
 int k22_conv3x3_skip(const void* x_padded, const void* Wp, const float* bias, const void* skip0, const void* skip1,
                      int SK0, int SK1, const void* Ws, const float* bias_s, void* out, void* partial, int B, int H, int W,
                      int Cin, int Cout, int Npad, int splitk, int bm, int dtype, void* stream) {
-  IgemmParams p = {};
-  p.stages = -1;
+  IgemmParams p = igemm_conv3_problem(B, H, W, Cin, Cout);
   p.A0 = x_padded; p.Wp = Wp; p.bias = bias; p.out = out; p.partial = reinterpret_cast<float*>(partial);
-  p.M = B * H * W; p.N = Cout; p.Npad = Npad; p.Kc = Cin; p.K0 = Cin; p.taps = 9; p.H = H; p.W = W;
-  p.ldo = Cout; p.ldr = Cout; p.out_mode = IG_OUT_ROWMAJOR; p.act = K22_ACT_NONE; p.splitk = splitk; p.force_bm = bm; p.force_bn = 0;
-  p.S0 = skip0; p.S1 = skip1; p.SK0 = SK0; p.SK1 = SK1; p.Ws = Ws; p.bias2 = bias_s; p.algo = 0;  /* "conv_algo" option 3 selects the 64-byte-row halo kernel */
+  p.Npad = Npad; p.splitk = splitk; p.force_bm = bm;
+  p.S0 = skip0; p.S1 = skip1; p.SK0 = SK0; p.SK1 = SK1; p.Ws = Ws; p.bias2 = bias_s;   // (the "conv_algo" option selects among the halo kernels)
   if (p.splitk == 0) p.splitk = partial ? igemm_choose_splitk(p, dtype) : 1;
   K22_DBG_FRAG(p);
   return launch_igemm(p, dtype, reinterpret_cast<hipStream_t>(stream));
@@ -249,13 +240,16 @@ static int igemm_problem_tuned(const K22IgemmProblem& d, Tuned& t) {
   if (d.taps == 9 && (d.H <= 0 || d.W <= 0 || d.M % (d.H * d.W))) return k22_set_error(K22_EINVAL, "igemm_cfg: a convolution needs M = B * H * W");
   const void* mark = reinterpret_cast<const void*>(1);
   IgemmParams& p = t.p;
-  p = IgemmParams{};
-  p.stages = -1;
-  p.M = d.M; p.N = d.N; p.Npad = (d.N + 63) / 64 * 64; p.Kc = d.Kc; p.K0 = d.K0; p.taps = d.taps; p.H = d.H; p.W = d.W;
-  p.lda0 = d.K0; p.lda1 = d.Kc - d.K0;
+  if (d.taps == 9) {
+    p = igemm_conv3_problem(d.M / (d.H * d.W), d.H, d.W, d.Kc, d.N, d.out_mode, d.act);
+    p.K0 = d.K0;   // as the line spells it
+  } else {
+    p = igemm_gemm_problem(d.M, d.N, d.K0, d.Kc - d.K0, d.out_mode, d.act);
+    p.H = d.H; p.W = d.W;   // rows per image
+  }
   p.ldo = d.ldo > 0 ? d.ldo : (d.out_mode == IG_OUT_QKV ? d.N / 3 : d.N);
   p.ldr = d.ldr > 0 ? d.ldr : (d.res_f32 ? p.ldo : d.N);
-  p.out_mode = d.out_mode; p.act = d.act; p.res_f32 = d.res_f32 ? 1 : 0; p.a_raw = d.a_raw ? 1 : 0;
+  p.res_f32 = d.res_f32 ? 1 : 0; p.a_raw = d.a_raw ? 1 : 0;
   p.Wp = mark; p.bias = reinterpret_cast<const float*>(mark);
   if (d.SK0 > 0) { p.S0 = mark; p.S1 = d.SK1 > 0 ? mark : nullptr; p.SK0 = d.SK0; p.SK1 = d.SK1; p.Ws = mark; p.bias2 = reinterpret_cast<const float*>(mark); }
   if (d.out_mode == IG_OUT_QKV) { p.att_T = d.att_T; p.att_S = d.att_S; p.att_Tkp = d.att_Tkp; }
@@ -290,8 +284,8 @@ int k22_igemm_cfg(const K22IgemmProblem* pr, const K22IgemmOperands* ops, int* r
   if (d.K0 < d.Kc && !o.A1) return k22_set_error(K22_EINVAL, "igemm_cfg: A1 missing for the concat operand");
   if (d.SK0 > 0 && (!o.S0 || !o.Ws || (d.SK1 > 0 && !o.S1))) return k22_set_error(K22_EINVAL, "igemm_cfg: fused-skip operands missing");
   if (d.out_mode == IG_OUT_QKV && (!o.kall || !o.vtall)) return k22_set_error(K22_EINVAL, "igemm_cfg: kall / vtall missing");
-  if ((c.splitk > 1 || c.algo == 20) && !o.partial) return k22_set_error(K22_EINVAL, "igemm_cfg: the configuration needs the fp32 partial buffer");
-  if (c.algo == 20 && (!o.Wfrag || (d.SK0 > 0 && !o.Wsfrag))) return k22_set_error(K22_EINVAL, "igemm_cfg: algo 20 needs the fragment-major weights");
+  if ((c.splitk > 1 || c.algo == IG_ALGO_STREAM) && !o.partial) return k22_set_error(K22_EINVAL, "igemm_cfg: the configuration needs the fp32 partial buffer");
+  if (c.algo == IG_ALGO_STREAM && (!o.Wfrag || (d.SK0 > 0 && !o.Wsfrag))) return k22_set_error(K22_EINVAL, "igemm_cfg: algo 20 needs the fragment-major weights");
   IgemmParams q = t.p;
   tuned_apply_cfg(q, c);
   q.A0 = o.A0; q.A1 = o.A1; q.Wp = o.Wp; q.bias = reinterpret_cast<const float*>(o.bias); q.residual = o.residual; q.out = o.out;
@@ -299,7 +293,7 @@ int k22_igemm_cfg(const K22IgemmProblem* pr, const K22IgemmOperands* ops, int* r
   q.S0 = d.SK0 > 0 ? o.S0 : nullptr; q.S1 = d.SK1 > 0 ? o.S1 : nullptr; q.Ws = d.SK0 > 0 ? o.Ws : nullptr;
   q.bias2 = d.SK0 > 0 ? reinterpret_cast<const float*>(o.bias2) : nullptr;
   q.kall = o.kall; q.vtall = o.vtall;
-  q.Wfrag = c.algo == 20 ? o.Wfrag : nullptr; q.Wsfrag = (c.algo == 20 && d.SK0 > 0) ? o.Wsfrag : nullptr;
+  q.Wfrag = c.algo == IG_ALGO_STREAM ? o.Wfrag : nullptr; q.Wsfrag = (c.algo == IG_ALGO_STREAM && d.SK0 > 0) ? o.Wsfrag : nullptr;
   if (t.want_stats) {
     const int rpi = igemm_stats_rows_per_image(q, d.dtype);
     const int B = d.H > 0 ? d.M / (d.H * d.W) : 1;
@@ -313,11 +307,9 @@ int k22_igemm_cfg(const K22IgemmProblem* pr, const K22IgemmOperands* ops, int* r
 
 int k22_debug_conv_trace(const void* x_padded, const void* Wp, const float* bias, void* out, int B, int H, int W, int Cin, int Cout,
                          int Npad, unsigned long long* trace, void* stream) {
-  IgemmParams p = {};
-  p.stages = -1;
+  IgemmParams p = igemm_conv3_problem(B, H, W, Cin, Cout);
   p.A0 = x_padded; p.Wp = Wp; p.bias = bias; p.out = out;
-  p.M = B * H * W; p.N = Cout; p.Npad = Npad; p.Kc = Cin; p.K0 = Cin; p.taps = 9; p.H = H; p.W = W;
-  p.ldo = Cout; p.ldr = Cout; p.out_mode = IG_OUT_ROWMAJOR; p.act = K22_ACT_NONE; p.splitk = 1; p.trace = trace;
+  p.Npad = Npad; p.splitk = 1; p.trace = trace;
   return launch_conv3_halo_trace(p, K22_BF16, reinterpret_cast<hipStream_t>(stream));
 }
 
@@ -355,19 +347,17 @@ int k22_conv3x3_gn(const void* x0, const void* x1, int C0, int C1, const float* 
   float* coeff = part + (size_t)B * 128 * C * 2;
   const int rc = launch_gn_stats_coeff(x0, x1, C0, C1, B, HW, eps, gamma, beta, film, film_ld, part, coeff, sdt, st);
   if (rc) return rc;
-  IgemmParams p = {};
-  p.stages = -1;
+  IgemmParams p = igemm_conv3_problem(B, H, W, C, Cout);   // (no A0: the input is read through gn_x0 / gn_x1)
   p.Wp = Wp; p.bias = bias; p.residual = residual; p.out = out; p.partial = reinterpret_cast<float*>(partial);
-  p.M = B * H * W; p.N = Cout; p.Npad = Npad; p.Kc = C; p.K0 = C; p.taps = 9; p.H = H; p.W = W;
-  p.ldo = Cout; p.ldr = Cout; p.out_mode = IG_OUT_ROWMAJOR; p.act = K22_ACT_NONE; p.splitk = splitk > 0 ? splitk : 1; p.force_bm = bm; p.algo = algo;
+  p.Npad = Npad; p.splitk = splitk > 0 ? splitk : 1; p.force_bm = bm; p.algo = algo;
   p.gn_coeff = coeff; p.gn_x0 = x0; p.gn_x1 = x1; p.gn_C0 = C0; p.gn_act = act;
   return launch_igemm(p, dtype, st);
 }
 
 
-int k22_attention(const void* qkv, const void* ctxkv, void* kall, void* vtall, void* out, int B, int H, int T, int S,
-                  int dtype, void* stream) {
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+// kv_pack, then attention, with the mask and output-format fields of AttentionParams the engines set
+static int attention_seq(const void* qkv, const void* ctxkv, void* kall, void* vtall, void* out, int B, int H, int T, int S, int causal,
+                         const float* key_valid, int kv_n, int out_x3, int dtype, hipStream_t st) {
   const int C = H * 64, Tk = S + T, Tkp = (Tk + 63) / 64 * 64;
   KvPackParams kp;
   kp.qkv = qkv; kp.ctxkv = ctxkv; kp.kall = kall; kp.vtall = vtall; kp.B = B; kp.H = H; kp.T = T; kp.S = S; kp.Tkp = Tkp;
@@ -376,18 +366,29 @@ int k22_attention(const void* qkv, const void* ctxkv, void* kall, void* vtall, v
   AttentionParams ap = {};
   ap.q = qkv; ap.ldq = 3 * C; ap.kall = kall; ap.vtall = vtall; ap.out = out; ap.ldo = C;
   ap.B = B; ap.H = H; ap.T = T; ap.Tk = Tk; ap.Tkp = Tkp; ap.scale = 0.125f;
+  ap.causal = causal ? 1 : 0; ap.key_valid = key_valid; ap.kv_ld = kv_n; ap.kv_n = kv_n; ap.out_x3 = out_x3 ? 1 : 0;
   return launch_attention(ap, dtype, st);
+}
+
+int k22_attention(const void* qkv, const void* ctxkv, void* kall, void* vtall, void* out, int B, int H, int T, int S,
+                  int dtype, void* stream) {
+  return attention_seq(qkv, ctxkv, kall, vtall, out, B, H, T, S, 0, nullptr, 0, 0, dtype, reinterpret_cast<hipStream_t>(stream));
+}
+
+// the qkv projection of an AttentionBlock: x [B * T][K] -> q rows, K / V^T behind the S context keys of the attention operands
+static IgemmParams qkv_problem(const void* x, const void* Wp, const float* bias, void* q_out, void* kall, void* vtall, int B, int H, int T, int S, int K) {
+  const int C = H * 64;
+  IgemmParams p = igemm_gemm_problem(B * T, 3 * C, K, 0, IG_OUT_QKV);
+  p.A0 = x; p.Wp = Wp; p.bias = bias; p.out = q_out; p.kall = kall; p.vtall = vtall;
+  p.ldo = C;
+  p.att_T = T; p.att_S = S; p.att_Tkp = (S + T + 63) / 64 * 64; p.H = 1; p.W = T;   // rows per image
+  return p;
 }
 
 int k22_qkv_project(const void* x, const void* Wp, const float* bias, void* q_out, void* kall, void* vtall,
                     int B, int H, int T, int S, int K, int bm, int bn, int dtype, void* stream) {
-  const int C = H * 64, Tkp = (S + T + 63) / 64 * 64;
-  IgemmParams p = {};
-  p.stages = -1;
-  p.A0 = x; p.Wp = Wp; p.bias = bias; p.out = q_out; p.kall = kall; p.vtall = vtall;
-  p.M = B * T; p.N = 3 * C; p.Npad = 3 * C; p.Kc = K; p.K0 = K; p.taps = 1; p.lda0 = K; p.lda1 = 0;
-  p.ldo = C; p.ldr = 3 * C; p.out_mode = IG_OUT_QKV; p.act = K22_ACT_NONE; p.splitk = 1; p.force_bm = bm; p.force_bn = bn;
-  p.att_T = T; p.att_S = S; p.att_Tkp = Tkp; p.H = 1; p.W = T;   /* rows per image */
+  IgemmParams p = qkv_problem(x, Wp, bias, q_out, kall, vtall, B, H, T, S, K);
+  p.splitk = 1; p.force_bm = bm; p.force_bn = bn;
   p.a_raw = k22_is_split(dtype) ? 1 : 0;
   K22_DBG_FRAG(p);
   return launch_igemm(p, dtype, reinterpret_cast<hipStream_t>(stream));
@@ -395,13 +396,9 @@ int k22_qkv_project(const void* x, const void* Wp, const float* bias, void* q_ou
 
 int k22_qkv_project_stream(const void* x, const void* Wp, const float* bias, void* q_out, void* kall, void* vtall, void* partial,
                            int B, int H, int T, int S, int K, int bm, int splitk, int dtype, void* stream) {
-  const int C = H * 64, Tkp = (S + T + 63) / 64 * 64;
-  IgemmParams p = {};
-  p.stages = -1;
-  p.A0 = x; p.Wp = Wp; p.bias = bias; p.out = q_out; p.kall = kall; p.vtall = vtall; p.partial = reinterpret_cast<float*>(partial);
-  p.M = B * T; p.N = 3 * C; p.Npad = 3 * C; p.Kc = K; p.K0 = K; p.taps = 1; p.lda0 = K; p.lda1 = 0;
-  p.ldo = C; p.ldr = 3 * C; p.out_mode = IG_OUT_QKV; p.act = K22_ACT_NONE; p.splitk = splitk > 0 ? splitk : 1; p.force_bm = bm; p.algo = 20;
-  p.att_T = T; p.att_S = S; p.att_Tkp = Tkp; p.H = 1; p.W = T;
+  IgemmParams p = qkv_problem(x, Wp, bias, q_out, kall, vtall, B, H, T, S, K);
+  p.partial = reinterpret_cast<float*>(partial);
+  p.splitk = splitk > 0 ? splitk : 1; p.force_bm = bm; p.algo = IG_ALGO_STREAM;
   if (!stream_supported(p, dtype, bm == 288 ? 9 : 5)) return k22_set_error(K22_EINVAL, "qkv_project_stream: unsupported problem");
   K22_DBG_FRAG(p);
   return launch_igemm(p, dtype, reinterpret_cast<hipStream_t>(stream));
@@ -531,7 +528,6 @@ int k22_to_uint8_nhwc(const float* x, unsigned char* y, int B, int C, int H, int
   if (!x || !y || B < 1 || C < 1 || H < 1 || W < 1) return k22_set_error(K22_EINVAL, "to_uint8_nhwc: bad argument");
   return launch_to_uint8_nhwc(x, y, B, C, H, W, reinterpret_cast<hipStream_t>(stream));
 }
-// k22_attention's sequence (kv_pack, then attention) with the mask and output-format fields of AttentionParams the engines set
 int k22_attention_masked(const void* qkv, const void* ctxkv, void* kall, void* vtall, void* out, int B, int H, int T, int S, int causal,
                          const float* key_valid, int kv_n, int out_x3, int dtype, void* stream) {
   if (!qkv || !kall || !vtall || !out || B < 1 || H < 1 || T < 1 || S < 0 || kv_n < 0 || (S > 0 && !ctxkv) || !(aux_dtype_ok(dtype) || k22_is_split(dtype)))
@@ -539,17 +535,7 @@ int k22_attention_masked(const void* qkv, const void* ctxkv, void* kall, void* v
   if (causal && S != 0) return k22_set_error(K22_EINVAL, "attention_masked: causal needs S == 0 (key index against query index)");
   if (kv_n > S + T) return k22_set_error(K22_EINVAL, "attention_masked: kv_n > S + T");
   if (out_x3 && !k22_is_split(dtype)) return k22_set_error(K22_EINVAL, "attention_masked: out_x3 needs a split dtype");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int C = H * 64, Tk = S + T, Tkp = (Tk + 63) / 64 * 64;
-  KvPackParams kp;
-  kp.qkv = qkv; kp.ctxkv = ctxkv; kp.kall = kall; kp.vtall = vtall; kp.B = B; kp.H = H; kp.T = T; kp.S = S; kp.Tkp = Tkp;
-  int rc = launch_kv_pack(kp, k22_storage_dtype(dtype), st);
-  if (rc) return rc;
-  AttentionParams ap = {};
-  ap.q = qkv; ap.ldq = 3 * C; ap.kall = kall; ap.vtall = vtall; ap.out = out; ap.ldo = C;
-  ap.B = B; ap.H = H; ap.T = T; ap.Tk = Tk; ap.Tkp = Tkp; ap.scale = 0.125f;
-  ap.causal = causal ? 1 : 0; ap.key_valid = key_valid; ap.kv_ld = kv_n; ap.kv_n = kv_n; ap.out_x3 = out_x3 ? 1 : 0;
-  return launch_attention(ap, dtype, st);
+  return attention_seq(qkv, ctxkv, kall, vtall, out, B, H, T, S, causal, key_valid, kv_n, out_x3, dtype, reinterpret_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

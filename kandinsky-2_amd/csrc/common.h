@@ -152,6 +152,22 @@ template <> __device__ __forceinline__ x2_t from_f32<x2_t>(float f) { return x2_
 template <typename T> struct is_x3 { static constexpr bool value = false; };
 template <> struct is_x3<x3_t> { static constexpr bool value = true; };
 template <> struct is_x3<x2_t> { static constexpr bool value = true; };
+// Host-side dispatch on an arithmetic type: f(k22_tag<T>{}) with T the element type of `dtype`; -1 (K22_EINVAL) for a dtype outside K22DType.
+// A kernel that is not instantiated for some T is kept out with `if constexpr` inside f.
+// The order of the cases is the order in which a file's kernels are instantiated, and the compiler's output is not independent of it: with
+// the 16-bit types first, conv3_halo_spec_kernel<x3_t, 256, 2 / 3> (kernels that spill SGPRs) come out with three more spills.  With this
+// order every kernel has the bytes it had under the hand-written ladders (tools/compare_device_code.py).
+template <typename T> struct k22_tag { using type = T; };
+template <typename F> inline int k22_with_dtype(int dtype, F&& f) {
+  switch (dtype) {
+    case K22_F16X2: return f(k22_tag<x2_t>{});
+    case K22_F16X3: return f(k22_tag<x3_t>{});
+    case K22_BF16: return f(k22_tag<bf16_t>{});
+    case K22_F16: return f(k22_tag<f16_t>{});
+    case K22_F32: return f(k22_tag<float>{});
+  }
+  return -1;
+}
 // arithmetic of the fused 1x1 skip connection inside a conv kernel of type T (the full split for the asymmetric one: see halo_tail)
 template <typename T> struct SkipT { using type = T; };
 template <> struct SkipT<x2_t> { using type = x3_t; };

@@ -1,4 +1,4 @@
-// k22 - shared by the LDS-resident-halo convolution kernels (conv3_halo.hip: lock-step kernels, gemm8; conv3_spec.hip: the
+// k22 - shared by the LDS-resident-halo convolution kernels (conv3_halo.hip: lock-step kernels; gemm8.hip; conv3_spec.hip: the
 // producer / consumer specialised kernel): fragment loaders, the LDS-DMA helper, the fused GroupNorm-apply rewrite, the common
 // epilogue halo_tail, and the LDS budget every launcher and kernel agrees on.
 #pragma once

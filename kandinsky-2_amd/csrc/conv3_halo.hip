@@ -24,18 +24,12 @@
 //   * split-K over channel slabs for the low-resolution levels (fp32 partials, finished by splitk_reduce)
 //   * variants selected by p.algo (measured in DESIGN.md section 9): 2 = this kernel; 7 = its LDS-DMA issued from inline asm
 //     (exact lgkmcnt for the fragment reads; the tuner's usual pick); 6 = 7 + explicit fragment pipeline; 3 = conv3_halo3 below;
-//     8 / 9 = measurement only.  gemm8_kernel (plain GEMM on the
-//     same frame, qkv / proj_out) lives in this file too because it shares the epilogue (halo_tail)
+//     8 / 9 = measurement only.  gemm8_kernel (plain GEMM on the same frame, qkv / proj_out) is in gemm8.hip; both share the epilogue
+//     (halo_tail, conv3_common.h)
 //   * optional fused 1x1 skip_connection of the ResBlock (out += x . Ws^T): a second, plain-GEMM K loop over the
 //     block input's channels (A rows = the tile's own pixels, no halo) that accumulates into the same registers,
 //     so the skip tensor is never written, re-read or launched separately
 #include "conv3_common.h"
-
-// conv3_spec.hip
-int launch_conv3_halo_spec(const IgemmParams& p, int dtype, int bm, int nbst, int splitk, hipStream_t stream);
-#ifdef K22_DEBUG_VARIANTS
-int launch_conv3_halo_spec_debug(const IgemmParams& p, int nbst, int splitk, hipStream_t stream);
-#endif
 
 // LW = number of waves that issue the LDS-DMA: 8 (every wave loads its share right after the barrier: 3 pieces per wave per tap).  (A
 // 4-loader form - p.algo 5 - measured 2-5 % slower in round 1 and was deleted in round 5; the parameter stays for the index arithmetic.)
@@ -283,295 +277,6 @@ __global__ __launch_bounds__(512) void conv3_halo_kernel(const IgemmParams p) {
 }
 
 // ================================================================================================================
-// gemm8_kernel: plain GEMM  out[m][n] = sum_k A[m][k] W[n][k]  (1x1 convolutions: qkv / proj_out of the AttentionBlocks,
-// kandinsky2/model/unet.py:244-268) on the frame of the halo kernel: 8 waves (4 x 2), BM x 128 tile, BM in {256, 128},
-// both operands through an NST-deep LDS-DMA ring (one 128-byte-row K slab of A and of W per stage, counted vmcnt, one
-// raw barrier per slab) and the same epilogue through LDS (halo_tail): 16-byte stores, bias + residual, GroupNorm
-// partial sums of the stored values, or the qkv-projection layout.  Against igemm_kernel (4 waves, <= 128 x 128):
-// twice the FLOPs per L2->LDS byte at 256 x 128 and two waves per SIMD; m-tiles never straddle an image (rows of a
-// tile past the image are masked), so the per-tile statistics are per-image statistics.
-// (Round 2: a variant that staged both operands through registers - plain global_load two slabs ahead, ds_write_b128 into a
-// two-stage LDS ring, no LDS-DMA - was built, parity-green, and measured equal: 1.29 ms against 1.26-1.31 ms for the GEMMs of one
-// step.  The K loop of these GEMMs is not bound by the LDS-DMA issue cost; removed.)
-// ================================================================================================================
-template <typename T, int BM, int NST, bool ARAW = false>
-__global__ __launch_bounds__(512) void gemm8_kernel(const IgemmParams p) {
-  using TR = TT<T>;
-  constexpr int BK = TR::BK, EPC = TR::EPC, KSTEPS = TR::KSTEPS;
-  constexpr int BN = HALO_BN, NW = HALO_NW, WM = 4, WN = 2;
-  constexpr int MI = BM / (WM * 32), NI = BN / (WN * 32);
-  constexpr int A_SLOTS = BM / 8 / NW, B_SLOTS = BN / 8 / NW, CH = A_SLOTS + B_SLOTS;
-  constexpr int A_BYTES = BM * 128, B_BYTES = BN * 128, BUF = A_BYTES + B_BYTES;
-  constexpr int GM = 8;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 1, wn = wave & 1;
-  const int h = lane >> 5, l31 = lane & 31;
-
-  const int HW = p.H > 0 ? p.H * p.W : p.M;   // rows per image
-  const int TPI = (HW + BM - 1) / BM;
-  const int B = p.M / HW;
-  const int gx = B * TPI, gy = (p.N + BN - 1) / BN;
-  int L = p.xcd_remap ? xcd_remap_h(blockIdx.x, gridDim.x) : (int)blockIdx.x;
-  const int per_z = gx * gy;
-  const int bz = L / per_z;
-  L -= bz * per_z;
-  const int grp = L / (GM * gy);
-  const int first_m = grp * GM;
-  const int gsz = gx - first_m < GM ? gx - first_m : GM;
-  const int lin = L - grp * GM * gy;
-  const int bx = first_m + lin % gsz, by = lin / gsz;
-  const int img = bx / TPI, v0 = (bx - img * TPI) * BM;
-  const int n0 = by * BN;
-
-  const T* __restrict__ A = reinterpret_cast<const T*>(p.A0) + (int64_t)img * HW * p.lda0;
-  const T* __restrict__ Wp = reinterpret_cast<const T*>(p.Wp);
-  int aoff[A_SLOTS], boff[B_SLOTS];
-#pragma unroll
-  for (int i = 0; i < A_SLOTS; ++i) {
-    const int row = 8 * (wave + NW * i) + (lane >> 3);
-    int v = v0 + row;
-    if (v > HW - 1) v = HW - 1;                 // rows past the image re-read its last pixel; they are never stored
-    aoff[i] = v * (int)p.lda0 + ((lane & 7) ^ ((row >> 1) & 7)) * EPC;
-  }
-#pragma unroll
-  for (int i = 0; i < B_SLOTS; ++i) {
-    const int row = 8 * (wave + NW * i) + (lane >> 3);
-    int n = n0 + row;
-    if (n > p.Npad - 1) n = p.Npad - 1;
-    boff[i] = n * p.Kc + ((lane & 7) ^ ((row >> 1) & 7)) * EPC;
-  }
-  const int nslab = p.Kc / BK;
-  int s0 = 0, s1 = nslab;
-  if (p.splitk > 1) {
-    const int per = (nslab + p.splitk - 1) / p.splitk;
-    s0 = bz * per;
-    s1 = s0 + per < nslab ? s0 + per : nslab;
-  }
-
-  f32x16_t acc[MI][NI];
-#pragma unroll
-  for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
-
-  const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) char*)smem);
-#define K22_ISSUE_G(SLAB, STAGE)                                                                           \
-  {                                                                                                        \
-    int sl_ = (SLAB);                                                                                      \
-    if (sl_ > s1 - 1) sl_ = s1 - 1;   /* past-the-end stages re-read the last slab: uniform counting */    \
-    const unsigned d_ = lds0 + (STAGE) * BUF + wave * 1024;                                                \
-    _Pragma("unroll") for (int i = 0; i < A_SLOTS; ++i)                                                    \
-        glds16_asm(A + aoff[i] + sl_ * BK, __builtin_amdgcn_readfirstlane(d_ + i * NW * 1024));            \
-    _Pragma("unroll") for (int i = 0; i < B_SLOTS; ++i)                                                    \
-        glds16w_asm(Wp + boff[i] + sl_ * BK, __builtin_amdgcn_readfirstlane(d_ + A_BYTES + i * NW * 1024)); \
-  }
-  int arow[MI], brow[NI];
-#pragma unroll
-  for (int mi = 0; mi < MI; ++mi) arow[mi] = (wm * (BM / WM) + mi * 32 + l31) * 128;
-#pragma unroll
-  for (int ni = 0; ni < NI; ++ni) brow[ni] = A_BYTES + (wn * (BN / WN) + ni * 32 + l31) * 128;
-  const int sw = (l31 >> 1) & 7;
-
-  if (s0 < s1) {
-#pragma unroll
-    for (int t = 0; t < NST - 1; ++t) K22_ISSUE_G(s0 + t, t);
-    int cur = 0, fill = NST - 1;
-    for (int s = s0; s < s1; ++s) {
-      wait_vmcnt<(NST - 2) * CH>();
-      raw_barrier();
-      K22_ISSUE_G(s + NST - 1, fill);
-      const char* St = smem + cur * BUF;
-#pragma unroll
-      for (int ks = 0; ks < KSTEPS; ++ks) {
-        FragA<T> a[MI];
-        Frag<T> b[NI];
-#pragma unroll
-        for (int mi = 0; mi < MI; ++mi) ld_frag_at_a<ARAW, T>(a[mi], St + arow[mi], sw, ks, h);
-#pragma unroll
-        for (int ni = 0; ni < NI; ++ni) ld_frag_at(b[ni], St + brow[ni], sw, ks, h);
-#pragma unroll
-        for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-          for (int ni = 0; ni < NI; ++ni) mma_atom(acc[mi][ni], b[ni], a[mi]);
-      }
-      cur = (cur + 1 == NST) ? 0 : cur + 1;
-      fill = (fill + 1 == NST) ? 0 : fill + 1;
-    }
-  }
-#undef K22_ISSUE_G
-  halo_tail<T, BM, true>(p, acc, smem, bx, bz, img, v0, n0);
-}
-
-// ================================================================================================================
-// gemm8_spec_kernel (round 6, p.stages == 3 / 4; 16-bit types): gemm8_kernel's tile, ring and epilogue with the eight waves SPECIALISED the way
-// conv3_halo_spec_kernel's are - what the tuning report of the C3 shape asked for: at M = 32 768 the lock-step GEMM ran at 0.18-0.29 of the
-// bf16 peak (qkv 64x64: 161 us for 116 GFLOP) beside 3x3 convolutions of the same tile at 0.57.
-//   waves 0-3 (consumers, one per SIMD): 2 x 2 over the BM x 128 tile, (BM/2) x 64 per wave; per slab they read fragments and issue MFMAs
-//              through the explicit two-set pipeline (reads of k-step ks + 1 interleaved one behind every MFMA of k-step ks; the last k-step
-//              of a slab is multiplied behind the next slab's barrier) - no LDS-DMA, no vmcnt wait;
-//   waves 4-7 (producers): all the LDS-DMA of a slab (BM/32 + 4 pieces each) right behind its barrier, then the counted vmcnt wait.
-// One raw barrier per slab for all eight waves; slot reuse as in gemm8_kernel (iteration s refills the stage iteration s - 1 read; the
-// consumers drain lgkmcnt before the next barrier).  Every accumulator sees the same MFMAs in the same k order as in gemm8_kernel: same bits.
-// ================================================================================================================
-template <typename T, int BM, int NST>
-__global__ __launch_bounds__(512) void gemm8_spec_kernel(const IgemmParams p) {
-  using TR = TT<T>;
-  static_assert(sizeof(T) == 2, "gemm8_spec_kernel: 16-bit operands");
-  constexpr int BK = TR::BK, EPC = TR::EPC, KSTEPS = TR::KSTEPS;
-  static_assert(KSTEPS % 2 == 0, "two-set fragment pipeline");
-  constexpr int BN = HALO_BN, NWL = 4, WM = 2, WN = 2;
-  constexpr int MI = BM / (WM * 32), NI = BN / (WN * 32);
-  constexpr int A_SLOTS = BM / 8 / NWL, B_SLOTS = BN / 8 / NWL, CH = A_SLOTS + B_SLOTS;
-  constexpr int A_BYTES = BM * 128, B_BYTES = BN * 128, BUF = A_BYTES + B_BYTES;
-  constexpr int GM = 8;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const bool producer = wave >= 4;   // wave-uniform
-  const int h = lane >> 5, l31 = lane & 31;
-
-  const int HW = p.H > 0 ? p.H * p.W : p.M;   // rows per image
-  const int TPI = (HW + BM - 1) / BM;
-  const int B = p.M / HW;
-  const int gx = B * TPI, gy = (p.N + BN - 1) / BN;
-  int L = p.xcd_remap ? xcd_remap_h(blockIdx.x, gridDim.x) : (int)blockIdx.x;
-  const int per_z = gx * gy;
-  const int bz = L / per_z;
-  L -= bz * per_z;
-  const int grp = L / (GM * gy);
-  const int first_m = grp * GM;
-  const int gsz = gx - first_m < GM ? gx - first_m : GM;
-  const int lin = L - grp * GM * gy;
-  const int bx = first_m + lin % gsz, by = lin / gsz;
-  const int img = bx / TPI, v0 = (bx - img * TPI) * BM;
-  const int n0 = by * BN;
-
-  const int nslab = p.Kc / BK;
-  int s0 = 0, s1 = nslab;
-  if (p.splitk > 1) {
-    const int per = (nslab + p.splitk - 1) / p.splitk;
-    s0 = bz * per;
-    s1 = s0 + per < nslab ? s0 + per : nslab;
-  }
-
-  f32x16_t acc[MI][NI];
-#pragma unroll
-  for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
-
-  if (s0 < s1) {
-    if (producer) {
-      const int lw = wave - 4;
-      const T* __restrict__ A = reinterpret_cast<const T*>(p.A0) + (int64_t)img * HW * p.lda0;
-      const T* __restrict__ Wp = reinterpret_cast<const T*>(p.Wp);
-      int aoff[A_SLOTS], boff[B_SLOTS];
-#pragma unroll
-      for (int i = 0; i < A_SLOTS; ++i) {
-        const int row = 8 * (lw + NWL * i) + (lane >> 3);
-        int v = v0 + row;
-        if (v > HW - 1) v = HW - 1;                 // rows past the image re-read its last pixel; they are never stored
-        aoff[i] = v * (int)p.lda0 + ((lane & 7) ^ ((row >> 1) & 7)) * EPC;
-      }
-#pragma unroll
-      for (int i = 0; i < B_SLOTS; ++i) {
-        const int row = 8 * (lw + NWL * i) + (lane >> 3);
-        int n = n0 + row;
-        if (n > p.Npad - 1) n = p.Npad - 1;
-        boff[i] = n * p.Kc + ((lane & 7) ^ ((row >> 1) & 7)) * EPC;
-      }
-      const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) char*)smem);
-#define K22_ISSUE_GS(SLAB, STAGE)                                                                          \
-      {                                                                                                    \
-        int sl_ = (SLAB);                                                                                  \
-        if (sl_ > s1 - 1) sl_ = s1 - 1;   /* past-the-end stages re-read the last slab: uniform counting */ \
-        const unsigned d_ = lds0 + (STAGE) * BUF + lw * 1024;                                              \
-        _Pragma("unroll") for (int i = 0; i < A_SLOTS; ++i)                                                \
-            glds16_asm(A + aoff[i] + sl_ * BK, __builtin_amdgcn_readfirstlane(d_ + i * NWL * 1024));       \
-        _Pragma("unroll") for (int i = 0; i < B_SLOTS; ++i)                                                \
-            glds16w_asm(Wp + boff[i] + sl_ * BK, __builtin_amdgcn_readfirstlane(d_ + A_BYTES + i * NWL * 1024)); \
-      }
-#pragma unroll
-      for (int t = 0; t < NST - 1; ++t) K22_ISSUE_GS(s0 + t, t);
-      int fill = NST - 1;
-      for (int s = s0; s < s1; ++s) {
-        wait_vmcnt<(NST - 2) * CH>();
-        raw_barrier();
-        K22_ISSUE_GS(s + NST - 1, fill);
-        fill = (fill + 1 == NST) ? 0 : fill + 1;
-      }
-#undef K22_ISSUE_GS
-    } else {
-      const int wm = wave >> 1, wn = wave & 1;
-      int arow[MI], brow[NI];
-#pragma unroll
-      for (int mi = 0; mi < MI; ++mi) arow[mi] = (wm * (BM / WM) + mi * 32 + l31) * 128;
-#pragma unroll
-      for (int ni = 0; ni < NI; ++ni) brow[ni] = A_BYTES + (wn * (BN / WN) + ni * 32 + l31) * 128;
-      const int sw = (l31 >> 1) & 7;
-      Frag<T> pa[MI], pb[NI];          // fragments read but not yet multiplied (zero = a no-op group before the first slab)
-#pragma unroll
-      for (int mi = 0; mi < MI; ++mi) pa[mi] = Frag<T>{};
-#pragma unroll
-      for (int ni = 0; ni < NI; ++ni) pb[ni] = Frag<T>{};
-      constexpr int NRD = MI + NI, NMF = MI * NI, MPR = NMF / NRD;
-#define K22_GS_INTERLEAVE()                                                                                \
-      {                                                                                                    \
-        _Pragma("unroll") for (int i_ = 0; i_ < NRD; ++i_) {                                               \
-          __builtin_amdgcn_sched_group_barrier(0x008, MPR, 0);                                             \
-          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                                               \
-        }                                                                                                  \
-        if constexpr (NMF - MPR * NRD > 0) __builtin_amdgcn_sched_group_barrier(0x008, NMF - MPR * NRD, 0); \
-        __builtin_amdgcn_sched_barrier(0);                                                                 \
-      }
-      int cur = 0;
-      for (int s = s0; s < s1; ++s) {
-        raw_barrier();
-        const char* St = smem + cur * BUF;
-        Frag<T> ca[MI], cb[NI];
-#pragma unroll
-        for (int ks = 0; ks < KSTEPS; ks += 2) {
-#pragma unroll
-          for (int mi = 0; mi < MI; ++mi) ld_frag_at(ca[mi], St + arow[mi], sw, ks, h);
-#pragma unroll
-          for (int ni = 0; ni < NI; ++ni) ld_frag_at(cb[ni], St + brow[ni], sw, ks, h);
-#pragma unroll
-          for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-            for (int ni = 0; ni < NI; ++ni) mma_atom(acc[mi][ni], pb[ni], pa[mi]);
-          K22_GS_INTERLEAVE();
-#pragma unroll
-          for (int mi = 0; mi < MI; ++mi) ld_frag_at(pa[mi], St + arow[mi], sw, ks + 1, h);
-#pragma unroll
-          for (int ni = 0; ni < NI; ++ni) ld_frag_at(pb[ni], St + brow[ni], sw, ks + 1, h);
-#pragma unroll
-          for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-            for (int ni = 0; ni < NI; ++ni) mma_atom(acc[mi][ni], cb[ni], ca[mi]);
-          K22_GS_INTERLEAVE();
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // no fragment read of this stage in flight when the producers refill it after the next barrier
-        cur = (cur + 1 == NST) ? 0 : cur + 1;
-      }
-#undef K22_GS_INTERLEAVE
-#pragma unroll
-      for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < NI; ++ni) mma_atom(acc[mi][ni], pb[ni], pa[mi]);
-    }
-  }
-  halo_tail<T, BM, true, true>(p, acc, smem, bx, bz, img, v0, n0);
-}
-
-// ================================================================================================================
 // conv3_halo3_kernel: the same LDS-resident halo scheme on 64-BYTE rows.  The K loop walks HALF slabs (32 bf16 / 16 fp32
 // channels); one iteration = the three taps of one filter row (ky) of one half slab = 24 MFMAs per wave between
 // barriers (16 before), its weight tiles (3 x 128 rows x 64 B = 24 KB) sit in an RB-deep ring (RB-1 iterations in
@@ -776,100 +481,14 @@ static int halo3_pick_rb(const IgemmParams& p, int bm) {
   return 0;
 }
 
-// ---- gemm8_kernel ---------------------------------------------------------------------------------------------------
-// ring depth: 3 stages of 48 KB at BM = 256; at BM = 128 (32 KB per stage) either 4 stages (one workgroup per CU) or,
-// on request (p.stages == 2), 2 stages = 68 KB with the epilogue tile, so that TWO workgroups share a CU and one's
-// prologue / epilogue overlaps the other's K loop (short-K GEMMs: K = 768 is 12 slabs).
-static int gemm8_nst(int bm, int stages) { return bm == 256 ? 3 : (stages == 2 ? 2 : 4); }
-static size_t gemm8_smem_bytes(int bm, int nst) {
-  const size_t main_loop = (size_t)nst * (bm + HALO_BN) * 128;
-  const size_t epi = (size_t)bm * (HALO_BN * 4 + 16);
-  return main_loop > epi ? main_loop : epi;
-}
-int gemm8_tiles_per_image(const IgemmParams& p, int bm) { return ((p.H > 0 ? p.H * p.W : p.M) + bm - 1) / bm; }
-
-bool gemm8_supported(const IgemmParams& p, int dtype, int bm) {
-  const int BK = k22_bk(dtype);
-  if (p.taps != 1 || (bm != 256 && bm != 128) || p.N < 128) return false;
-  if (p.K0 != p.Kc || p.S0 != nullptr || p.res_f32) return false;          // one A operand, no fused skip, T residual
-  if (p.out_mode != IG_OUT_ROWMAJOR && p.out_mode != IG_OUT_ROWMAJOR_F32 && p.out_mode != IG_OUT_QKV) return false;
-  if (p.N % 8 || p.ldo % 8 || (p.residual && p.ldr % 8) || p.Kc % BK || p.lda0 % 8) return false;
-  const int hw = p.H > 0 ? p.H * p.W : p.M;
-  if (hw <= 0 || p.M % hw) return false;
-  if (p.out_mode == IG_OUT_QKV && (p.att_T != hw || p.N % 384)) return false;  // an n-tile stays inside q, k or v
-  if ((int64_t)p.M * p.lda0 >= (1ll << 31) || (int64_t)p.Npad * p.Kc >= (1ll << 31)) return false;
-  return true;
-}
-
-template <typename T, int BM, int NST, bool ARAW = false>
-static int launch_gemm8_cfg(const IgemmParams& p, int splitk, hipStream_t stream) {
-  if constexpr (is_x3<T>::value && !ARAW) { if (p.a_raw) return launch_gemm8_cfg<T, BM, NST, true>(p, splitk, stream); }
-  const size_t smem = gemm8_smem_bytes(BM, NST);
-  static LdsAttrGuard attr_guard;
-  if (int rc_ = k22_ensure_lds_attr(attr_guard, reinterpret_cast<const void*>(&gemm8_kernel<T, BM, NST, ARAW>), 160 * 1024, __FILE__, __LINE__)) return rc_;
-  IgemmParams q = p;
-  q.splitk = splitk;
-  const int hw = p.H > 0 ? p.H * p.W : p.M;
-  const int nblocks = (p.M / hw) * gemm8_tiles_per_image(p, BM) * ((p.N + HALO_BN - 1) / HALO_BN) * splitk;
-  hipLaunchKernelGGL((gemm8_kernel<T, BM, NST, ARAW>), dim3(nblocks), dim3(512), smem, stream, q);
-  K22_CHECK_LAUNCH();
-  return K22_OK;
-}
-
-template <typename T, int BM, int NST>
-static int launch_gemm8_spec_cfg(const IgemmParams& p, int splitk, hipStream_t stream) {
-  const size_t smem = gemm8_smem_bytes(BM, NST);
-  static LdsAttrGuard attr_guard;
-  if (int rc_ = k22_ensure_lds_attr(attr_guard, reinterpret_cast<const void*>(&gemm8_spec_kernel<T, BM, NST>), 160 * 1024, __FILE__, __LINE__)) return rc_;
-  IgemmParams q = p;
-  q.splitk = splitk;
-  const int hw = p.H > 0 ? p.H * p.W : p.M;
-  const int nblocks = (p.M / hw) * gemm8_tiles_per_image(p, BM) * ((p.N + HALO_BN - 1) / HALO_BN) * splitk;
-  hipLaunchKernelGGL((gemm8_spec_kernel<T, BM, NST>), dim3(nblocks), dim3(512), smem, stream, q);
-  K22_CHECK_LAUNCH();
-  return K22_OK;
-}
-
-// p.stages == 3 selects the specialised, pipelined form (16-bit types; the split types keep the lock-step kernel)
-bool gemm8_spec_supported(int dtype) { return dtype == K22_BF16 || dtype == K22_F16; }
-
-// Launches gemm8_kernel only (a split-K reduction, if any, is the caller's: launch_igemm).
-int launch_gemm8(const IgemmParams& p, int dtype, int bm, int splitk, hipStream_t stream) {
-  if (!gemm8_supported(p, dtype, bm)) return k22_set_error(K22_EINVAL, "gemm8: unsupported problem");
-  if ((p.stages == 3 || p.stages == 4) && gemm8_spec_supported(dtype)) {
-    // 4 (BM = 128 only): 2-deep ring = 68 KB with the epilogue tile, so that TWO workgroups share a CU and one's prologue / epilogue (a burst of
-    // output traffic that every CU of a lock-step round issues at the same time) overlaps the other's K loop - the p.stages == 2 idea of gemm8_kernel
-    if (p.stages == 4 && bm == 128) return dtype == K22_BF16 ? launch_gemm8_spec_cfg<bf16_t, 128, 2>(p, splitk, stream) : launch_gemm8_spec_cfg<f16_t, 128, 2>(p, splitk, stream);
-    if (dtype == K22_BF16) return bm == 256 ? launch_gemm8_spec_cfg<bf16_t, 256, 3>(p, splitk, stream) : launch_gemm8_spec_cfg<bf16_t, 128, 4>(p, splitk, stream);
-    return bm == 256 ? launch_gemm8_spec_cfg<f16_t, 256, 3>(p, splitk, stream) : launch_gemm8_spec_cfg<f16_t, 128, 4>(p, splitk, stream);
-  }
-  const int nst = gemm8_nst(bm, p.stages);
-  if (dtype == K22_BF16) {
-    if (bm == 256) return launch_gemm8_cfg<bf16_t, 256, 3>(p, splitk, stream);
-    return nst == 2 ? launch_gemm8_cfg<bf16_t, 128, 2>(p, splitk, stream) : launch_gemm8_cfg<bf16_t, 128, 4>(p, splitk, stream);
-  }
-  if (dtype == K22_F16) {
-    if (bm == 256) return launch_gemm8_cfg<f16_t, 256, 3>(p, splitk, stream);
-    return nst == 2 ? launch_gemm8_cfg<f16_t, 128, 2>(p, splitk, stream) : launch_gemm8_cfg<f16_t, 128, 4>(p, splitk, stream);
-  }
-  if (dtype == K22_F16X3) {
-    if (bm == 256) return launch_gemm8_cfg<x3_t, 256, 3>(p, splitk, stream);
-    return nst == 2 ? launch_gemm8_cfg<x3_t, 128, 2>(p, splitk, stream) : launch_gemm8_cfg<x3_t, 128, 4>(p, splitk, stream);
-  }
-  if (dtype == K22_F16X2) {
-    if (bm == 256) return launch_gemm8_cfg<x2_t, 256, 3>(p, splitk, stream);
-    return nst == 2 ? launch_gemm8_cfg<x2_t, 128, 2>(p, splitk, stream) : launch_gemm8_cfg<x2_t, 128, 4>(p, splitk, stream);
-  }
-  if (bm == 256) return launch_gemm8_cfg<float, 256, 3>(p, splitk, stream);
-  return nst == 2 ? launch_gemm8_cfg<float, 128, 2>(p, splitk, stream) : launch_gemm8_cfg<float, 128, 4>(p, splitk, stream);
-}
+int conv3_halo_ring(const IgemmParams& p, int bm) { return p.algo == IG_ALGO_HALO3 ? halo3_pick_rb(p, bm) : halo_pick_nbst(p, bm); }
 
 bool conv3_halo_supported(const IgemmParams& p, int dtype, int bm) {
   const int BK = k22_bk(dtype);
   if (p.taps != 9 || (bm != 256 && bm != 128)) return false;
-  // split precision: the input is read in x3 chunks; instantiated forms = the lock-step kernel with asm LDS-DMA (algo 2 / 5 / 6 / 7 all
+  // split precision: the input is read in x3 chunks; instantiated forms = the lock-step kernel with asm LDS-DMA (algo 2 / 6 / 7 all
   // run it) and the specialised kernel (11 / 12)
-  if (k22_is_split(dtype) && (p.a_raw || p.algo == 3)) return false;
+  if (k22_is_split(dtype) && (p.a_raw || p.algo == IG_ALGO_HALO3)) return false;
   if (p.gn_coeff != nullptr) {   // fused GroupNorm-apply: the specialised kernels only; slabs never straddle the two raw sources
     if (!conv3_algo_fuses_gn(p.algo) || !p.gn_x0 || p.gn_C0 <= 0 || p.gn_C0 > p.Kc || p.gn_C0 % BK || (p.gn_C0 < p.Kc && !p.gn_x1)) return false;
     if ((int64_t)p.H * p.W * p.Kc >= (1ll << 31)) return false;
@@ -881,53 +500,41 @@ bool conv3_halo_supported(const IgemmParams& p, int dtype, int bm) {
     if (!p.Ws || p.SK0 % BK || p.SK1 % BK || (p.SK1 > 0 && !p.S1) || p.SK0 <= 0) return false;
     if ((int64_t)p.M * (p.SK0 > p.SK1 ? p.SK0 : p.SK1) >= (1ll << 31) || (int64_t)p.Npad * (p.SK0 + p.SK1) >= (1ll << 31)) return false;
   }
-  if ((p.algo == 3 ? halo3_pick_rb(p, bm) : halo_pick_nbst(p, bm)) == 0) return false;
+  if (conv3_halo_ring(p, bm) == 0) return false;
   if ((int64_t)(p.H + 2) * (p.W + 2) * p.Kc >= (1ll << 31) || (int64_t)p.Npad * 9 * p.Kc >= (1ll << 31)) return false;
   return true;
 }
 
 int conv3_halo_tiles_per_image(const IgemmParams& p, int bm) { return (p.H * (p.W + 2) + bm - 1) / bm; }
+size_t conv3_halo_lds_bytes(const IgemmParams& p, int bm, int depth) { return p.algo == IG_ALGO_HALO3 ? halo3_smem_bytes(p, bm, depth) : halo_smem_bytes(p, bm, depth); }
 
-template <typename T, int BM, int NBST, int LW, int MODE>
-static int launch_halo_cfg(const IgemmParams& p, int splitk, hipStream_t stream) {
-  const size_t smem = halo_smem_bytes(p, BM, NBST);
-  static LdsAttrGuard attr_guard;
-  if (int rc_ = k22_ensure_lds_attr(attr_guard, reinterpret_cast<const void*>(&conv3_halo_kernel<T, BM, NBST, false, LW, MODE>), 160 * 1024, __FILE__, __LINE__)) return rc_;
-  IgemmParams q = p;
-  q.splitk = splitk;
-  const int B = p.M / (p.H * p.W);
-  const int nblocks = B * conv3_halo_tiles_per_image(p, BM) * ((p.N + HALO_BN - 1) / HALO_BN) * splitk;
-  hipLaunchKernelGGL((conv3_halo_kernel<T, BM, NBST, false, LW, MODE>), dim3(nblocks), dim3(512), smem, stream, q);
-  K22_CHECK_LAUNCH();
-  return K22_OK;
+template <typename T, int BM, int NBST, int MODE>
+static int run_halo(const IgemmParams& p, const IgemmLaunch& L, hipStream_t stream) {
+  static LdsAttrGuard guard;
+  return launch_lds_kernel(conv3_halo_kernel<T, BM, NBST, false, 8, MODE>, guard, L.grid, L.block, L.lds, 160 * 1024, stream, p);
 }
-
-template <typename T, int BM, int LW, int MODE>
-static int launch_halo_nbst(const IgemmParams& p, int nbst, int splitk, hipStream_t stream) {
-  if (nbst == 2) return launch_halo_cfg<T, BM, 2, LW, MODE>(p, splitk, stream);
-  if (nbst == 3) return launch_halo_cfg<T, BM, 3, LW, MODE>(p, splitk, stream);
-  if (nbst <= 5) return launch_halo_cfg<T, BM, 4, LW, MODE>(p, splitk, stream);
-  return launch_halo_cfg<T, BM, 6, LW, MODE>(p, splitk, stream);
+template <typename T, int BM, int MODE>
+static int launch_halo_depth(const IgemmParams& p, const IgemmLaunch& L, hipStream_t stream) {
+  if (L.depth == 2) return run_halo<T, BM, 2, MODE>(p, L, stream);
+  if (L.depth == 3) return run_halo<T, BM, 3, MODE>(p, L, stream);
+  if (L.depth == 4) return run_halo<T, BM, 4, MODE>(p, L, stream);
+  return run_halo<T, BM, 6, MODE>(p, L, stream);
+}
+template <typename T, int MODE>
+static int launch_halo_bm(const IgemmParams& p, const IgemmLaunch& L, hipStream_t stream) {
+  return L.bm == 256 ? launch_halo_depth<T, 256, MODE>(p, L, stream) : launch_halo_depth<T, 128, MODE>(p, L, stream);
 }
 
 template <typename T, int BM, int RB>
-static int launch_halo3_cfg(const IgemmParams& p, int splitk, hipStream_t stream) {
-  const size_t smem = halo3_smem_bytes(p, BM, RB);
-  static LdsAttrGuard attr_guard;
-  if (int rc_ = k22_ensure_lds_attr(attr_guard, reinterpret_cast<const void*>(&conv3_halo3_kernel<T, BM, RB>), 160 * 1024, __FILE__, __LINE__)) return rc_;
-  IgemmParams q = p;
-  q.splitk = splitk;
-  const int B = p.M / (p.H * p.W);
-  const int nblocks = B * conv3_halo_tiles_per_image(p, BM) * ((p.N + HALO_BN - 1) / HALO_BN) * splitk;
-  hipLaunchKernelGGL((conv3_halo3_kernel<T, BM, RB>), dim3(nblocks), dim3(512), smem, stream, q);
-  K22_CHECK_LAUNCH();
-  return K22_OK;
+static int run_halo3(const IgemmParams& p, const IgemmLaunch& L, hipStream_t stream) {
+  static LdsAttrGuard guard;
+  return launch_lds_kernel(conv3_halo3_kernel<T, BM, RB>, guard, L.grid, L.block, L.lds, 160 * 1024, stream, p);
 }
 template <typename T, int BM>
-static int launch_halo3_rb(const IgemmParams& p, int rb, int splitk, hipStream_t stream) {
-  if (rb == 2) return launch_halo3_cfg<T, BM, 2>(p, splitk, stream);
-  if (rb == 3) return launch_halo3_cfg<T, BM, 3>(p, splitk, stream);
-  return launch_halo3_cfg<T, BM, 4>(p, splitk, stream);
+static int launch_halo3_depth(const IgemmParams& p, const IgemmLaunch& L, hipStream_t stream) {
+  if (L.depth == 2) return run_halo3<T, BM, 2>(p, L, stream);
+  if (L.depth == 3) return run_halo3<T, BM, 3>(p, L, stream);
+  return run_halo3<T, BM, 4>(p, L, stream);
 }
 
 // developer tool: conv3_halo_kernel<bf16, 256, NBST> with per-tap s_memtime stamps (wave 0 and wave 5 of block 0):
@@ -951,56 +558,24 @@ int launch_conv3_halo_trace(const IgemmParams& p, int dtype, hipStream_t stream)
   return K22_OK;
 }
 
-// Launches the halo kernel only (the split-K reduction, if any, is the caller's: launch_igemm).
-// p.algo == 3 selects the 64-byte-row kernel (conv3_halo3_kernel), anything else the 128-byte-row one (6 / 7: its pipelined / asm-DMA
-// forms; 11 / 12: the specialised kernel of conv3_spec.hip).  (Algos 4 - two wave groups in opposite phases - and 5 - loader-wave
-// specialisation - measured 12-20 % / 2-5 % slower in round 1, were never tuner candidates, and were deleted in round 5.)
-int launch_conv3_halo(const IgemmParams& p, int dtype, int bm, int splitk, hipStream_t stream) {
-  if (!conv3_halo_supported(p, dtype, bm)) return k22_set_error(K22_EINVAL, "conv3_halo: unsupported problem");
-  if (k22_is_split(dtype)) {
-    int nb = halo_pick_nbst(p, bm);
-    if (p.stages >= 2 && p.stages < nb) nb = p.stages == 5 ? 4 : p.stages;
-    if (p.algo == 11 || p.algo == 12) return launch_conv3_halo_spec(p, dtype, bm, nb, splitk, stream);
-    if (p.algo == 13 || p.algo == 14 || p.algo == 8 || p.algo == 9) return k22_set_error(K22_EINVAL, "conv3_halo: no measurement-only variants in split precision");
-    if (dtype == K22_F16X2) return bm == 256 ? launch_halo_nbst<x2_t, 256, 8, 2>(p, nb, splitk, stream) : launch_halo_nbst<x2_t, 128, 8, 2>(p, nb, splitk, stream);
-    return bm == 256 ? launch_halo_nbst<x3_t, 256, 8, 2>(p, nb, splitk, stream) : launch_halo_nbst<x3_t, 128, 8, 2>(p, nb, splitk, stream);
-  }
-  if (p.algo == 3) {
-    int rb = halo3_pick_rb(p, bm);
-    if (p.stages >= 2 && p.stages < rb) rb = p.stages;
-    if (dtype == K22_BF16) return bm == 256 ? launch_halo3_rb<bf16_t, 256>(p, rb, splitk, stream) : launch_halo3_rb<bf16_t, 128>(p, rb, splitk, stream);
-    else if (dtype == K22_F16) return bm == 256 ? launch_halo3_rb<f16_t, 256>(p, rb, splitk, stream) : launch_halo3_rb<f16_t, 128>(p, rb, splitk, stream);
-    return bm == 256 ? launch_halo3_rb<float, 256>(p, rb, splitk, stream) : launch_halo3_rb<float, 128>(p, rb, splitk, stream);
-  }
-  int nbst = halo_pick_nbst(p, bm);
-  if (p.stages >= 2 && p.stages < nbst) nbst = p.stages == 5 ? 4 : p.stages;  // tuning knob: shallower ring on request
-  // producer / consumer wave specialisation (conv3_spec.hip): 11 = compiler-scheduled consumers, 12 = explicit, interleaved fragment pipeline
-  if (p.algo == 11 || p.algo == 12) return launch_conv3_halo_spec(p, dtype, bm, nbst, splitk, stream);
-#ifdef K22_DEBUG_VARIANTS   // measurement-only kernels (wrong results) are compiled only into a developer build: make CXXFLAGS+=-DK22_DEBUG_VARIANTS
-  if (p.algo == 13 || p.algo == 14) {  // measurement-only forms of algo 12 (wrong results): 13 = no LDS-DMA inside the tap loop, 14 = LDS-DMA issued but never waited for
-    if (dtype != K22_BF16 || bm != 256) return k22_set_error(K22_EINVAL, "conv3_halo: the debug variants are bf16, BM = 256 only");
-    return launch_conv3_halo_spec_debug(p, nbst, splitk, stream);
-  }
-#else
-  if (p.algo == 13 || p.algo == 14 || p.algo == 8 || p.algo == 9) return k22_set_error(K22_EINVAL, "conv3_halo: measurement-only variants need a -DK22_DEBUG_VARIANTS build");
+// Launches the lock-step kernel the resolved launch names (the split-K reduction, if any, is the caller's: launch_igemm): conv3_halo3_kernel, or
+// conv3_halo_kernel in form L.pipe = MODE (0 compiler-issued LDS-DMA, 1 asm LDS-DMA + explicit fragment pipeline, 2 asm LDS-DMA).  The split
+// types have MODE 2 only.  (Two wave groups in opposite phases and loader-wave specialisation measured 12-20 % / 2-5 % slower in round 1, were
+// never tuner candidates, and were deleted in round 5.)
+int launch_conv3_halo(const IgemmParams& p, int dtype, const IgemmLaunch& L, hipStream_t stream) {
+  return k22_with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    if constexpr (!is_x3<T>::value) {
+      if (L.family == IG_FAM_HALO3) return L.bm == 256 ? launch_halo3_depth<T, 256>(p, L, stream) : launch_halo3_depth<T, 128>(p, L, stream);
+      if (L.pipe == 0) return launch_halo_bm<T, 0>(p, L, stream);
+      if (L.pipe == 1) return launch_halo_bm<T, 1>(p, L, stream);
+#ifdef K22_DEBUG_VARIANTS   // measurement-only variants (wrong results), bf16 at BM = 256: 3 = no LDS-DMA in the loop, 4 = no MFMA
+      if constexpr (std::is_same<T, bf16_t>::value) {
+        if (L.pipe == 3) return launch_halo_depth<T, 256, 3>(p, L, stream);
+        if (L.pipe == 4) return launch_halo_depth<T, 256, 4>(p, L, stream);
+      }
 #endif
-  if (p.algo == 6) {  // explicit fragment pipeline across the barrier + asm LDS-DMA
-    if (dtype == K22_BF16) return bm == 256 ? launch_halo_nbst<bf16_t, 256, 8, 1>(p, nbst, splitk, stream) : launch_halo_nbst<bf16_t, 128, 8, 1>(p, nbst, splitk, stream);
-    else if (dtype == K22_F16) return bm == 256 ? launch_halo_nbst<f16_t, 256, 8, 1>(p, nbst, splitk, stream) : launch_halo_nbst<f16_t, 128, 8, 1>(p, nbst, splitk, stream);
-    return bm == 256 ? launch_halo_nbst<float, 256, 8, 1>(p, nbst, splitk, stream) : launch_halo_nbst<float, 128, 8, 1>(p, nbst, splitk, stream);
-  }
-#ifdef K22_DEBUG_VARIANTS
-  if (p.algo == 8 || p.algo == 9) {  // measurement-only variants (wrong results): 8 = no LDS-DMA in the loop, 9 = no MFMA
-    if (dtype != K22_BF16 || bm != 256) return k22_set_error(K22_EINVAL, "conv3_halo: debug variants are bf16, BM = 256 only");
-    return p.algo == 8 ? launch_halo_nbst<bf16_t, 256, 8, 3>(p, nbst, splitk, stream) : launch_halo_nbst<bf16_t, 256, 8, 4>(p, nbst, splitk, stream);
-  }
-#endif
-  if (p.algo == 7) {  // compiler schedule + asm LDS-DMA
-    if (dtype == K22_BF16) return bm == 256 ? launch_halo_nbst<bf16_t, 256, 8, 2>(p, nbst, splitk, stream) : launch_halo_nbst<bf16_t, 128, 8, 2>(p, nbst, splitk, stream);
-    else if (dtype == K22_F16) return bm == 256 ? launch_halo_nbst<f16_t, 256, 8, 2>(p, nbst, splitk, stream) : launch_halo_nbst<f16_t, 128, 8, 2>(p, nbst, splitk, stream);
-    return bm == 256 ? launch_halo_nbst<float, 256, 8, 2>(p, nbst, splitk, stream) : launch_halo_nbst<float, 128, 8, 2>(p, nbst, splitk, stream);
-  }
-  if (dtype == K22_BF16) return bm == 256 ? launch_halo_nbst<bf16_t, 256, 8, 0>(p, nbst, splitk, stream) : launch_halo_nbst<bf16_t, 128, 8, 0>(p, nbst, splitk, stream);
-  else if (dtype == K22_F16) return bm == 256 ? launch_halo_nbst<f16_t, 256, 8, 0>(p, nbst, splitk, stream) : launch_halo_nbst<f16_t, 128, 8, 0>(p, nbst, splitk, stream);
-  return bm == 256 ? launch_halo_nbst<float, 256, 8, 0>(p, nbst, splitk, stream) : launch_halo_nbst<float, 128, 8, 0>(p, nbst, splitk, stream);
+    }
+    return launch_halo_bm<T, 2>(p, L, stream);
+  });
 }

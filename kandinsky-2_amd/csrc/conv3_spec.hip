@@ -4,7 +4,7 @@
 #include "conv3_common.h"
 
 // ================================================================================================================
-// conv3_halo_spec_kernel (p.algo == 11 / 12): the same tile, LDS images and epilogue with the eight waves SPECIALISED.
+// conv3_halo_spec_kernel (IG_ALGO_SPEC / IG_ALGO_SPEC_PIPE = algo 11 / 12): the same tile, LDS images and epilogue with the eight waves SPECIALISED.
 //   waves 0-3 ("consumers", one per SIMD): 2 x 2 over the BM x 128 tile, (BM/2) x 64 per wave (BM = 256: 128 x 64 = 8
 //              accumulators, 6 fragment reads per 8 MFMAs instead of 4 per 4); per tap they do nothing but read fragments and
 //              issue MFMAs - no LDS-DMA instruction, no vmcnt wait;
@@ -12,7 +12,7 @@
 //              each) right after its barrier and sit in the counted vmcnt wait for the next tap's tile.
 // Producers and consumers execute the same barriers (one per tap): the ring-slot / halo-buffer reuse argument of
 // conv3_halo_kernel holds unchanged.
-// PIPE (p.algo == 12): explicit fragment pipeline in the consumers.  The fragments of k-step ks+1 are read while the MFMAs of
+// PIPE (algo 12): explicit fragment pipeline in the consumers.  The fragments of k-step ks+1 are read while the MFMAs of
 // k-step ks are issued (two register sets), and the last k-step of a tap is multiplied after the next tap's barrier, where
 // its eight MFMAs cover the latency of that tap's first fragment reads.  Within a block the reads and the MFMAs are
 // INTERLEAVED one read behind every MFMA (sched_group_barrier): issued as a read burst and an MFMA burst, the matrix pipe
@@ -20,8 +20,8 @@
 // convolutions of one step): 4.09 ms against 4.51 ms for the best lock-step variant at BM = 256, 4.43 against 4.77 at
 // BM = 128; the specialisation alone (algo 11, compiler-scheduled consumers) is +-0 - it is the interleaved pipeline that the
 // one-owner matrix pipe makes worthwhile.
-// DBG (measurement only, wrong results): 1 (p.algo == 13) = the producers issue nothing inside the tap loop - what is left is
-// the consumers' speed limit under the same barriers; 2 (p.algo == 14) = the LDS-DMA is issued but never waited for.  At 96x96
+// DBG (measurement only, wrong results): 1 (algo 13) = the producers issue nothing inside the tap loop - what is left is
+// the consumers' speed limit under the same barriers; 2 (algo 14) = the LDS-DMA is issued but never waited for.  At 96x96
 // 768->768, same box: 1.08 PFLOP/s complete, 1.22 without the waits, 1.39 without the loads - half of what the loads cost
 // there is the ONE tap a tile has to land in (2-slot ring: the LDS holds the double-buffered halo), half is contention;
 // where four slots fit (48x48) the waits cost nothing and the contention is the same 12-14 %.  Staging the weight tiles
@@ -387,55 +387,33 @@ __global__ __launch_bounds__(512) void conv3_halo_spec_kernel(const IgemmParams 
   halo_tail<T, BM, false, true>(p, acc, smem, bx, bz, img, v0, n0);
 }
 
-
 template <typename T, int BM, int NBST, bool PIPE, int DBG = 0>
-static int launch_halo_spec_cfg(const IgemmParams& p, int splitk, hipStream_t stream) {
-  const size_t smem = halo_smem_bytes(p, BM, NBST);
-  static LdsAttrGuard attr_guard;
-  if (int rc_ = k22_ensure_lds_attr(attr_guard, reinterpret_cast<const void*>(&conv3_halo_spec_kernel<T, BM, NBST, PIPE, DBG>), 160 * 1024, __FILE__, __LINE__)) return rc_;
-  IgemmParams q = p;
-  q.splitk = splitk;
-  const int B = p.M / (p.H * p.W);
-  const int nblocks = B * conv3_halo_tiles_per_image(p, BM) * ((p.N + HALO_BN - 1) / HALO_BN) * splitk;
-  hipLaunchKernelGGL((conv3_halo_spec_kernel<T, BM, NBST, PIPE, DBG>), dim3(nblocks), dim3(512), smem, stream, q);
-  K22_CHECK_LAUNCH();
-  return K22_OK;
+static int run_spec(const IgemmParams& p, const IgemmLaunch& L, hipStream_t stream) {
+  static LdsAttrGuard guard;
+  return launch_lds_kernel(conv3_halo_spec_kernel<T, BM, NBST, PIPE, DBG>, guard, L.grid, L.block, L.lds, 160 * 1024, stream, p);
 }
 template <typename T, int BM, bool PIPE>
-static int launch_halo_spec_nbst(const IgemmParams& p, int nbst, int splitk, hipStream_t stream) {
-  if (nbst == 2) return launch_halo_spec_cfg<T, BM, 2, PIPE>(p, splitk, stream);
-  if (nbst == 3) return launch_halo_spec_cfg<T, BM, 3, PIPE>(p, splitk, stream);
-  if (nbst <= 5) return launch_halo_spec_cfg<T, BM, 4, PIPE>(p, splitk, stream);
-  return launch_halo_spec_cfg<T, BM, 6, PIPE>(p, splitk, stream);
+static int launch_spec_depth(const IgemmParams& p, const IgemmLaunch& L, hipStream_t stream) {
+  if (L.depth == 2) return run_spec<T, BM, 2, PIPE>(p, L, stream);
+  if (L.depth == 3) return run_spec<T, BM, 3, PIPE>(p, L, stream);
+  if (L.depth == 4) return run_spec<T, BM, 4, PIPE>(p, L, stream);
+  return run_spec<T, BM, 6, PIPE>(p, L, stream);
 }
 
-// p.algo == 11 (compiler-scheduled consumers) / 12 (explicit, interleaved fragment pipeline); nbst = ring depth already chosen by the caller
-int launch_conv3_halo_spec(const IgemmParams& p, int dtype, int bm, int nbst, int splitk, hipStream_t stream) {
-  const bool pipe = p.algo == 12;
-  if (dtype == K22_F16X2) {
-    // asymmetric split: activation fragments are 4 registers (hi halves only), so the two-set pipeline fits at BM = 256 too
-    if (!pipe) return bm == 256 ? launch_halo_spec_nbst<x2_t, 256, false>(p, nbst, splitk, stream) : launch_halo_spec_nbst<x2_t, 128, false>(p, nbst, splitk, stream);
-    return bm == 256 ? launch_halo_spec_nbst<x2_t, 256, true>(p, nbst, splitk, stream) : launch_halo_spec_nbst<x2_t, 128, true>(p, nbst, splitk, stream);
-  }
-  if (dtype == K22_F16X3) {
-    // BM = 256: two fragment sets of 8 registers per fragment do not fit beside 128 accumulators (as for fp32): compiler-scheduled consumers
-    if (!pipe) return bm == 256 ? launch_halo_spec_nbst<x3_t, 256, false>(p, nbst, splitk, stream) : launch_halo_spec_nbst<x3_t, 128, false>(p, nbst, splitk, stream);
-    return bm == 256 ? launch_halo_spec_nbst<x3_t, 256, false>(p, nbst, splitk, stream) : launch_halo_spec_nbst<x3_t, 128, true>(p, nbst, splitk, stream);
-  }
-  if (!pipe) {
-    if (dtype == K22_BF16) return bm == 256 ? launch_halo_spec_nbst<bf16_t, 256, false>(p, nbst, splitk, stream) : launch_halo_spec_nbst<bf16_t, 128, false>(p, nbst, splitk, stream);
-    else if (dtype == K22_F16) return bm == 256 ? launch_halo_spec_nbst<f16_t, 256, false>(p, nbst, splitk, stream) : launch_halo_spec_nbst<f16_t, 128, false>(p, nbst, splitk, stream);
-    return bm == 256 ? launch_halo_spec_nbst<float, 256, false>(p, nbst, splitk, stream) : launch_halo_spec_nbst<float, 128, false>(p, nbst, splitk, stream);
-  }
-  if (dtype == K22_BF16) return bm == 256 ? launch_halo_spec_nbst<bf16_t, 256, true>(p, nbst, splitk, stream) : launch_halo_spec_nbst<bf16_t, 128, true>(p, nbst, splitk, stream);
-  else if (dtype == K22_F16) return bm == 256 ? launch_halo_spec_nbst<f16_t, 256, true>(p, nbst, splitk, stream) : launch_halo_spec_nbst<f16_t, 128, true>(p, nbst, splitk, stream);
-  // fp32, BM = 256: two fragment sets of 8 registers per fragment do not fit beside 128 accumulators (the pipelined form spills):
-  // the compiler-scheduled consumer is used there
-  return bm == 256 ? launch_halo_spec_nbst<float, 256, false>(p, nbst, splitk, stream) : launch_halo_spec_nbst<float, 128, true>(p, nbst, splitk, stream);
-}
-#ifdef K22_DEBUG_VARIANTS   // measurement-only forms of algo 12 (wrong results): 13 = no LDS-DMA inside the tap loop, 14 = LDS-DMA issued but never waited for
-int launch_conv3_halo_spec_debug(const IgemmParams& p, int nbst, int splitk, hipStream_t stream) {
-  if (p.algo == 13) return nbst == 2 ? launch_halo_spec_cfg<bf16_t, 256, 2, true, 1>(p, splitk, stream) : launch_halo_spec_cfg<bf16_t, 256, 4, true, 1>(p, splitk, stream);
-  return nbst == 2 ? launch_halo_spec_cfg<bf16_t, 256, 2, true, 2>(p, splitk, stream) : launch_halo_spec_cfg<bf16_t, 256, 4, true, 2>(p, splitk, stream);
-}
+// L.pipe: 0 = compiler-scheduled consumers, 1 = explicit, interleaved fragment pipeline.  x3 and fp32 at BM = 256 have no pipelined form (two
+// fragment sets of 8 registers per fragment do not fit beside 128 accumulators: it spills); the asymmetric split's activation fragments are 4
+// registers (hi halves only), so its two-set pipeline fits at BM = 256 too.
+int launch_conv3_halo_spec(const IgemmParams& p, int dtype, const IgemmLaunch& L, hipStream_t stream) {
+  return k22_with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+#ifdef K22_DEBUG_VARIANTS   // measurement-only forms of the pipelined kernel (wrong results), bf16 at BM = 256: DBG 1 = no LDS-DMA inside the tap loop, 2 = LDS-DMA issued but never waited for
+    if constexpr (std::is_same<T, bf16_t>::value) {
+      if (L.dbg == 1) return L.depth == 2 ? run_spec<T, 256, 2, true, 1>(p, L, stream) : run_spec<T, 256, 4, true, 1>(p, L, stream);
+      if (L.dbg == 2) return L.depth == 2 ? run_spec<T, 256, 2, true, 2>(p, L, stream) : run_spec<T, 256, 4, true, 2>(p, L, stream);
+    }
 #endif
+    if (!L.pipe) return L.bm == 256 ? launch_spec_depth<T, 256, false>(p, L, stream) : launch_spec_depth<T, 128, false>(p, L, stream);
+    if constexpr (!std::is_same<T, x3_t>::value && !std::is_same<T, float>::value) { if (L.bm == 256) return launch_spec_depth<T, 256, true>(p, L, stream); }
+    return launch_spec_depth<T, 128, true>(p, L, stream);
+  });
+}

@@ -363,10 +363,8 @@ struct K22Encoder : GraphPlan {   // tuned: every transformer Linear; graph: the
       const int S = cfg.image_size, patch = cfg.patch;
       ops.push_back([=](hipStream_t st) { return launch_enc_patchify(ptr<float>(s_img), ptr(s_patch), Bn, S, patch, Kp, dt, st); });
       {
-        IgemmParams p = {};
-        p.stages = -1;
-        p.M = B * P; p.N = D; p.Npad = D; p.Kc = Kp; p.K0 = Kp; p.taps = 1; p.lda0 = Kp; p.ldo = D; p.ldr = D;
-        p.out_mode = IG_OUT_ROWMAJOR_F32; p.act = K22_ACT_NONE; p.splitk = 1; p.Wp = wp; p.bias = nullptr;
+        IgemmParams p = igemm_gemm_problem(B * P, D, Kp, 0, IG_OUT_ROWMAJOR_F32);
+        p.splitk = 1; p.Wp = wp;
         ops.push_back([=](hipStream_t st) {
           IgemmParams q = p;
           q.A0 = ptr(s_patch); q.out = ptr(s_pout); q.partial = ptr<float>(s_splitk);

@@ -324,7 +324,7 @@ struct K22UNet : GraphPlan {   // dtype: arithmetic type of the MFMA kernels (K2
   void make_candidates(Tuned& t) { tuned_make_candidates(t, op_dt(t)); }
   void default_cfg(Tuned& t) { tuned_default_cfg(t, op_dt(t)); }
   void finish_cfg(Tuned& t) { tuned_finish_cfg(t, op_dt(t)); }
-  size_t max_splitk_bytes(const Tuned& t) const { return tuned_max_splitk_bytes(t, autotune != 0); }
+  size_t max_splitk_bytes(const Tuned& t) const { return tuned_max_splitk_bytes(t, op_dt(t), autotune != 0); }
   int max_rpi(const Tuned& t) const { return tuned_max_rpi(t, op_dt(t), autotune != 0); }
 
   // ---- precision plan of the asymmetric split engine (K22_F16X2; round 5) -----------------------------------------------------------
@@ -363,9 +363,7 @@ struct K22UNet : GraphPlan {   // dtype: arithmetic type of the MFMA kernels (K2
     Tuned* t = &tuned.back();
     t->dt = conv_dt(role, Hc);
     IgemmParams& p = t->p;
-    p.stages = -1;
-    p.M = B * Hc * Wc; p.N = Cout; p.Npad = (Cout + 63) / 64 * 64; p.Kc = Cin; p.K0 = Cin; p.taps = 9;
-    p.H = Hc; p.W = Wc; p.ldo = Cout; p.ldr = Cout; p.out_mode = out_mode; p.act = K22_ACT_NONE;
+    p = igemm_conv3_problem(B, Hc, Wc, Cin, Cout, out_mode);
     p.Wp = W_(pfx + ".weight"); p.bias = Wf(pfx + ".bias");
     Act sk;
     if (skip_in) {
@@ -395,7 +393,7 @@ struct K22UNet : GraphPlan {   // dtype: arithmetic type of the MFMA kernels (K2
     // The fragment-major copy costs one more copy of this layer's weights in every plan's workspace and a repack per bind:
     // keep it only where the weight-streaming kernel can actually run - the tile table (or the fixed heuristic, autotune off) names it
     // for this problem, or the problem is unknown and will be measured with it as a candidate.
-    if (wf && t->cfg.algo != 20 && (t->from_table || !autotune)) {
+    if (wf && t->cfg.algo != IG_ALGO_STREAM && (t->from_table || !autotune)) {
       wf->bytes = 0; wf = nullptr;
       if (wsf) { wsf->bytes = 0; wsf = nullptr; frag_jobs.pop_back(); }
       frag_jobs.pop_back();
@@ -439,10 +437,8 @@ struct K22UNet : GraphPlan {   // dtype: arithmetic type of the MFMA kernels (K2
     Tuned* t = &tuned.back();
     t->dt = gemm_dt(out_mode == IG_OUT_QKV);
     IgemmParams& p = t->p;
-    p.stages = -1;
-    p.M = M; p.N = N; p.Npad = (N + 63) / 64 * 64; p.Kc = in.C(); p.K0 = in.C0; p.taps = 1;
-    p.lda0 = in.C0; p.lda1 = in.C1; p.ldo = ldo ? ldo : N; p.ldr = N; p.out_mode = out_mode;
-    p.act = K22_ACT_NONE;
+    p = igemm_gemm_problem(M, N, in.C0, in.C1, out_mode);
+    if (ldo) p.ldo = ldo;
     if (in.H > 0 && in.W > 0 && M % (in.H * in.W) == 0 && M / (in.H * in.W) == B) { p.H = in.H; p.W = in.W; }  // rows per image
     if (out_mode == IG_OUT_QKV) p.att_T = in.H * in.W;
     p.Wp = W_(pfx + ".weight"); p.bias = Wf(pfx + ".bias");
@@ -500,9 +496,7 @@ struct K22UNet : GraphPlan {   // dtype: arithmetic type of the MFMA kernels (K2
       skip.s0 = s_S;
     } else if (Cin != Cout) {
       // 1x1 skip_connection: fused into the second conv (halo kernel) when it applies, else its own GEMM
-      IgemmParams probe = {};
-      probe.M = B * Ho * Wo; probe.N = Cout; probe.Npad = (Cout + 63) / 64 * 64; probe.Kc = Cout; probe.K0 = Cout; probe.taps = 9;
-      probe.H = Ho; probe.W = Wo; probe.ldo = Cout; probe.ldr = Cout; probe.out_mode = IG_OUT_ROWMAJOR;
+      IgemmParams probe = igemm_conv3_problem(B, Ho, Wo, Cout, Cout);
       probe.S0 = reinterpret_cast<const void*>(1); probe.S1 = in.s1 ? reinterpret_cast<const void*>(1) : nullptr;
       probe.SK0 = in.C0; probe.SK1 = in.C1; probe.Ws = reinterpret_cast<const void*>(1);
       if (fuse_skip && Cout >= 128 && (conv3_halo_supported(probe, dtype, 256) || conv3_halo_supported(probe, dtype, 128))) {
@@ -827,10 +821,8 @@ struct K22UNet : GraphPlan {   // dtype: arithmetic type of the MFMA kernels (K2
     });
     // ctx[b][nie:S] = to_model_dim_n(full_emb[b])   (one GEMM per batch element: rows re-strided)
     {
-      IgemmParams p = {};
-    p.stages = -1;
-      p.M = ntext; p.N = cd; p.Npad = (cd + 63) / 64 * 64; p.Kc = d1; p.K0 = d1; p.taps = 1; p.lda0 = d1; p.ldo = cd;
-      p.out_mode = IG_OUT_ROWMAJOR; p.splitk = 1;
+      IgemmParams p = igemm_gemm_problem(ntext, cd, d1, 0);
+      p.splitk = 1;
       p.a_raw = k22_is_split(dtype) ? 1 : 0;   // s_fullT: plain rows written by cast_rows
       p.Wp = W_("to_model_dim_n.weight"); p.bias = Wf("to_model_dim_n.bias");
       const size_t es = esz;

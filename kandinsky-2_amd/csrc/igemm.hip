@@ -28,6 +28,7 @@
 //     partials that splitk_reduce_kernel finishes.
 #include "kernels.h"
 #include <stdlib.h>
+#include <type_traits>
 
 template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
@@ -445,224 +446,240 @@ __global__ __launch_bounds__(256) void splitk_reduce_rows_kernel(const IgemmPara
 }
 
 // ---- host side ------------------------------------------------------------------------
-struct IgemmPlan { int halo, bm, bn, splitk, stages; };  // halo: conv3_halo.hip kernel (bm = 256 / 128, bn = 128)
-
-static int g_stages_override = -1;
-static int g_xcd_remap = 1;
-static int g_conv_algo = 0;
-void igemm_set_default_stages(int v) { g_stages_override = (v >= 2 && v <= 4) ? v : -1; }
-void igemm_set_xcd_remap(int v) { g_xcd_remap = v ? 1 : 0; }
-#ifdef K22_DEBUG_VARIANTS
-void igemm_set_conv_algo(int v) { g_conv_algo = ((v >= 0 && v <= 9 && v != 4 && v != 5) || (v >= 11 && v <= 14) || v == 20) ? v : 0; }
-#else   // 8, 9, 13, 14 are measurement-only kernels (wrong results): not reachable in a release build
-void igemm_set_conv_algo(int v) { g_conv_algo = ((v >= 0 && v <= 7 && v != 4 && v != 5) || v == 11 || v == 12 || v == 20) ? v : 0; }
+static IgemmOptions g_opts;
+void igemm_set_default_stages(int v) { g_opts.stages = (v >= 2 && v <= 4) ? v : -1; }
+void igemm_set_xcd_remap(int v) { g_opts.xcd_remap = v ? 1 : 0; }
+void igemm_set_gemm_algo(int v) { g_opts.gemm_algo = (v == IG_ALGO_GEMM8 || v == IG_ALGO_STREAM) ? v : 0; }
+void igemm_set_conv_algo(int v) {
+  bool ok = v == IG_ALGO_GENERIC || v == IG_ALGO_STREAM || (igemm_algo_is_halo(v) && !igemm_algo_is_debug(v));
+#ifdef K22_DEBUG_VARIANTS   // the measurement-only kernels (wrong results) are not reachable in a release build
+  ok = ok || igemm_algo_is_debug(v);
 #endif
-static int g_gemm_algo = 0;   // 0 = generic igemm_kernel, 10 = gemm8_kernel where it applies (unit tests / kernel benches)
-void igemm_set_gemm_algo(int v) { g_gemm_algo = (v == 10 || v == 20) ? v : 0; }
-
-static int g_default_stages() {
-  static int v = -1;
-  if (g_stages_override >= 0) return g_stages_override;
-  if (v < 0) {
-    const char* e = getenv("K22_IGEMM_STAGES");  // 2..4 = LDS-DMA pipeline depth
-    v = e ? atoi(e) : 2;
-    if (v < 2 || v > 4) v = 2;
-  }
-  return v;
+  g_opts.conv_algo = ok ? v : 0;
 }
 
-static IgemmPlan igemm_plan(const IgemmParams& p, int dtype) {
+// Can the split-K finish run row-tiled (splitk_reduce_rows_kernel: 16 rows of one image per workgroup, GroupNorm sums on request)?  3x3
+// convolutions always finish that way; plain GEMMs only when they owe GroupNorm sums.
+static bool reduce_rows_ok(const IgemmParams& p, bool stats) {
+  const int hw = (p.taps == 9 || stats) ? p.H * p.W : 0;
+  return hw > 0 && hw % 16 == 0 && (p.N & 3) == 0 && (p.ldo & 3) == 0 && (p.ldr & 3) == 0 &&
+         (p.out_mode == IG_OUT_ROWMAJOR || p.out_mode == IG_OUT_ROWMAJOR_F32);
+}
+
+int igemm_resolve(const IgemmParams& p, int dtype, IgemmLaunch* out) {
+  const IgemmOptions o = g_opts;
+  if (dtype < K22_BF16 || dtype > K22_F16X2) return k22_set_error(K22_EINVAL, "igemm: bad dtype");
   const int BK = k22_bk(dtype);
   const int nkt = p.taps * (p.Kc / BK);
-  IgemmPlan pl;
-  pl.halo = 0;
-  pl.stages = (p.stages >= 2 && p.stages <= 4) ? p.stages : g_default_stages();
+  const bool qkv = p.out_mode == IG_OUT_QKV;
+  IgemmLaunch L = {};
+  L.xcd_remap = o.xcd_remap;
+  L.block = 512;
+  // ring depth asked for on the 8-wave kernels: the problem's, else the "igemm_stages" option
+  const int want = (p.stages < 2 && o.stages >= 0) ? o.stages : p.stages;
   auto blocks = [&](int bm, int bn) { return ((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn); };
-  // ---- weight-streaming small-M kernel (stream_gemm.hip): p.algo == 20 (tuner candidate) or the conv_algo / gemm_algo option --
-  if (p.algo == 20 || (p.algo == 0 && (p.taps == 9 ? g_conv_algo : g_gemm_algo) == 20)) {
+  // ---- weight-streaming small-M kernel (stream_gemm.hip): the tuner's candidate or the conv_algo / gemm_algo option -----------
+  if (p.algo == IG_ALGO_STREAM || (p.algo == IG_ALGO_AUTO && (p.taps == 9 ? o.conv_algo : o.gemm_algo) == IG_ALGO_STREAM)) {
     const int mb = p.force_bm == 288 ? 9 : 5;
     if (stream_supported(p, dtype, mb)) {
-      pl.halo = 20; pl.bm = mb * 32; pl.bn = 64;
-      const int nslab = p.Kc / 64;
-      if (p.splitk > 0) {
-        pl.splitk = p.splitk;
-      } else {
-        const int nb = stream_mtiles(p, mb);
-        pl.splitk = nb >= 240 ? 1 : 240 / nb;
-      }
-      if (pl.splitk > nslab) pl.splitk = nslab;
-      if (pl.splitk < 1) pl.splitk = 1;
-      return pl;
+      L.family = IG_FAM_STREAM; L.algo = IG_ALGO_STREAM; L.bm = mb * 32; L.bn = 64;
+      const int nslab = p.Kc / 64, nb = stream_mtiles(p, mb);
+      L.splitk = p.splitk > 0 ? p.splitk : (nb >= 240 ? 1 : 240 / nb);
+      if (L.splitk > nslab) L.splitk = nslab;
+      if (L.splitk < 1) L.splitk = 1;
+      L.block = 256; L.grid = (unsigned)nb; L.lds = stream_lds_bytes(p, mb);
     }
   }
-  // ---- 3x3 convolution: LDS-resident halo kernels when they apply (algo 2 = 128-byte rows, 3 = 64-byte rows) -----
-  const int algo = (p.algo && p.algo != 20) ? p.algo : (g_conv_algo == 20 ? 0 : g_conv_algo);
-  if (p.taps == 9 && algo != 1 && p.N >= 128 && !p.a_raw) {   // (the halo kernels read their input in x3 chunks only)
+  // ---- 3x3 convolution: the LDS-resident halo kernels when they apply -----------------------------------------------------------
+  const int conv_algo = (p.algo && p.algo != IG_ALGO_STREAM) ? p.algo : (o.conv_algo == IG_ALGO_STREAM ? 0 : o.conv_algo);
+  if (!L.algo && p.taps == 9 && conv_algo != IG_ALGO_GENERIC && p.N >= 128 && !p.a_raw) {   // (the halo kernels read their input in x3 chunks only)
     IgemmParams ph = p;
-    ph.algo = ((algo >= 3 && algo <= 9 && algo != 4 && algo != 5) || (algo >= 11 && algo <= 14)) ? algo : 2;
+    ph.algo = igemm_algo_is_halo(conv_algo) ? conv_algo : IG_ALGO_HALO;
     int bm = 0;
     if (p.force_bm == 256 || p.force_bm == 128) {
-      if (conv3_halo_supported(ph, dtype, p.force_bm) && (algo >= 2 || p.force_bn == 0)) bm = p.force_bm;
+      if (conv3_halo_supported(ph, dtype, p.force_bm) && (conv_algo >= IG_ALGO_HALO || p.force_bn == 0)) bm = p.force_bm;
     } else if (p.force_bm == 0) {
       if (conv3_halo_supported(ph, dtype, 256)) bm = 256;
       else if (conv3_halo_supported(ph, dtype, 128)) bm = 128;
     }
     if (bm) {
-      const int nslab = (p.Kc / BK) * (ph.algo == 3 ? 2 : 1);   // split-K granularity: slabs / half slabs
-      pl.halo = ph.algo; pl.bm = bm; pl.bn = 128;
+      L.algo = ph.algo; L.bm = bm; L.bn = 128;
+      const int nslab = (p.Kc / BK) * (L.algo == IG_ALGO_HALO3 ? 2 : 1);   // split-K granularity: slabs / half slabs
+      const int nb = (p.M / (p.H * p.W)) * conv3_halo_tiles_per_image(p, bm) * ((p.N + 127) / 128);
       if (p.splitk > 0) {
-        pl.splitk = p.splitk;
+        L.splitk = p.splitk;
       } else {
-        const int B = p.M / (p.H * p.W);
-        const int nb = B * conv3_halo_tiles_per_image(p, bm) * ((p.N + 127) / 128);
         int sk = 1;
         while (nb * sk < 200 && sk < 16 && (p.Kc / BK) / (sk * 2) >= 2) sk *= 2;
-        pl.splitk = sk;
+        L.splitk = sk;
       }
-      if (pl.splitk > nslab) pl.splitk = nslab;
-      if (pl.splitk < 1) pl.splitk = 1;
-      return pl;
+      if (L.splitk > nslab) L.splitk = nslab;
+      if (L.splitk < 1) L.splitk = 1;
+      L.grid = (unsigned)nb;
+      L.depth = conv3_halo_ring(ph, bm);
+      if (want >= 2 && want < L.depth) L.depth = want == 5 ? 4 : want;   // shallower ring on request (instantiated: 2, 3, 4, 6; halo3: 2, 3, 4)
+      const bool split = k22_is_split(dtype);
+      if (conv3_algo_fuses_gn(L.algo)) {
+        // x3 and fp32 at BM = 256: two fragment sets of 8 registers per fragment do not fit beside 128 accumulators: compiler-scheduled consumers
+        L.family = IG_FAM_SPEC;
+        L.pipe = (L.algo == IG_ALGO_SPEC_PIPE && !(bm == 256 && (dtype == K22_F16X3 || dtype == K22_F32))) ? 1 : 0;
+      } else if (split) {
+        // split precision: one lock-step form (asm LDS-DMA) whichever of 2 / 6 / 7 was named
+        if (igemm_algo_is_debug(L.algo)) return k22_set_error(K22_EINVAL, "conv3_halo: no measurement-only variants in split precision");
+        L.family = IG_FAM_HALO; L.pipe = 2;
+      } else if (L.algo == IG_ALGO_HALO3) {
+        L.family = IG_FAM_HALO3;
+      } else if (igemm_algo_is_debug(L.algo)) {
+#ifdef K22_DEBUG_VARIANTS   // measurement-only kernels (wrong results) are compiled only into a developer build: make EXTRA=-DK22_DEBUG_VARIANTS
+        if (L.algo == IG_ALGO_DBG_SPEC_NO_DMA || L.algo == IG_ALGO_DBG_SPEC_NO_WAIT) {
+          if (dtype != K22_BF16 || bm != 256) return k22_set_error(K22_EINVAL, "conv3_halo: the debug variants are bf16, BM = 256 only");
+          L.family = IG_FAM_SPEC; L.pipe = 1; L.dbg = L.algo == IG_ALGO_DBG_SPEC_NO_DMA ? 1 : 2; L.depth = L.depth == 2 ? 2 : 4;
+        } else {
+          if (dtype != K22_BF16 || bm != 256) return k22_set_error(K22_EINVAL, "conv3_halo: debug variants are bf16, BM = 256 only");
+          L.family = IG_FAM_HALO; L.pipe = L.algo == IG_ALGO_DBG_NO_DMA ? 3 : 4;
+        }
+#else
+        return k22_set_error(K22_EINVAL, "conv3_halo: measurement-only variants need a -DK22_DEBUG_VARIANTS build");
+#endif
+      } else {
+        L.family = IG_FAM_HALO;
+        L.pipe = L.algo == IG_ALGO_HALO_PIPE ? 1 : (L.algo == IG_ALGO_HALO_ASM ? 2 : 0);
+      }
+      L.lds = conv3_halo_lds_bytes(ph, bm, L.depth);
     }
   }
-  // ---- plain GEMM on the 8-wave frame (p.algo == 10: tuner candidate; or the "gemm_algo" option) --------------
-  if (p.taps == 1 && (p.algo == 10 || (p.algo == 0 && g_gemm_algo == 10))) {
+  // ---- plain GEMM on the 8-wave frame (gemm8.hip): the tuner's candidate or the "gemm_algo" option -----------------------------
+  if (!L.algo && p.taps == 1 && (p.algo == IG_ALGO_GEMM8 || (p.algo == IG_ALGO_AUTO && o.gemm_algo == IG_ALGO_GEMM8))) {
+    const int hw = p.H > 0 ? p.H * p.W : p.M;
     int bm = 0;
     if (p.force_bm == 256 || p.force_bm == 128) { if (gemm8_supported(p, dtype, p.force_bm)) bm = p.force_bm; }
-    else if (gemm8_supported(p, dtype, 256)) {
-      const int hw = p.H > 0 ? p.H * p.W : p.M;
+    else if (gemm8_supported(p, dtype, 256))
       bm = ((p.M / hw) * ((hw + 255) / 256) * ((p.N + 127) / 128) >= 400 || hw % 256 == 0) ? 256 : 128;
-    }
     if (bm) {
-      pl.halo = 10; pl.bm = bm; pl.bn = 128;
-      pl.splitk = p.splitk > 0 ? p.splitk : 1;
-      if (p.out_mode == IG_OUT_QKV) pl.splitk = 1;
-      if (pl.splitk > p.Kc / BK) pl.splitk = p.Kc / BK;
-      return pl;
+      L.algo = IG_ALGO_GEMM8; L.bm = bm; L.bn = 128;
+      L.splitk = p.splitk > 0 ? p.splitk : 1;
+      if (qkv) L.splitk = 1;
+      if (L.splitk > p.Kc / BK) L.splitk = p.Kc / BK;
+      L.grid = (unsigned)((p.M / hw) * gemm8_tiles_per_image(p, bm) * ((p.N + 127) / 128));
+      // ring: 3 stages of 48 KB at BM = 256; at BM = 128 (32 KB per stage) 4 stages, or 2 = 68 KB with the epilogue tile, so that TWO workgroups
+      // share a CU and one's prologue / epilogue overlaps the other's K loop (short-K GEMMs).  A request of 3 / 4 selects the specialised,
+      // pipelined kernel where it exists (16-bit types; the split types keep the lock-step kernel), 4 = its two-per-CU form (BM = 128 only).
+      if ((want == 3 || want == 4) && gemm8_spec_supported(dtype)) {
+        L.family = IG_FAM_GEMM8_SPEC; L.pipe = 1;
+        L.depth = (want == 4 && bm == 128) ? 2 : (bm == 256 ? 3 : 4);
+      } else {
+        L.family = IG_FAM_GEMM8;
+        L.depth = bm == 256 ? 3 : (want == 2 ? 2 : 4);
+        L.a_raw = (k22_is_split(dtype) && p.a_raw) ? 1 : 0;
+      }
+      L.lds = gemm8_lds_bytes(bm, L.depth);
     }
   }
-  if (p.force_bm && p.force_bn) {
-    pl.bm = p.force_bm;
-    pl.bn = p.force_bn;
-  } else if (p.N <= 64) {
-    pl.bm = (p.M >= 128) ? 128 : 64;
-    pl.bn = 64;
-  } else if (blocks(128, 128) >= 160) {
-    pl.bm = 128; pl.bn = 128;
-  } else if (p.M > 64) {
-    pl.bm = 128; pl.bn = 64;
-  } else {
-    pl.bm = 64; pl.bn = 64;
+  // ---- generic implicit GEMM (igemm_kernel) ---------------------------------------------------------------------------------------
+  if (!L.algo) {
+    L.family = IG_FAM_GENERIC; L.algo = IG_ALGO_GENERIC; L.block = 256;
+    if (p.force_bm && p.force_bn) { L.bm = p.force_bm; L.bn = p.force_bn; }
+    else if (p.N <= 64) { L.bm = (p.M >= 128) ? 128 : 64; L.bn = 64; }
+    else if (blocks(128, 128) >= 160) { L.bm = 128; L.bn = 128; }
+    else if (p.M > 64) { L.bm = 128; L.bn = 64; }
+    else { L.bm = 64; L.bn = 64; }
+    if ((L.bm != 128 && L.bm != 64) || (L.bn != 128 && L.bn != 64)) return k22_set_error(K22_EINVAL, "igemm: unsupported tile configuration");
+    L.grid = (unsigned)blocks(L.bm, L.bn);
+    if (p.splitk > 0) {
+      L.splitk = p.splitk;
+    } else {
+      int sk = 1;
+      while ((int)L.grid * sk < 200 && sk < 16 && nkt / (sk * 2) >= 6) sk *= 2;
+      L.splitk = sk;
+    }
+    if (L.splitk > nkt) L.splitk = nkt > 0 ? nkt : 1;
+    // LDS-DMA ring: the problem's request, else the option, else env K22_IGEMM_STAGES, else 2
+    static const int env_stages = [] { const char* e = getenv("K22_IGEMM_STAGES"); const int v = e ? atoi(e) : 2; return (v < 2 || v > 4) ? 2 : v; }();
+    L.depth = (p.stages >= 2 && p.stages <= 4) ? p.stages : (o.stages >= 0 ? o.stages : env_stages);
+    L.a_raw = (k22_is_split(dtype) && p.a_raw) ? 1 : 0;
+    static const int dbg_pad = getenv("K22_DBG_LDS_PAD") ? atoi(getenv("K22_DBG_LDS_PAD")) : 0;   // debug (tools/lds_victim_probe.py)
+    const size_t smem0 = (size_t)L.depth * (L.bm + L.bn) * 128;
+    L.lds = dbg_pad == 1 ? (smem0 + 1279) / 1280 * 1280 : (dbg_pad == 2 ? smem0 + 4096 : smem0);
   }
-  if (p.splitk > 0) {
-    pl.splitk = p.splitk;
-  } else {
-    const int nb = blocks(pl.bm, pl.bn);
-    int sk = 1;
-    while (nb * sk < 200 && sk < 16 && nkt / (sk * 2) >= 6) sk *= 2;
-    pl.splitk = sk;
+  const bool stream = L.family == IG_FAM_STREAM, generic = L.family == IG_FAM_GENERIC;
+  if (qkv && !stream) {
+    if (p.splitk > 1) return k22_set_error(K22_EINVAL, "igemm: the qkv projection splits K only on the streaming kernel");
+    L.splitk = 1;
   }
-  if (pl.splitk > nkt) pl.splitk = nkt > 0 ? nkt : 1;
-  return pl;
+  if (!stream) {
+    if (p.res_f32 && !generic) return k22_set_error(K22_EINVAL, "igemm: fp32 residual is not supported by the halo kernel");
+    if (p.gn_coeff != nullptr && !conv3_algo_fuses_gn(L.algo))
+      return k22_set_error(K22_EINVAL, "igemm: the fused GroupNorm-apply input needs the specialised halo kernel (algo 11 / 12)");
+    if (p.S0 != nullptr && generic) return k22_set_error(K22_EINVAL, "igemm: the fused 1x1 skip connection needs the halo kernel");
+    if (p.stats != nullptr && L.splitk == 1 && generic)
+      return k22_set_error(K22_EINVAL, "igemm: GroupNorm partial sums requested from a configuration that cannot produce them");
+  }
+  L.grid *= (unsigned)L.splitk;   // (so far: the workgroups of one split)
+  // the streaming kernel always leaves fp32 partials; the others finish a split only
+  const bool finishes = stream || L.splitk > 1;
+  L.finish = !finishes ? IG_FINISH_NONE : (reduce_rows_ok(p, p.stats != nullptr) ? IG_FINISH_ROWS : IG_FINISH_FLAT);
+  // GroupNorm partial sums the launch could write: the row-tiled finish's 16-row blocks, else the 8-wave kernels' own m-tiles
+  if (p.taps == 1 && (generic || p.H <= 0 || qkv)) L.stats_rows_per_image = 0;
+  else if (finishes) L.stats_rows_per_image = reduce_rows_ok(p, true) ? p.H * p.W / 16 : 0;
+  else if (generic) L.stats_rows_per_image = 0;
+  else L.stats_rows_per_image = p.taps == 1 ? gemm8_tiles_per_image(p, L.bm) : conv3_halo_tiles_per_image(p, L.bm);
+  *out = L;
+  return K22_OK;
 }
 
 int igemm_choose_splitk(const IgemmParams& p, int dtype) {
   IgemmParams q = p;
   q.splitk = 0;
-  return igemm_plan(q, dtype).splitk;
-}
-
-static bool reduce_rows_ok(const IgemmParams& p) {
-  // 3x3 convolutions always finish through the row-tiled reduction; plain GEMMs only when they owe GroupNorm sums
-  const int hw = (p.taps == 9 || p.stats != nullptr) ? p.H * p.W : 0;
-  return hw > 0 && hw % 16 == 0 && (p.N & 3) == 0 && (p.ldo & 3) == 0 && (p.ldr & 3) == 0 &&
-         (p.out_mode == IG_OUT_ROWMAJOR || p.out_mode == IG_OUT_ROWMAJOR_F32);
+  IgemmLaunch L;
+  return igemm_resolve(q, dtype, &L) == K22_OK ? L.splitk : 1;
 }
 
 int igemm_stats_rows_per_image(const IgemmParams& p, int dtype) {
-  const IgemmPlan pl = igemm_plan(p, dtype);
-  if (pl.halo == 20) {   // always finished by the row-tiled reduction
-    if (p.H <= 0 || p.out_mode == IG_OUT_QKV) return 0;
-    IgemmParams q = p;
-    q.stats = reinterpret_cast<float*>(1);
-    return reduce_rows_ok(q) ? p.H * p.W / 16 : 0;
-  }
-  if (p.taps == 1) {
-    if (pl.halo != 10 || p.H <= 0 || p.out_mode == IG_OUT_QKV) return 0;
-    if (pl.splitk > 1) {
-      IgemmParams q = p;
-      q.stats = reinterpret_cast<float*>(1);   // "owes GroupNorm sums": the row-tiled reduction
-      return reduce_rows_ok(q) ? p.H * p.W / 16 : 0;
-    }
-    return gemm8_tiles_per_image(p, pl.bm);
-  }
-  if (pl.splitk > 1) return reduce_rows_ok(p) ? p.H * p.W / 16 : 0;
-  if (pl.halo) return conv3_halo_tiles_per_image(p, pl.bm);
-  return 0;
-}
-
-template <typename T>
-static int launch_reduce(const IgemmParams& q, hipStream_t stream) {
-  if (q.stats != nullptr || reduce_rows_ok(q)) {
-    if (!reduce_rows_ok(q)) return k22_set_error(K22_EINVAL, "igemm: GroupNorm partial sums are not available for this split-K problem");
-    hipLaunchKernelGGL((splitk_reduce_rows_kernel<T>), dim3((q.M + 15) / 16, (q.N + 63) / 64), dim3(256), 0, stream, q);
-    K22_CHECK_LAUNCH();
-    return K22_OK;
-  }
-  const int64_t total = (int64_t)q.M * q.N;
-  int nb = (int)((total / 4 + 255) / 256);
-  if (nb > 2048) nb = 2048;
-  if (nb < 1) nb = 1;
-  hipLaunchKernelGGL((splitk_reduce_kernel<T>), dim3(nb), dim3(256), 0, stream, q);
-  K22_CHECK_LAUNCH();
-  return K22_OK;
-}
-
-template <typename T, int BM, int BN, int STAGES, bool ARAW = false>
-static int launch_cfg(const IgemmParams& p, int splitk, hipStream_t stream) {
-  constexpr int smem0 = STAGES * (BM + BN) * 128;
-  static const int dbg_pad = getenv("K22_DBG_LDS_PAD") ? atoi(getenv("K22_DBG_LDS_PAD")) : 0;   // debug (tools/lds_victim_probe.py)
-  const int smem = dbg_pad == 1 ? (smem0 + 1279) / 1280 * 1280 : (dbg_pad == 2 ? smem0 + 4096 : smem0);
-  static LdsAttrGuard attr_guard;
-  if (int rc_ = k22_ensure_lds_attr(attr_guard, reinterpret_cast<const void*>(&igemm_kernel<T, BM, BN, STAGES, ARAW>), smem, __FILE__, __LINE__)) return rc_;
-  IgemmParams q = p;
-  q.splitk = splitk;
-  q.xcd_remap = g_xcd_remap;
-  const int nblocks = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN) * splitk;
-  hipLaunchKernelGGL((igemm_kernel<T, BM, BN, STAGES, ARAW>), dim3(nblocks), dim3(256), smem, stream, q);
-  K22_CHECK_LAUNCH();
-  if (splitk > 1) {
-    if constexpr (is_x3<T>::value) return launch_reduce<float>(q, stream);   // an x3 epilogue stores fp32
-    else return launch_reduce<T>(q, stream);
-  }
-  return K22_OK;
-}
-
-template <typename T, int BM, int BN>
-static int launch_stages(const IgemmParams& p, const IgemmPlan& pl, hipStream_t stream) {
-  if constexpr (is_x3<T>::value) {
-    if (p.a_raw) {
-      if (pl.stages == 2) return launch_cfg<T, BM, BN, 2, true>(p, pl.splitk, stream);
-      if (pl.stages == 3) return launch_cfg<T, BM, BN, 3, true>(p, pl.splitk, stream);
-      return launch_cfg<T, BM, BN, 4, true>(p, pl.splitk, stream);
-    }
-  }
-  if (pl.stages == 2) return launch_cfg<T, BM, BN, 2>(p, pl.splitk, stream);
-  if (pl.stages == 3) return launch_cfg<T, BM, BN, 3>(p, pl.splitk, stream);
-  return launch_cfg<T, BM, BN, 4>(p, pl.splitk, stream);
-}
-
-template <typename T>
-static int launch_typed(const IgemmParams& p, const IgemmPlan& pl, hipStream_t stream) {
-  if (pl.bm == 128 && pl.bn == 128) return launch_stages<T, 128, 128>(p, pl, stream);
-  if (pl.bm == 128 && pl.bn == 64) return launch_stages<T, 128, 64>(p, pl, stream);
-  if (pl.bm == 64 && pl.bn == 128) return launch_stages<T, 64, 128>(p, pl, stream);
-  if (pl.bm == 64 && pl.bn == 64) return launch_stages<T, 64, 64>(p, pl, stream);
-  return k22_set_error(K22_EINVAL, "igemm: unsupported tile configuration");
+  IgemmLaunch L;
+  return igemm_resolve(p, dtype, &L) == K22_OK ? L.stats_rows_per_image : 0;
 }
 
 // split-K finish of an engine of arithmetic type `dtype`: the partials are fp32 and so is what an x3 epilogue stores
-static int launch_reduce_dt(const IgemmParams& q, int dtype, hipStream_t stream) {
-  return dtype == K22_BF16 ? launch_reduce<bf16_t>(q, stream) : (dtype == K22_F16 ? launch_reduce<f16_t>(q, stream) : launch_reduce<float>(q, stream));
+static int launch_finish(const IgemmParams& q, int dtype, const IgemmLaunch& L, hipStream_t stream) {
+  return k22_with_dtype(dtype, [&](auto tag) {
+    using T0 = typename decltype(tag)::type;
+    using T = typename std::conditional<is_x3<T0>::value, float, T0>::type;
+    if (L.finish == IG_FINISH_ROWS) {
+      hipLaunchKernelGGL((splitk_reduce_rows_kernel<T>), dim3((q.M + 15) / 16, (q.N + 63) / 64), dim3(256), 0, stream, q);
+    } else {
+      const int64_t total = (int64_t)q.M * q.N;
+      int nb = (int)((total / 4 + 255) / 256);
+      if (nb > 2048) nb = 2048;
+      if (nb < 1) nb = 1;
+      hipLaunchKernelGGL((splitk_reduce_kernel<T>), dim3(nb), dim3(256), 0, stream, q);
+    }
+    K22_CHECK_LAUNCH();
+    return (int)K22_OK;
+  });
+}
+
+template <typename T, int BM, int BN, int STAGES, bool ARAW>
+static int run_generic(const IgemmParams& q, const IgemmLaunch& L, hipStream_t stream) {
+  static LdsAttrGuard guard;
+  return launch_lds_kernel(igemm_kernel<T, BM, BN, STAGES, ARAW>, guard, L.grid, L.block, L.lds, (int)L.lds, stream, q);
+}
+template <typename T, int BM, int BN>
+static int launch_generic_tile(const IgemmParams& q, const IgemmLaunch& L, hipStream_t stream) {
+  auto depth = [&](auto araw) {
+    constexpr bool ARAW = decltype(araw)::value;
+    if (L.depth == 2) return run_generic<T, BM, BN, 2, ARAW>(q, L, stream);
+    if (L.depth == 3) return run_generic<T, BM, BN, 3, ARAW>(q, L, stream);
+    return run_generic<T, BM, BN, 4, ARAW>(q, L, stream);
+  };
+  if constexpr (is_x3<T>::value) { if (L.a_raw) return depth(std::true_type{}); }
+  return depth(std::false_type{});
+}
+static int launch_generic(const IgemmParams& q, int dtype, const IgemmLaunch& L, hipStream_t stream) {
+  return k22_with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    if (L.bm == 128) return L.bn == 128 ? launch_generic_tile<T, 128, 128>(q, L, stream) : launch_generic_tile<T, 128, 64>(q, L, stream);
+    return L.bn == 128 ? launch_generic_tile<T, 64, 128>(q, L, stream) : launch_generic_tile<T, 64, 64>(q, L, stream);
+  });
 }
 
 int launch_igemm(const IgemmParams& p, int dtype, hipStream_t stream) {
@@ -677,51 +694,26 @@ int launch_igemm(const IgemmParams& p, int dtype, hipStream_t stream) {
     if (p.taps != 1 || p.N % 192 || (p.ldo & 3) || !p.kall || !p.vtall || p.att_T <= 0 || p.M % p.att_T || p.residual)
       return k22_set_error(K22_EINVAL, "igemm: bad qkv-projection problem (N = 3*heads*64, no residual)");
   }
-  IgemmPlan pl = igemm_plan(p, dtype);
-  if (p.out_mode == IG_OUT_QKV && pl.halo != 20) {
-    if (p.splitk > 1) return k22_set_error(K22_EINVAL, "igemm: the qkv projection splits K only on the streaming kernel");
-    pl.splitk = 1;
-  }
-  if (pl.halo == 20) {
-    // weight-streaming kernel: fp32 partial tiles, then the common split-K finish (also for splitk == 1)
+  IgemmParams q = p;
+  IgemmLaunch L;
+  if (int rc = igemm_resolve(q, dtype, &L)) return rc;
+  if (L.family == IG_FAM_STREAM) {
     if (p.partial == nullptr) return k22_set_error(K22_EINVAL, "igemm: the streaming kernel needs the fp32 partial buffer");
-    IgemmParams q = p;
-    q.splitk = pl.splitk;
-    q.xcd_remap = g_xcd_remap;
-    int rc = launch_stream(q, dtype, pl.bm / 32, pl.splitk, stream);
-    if (rc) return rc;
-    return launch_reduce_dt(q, dtype, stream);
+  } else if (L.splitk > 1 && p.partial == nullptr) {   // no scratch given: the problem runs unsplit
+    q.splitk = 1;
+    if (int rc = igemm_resolve(q, dtype, &L)) return rc;
   }
-  if (pl.splitk > 1 && p.partial == nullptr) pl.splitk = 1;
-  if (p.res_f32 && pl.halo) return k22_set_error(K22_EINVAL, "igemm: fp32 residual is not supported by the halo kernel");
-  if (p.gn_coeff != nullptr && !conv3_algo_fuses_gn(pl.halo))
-    return k22_set_error(K22_EINVAL, "igemm: the fused GroupNorm-apply input needs the specialised halo kernel (algo 11 / 12)");
-  if (p.S0 != nullptr && !pl.halo) return k22_set_error(K22_EINVAL, "igemm: the fused 1x1 skip connection needs the halo kernel");
-  if (p.stats != nullptr && pl.splitk == 1 && !pl.halo)
-    return k22_set_error(K22_EINVAL, "igemm: GroupNorm partial sums requested from a configuration that cannot produce them");
-  if (pl.halo == 10) {
-    IgemmParams q = p;
-    q.splitk = pl.splitk;
-    q.xcd_remap = g_xcd_remap;
-    if (q.stages < 2 && g_stages_override >= 0) q.stages = g_stages_override;   // "igemm_stages" option (benches / tests)
-    int rc = launch_gemm8(q, dtype, pl.bm, pl.splitk, stream);
-    if (rc || pl.splitk == 1) return rc;
-    return launch_reduce_dt(q, dtype, stream);
+  if (L.finish == IG_FINISH_FLAT && q.stats != nullptr)
+    return k22_set_error(K22_EINVAL, "igemm: GroupNorm partial sums are not available for this split-K problem");
+  q.splitk = L.splitk; q.xcd_remap = L.xcd_remap; q.algo = L.algo;
+  int rc;
+  switch (L.family) {
+    case IG_FAM_STREAM: rc = launch_stream(q, dtype, L, stream); break;
+    case IG_FAM_GEMM8: case IG_FAM_GEMM8_SPEC: rc = launch_gemm8(q, dtype, L, stream); break;
+    case IG_FAM_SPEC: rc = launch_conv3_halo_spec(q, dtype, L, stream); break;
+    case IG_FAM_GENERIC: rc = launch_generic(q, dtype, L, stream); break;
+    default: rc = launch_conv3_halo(q, dtype, L, stream); break;
   }
-  if (pl.halo) {
-    IgemmParams q = p;
-    q.splitk = pl.splitk;
-    q.xcd_remap = g_xcd_remap;
-    q.algo = pl.halo;
-    if (q.stages < 2 && g_stages_override >= 0) q.stages = g_stages_override;   // "igemm_stages" option (benches / tests)
-    int rc = launch_conv3_halo(q, dtype, pl.bm, pl.splitk, stream);
-    if (rc || pl.splitk == 1) return rc;
-    return launch_reduce_dt(q, dtype, stream);
-  }
-  if (dtype == K22_BF16) return launch_typed<bf16_t>(p, pl, stream);
-  else if (dtype == K22_F16) return launch_typed<f16_t>(p, pl, stream);
-  if (dtype == K22_F32) return launch_typed<float>(p, pl, stream);
-  if (dtype == K22_F16X3) return launch_typed<x3_t>(p, pl, stream);
-  if (dtype == K22_F16X2) return launch_typed<x2_t>(p, pl, stream);
-  return k22_set_error(K22_EINVAL, "igemm: bad dtype");
+  if (rc || L.finish == IG_FINISH_NONE) return rc;
+  return launch_finish(q, dtype, L, stream);
 }

@@ -4,6 +4,7 @@
 #include "common.h"
 
 #include <atomic>
+#include <type_traits>
 
 #define K22_OK 0
 #define K22_EINVAL (-1)
@@ -58,9 +59,10 @@ struct IgemmParams {
   int act;               // K22Act applied after bias+residual
   int splitk;            // >= 1 (0 = let the launcher choose)
   int force_bm, force_bn;  // 0 = heuristic
-  int stages;            // 2..4 = LDS-DMA pipeline depth, anything else = default (env K22_IGEMM_STAGES, else 2)
+  int stages = -1;       // ring depth request (see igemm_resolve): 2..4 generic kernel, 2..5 halo kernels, gemm8: 2 = two per CU, 3 / 4 = specialised form;
+                         // anything else = default ("igemm_stages" option, env K22_IGEMM_STAGES, else 2 / the deepest ring that fits)
   int xcd_remap;         // set by the launcher: XCD-aware block renumbering on/off
-  int algo;              // taps == 9 only: 0 auto, 1 generic implicit GEMM, 2 LDS-resident halo kernel (conv3_halo.hip)
+  int algo;              // IgemmAlgo (below): 0 = heuristic / "conv_algo", "gemm_algo" options
   // optional fused 1x1 "skip_connection" of a ResBlock (unet.py:191), halo kernel only:
   //   out += [S0 | S1](unpadded NHWC rows m, SK0 + SK1 channels) . Ws[n][SK0+SK1]^T + bias2[n]
   const void* S0; const void* S1; const void* Ws; const float* bias2;
@@ -87,31 +89,118 @@ struct IgemmParams {
   unsigned long long* st_trace;          // K22_STREAM_DEBUG builds only: 16 stamps per workgroup
   int st_tm, st_rb, st_mtiles, st_buf;   // set by launch_stream (stream_gemm.hip): rows per m-tile, image rows per band, m-tiles, bytes of one LDS A buffer
 };
+// kernel argument, copied by value into every launch: the layout is what the kernels were compiled against
+static_assert(sizeof(IgemmParams) == 320 && std::is_trivially_copyable<IgemmParams>::value, "IgemmParams layout");
+
+// The kernel variants.  The numbers are ABI: K22IgemmProblem.algo, the "conv_algo" / "gemm_algo" options and the tile table use them.
+enum IgemmAlgo {
+  IG_ALGO_AUTO = 0,             // heuristic
+  IG_ALGO_GENERIC = 1,          // igemm_kernel (igemm.hip): 4 waves, bm x bn tile
+  IG_ALGO_HALO = 2,             // conv3_halo_kernel, lock-step, compiler-issued LDS-DMA
+  IG_ALGO_HALO3 = 3,            // conv3_halo3_kernel: 64-byte rows, one filter row per iteration
+  IG_ALGO_HALO_PIPE = 6,        // conv3_halo_kernel, asm LDS-DMA + explicit fragment pipeline
+  IG_ALGO_HALO_ASM = 7,         // conv3_halo_kernel, asm LDS-DMA
+  IG_ALGO_DBG_NO_DMA = 8,       // measurement only (K22_DEBUG_VARIANTS builds, wrong results): no LDS-DMA in the tap loop
+  IG_ALGO_DBG_NO_MFMA = 9,      //   no MFMA
+  IG_ALGO_GEMM8 = 10,           // gemm8_kernel / gemm8_spec_kernel (gemm8.hip): plain GEMM on the 8-wave frame
+  IG_ALGO_SPEC = 11,            // conv3_halo_spec_kernel (conv3_spec.hip): producer / consumer waves
+  IG_ALGO_SPEC_PIPE = 12,       //   + explicit, interleaved fragment pipeline in the consumers
+  IG_ALGO_DBG_SPEC_NO_DMA = 13, // measurement only: forms of 12 without the LDS-DMA in the tap loop /
+  IG_ALGO_DBG_SPEC_NO_WAIT = 14,//   with LDS-DMA that is never waited for
+  IG_ALGO_STREAM = 20           // stream_kernel (stream_gemm.hip): weight streaming for small M
+};
+struct IgemmAlgoName { int algo; const char* name; };   // tuning_report_text's column
+constexpr IgemmAlgoName IGEMM_ALGO_NAMES[] = {{IG_ALGO_GENERIC, "gen"},   {IG_ALGO_HALO, "halo"},   {IG_ALGO_HALO3, "hal3"}, {IG_ALGO_HALO_PIPE, "hal6"},
+                                              {IG_ALGO_HALO_ASM, "hal7"}, {IG_ALGO_GEMM8, "gem8"}, {IG_ALGO_SPEC, "spec"},  {IG_ALGO_SPEC_PIPE, "spcp"}};
+inline const char* igemm_algo_name(int algo) {
+  for (const IgemmAlgoName& a : IGEMM_ALGO_NAMES) if (a.algo == algo) return a.name;
+  return "auto";
+}
+inline bool igemm_algo_is_halo(int a) { return a == IG_ALGO_HALO || a == IG_ALGO_HALO3 || (a >= IG_ALGO_HALO_PIPE && a <= IG_ALGO_DBG_NO_MFMA) || (a >= IG_ALGO_SPEC && a <= IG_ALGO_DBG_SPEC_NO_WAIT); }
+inline bool igemm_algo_is_debug(int a) { return a == IG_ALGO_DBG_NO_DMA || a == IG_ALGO_DBG_NO_MFMA || a == IG_ALGO_DBG_SPEC_NO_DMA || a == IG_ALGO_DBG_SPEC_NO_WAIT; }
+
+// The derived fields of a problem descriptor (Npad, Kc, taps, row strides, geometry); operands, configuration and whatever is particular
+// to a call site are set by the caller.
+inline IgemmParams igemm_gemm_problem(int M, int N, int K0, int K1, int out_mode = IG_OUT_ROWMAJOR, int act = 0) {
+  IgemmParams p = {};
+  p.M = M; p.N = N; p.Npad = (N + 63) / 64 * 64; p.Kc = K0 + K1; p.K0 = K0; p.taps = 1;
+  p.lda0 = K0; p.lda1 = K1; p.ldo = N; p.ldr = N; p.out_mode = out_mode; p.act = act;
+  return p;
+}
+inline IgemmParams igemm_conv3_problem(int B, int H, int W, int Cin, int Cout, int out_mode = IG_OUT_ROWMAJOR, int act = 0) {
+  IgemmParams p = {};
+  p.M = B * H * W; p.N = Cout; p.Npad = (Cout + 63) / 64 * 64; p.Kc = Cin; p.K0 = Cin; p.taps = 9; p.H = H; p.W = W;
+  p.ldo = Cout; p.ldr = Cout; p.out_mode = out_mode; p.act = act;
+  return p;
+}
+
+// ---- one resolved launch ----------------------------------------------------------------------------------------------------------
+// What launch_igemm runs for a problem: igemm_resolve is the ONE place that reads p.algo / p.force_bm / p.force_bn / p.splitk / p.stages and
+// the process-wide options; the plan-time questions (split-K scratch, GroupNorm stats rows) and the launch read the same result.
+enum IgemmFamily { IG_FAM_GENERIC, IG_FAM_HALO, IG_FAM_HALO3, IG_FAM_SPEC, IG_FAM_GEMM8, IG_FAM_GEMM8_SPEC, IG_FAM_STREAM };
+enum IgemmFinish { IG_FINISH_NONE, IG_FINISH_FLAT, IG_FINISH_ROWS };   // split-K finish: none, splitk_reduce_kernel, splitk_reduce_rows_kernel
+struct IgemmLaunch {
+  int family;                // IgemmFamily
+  int algo;                  // IgemmAlgo the problem resolved to (never AUTO)
+  int bm, bn;                // tile (stream: bm = 32 * m-blocks per workgroup)
+  int splitk;
+  int depth;                 // template ring depth instantiated: STAGES (generic), NBST (halo, spec), RB (halo3), NST (gemm8); 0 = stream
+  int pipe;                  // form instantiated: halo = MODE (0 lock-step, 1 pipelined, 2 asm LDS-DMA, 3 / 4 debug); spec / gemm8_spec = PIPE after the
+                             // BM = 256 fall-back of x3 / fp32
+  int dbg;                   // conv3_halo_spec_kernel's DBG (K22_DEBUG_VARIANTS builds)
+  int a_raw;                 // ARAW instantiation (split types, generic kernel and gemm8)
+  int xcd_remap;
+  int finish;                // IgemmFinish
+  int stats_rows_per_image;  // GroupNorm partial-sum rows per image this launch can write (0 = none)
+  unsigned grid, block;
+  size_t lds;                // dynamic LDS bytes
+};
+struct IgemmOptions { int conv_algo = 0, gemm_algo = 0, stages = -1, xcd_remap = 1; };   // k22_set_option; read by igemm_resolve only
+// 0, or the error the launch would fail with.  Operands may be markers / null (plan time): only their presence is looked at.
+int igemm_resolve(const IgemmParams& p, int dtype, IgemmLaunch* L);
+
+// The one launch sequence of the kernels with dynamic LDS: per-device attribute (guard: one per instantiation), launch, check.
+template <typename K>
+inline int launch_lds_kernel(K kernel, LdsAttrGuard& guard, unsigned grid, unsigned block, size_t smem, int attr_bytes, hipStream_t stream, const IgemmParams& params) {
+  if (int rc = k22_ensure_lds_attr(guard, reinterpret_cast<const void*>(kernel), attr_bytes, __FILE__, __LINE__)) return rc;
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), smem, stream, params);
+  K22_CHECK_LAUNCH();
+  return K22_OK;
+}
 
 // How a producer laid out its GroupNorm partial sums: image b owns rows [b*rows_per_image, (b+1)*rows_per_image).
 struct IgemmStatsInfo { int rows_per_image; };
 // Number of stats rows per image launch_igemm will write for this problem (0 = this configuration cannot
-// produce stats; the caller must run the stand-alone gn_stats kernel instead).
+// produce stats; the caller must run the stand-alone gn_stats kernel instead).  igemm_resolve's stats_rows_per_image.
 int igemm_stats_rows_per_image(const IgemmParams& p, int dtype);
 
 int launch_igemm(const IgemmParams& p, int dtype, hipStream_t stream);
-// conv3_halo.hip: 3x3 convolution with the input tile (+halo) resident in LDS across the 9 taps.
+
+// The kernel families behind launch_igemm.  *_supported: can the family run the problem at this tile (the tuner's candidate list, the
+// engines and igemm_resolve ask the same predicates); *_lds_bytes / *_ring: their LDS budget, for igemm_resolve; launch_*: select the
+// instantiation the resolved launch names and run it with the parameters as given (a split-K finish is launch_igemm's).
+// conv3_halo.hip: 3x3 convolution with the input tile (+halo) resident in LDS across the 9 taps (p.algo: which of its kernels).
 bool conv3_halo_supported(const IgemmParams& p, int dtype, int bm);
 // the kernel variants that can take the fused GroupNorm-apply input (IgemmParams::gn_coeff): the specialised halo kernels
-inline bool conv3_algo_fuses_gn(int algo) { return algo == 11 || algo == 12; }
+inline bool conv3_algo_fuses_gn(int algo) { return algo == IG_ALGO_SPEC || algo == IG_ALGO_SPEC_PIPE; }
 int conv3_halo_tiles_per_image(const IgemmParams& p, int bm);
-int launch_conv3_halo(const IgemmParams& p, int dtype, int bm, int splitk, hipStream_t stream);
+int conv3_halo_ring(const IgemmParams& p, int bm);                     // deepest weight ring that fits (0 = none)
+size_t conv3_halo_lds_bytes(const IgemmParams& p, int bm, int depth);
+int launch_conv3_halo(const IgemmParams& p, int dtype, const IgemmLaunch& L, hipStream_t stream);
+int launch_conv3_halo_spec(const IgemmParams& p, int dtype, const IgemmLaunch& L, hipStream_t stream);   // conv3_spec.hip
 int launch_conv3_halo_trace(const IgemmParams& p, int dtype, hipStream_t stream);
-// 8-wave BM x 128 GEMM on the halo kernels' frame (conv3_halo.hip: gemm8_kernel); p.algo == 10 selects it in launch_igemm
+// gemm8.hip: 8-wave BM x 128 GEMM on the halo kernels' frame
 bool gemm8_supported(const IgemmParams& p, int dtype, int bm);
-bool gemm8_spec_supported(int dtype);   // p.stages == 3: gemm8_spec_kernel (producer / consumer waves, explicit fragment pipeline)
+bool gemm8_spec_supported(int dtype);   // gemm8_spec_kernel (producer / consumer waves, explicit fragment pipeline): 16-bit types
 int gemm8_tiles_per_image(const IgemmParams& p, int bm);
-int launch_gemm8(const IgemmParams& p, int dtype, int bm, int splitk, hipStream_t stream);
-// stream_gemm.hip: weight-streaming kernel for small M (p.algo == 20; bm = 160 / 288 selects 5 / 9 m-blocks per workgroup).
+size_t gemm8_lds_bytes(int bm, int depth);
+int launch_gemm8(const IgemmParams& p, int dtype, const IgemmLaunch& L, hipStream_t stream);
+// stream_gemm.hip: weight-streaming kernel for small M (mb = 5 / 9 m-blocks per workgroup: force_bm 160 / 288).
 // It leaves fp32 partial tiles [splitk][M][N] in p.partial (also for splitk == 1); launch_igemm runs the split-K finish.
 bool stream_supported(const IgemmParams& p, int dtype, int mb);
 int stream_mtiles(const IgemmParams& p, int mb);
-int launch_stream(const IgemmParams& p, int dtype, int mb, int splitk, hipStream_t stream);
+size_t stream_lds_bytes(const IgemmParams& p, int mb);
+int launch_stream(const IgemmParams& p, int dtype, const IgemmLaunch& L, hipStream_t stream);
 long stream_launch_count();
 // engine.hip: whole-loop graphs captured / whole-loop replays or eager loop runs since the library was loaded
 long loop_capture_count();
@@ -119,9 +208,10 @@ long loop_launch_count();
 // bytes of the fragment-major copy of a [Npad][taps * Kc] weight matrix, and the one-time repack (any 16-bit dtype)
 size_t stream_frag_bytes(int Npad, int taps, int Kc, int dtype);
 int launch_stream_repack(const void* W, void* out, int Npad, int taps, int Kc, int dtype, hipStream_t stream);
-void igemm_set_gemm_algo(int v);
-void igemm_set_conv_algo(int v);       // tuning knob: 0 auto, 1 generic, 2 halo
-void igemm_set_default_stages(int v);  // tuning knob: 2..4 LDS-DMA stages, -1 env/default
-void igemm_set_xcd_remap(int v);       // tuning knob: XCD-aware block renumbering (default on)
+// k22_set_option's conv / GEMM knobs (IgemmOptions; values outside the accepted set select the default)
+void igemm_set_gemm_algo(int v);       // 0 auto, IG_ALGO_GEMM8, IG_ALGO_STREAM
+void igemm_set_conv_algo(int v);       // 0 auto or an IgemmAlgo of the convolutions
+void igemm_set_default_stages(int v);  // 2..4 ring depth, -1 env/default
+void igemm_set_xcd_remap(int v);       // XCD-aware block renumbering (default on)
 void attention_set_pipe(int v);        // test knob: -1 K22_ATT_PIPE / default, 0 attention_kernel, 1 attention_pipe_kernel (unmasked 16-bit attention)
 int igemm_choose_splitk(const IgemmParams& p, int dtype);  // split-K factor the heuristic picks (scratch = splitk*M*N*4 B)

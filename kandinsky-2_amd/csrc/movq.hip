@@ -45,7 +45,6 @@ struct K22MoVQ : PlanBase {
 
   // generic launch of one igemm problem with the library's heuristics
   void push_igemm(IgemmParams p, std::function<void(IgemmParams&)> bind) {
-    p.stages = -1;
     p.splitk = igemm_choose_splitk(p, dtype);
     if (p.splitk > 1) need(s_splitk, (size_t)p.splitk * p.M * p.N * sizeof(float));
     const int dt = dtype;
@@ -102,18 +101,14 @@ struct K22MoVQ : PlanBase {
   }
 
   void op_conv3(Slot* src, int H, int W, int Cin, int Cout, const std::string& pfx, Slot* residual, Slot* dst, int out_mode) {
-    IgemmParams p = {};
-    p.M = B * H * W; p.N = Cout; p.Npad = (Cout + 63) / 64 * 64; p.Kc = Cin; p.K0 = Cin; p.taps = 9; p.H = H; p.W = W;
-    p.ldo = Cout; p.ldr = Cout; p.out_mode = out_mode; p.act = K22_ACT_NONE;
+    IgemmParams p = igemm_conv3_problem(B, H, W, Cin, Cout, out_mode);
     p.Wp = W_(pfx + ".weight"); p.bias = Wf(pfx + ".bias");
     need(dst, out_mode == IG_OUT_ROWMAJOR ? (size_t)p.M * Cout * esz : (size_t)p.M * Cout * sizeof(float));
     push_igemm(p, [=](IgemmParams& q) { q.A0 = ptr(src); q.residual = residual ? ptr(residual) : nullptr; q.out = ptr(dst); });
   }
 
   void op_gemm(Slot* a, int M, int N, int K, const std::string& pfx, Slot* residual, Slot* dst) {
-    IgemmParams p = {};
-    p.M = M; p.N = N; p.Npad = (N + 63) / 64 * 64; p.Kc = K; p.K0 = K; p.taps = 1; p.lda0 = K; p.ldo = N; p.ldr = N;
-    p.out_mode = IG_OUT_ROWMAJOR; p.act = K22_ACT_NONE;
+    IgemmParams p = igemm_gemm_problem(M, N, K, 0);
     p.Wp = W_(pfx + ".weight"); p.bias = Wf(pfx + ".bias");
     need(dst, (size_t)M * N * esz);
     push_igemm(p, [=](IgemmParams& q) { q.A0 = ptr(a); q.residual = residual ? ptr(residual) : nullptr; q.out = ptr(dst); });
@@ -153,14 +148,12 @@ struct K22MoVQ : PlanBase {
     for (int b = 0; b < Bn; ++b) {
       // V^T_b [C][T] = Wv [C][C] . N_b [T][C]^T
       {
-        IgemmParams p = {};
-        p.M = C; p.N = T; p.Npad = T; p.Kc = C; p.K0 = C; p.taps = 1; p.lda0 = C; p.ldo = T; p.ldr = T; p.out_mode = IG_OUT_ROWMAJOR;
+        IgemmParams p = igemm_gemm_problem(C, T, C, 0);   // (T % 64 == 0: Npad = T)
         push_igemm(p, [=](IgemmParams& q) { q.A0 = wv; q.Wp = ptr(s_N) + (size_t)b * T * C * es; q.bias = nullptr; q.out = ptr(s_VT) + (size_t)b * C * T * es; });
       }
       // scores_b [T][T] = Q_b . K_b^T
       {
-        IgemmParams p = {};
-        p.M = T; p.N = T; p.Npad = T; p.Kc = C; p.K0 = C; p.taps = 1; p.lda0 = C; p.ldo = T; p.ldr = T; p.out_mode = IG_OUT_ROWMAJOR;
+        IgemmParams p = igemm_gemm_problem(T, T, C, 0);
         push_igemm(p, [=](IgemmParams& q) { q.A0 = ptr(s_Q) + (size_t)b * T * C * es; q.Wp = ptr(s_K) + (size_t)b * T * C * es; q.bias = nullptr;
                                             q.out = ptr(s_SC) + (size_t)b * T * T * es; });
       }
@@ -168,8 +161,7 @@ struct K22MoVQ : PlanBase {
     const float scale = 1.0f / sqrtf((float)C);
     ops.push_back([=](hipStream_t st) { return launch_softmax_rows(ptr(s_SC), (int64_t)Bn * T, T, scale, dt, st); });
     for (int b = 0; b < Bn; ++b) {
-      IgemmParams p = {};
-      p.M = T; p.N = C; p.Npad = C; p.Kc = T; p.K0 = T; p.taps = 1; p.lda0 = T; p.ldo = C; p.ldr = C; p.out_mode = IG_OUT_ROWMAJOR;
+      IgemmParams p = igemm_gemm_problem(T, C, T, 0);
       push_igemm(p, [=](IgemmParams& q) { q.A0 = ptr(s_SC) + (size_t)b * T * T * es; q.Wp = ptr(s_VT) + (size_t)b * C * T * es; q.bias = bv;
                                           q.out = ptr(s_O) + (size_t)b * T * C * es; });
     }

@@ -164,13 +164,12 @@ struct GraphPlan : PlanBase {
     tuned.emplace_back();
     Tuned* t = &tuned.back();
     IgemmParams& p = t->p;
-    p.stages = -1;
-    p.M = M; p.N = N; p.Npad = (N + 63) / 64 * 64; p.Kc = K; p.K0 = K; p.taps = 1; p.lda0 = K; p.ldo = ldo; p.ldr = ldo;
-    p.out_mode = mode == 0 ? IG_OUT_ROWMAJOR : IG_OUT_ROWMAJOR_F32; p.act = act; p.res_f32 = mode == 2 ? 1 : 0;
+    p = igemm_gemm_problem(M, N, K, 0, mode == 0 ? IG_OUT_ROWMAJOR : IG_OUT_ROWMAJOR_F32, act);
+    p.ldo = ldo; p.ldr = ldo; p.res_f32 = mode == 2 ? 1 : 0;   // rows of a wider tensor; mode 2: the residual is the output row itself
     p.Wp = W_(pfx + ".weight"); p.bias = Wf(pfx + ".bias");
     tuned_make_candidates(*t, dtype);
     tuned_default_cfg(*t, dtype);
-    need(s_splitk, tuned_max_splitk_bytes(*t, autotune != 0));
+    need(s_splitk, tuned_max_splitk_bytes(*t, dtype, autotune != 0));
     const int dt = dtype;
     t->run = [=](hipStream_t st) {
       IgemmParams q = t->p;

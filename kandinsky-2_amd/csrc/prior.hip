@@ -215,10 +215,8 @@ struct K22Prior : GraphPlan {   // tuned: every transformer Linear; graph: the ~
       });
       // text_enc_proj: one GEMM per batch element straight into rows 0..n_text-1 of the sequence (fp32 out)
       for (int b = 0; b < B; ++b) {
-        IgemmParams p = {};
-        p.stages = -1;
-        p.M = nt; p.N = D; p.Npad = D; p.Kc = cw; p.K0 = cw; p.taps = 1; p.lda0 = cw; p.ldo = D; p.ldr = D;
-        p.out_mode = IG_OUT_ROWMAJOR_F32; p.act = K22_ACT_NONE; p.splitk = 1;
+        IgemmParams p = igemm_gemm_problem(nt, D, cw, 0, IG_OUT_ROWMAJOR_F32);
+        p.splitk = 1;
         p.Wp = W_("text_enc_proj.weight"); p.bias = Wf("text_enc_proj.bias");
         ops.push_back([=](hipStream_t st) {
           IgemmParams q = p;

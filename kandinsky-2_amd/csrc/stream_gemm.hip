@@ -383,55 +383,55 @@ int stream_mtiles(const IgemmParams& p, int mb) {
 static std::atomic<long> g_stream_launches{0};
 long stream_launch_count() { return g_stream_launches.load(); }
 
-template <typename T, int MB, int NB, int DBG, bool FRAG>
-static int launch_stream_cfg(const IgemmParams& p, const StreamGeom& g, int splitk, hipStream_t stream) {
-  static LdsAttrGuard attr_guard;
-  if (int rc_ = k22_ensure_lds_attr(attr_guard, reinterpret_cast<const void*>(&stream_kernel<T, MB, NB, DBG, FRAG>), 160 * 1024, __FILE__, __LINE__)) return rc_;
-  IgemmParams q = p;
-  q.splitk = splitk;
-  q.st_tm = g.tm; q.st_rb = g.rb; q.st_mtiles = g.mtiles; q.st_buf = g.buf;
-  const int nblocks = g.mtiles * (p.Npad / g.nt) * splitk;
-  hipLaunchKernelGGL((stream_kernel<T, MB, NB, DBG, FRAG>), dim3(nblocks), dim3(256), g.smem, stream, q);
-  K22_CHECK_LAUNCH();
-  g_stream_launches.fetch_add(1, std::memory_order_relaxed);
-  return K22_OK;
+size_t stream_lds_bytes(const IgemmParams& p, int mb) {
+  StreamGeom g;
+  return stream_geom(p, mb, &g) ? (size_t)g.smem : 0;
 }
 
-template <typename T>
-static int launch_stream_typed(const IgemmParams& p, const StreamGeom& g, int mb, int splitk, hipStream_t stream) {
+template <typename T, int MB, int NB, int DBG, bool FRAG>
+static int run_stream(const IgemmParams& q, const IgemmLaunch& L, hipStream_t stream) {
+  static LdsAttrGuard guard;
+  const int rc = launch_lds_kernel(stream_kernel<T, MB, NB, DBG, FRAG>, guard, L.grid, L.block, L.lds, 160 * 1024, stream, q);
+  if (rc == K22_OK) g_stream_launches.fetch_add(1, std::memory_order_relaxed);
+  return rc;
+}
+
+// Launches stream_kernel only (L.bm / 32 = 5 or 9 m-blocks per workgroup): it always leaves fp32 partial tiles [splitk][M][N] in p.partial; the
+// finish (bias, residual, activation, rounding, GroupNorm partial sums) is the caller's (launch_igemm), also for splitk == 1.
+int launch_stream(const IgemmParams& p, int dtype, const IgemmLaunch& L, hipStream_t stream) {
+  const int mb = L.bm / 32;
   const bool frag = p.Wfrag != nullptr;
   if (frag && p.S0 != nullptr && p.Wsfrag == nullptr) return k22_set_error(K22_EINVAL, "stream: fragment-major weights given without the skip weights' copy");
-#ifdef K22_STREAM_DEBUG
-  // measurement-only variants: K22_STREAM_DBG bits 1 = no MFMA, 2 = weight ring never refilled, 4 = one LDS read per phase (all three: wrong
-  // results), 8 = cycle stamps of every workgroup into p.st_trace (results intact)
-  if (const char* e = getenv("K22_STREAM_DBG")) {
-    const int dbg = atoi(e);
-    if (frag && mb == 5) {
-      if (dbg == 1) return launch_stream_cfg<T, 5, 2, 1, true>(p, g, splitk, stream);
-      if (dbg == 2) return launch_stream_cfg<T, 5, 2, 2, true>(p, g, splitk, stream);
-      if (dbg == 4) return launch_stream_cfg<T, 5, 2, 4, true>(p, g, splitk, stream);
-      if (dbg == 8) return launch_stream_cfg<T, 5, 2, 8, true>(p, g, splitk, stream);
-      if (dbg == 9) return launch_stream_cfg<T, 5, 2, 9, true>(p, g, splitk, stream);
-      if (dbg == 10) return launch_stream_cfg<T, 5, 2, 10, true>(p, g, splitk, stream);
-      if (dbg == 12) return launch_stream_cfg<T, 5, 2, 12, true>(p, g, splitk, stream);
-    }
-    if (frag && mb == 9 && dbg == 8) return launch_stream_cfg<T, 9, 1, 8, true>(p, g, splitk, stream);
-  }
-#endif
-  if (mb == 5) return frag ? launch_stream_cfg<T, 5, 2, 0, true>(p, g, splitk, stream) : launch_stream_cfg<T, 5, 2, 0, false>(p, g, splitk, stream);
-  return frag ? launch_stream_cfg<T, 9, 1, 0, true>(p, g, splitk, stream) : launch_stream_cfg<T, 9, 1, 0, false>(p, g, splitk, stream);
-}
-
-// Launches stream_kernel only: it always leaves fp32 partial tiles [splitk][M][N] in p.partial; the finish (bias, residual,
-// activation, rounding, GroupNorm partial sums) is the caller's (launch_igemm -> launch_reduce), also for splitk == 1.
-int launch_stream(const IgemmParams& p, int dtype, int mb, int splitk, hipStream_t stream) {
-  if (!stream_supported(p, dtype, mb)) return k22_set_error(K22_EINVAL, "stream: unsupported problem");
-  if (p.partial == nullptr) return k22_set_error(K22_EINVAL, "stream: needs the fp32 partial buffer [splitk][M][N]");
   StreamGeom g;
-  (void)stream_geom(p, mb, &g);
-  if (dtype == K22_BF16) return launch_stream_typed<bf16_t>(p, g, mb, splitk, stream);
-  if (dtype == K22_F16) return launch_stream_typed<f16_t>(p, g, mb, splitk, stream);
-  return k22_set_error(K22_EINVAL, "stream: bad dtype");
+  if (!stream_geom(p, mb, &g)) return k22_set_error(K22_EINVAL, "stream: unsupported problem");
+  IgemmParams q = p;
+  q.st_tm = g.tm; q.st_rb = g.rb; q.st_mtiles = g.mtiles; q.st_buf = g.buf;
+  return k22_with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    if constexpr (sizeof(T) == 2) {
+#ifdef K22_STREAM_DEBUG
+      // measurement-only variants: K22_STREAM_DBG bits 1 = no MFMA, 2 = weight ring never refilled, 4 = one LDS read per phase (all three: wrong
+      // results), 8 = cycle stamps of every workgroup into p.st_trace (results intact)
+      if (const char* e = getenv("K22_STREAM_DBG")) {
+        const int dbg = atoi(e);
+        if (frag && mb == 5) {
+          if (dbg == 1) return run_stream<T, 5, 2, 1, true>(q, L, stream);
+          if (dbg == 2) return run_stream<T, 5, 2, 2, true>(q, L, stream);
+          if (dbg == 4) return run_stream<T, 5, 2, 4, true>(q, L, stream);
+          if (dbg == 8) return run_stream<T, 5, 2, 8, true>(q, L, stream);
+          if (dbg == 9) return run_stream<T, 5, 2, 9, true>(q, L, stream);
+          if (dbg == 10) return run_stream<T, 5, 2, 10, true>(q, L, stream);
+          if (dbg == 12) return run_stream<T, 5, 2, 12, true>(q, L, stream);
+        }
+        if (frag && mb == 9 && dbg == 8) return run_stream<T, 9, 1, 8, true>(q, L, stream);
+      }
+#endif
+      if (mb == 5) return frag ? run_stream<T, 5, 2, 0, true>(q, L, stream) : run_stream<T, 5, 2, 0, false>(q, L, stream);
+      return frag ? run_stream<T, 9, 1, 0, true>(q, L, stream) : run_stream<T, 9, 1, 0, false>(q, L, stream);
+    } else {
+      return k22_set_error(K22_EINVAL, "stream: bad dtype");
+    }
+  });
 }
 
 // ---- one-time repack of a row-major weight matrix [Npad][taps * Kc] into fragment-major order ----------------------------------------

@@ -16,8 +16,10 @@
 #include <stdio.h>
 #include <stdlib.h>
 
-// One tile configuration of launch_igemm: algo 1 = generic implicit GEMM (bm x bn tile, LDS-DMA depth `stages`),
-// algo 2 = LDS-resident halo kernel for 3x3 convolutions (bm = 256 / 128); splitk >= 1.
+// One tile configuration of launch_igemm, as a table line spells it: algo = IgemmAlgo (kernels.h) - the generic implicit GEMM (bm x bn tile,
+// LDS-DMA depth `stages`), the LDS-resident halo kernels for 3x3 convolutions and their specialised forms (bm = 256 / 128), gemm8 (bm = 256 /
+// 128; stages 2 = two workgroups per CU, 3 / 4 = the specialised kernel) or the weight-streaming kernel (bm = 160 / 288); splitk >= 1.
+// igemm_resolve (igemm.hip) turns a problem with a Cfg applied into the launch that runs.
 struct Cfg { int algo = 0, bm = 0, bn = 0, splitk = 0, stages = 0; };
 
 struct TunedSlot;  // engine-specific workspace slot (opaque here)
@@ -108,17 +110,15 @@ inline void tuned_make_candidates(Tuned& t, int dtype) {
   std::vector<Cfg> all;
   if (p.taps == 9) {
     const int B = p.M / (p.H * p.W);
-    // algo 2 = lock-step halo kernel; 3 = 64-byte rows / filter-row iterations (only ever wins at the smallest level,
-    // deep split-K); 4 = two-phase kernel (measured 12-20 % slower than 2 on every shape: not a candidate)
-    // 5 = loader-wave specialisation (measured 2-5 % slower: not a candidate); 7 = LDS-DMA from inline asm (exact
-    // lgkmcnt for the fragment reads, +1-3 %); 6 = 7 + explicit fragment pipeline across the barrier
-    // 11 = producer / consumer wave specialisation (conv3_halo_spec_kernel)
-    for (int algo : {2, 7, 6, 3, 11, 12}) {
-      if (algo == 3 && p.H > 16) continue;
-      if (k22_is_split(dtype) && (algo == 2 || algo == 6)) continue;   // split precision: one lock-step form (7) + the specialised ones
+    // the lock-step halo kernel; its asm LDS-DMA form (exact lgkmcnt for the fragment reads, +1-3 %); that + the explicit fragment pipeline
+    // across the barrier; 64-byte rows / filter-row iterations (only ever wins at the smallest level, deep split-K); producer / consumer
+    // wave specialisation (conv3_halo_spec_kernel) without / with the interleaved pipeline
+    for (int algo : {IG_ALGO_HALO, IG_ALGO_HALO_ASM, IG_ALGO_HALO_PIPE, IG_ALGO_HALO3, IG_ALGO_SPEC, IG_ALGO_SPEC_PIPE}) {
+      if (algo == IG_ALGO_HALO3 && p.H > 16) continue;
+      if (k22_is_split(dtype) && (algo == IG_ALGO_HALO || algo == IG_ALGO_HALO_PIPE)) continue;   // split precision: one lock-step form + the specialised ones
       IgemmParams ph = p;
       ph.algo = algo;
-      const int nsplit_max = (p.Kc / BK) * (algo == 3 ? 2 : 1);
+      const int nsplit_max = (p.Kc / BK) * (algo == IG_ALGO_HALO3 ? 2 : 1);
       for (int bm : {256, 128}) {
         if (!conv3_halo_supported(ph, dtype, bm) || p.N < 128) continue;
         const int nb = B * conv3_halo_tiles_per_image(p, bm) * ((p.N + 127) / 128);
@@ -135,7 +135,7 @@ inline void tuned_make_candidates(Tuned& t, int dtype) {
     const int hw = p.H > 0 ? p.H * p.W : p.M;
     for (int bm : {256, 128}) {
       IgemmParams q = p;
-      q.algo = 10; q.force_bm = bm;
+      q.algo = IG_ALGO_GEMM8; q.force_bm = bm;
       if (!gemm8_supported(q, dtype, bm)) continue;
       const int nb = (p.M / hw) * gemm8_tiles_per_image(p, bm) * ((p.N + 127) / 128);
       for (int sk : {1, 2, 3, 4, 6}) {
@@ -143,7 +143,7 @@ inline void tuned_make_candidates(Tuned& t, int dtype) {
         for (int stg : {0, 2, 3, 4}) {   // 2: two co-resident workgroups per CU with a 2-deep ring (BM = 128 only); 3 / 4: gemm8_spec_kernel (16-bit types), 4 = its two-per-CU form
           if ((stg == 2 || stg == 4) && bm != 128) continue;
           if (stg >= 3 && !gemm8_spec_supported(dtype)) continue;
-          Cfg c; c.algo = 10; c.bm = bm; c.bn = 0; c.splitk = sk; c.stages = stg;
+          Cfg c; c.algo = IG_ALGO_GEMM8; c.bm = bm; c.bn = 0; c.splitk = sk; c.stages = stg;
           all.push_back(c);
         }
       }
@@ -155,14 +155,14 @@ inline void tuned_make_candidates(Tuned& t, int dtype) {
   if (k22_esz(dtype) == 2 && p.Wfrag != nullptr && p.taps == 9) {
     for (int mb : {5, 9}) {
       IgemmParams q = p;
-      q.algo = 20; q.force_bm = mb * 32;
+      q.algo = IG_ALGO_STREAM; q.force_bm = mb * 32;
       if (!stream_supported(q, dtype, mb)) continue;
       const int nb = stream_mtiles(q, mb);
       if (nb > 320) continue;
       const int nslab = p.Kc / 64;
       for (int sk : {1, 2, 3, 4, 5, 6, 8, 10, 12, 16}) {
         if (sk > nslab || (sk > 1 && nb * sk > 320)) continue;
-        Cfg c; c.algo = 20; c.bm = mb * 32; c.bn = 0; c.splitk = sk; c.stages = 0;
+        Cfg c; c.algo = IG_ALGO_STREAM; c.bm = mb * 32; c.bn = 0; c.splitk = sk; c.stages = 0;
         all.push_back(c);
       }
     }
@@ -181,7 +181,7 @@ inline void tuned_make_candidates(Tuned& t, int dtype) {
       for (int stg : {2, 3, 4}) {
         if (stg > 2 && !skinny) continue;
         if (stg * (tl[0] + tl[1]) * 128 > 160 * 1024) continue;
-        Cfg c; c.algo = 1; c.bm = tl[0]; c.bn = tl[1]; c.splitk = sk; c.stages = stg;
+        Cfg c; c.algo = IG_ALGO_GENERIC; c.bm = tl[0]; c.bn = tl[1]; c.splitk = sk; c.stages = stg;
         all.push_back(c);
       }
     }
@@ -210,7 +210,7 @@ inline TileKey tuned_key(const Tuned& t, int dtype) {
 // a table line from an older build may name a configuration this build would not generate: only candidates are accepted
 inline bool tuned_is_candidate(const Tuned& t, const Cfg& c) {
   for (auto& k : t.cands)
-    if (k.algo == c.algo && k.bm == c.bm && k.bn == c.bn && k.splitk == c.splitk && (k.stages == c.stages || (c.algo >= 2 && c.algo != 10))) return true;
+    if (k.algo == c.algo && k.bm == c.bm && k.bn == c.bn && k.splitk == c.splitk && (k.stages == c.stages || (c.algo >= IG_ALGO_HALO && c.algo != IG_ALGO_GEMM8))) return true;
   return false;
 }
 
@@ -254,9 +254,17 @@ inline void tuned_default_cfg(Tuned& t, int dtype) {
   tuned_finish_cfg(t, dtype);
 }
 
-inline size_t tuned_max_splitk_bytes(const Tuned& t, bool autotune) {
+// fp32 partial scratch the launch of t under its configuration (autotune: under any candidate) writes: [splitk][M][N] of the resolved launch
+inline size_t tuned_max_splitk_bytes(const Tuned& t, int dtype, bool autotune) {
   size_t m = 0;
-  auto upd = [&](const Cfg& c) { if (c.splitk > 1 || c.algo == 20) m = std::max(m, (size_t)c.splitk * t.p.M * t.p.N * sizeof(float)); };
+  auto upd = [&](const Cfg& c) {
+    IgemmParams q = t.p;
+    tuned_apply_cfg(q, c);
+    IgemmLaunch L;
+    const bool ok = igemm_resolve(q, dtype, &L) == K22_OK;   // (a configuration the resolver refuses is sized as the line spells it)
+    const int splitk = ok ? (L.finish != IG_FINISH_NONE ? L.splitk : 0) : ((c.splitk > 1 || c.algo == IG_ALGO_STREAM) ? c.splitk : 0);
+    m = std::max(m, (size_t)splitk * t.p.M * t.p.N * sizeof(float));
+  };
   upd(t.cfg);
   if (autotune) for (auto& c : t.cands) upd(c);
   return m;
@@ -332,7 +340,7 @@ inline std::string tuning_report_text(const std::deque<Tuned>& tuned) {
   for (auto& t : tuned) {
     char line[256];
     snprintf(line, sizeof line, "%4d %6d %5d %5d %4d %4d %5d | %4s %3d %3d %6d %3d | %8.1f", t.p.taps, t.p.M, t.p.N, t.p.Kc,
-             t.p.H, t.p.W, t.want_stats ? 1 : 0, t.cfg.algo == 2 ? "halo" : (t.cfg.algo == 3 ? "hal3" : (t.cfg.algo == 4 ? "hal4" : (t.cfg.algo == 5 ? "hal5" : (t.cfg.algo == 6 ? "hal6" : (t.cfg.algo == 7 ? "hal7" : (t.cfg.algo == 10 ? "gem8" : (t.cfg.algo == 11 ? "spec" : (t.cfg.algo == 12 ? "spcp" : (t.cfg.algo == 1 ? "gen" : "auto"))))))))), t.cfg.bm, t.cfg.bn,
+             t.p.H, t.p.W, t.want_stats ? 1 : 0, igemm_algo_name(t.cfg.algo), t.cfg.bm, t.cfg.bn,
              t.cfg.splitk, t.cfg.stages, t.best_us);
     if (!seen.count(line)) order.push_back(line);
     seen[line]++;
