@@ -215,30 +215,6 @@ def check(rc: int) -> None:
         raise RuntimeError(f"k22 error {rc}: {msg.decode() if msg else ''}")
 
 
-def weight_array(arena, table):
-    """(K22Weight array over the tensors of a packed arena, list that keeps the name bytes alive) - the weight table of k22_*_create."""
-    base = arena.data_ptr()
-    arr = (K22Weight * len(table))()
-    names = []
-    for i, (name, (off, _n)) in enumerate(table.items()):
-        nb = name.encode()
-        names.append(nb)
-        arr[i].name = nb
-        arr[i].ptr = base + off
-    return arr, names
-
-
-def plan_and_bind(plan_fn, bind_fn, handle, device, *shape):
-    """Plans `handle` for `shape` and binds a fresh workspace (the native side wants 256-byte alignment); returns the workspace tensor, which
-    the caller keeps alive as long as the plan is used.  A failed plan / bind raises and leaves the native engine without a plan."""
-    import torch
-    nbytes = C.c_size_t()
-    check(plan_fn(handle, *shape, C.byref(nbytes)))
-    ws = torch.empty(nbytes.value + 256, dtype=torch.uint8, device=device)
-    check(bind_fn(handle, (ws.data_ptr() + 255) // 256 * 256, nbytes.value))
-    return ws
-
-
 def ptr(t) -> int:
     """data pointer of a (contiguous) torch tensor, or NULL for None."""
     if t is None:

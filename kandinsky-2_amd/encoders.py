@@ -18,17 +18,15 @@ with the tokenizer / preprocess objects the caller passes in, as in the referenc
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 from collections import OrderedDict
-from typing import Dict, Optional, Tuple
+from typing import Optional
 
 import torch
 import torch.nn as nn
 
 from . import _lib
-from .prior import _pad_rows
-from .unet import _register
+from .native import NativeEngine, NativeModule, _pad_rows, layout_arena
 
 ENC_CLIP_TEXT, ENC_CLIP_VISION, ENC_XLMR = 0, 1, 2
 
@@ -183,20 +181,6 @@ def init_multiclip_state_dict(cfg: dict, in_features=1024, out_features=768, see
 
 
 # ---- arenas: reference keys -> the engine's names and layouts (include/k22.h, "conditioning encoders") -----------------------------
-def _finish_arena(ent, device):
-    table: "OrderedDict[str, Tuple[int, int]]" = OrderedDict()
-    off = 0
-    for name, t in ent.items():
-        nb = t.numel() * t.element_size()
-        table[name] = (off, nb)
-        off += (nb + 255) // 256 * 256
-    arena = torch.zeros(off + 256, dtype=torch.uint8, device=device)
-    for name, t in ent.items():
-        o, nb = table[name]
-        arena[o:o + nb] = t.reshape(-1).view(torch.uint8)
-    return arena, table
-
-
 def _clip_layers(ent, sd, src, n_layers, tdtype, f):
     for l in range(n_layers):
         p, q = f"{src}.resblocks.{l}", f"layers.{l}"
@@ -221,7 +205,7 @@ def pack_clip_text_arena(cfg, sd, tdtype, device):
     _clip_layers(ent, sd, "transformer", cfg["transformer_layers"], tdtype, f)
     ent["ln_final.weight"] = f(sd["ln_final.weight"]).contiguous(); ent["ln_final.bias"] = f(sd["ln_final.bias"]).contiguous()
     ent["head.weight"] = f(sd["text_projection"]).t().contiguous()          # x @ text_projection == Linear(weight = text_projection^T)
-    return _finish_arena(ent, device)
+    return layout_arena(ent, device)
 
 
 def pack_clip_vision_arena(cfg, sd, tdtype, device):
@@ -239,7 +223,7 @@ def pack_clip_vision_arena(cfg, sd, tdtype, device):
         ent[k + ".weight"] = f(sd[f"visual.{k}.weight"]).contiguous(); ent[k + ".bias"] = f(sd[f"visual.{k}.bias"]).contiguous()
     _clip_layers(ent, sd, "visual.transformer", cfg["vision_layers"], tdtype, f)
     ent["head.weight"] = f(sd["visual.proj"]).t().contiguous()
-    return _finish_arena(ent, device)
+    return layout_arena(ent, device)
 
 
 def pack_clip_vision_hf_arena(cfg, sd, tdtype, device):
@@ -272,7 +256,7 @@ def pack_clip_vision_hf_arena(cfg, sd, tdtype, device):
         ent[q + ".ln_1.weight"] = f(sd[s_ + "layer_norm1.weight"]).contiguous(); ent[q + ".ln_1.bias"] = f(sd[s_ + "layer_norm1.bias"]).contiguous()
         ent[q + ".ln_2.weight"] = f(sd[s_ + "layer_norm2.weight"]).contiguous(); ent[q + ".ln_2.bias"] = f(sd[s_ + "layer_norm2.bias"]).contiguous()
     ent["head.weight"] = f(sd["visual_projection.weight"]).contiguous()
-    return _finish_arena(ent, device)
+    return layout_arena(ent, device)
 
 
 def pack_multiclip_arena(cfg, sd, tdtype, device):
@@ -300,95 +284,35 @@ def pack_multiclip_arena(cfg, sd, tdtype, device):
         ent[q + ".ln_2.bias"] = f(sd[p + "output.LayerNorm.bias"]).contiguous()
     ent["head.weight"] = f(sd["LinearTransformation.weight"]).contiguous()
     ent["head.bias"] = f(sd["LinearTransformation.bias"]).contiguous()
-    return _finish_arena(ent, device)
+    return layout_arena(ent, device)
 
 
-class _Engine:
-    """One K22Encoder handle: arena + config + a plan per batch size (<= 8 rows per call; larger batches run in chunks)."""
-
-    def __init__(self, ecfg: dict, arena: torch.Tensor, table, backend_dtype):
-        self.cfg, self.arena = ecfg, arena
-        c = _lib.K22EncoderConfig()
-        c.dtype = _lib.dtype_code(backend_dtype)
-        for k, v in ecfg.items():
-            setattr(c, k, v)
-        arr, self._names = _lib.weight_array(arena, table)
-        h = C.c_void_p()
-        _lib.check(_lib.lib().k22_encoder_create(C.byref(c), arr, len(table), C.byref(h)))
-        self.handle, self._plan_B, self._ws = h, None, None
-
-    def close(self):
-        if self.handle is not None:
-            _lib.lib().k22_encoder_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _plan(self, B):
-        if self._plan_B != B:
-            self._plan_B = None
-            L = _lib.lib()
-            self._ws = _lib.plan_and_bind(L.k22_encoder_plan, L.k22_encoder_bind, self.handle, self.arena.device, B)
-            self._plan_B = B
-
-    def run(self, tokens=None, key_valid=None, image=None, want_seq=True):
-        dev = self.arena.device
-        N = (image if tokens is None else tokens).shape[0]
-        c = self.cfg
-        seqs, pools = [], []
-        for s in range(0, N, 8):
-            B = min(8, N - s)
-            self._plan(B)
-            tk = None if tokens is None else tokens[s:s + B].to(device=dev, dtype=torch.int32).contiguous()
-            kv = None if key_valid is None else key_valid[s:s + B].to(device=dev, dtype=torch.float32).contiguous()
-            im = None if image is None else image[s:s + B].to(device=dev, dtype=torch.float32).contiguous()
-            seq = torch.empty(B, c["n_ctx"], c["width"], dtype=torch.float32, device=dev) if (want_seq and image is None) else None
-            pooled = torch.empty(B, c["out_dim"], dtype=torch.float32, device=dev)
-            _lib.check(_lib.lib().k22_encoder_forward(self.handle, _lib.ptr(tk), _lib.ptr(kv), _lib.ptr(im), _lib.ptr(seq), pooled.data_ptr(),
-                                                      _lib.current_stream()))
-            seqs.append(seq); pools.append(pooled)
-        return (None if seqs[0] is None else torch.cat(seqs, 0)), torch.cat(pools, 0)
+def _tower_engine(ecfg: dict, arena: torch.Tensor, table, backend_dtype) -> NativeEngine:
+    """One K22Encoder handle: arena + config + a plan per batch size"""
+    return NativeEngine("encoder", _lib.K22EncoderConfig(dtype=_lib.dtype_code(backend_dtype), **ecfg), arena, table)
 
 
-class _HIPModule(nn.Module):
-    def __init__(self, shapes, backend_dtype):
-        super().__init__()
-        self.backend_dtype = backend_dtype
-        for name, shape in shapes.items():
-            _register(self, name, nn.Parameter(torch.zeros(shape), requires_grad=False))
-        self._engines: Dict[str, _Engine] = {}
-
-    def _release(self):
-        for e in self._engines.values():
-            e.close()
-        self._engines = {}
-
-    def load_state_dict(self, state_dict, strict: bool = True, **kw):
-        r = super().load_state_dict(state_dict, strict=strict, **kw)
-        self._release()
-        return r
-
-    def _apply(self, fn, *args, **kwargs):
-        r = super()._apply(fn, *args, **kwargs)
-        self._release()
-        return r
-
-    def _device(self):
-        dev = next(self.parameters()).device
-        if dev.type != "cuda":
-            raise RuntimeError(f"{type(self).__name__} runs on the GPU only (no CPU fallback): move it with .to('cuda')")
-        return dev
-
-    @property
-    def dtype(self):
-        return torch.float32        # public tensors; the engine's arithmetic type is backend_dtype
+def _run_tower(e: NativeEngine, tokens=None, key_valid=None, image=None, want_seq=True):
+    """-> (sequence or None, pooled) of one tower call; <= 8 rows per engine call, larger batches run in chunks"""
+    dev = e.arena.device
+    N = (image if tokens is None else tokens).shape[0]
+    c = e.cfg
+    seqs, pools = [], []
+    for s in range(0, N, 8):
+        B = min(8, N - s)
+        e.ensure_plan(B)
+        tk = None if tokens is None else tokens[s:s + B].to(device=dev, dtype=torch.int32).contiguous()
+        kv = None if key_valid is None else key_valid[s:s + B].to(device=dev, dtype=torch.float32).contiguous()
+        im = None if image is None else image[s:s + B].to(device=dev, dtype=torch.float32).contiguous()
+        seq = torch.empty(B, c.n_ctx, c.width, dtype=torch.float32, device=dev) if (want_seq and image is None) else None
+        pooled = torch.empty(B, c.out_dim, dtype=torch.float32, device=dev)
+        _lib.check(_lib.lib().k22_encoder_forward(e.handle, _lib.ptr(tk), _lib.ptr(kv), _lib.ptr(im), _lib.ptr(seq), pooled.data_ptr(),
+                                                  _lib.current_stream()))
+        seqs.append(seq); pools.append(pooled)
+    return (None if seqs[0] is None else torch.cat(seqs, 0)), torch.cat(pools, 0)
 
 
-class CLIPModelHIP(_HIPModule):
+class CLIPModelHIP(NativeModule):
     """clip.model.CLIP (ViT image tower) for the calls the reference makes: encode_image, encode_text, and the text-tower walk of
     generate_clip_emb exposed as `encode_text_with_sequence(tokens) -> (txt_feat, txt_feat_seq)`."""
 
@@ -414,7 +338,7 @@ class CLIPModelHIP(_HIPModule):
                 ecfg = dict(kind=ENC_CLIP_VISION, width=c["vision_width"], layers=c["vision_layers"], heads=c["vision_width"] // 64,
                             n_ctx=g * g + 1, vocab=0, out_dim=c["embed_dim"], image_size=c["image_resolution"], patch=c["vision_patch_size"],
                             max_pos=0, pad_id=0, ln_eps=1e-5)
-            self._engines[which] = _Engine(ecfg, arena, table, self.backend_dtype)
+            self._engines[which] = _tower_engine(ecfg, arena, table, self.backend_dtype)
         return self._engines[which]
 
     def _check_tokens(self, text):
@@ -427,7 +351,7 @@ class CLIPModelHIP(_HIPModule):
     def encode_text_with_sequence(self, text):
         """-> (txt_feat [n, embed_dim], txt_feat_seq [n, 77, width]) = (x[arange, text.argmax(-1)] @ text_projection, ln_final(x))."""
         self._check_tokens(text)
-        seq, pooled = self._engine("text").run(tokens=text)
+        seq, pooled = _run_tower(self._engine("text"), tokens=text)
         return pooled, seq
 
     @torch.no_grad()
@@ -439,10 +363,10 @@ class CLIPModelHIP(_HIPModule):
         r = self.input_resolution
         if image.dim() != 4 or tuple(image.shape[1:]) != (3, r, r):
             raise ValueError(f"CLIP image batch must be [n, 3, {r}, {r}] (preprocessed), got {tuple(image.shape)}")
-        return self._engine("vision").run(image=image)[1]
+        return _run_tower(self._engine("vision"), image=image)[1]
 
 
-class CLIPVisionModelWithProjectionHIP(_HIPModule):
+class CLIPVisionModelWithProjectionHIP(NativeModule):
     """transformers' `CLIPVisionModelWithProjection` - the `image_encoder` Kandinsky2_2.__init__ loads from the prior repository
     (kandinsky2/kandinsky2_2_model.py:24; CLIP ViT-bigG/14) and diffusers' prior pipeline calls as
     `image_encoder(pixel_values).image_embeds` (mix_images / interpolate, the zero-image negative embedding) - on the encoder engine.
@@ -473,7 +397,7 @@ class CLIPVisionModelWithProjectionHIP(_HIPModule):
                         vocab=0, out_dim=c["projection_dim"], image_size=c["image_size"], patch=c["patch_size"], max_pos=0, pad_id=0,
                         ln_eps=float(c.get("layer_norm_eps", 1e-5)), mlp_dim=c["intermediate_size"],
                         hidden_act=1 if c.get("hidden_act", "quick_gelu") == "gelu" else 0)
-            self._engines["vision"] = _Engine(ecfg, arena, table, self.backend_dtype)
+            self._engines["vision"] = _tower_engine(ecfg, arena, table, self.backend_dtype)
         return self._engines["vision"]
 
     @torch.no_grad()
@@ -482,10 +406,10 @@ class CLIPVisionModelWithProjectionHIP(_HIPModule):
         if pixel_values.dim() != 4 or tuple(pixel_values.shape[1:]) != (3, r, r):
             raise ValueError(f"pixel_values must be [n, 3, {r}, {r}] (preprocessed), got {tuple(pixel_values.shape)}")
         from types import SimpleNamespace
-        return SimpleNamespace(image_embeds=self._engine().run(image=pixel_values)[1])
+        return SimpleNamespace(image_embeds=_run_tower(self._engine(), image=pixel_values)[1])
 
 
-class MultilingualCLIPHIP(_HIPModule):
+class MultilingualCLIPHIP(NativeModule):
     """MultilingualCLIP (text_encoders.py:108-122): forward(input_ids, attention_mask) -> (LinearTransformation(masked mean), embs)."""
 
     def __init__(self, config: Optional[dict] = None, in_features=1024, out_features=768, backend_dtype: torch.dtype = torch.bfloat16):
@@ -510,7 +434,7 @@ class MultilingualCLIPHIP(_HIPModule):
             ecfg = dict(kind=ENC_XLMR, width=c["hidden_size"], layers=c["num_hidden_layers"], heads=c["num_attention_heads"], n_ctx=n_ctx,
                         vocab=c["vocab_size"], out_dim=self.out_features, image_size=0, patch=0, max_pos=c["max_position_embeddings"],
                         pad_id=c["pad_token_id"], ln_eps=float(c["layer_norm_eps"]))
-            self._engines[key] = _Engine(ecfg, arena, table, self.backend_dtype)
+            self._engines[key] = _tower_engine(ecfg, arena, table, self.backend_dtype)
         return self._engines[key]
 
     def _release(self):
@@ -527,7 +451,7 @@ class MultilingualCLIPHIP(_HIPModule):
             raise ValueError("MultilingualCLIPHIP: sequence longer than the position-embedding table")
         if input_ids.numel() and (int(input_ids.min()) < 0 or int(input_ids.max()) >= c["vocab_size"]):
             raise ValueError("XLM-R token id outside the vocabulary")
-        embs, pooled = self._engine_for(n_ctx).run(tokens=input_ids, key_valid=attention_mask)
+        embs, pooled = _run_tower(self._engine_for(n_ctx), tokens=input_ids, key_valid=attention_mask)
         return pooled, embs
 
 

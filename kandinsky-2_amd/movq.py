@@ -11,15 +11,14 @@ checkpoint are accepted and ignored (load_state_dict(strict=False)).  No CPU fal
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 from collections import OrderedDict
 from typing import Dict, Optional, Tuple
 
 import torch
-import torch.nn as nn
 
 from . import _lib
+from .native import NativeEngine, NativeModule, _pad_rows, layout_arena
 
 MOVQ_CONFIG_2_1 = {  # CONFIG_2_1["image_enc_params"]["params"] (kandinsky2/configs.py:68-90)
     "embed_dim": 4, "n_embed": 16384,
@@ -119,14 +118,6 @@ def init_movq_state_dict(a: MoVQArch, seed: int = 0) -> "OrderedDict[str, torch.
     return sd
 
 
-def _pad_rows(w: torch.Tensor, mult: int = 64) -> torch.Tensor:
-    o = w.shape[0]
-    op = (o + mult - 1) // mult * mult
-    if op == o:
-        return w
-    return torch.cat([w, torch.zeros((op - o,) + tuple(w.shape[1:]), dtype=w.dtype, device=w.device)], 0)
-
-
 def pack_movq_arena(a: MoVQArch, sd: Dict[str, torch.Tensor], tdtype: torch.dtype, device) -> Tuple[torch.Tensor, "OrderedDict[str, Tuple[int, int]]"]:
     f32 = torch.float32
     ent: "OrderedDict[str, torch.Tensor]" = OrderedDict()
@@ -146,92 +137,49 @@ def pack_movq_arena(a: MoVQArch, sd: Dict[str, torch.Tensor], tdtype: torch.dtyp
             ent[name] = _pad_rows(w.permute(0, 2, 3, 1).reshape(w.shape[0], -1)).to(tdtype).contiguous()
         else:  # 1x1 projections feeding the MFMA GEMM
             ent[name] = _pad_rows(w.reshape(w.shape[0], -1)).to(tdtype).contiguous()
-    table: "OrderedDict[str, Tuple[int, int]]" = OrderedDict()
-    off = 0
-    for name, t in ent.items():
-        nb = t.numel() * t.element_size()
-        table[name] = (off, nb)
-        off += (nb + 255) // 256 * 256
-    arena = torch.zeros(off + 256, dtype=torch.uint8, device=device)
-    for name, t in ent.items():
-        o, nb = table[name]
-        arena[o:o + nb] = t.reshape(-1).view(torch.uint8)
-    return arena, table
+    return layout_arena(ent, device)
 
 
-class MoVQDecoderHIP(nn.Module):
+def _movq_config(a: MoVQArch, backend_dtype) -> _lib.K22MoVQConfig:
+    cfg = _lib.K22MoVQConfig()
+    cfg.dtype = _lib.dtype_code(backend_dtype)
+    cfg.ch = a.ch
+    cfg.n_levels = len(a.ch_mult)
+    for i, v in enumerate(a.ch_mult):
+        cfg.ch_mult[i] = v
+    cfg.num_res_blocks = a.num_res_blocks
+    cfg.attn_levels = sum(1 << i for i in a.attn_levels)
+    cfg.z_channels = a.z_channels
+    cfg.out_ch = a.out_ch
+    return cfg
+
+
+class MoVQDecoderHIP(NativeModule):
     """MI355X-native `MOVQ.decode` (kandinsky2/vqgan/autoencoder.py:182-185)."""
 
     def __init__(self, ddconfig: Optional[dict] = None, n_embed: int = 16384, embed_dim: int = 4,
                  backend_dtype: torch.dtype = torch.bfloat16):
-        super().__init__()
         self.arch = MoVQArch(ddconfig or MOVQ_CONFIG_2_1["ddconfig"], embed_dim)
-        self.backend_dtype = backend_dtype
-        from .unet import _register
-        for name, shape in movq_param_shapes(self.arch).items():
-            _register(self, name, nn.Parameter(torch.zeros(shape), requires_grad=False))
-        self._handle = None
-        self._arena = None
-        self._ws = None
-        self._plan_key = None
-
-    def _release(self):
-        if self._handle is not None:
-            _lib.lib().k22_movq_destroy(self._handle)
-            self._handle = None
-        self._arena = self._ws = self._plan_key = None
-
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass
+        super().__init__(movq_param_shapes(self.arch), backend_dtype)
 
     def load_state_dict(self, state_dict, strict: bool = False, **kw):
         own = set(movq_param_shapes(self.arch).keys())
         r = super().load_state_dict({k: v for k, v in state_dict.items() if k in own}, strict=False, **kw)
-        self._release()
         if strict and r.missing_keys:
             raise RuntimeError(f"missing decoder keys: {r.missing_keys[:4]} ...")
         return r
 
-    def _apply(self, fn, *args, **kwargs):
-        r = super()._apply(fn, *args, **kwargs)
-        self._release()
-        return r
-
     def prepare(self):
-        dev = next(self.parameters()).device
-        if dev.type != "cuda":
-            raise RuntimeError("MoVQDecoderHIP runs on the GPU only (no CPU fallback): move it with .to('cuda')")
-        L = _lib.lib()
+        dev = self._device()
         self._release()
-        self._arena, table = pack_movq_arena(self.arch, self.state_dict(), self.backend_dtype, dev)
-        a = self.arch
-        cfg = _lib.K22MoVQConfig()
-        cfg.dtype = _lib.dtype_code(self.backend_dtype)
-        cfg.ch = a.ch
-        cfg.n_levels = len(a.ch_mult)
-        for i, v in enumerate(a.ch_mult):
-            cfg.ch_mult[i] = v
-        cfg.num_res_blocks = a.num_res_blocks
-        cfg.attn_levels = sum(1 << i for i in a.attn_levels)
-        cfg.z_channels = a.z_channels
-        cfg.out_ch = a.out_ch
-        arr, self._names = _lib.weight_array(self._arena, table)
-        h = C.c_void_p()
-        _lib.check(L.k22_movq_create(C.byref(cfg), arr, len(table), C.byref(h)))
-        self._handle = h
+        arena, table = pack_movq_arena(self.arch, self.state_dict(), self.backend_dtype, dev)
+        self._engines["movq"] = NativeEngine("movq", _movq_config(self.arch, self.backend_dtype), arena, table)
         return self
 
     def _ensure_plan(self, B, h, w):
-        if self._handle is None:
+        if not self._engines:
             self.prepare()
-        if self._plan_key != (B, h, w):
-            self._plan_key = None   # a failed plan / bind leaves the native engine without a plan: never skip re-planning after it
-            L = _lib.lib()
-            self._ws = _lib.plan_and_bind(L.k22_movq_plan, L.k22_movq_bind, self._handle, self._arena.device, B, h, w)
-            self._plan_key = (B, h, w)
+        self._engines["movq"].ensure_plan(B, h, w)
 
     @torch.no_grad()
     def decode(self, quant: torch.Tensor, return_uint8: bool = False):
@@ -342,86 +290,35 @@ def pack_movq_encoder_arena(a: MoVQArch, sd: Dict[str, torch.Tensor], tdtype: to
             ent[name] = _pad_rows(w.permute(0, 2, 3, 1).reshape(w.shape[0], -1)).to(tdtype).contiguous()
         else:
             ent[name] = _pad_rows(w.reshape(w.shape[0], -1)).to(tdtype).contiguous()
-    table: "OrderedDict[str, Tuple[int, int]]" = OrderedDict()
-    off = 0
-    for name, t in ent.items():
-        nb = t.numel() * t.element_size()
-        table[name] = (off, nb)
-        off += (nb + 255) // 256 * 256
-    arena = torch.zeros(off + 256, dtype=torch.uint8, device=device)
-    for name, t in ent.items():
-        o, nb = table[name]
-        arena[o:o + nb] = t.reshape(-1).view(torch.uint8)
-    return arena, table
+    return layout_arena(ent, device)
 
 
-class MoVQEncoderHIP(nn.Module):
+class MoVQEncoderHIP(NativeModule):
     """MI355X-native `MOVQ.encode` (kandinsky2/vqgan/autoencoder.py:176-180): image [B,3,H,W] in [-1,1] -> latent [B,4,H/8,W/8]
     (before the pipeline multiplies by its latent scale, kandinsky2_1_model.py:467).  State-dict keys are the reference's
     `encoder.*` and `quant_conv.*`; the other keys of a full MOVQ checkpoint are ignored."""
 
     def __init__(self, ddconfig: Optional[dict] = None, n_embed: int = 16384, embed_dim: int = 4,
                  backend_dtype: torch.dtype = torch.bfloat16):
-        super().__init__()
         dd = ddconfig or MOVQ_CONFIG_2_1["ddconfig"]
         self.arch = MoVQArch(dd, embed_dim)
         self.in_channels = dd.get("in_channels", 3)
         if self.in_channels != 3:
             raise NotImplementedError("the encoder engine takes 3-channel images")
-        self.backend_dtype = backend_dtype
-        from .unet import _register
-        for name, shape in movq_encoder_param_shapes(self.arch).items():
-            _register(self, name, nn.Parameter(torch.zeros(shape), requires_grad=False))
-        self._handle = None
-        self._arena = self._ws = self._plan_key = None
-
-    def _release(self):
-        if self._handle is not None:
-            _lib.lib().k22_movq_destroy(self._handle)
-            self._handle = None
-        self._arena = self._ws = self._plan_key = None
-
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass
+        super().__init__(movq_encoder_param_shapes(self.arch), backend_dtype)
 
     def load_state_dict(self, state_dict, strict: bool = False, **kw):
         own = set(movq_encoder_param_shapes(self.arch).keys())
         r = super().load_state_dict({k: v for k, v in state_dict.items() if k in own}, strict=False, **kw)
-        self._release()
         if strict and r.missing_keys:
             raise RuntimeError(f"missing encoder keys: {r.missing_keys[:4]} ...")
         return r
 
-    def _apply(self, fn, *args, **kwargs):
-        r = super()._apply(fn, *args, **kwargs)
-        self._release()
-        return r
-
     def prepare(self):
-        dev = next(self.parameters()).device
-        if dev.type != "cuda":
-            raise RuntimeError("MoVQEncoderHIP runs on the GPU only (no CPU fallback): move it with .to('cuda')")
-        L = _lib.lib()
+        dev = self._device()
         self._release()
-        self._arena, table = pack_movq_encoder_arena(self.arch, self.state_dict(), self.backend_dtype, dev)
-        a = self.arch
-        cfg = _lib.K22MoVQConfig()
-        cfg.dtype = _lib.dtype_code(self.backend_dtype)
-        cfg.ch = a.ch
-        cfg.n_levels = len(a.ch_mult)
-        for i, v in enumerate(a.ch_mult):
-            cfg.ch_mult[i] = v
-        cfg.num_res_blocks = a.num_res_blocks
-        cfg.attn_levels = sum(1 << i for i in a.attn_levels)
-        cfg.z_channels = a.z_channels
-        cfg.out_ch = a.out_ch
-        arr, self._names = _lib.weight_array(self._arena, table)
-        h = C.c_void_p()
-        _lib.check(L.k22_movq_create(C.byref(cfg), arr, len(table), C.byref(h)))
-        self._handle = h
+        arena, table = pack_movq_encoder_arena(self.arch, self.state_dict(), self.backend_dtype, dev)
+        self._engines["movq"] = NativeEngine("movq_encoder", _movq_config(self.arch, self.backend_dtype), arena, table)
         return self
 
     @torch.no_grad()
@@ -431,13 +328,9 @@ class MoVQEncoderHIP(nn.Module):
         B, Ci, H, W = image.shape
         if Ci != 3:
             raise ValueError("expected a 3-channel image")
-        if self._handle is None:
+        if not self._engines:
             self.prepare()
-        if self._plan_key != (B, H, W):
-            self._plan_key = None   # a failed plan / bind leaves the native engine without a plan: never skip re-planning after it
-            L = _lib.lib()
-            self._ws = _lib.plan_and_bind(L.k22_movq_plan_encoder, L.k22_movq_bind, self._handle, self._arena.device, B, H, W)
-            self._plan_key = (B, H, W)
+        self._engines["movq"].ensure_plan(B, H, W)
         x = image.detach().float().contiguous()
         down = 1 << (len(self.arch.ch_mult) - 1)
         out = torch.empty(B, 4, H // down, W // down, dtype=torch.float32, device=image.device)

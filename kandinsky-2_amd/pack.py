@@ -24,15 +24,7 @@ from typing import Dict, Tuple
 import torch
 
 from .arch import UNetArch
-
-
-def _pad_rows(w: torch.Tensor, mult: int = 64) -> torch.Tensor:
-    o = w.shape[0]
-    op = (o + mult - 1) // mult * mult
-    if op == o:
-        return w
-    pad = torch.zeros((op - o,) + tuple(w.shape[1:]), dtype=w.dtype, device=w.device)
-    return torch.cat([w, pad], 0)
+from .native import _pad_rows, layout_arena
 
 
 def to_x3(w: torch.Tensor, scale: float = 256.0) -> torch.Tensor:
@@ -138,15 +130,4 @@ def packed_entries(arch: UNetArch, sd: Dict[str, torch.Tensor], tdtype, device) 
 
 def pack_arena(arch: UNetArch, sd: Dict[str, torch.Tensor], tdtype, device) -> Tuple[torch.Tensor, "OrderedDict[str, Tuple[int, int]]"]:
     """Returns (arena uint8 tensor on `device`, name -> (byte offset, byte size))."""
-    entries = packed_entries(arch, sd, tdtype, device)
-    table: "OrderedDict[str, Tuple[int, int]]" = OrderedDict()
-    off = 0
-    for name, t in entries.items():
-        nbytes = t.numel() * t.element_size()
-        table[name] = (off, nbytes)
-        off += (nbytes + 255) // 256 * 256
-    arena = torch.zeros(off + 256, dtype=torch.uint8, device=device)
-    for name, t in entries.items():
-        o, nbytes = table[name]
-        arena[o:o + nbytes] = t.reshape(-1).view(torch.uint8)
-    return arena, table
+    return layout_arena(packed_entries(arch, sd, tdtype, device), device)

@@ -17,10 +17,10 @@ from typing import Dict, Optional, Tuple
 
 import numpy as np
 import torch
-import torch.nn as nn
 
 from . import _lib
 from .diffusion import named_betas, space_timesteps
+from .native import NativeEngine, NativeModule, _pad_rows, layout_arena
 
 PRIOR_HPARAMS_2_1 = {  # CONFIG_2_1["prior"]["params"]["model"]["hparams"] (kandinsky2/configs.py:101-111)
     "text_ctx": 77, "xf_width": 2048, "xf_layers": 20, "xf_heads": 32, "xf_final_ln": True, "xf_padding": False,
@@ -85,12 +85,6 @@ def init_prior_state_dict(hp: dict, seed: int = 0) -> "OrderedDict[str, torch.Te
     return sd
 
 
-def _pad_rows(w, mult=64):
-    o = w.shape[0]
-    op = (o + mult - 1) // mult * mult
-    return w if op == o else torch.cat([w, torch.zeros((op - o,) + tuple(w.shape[1:]), dtype=w.dtype, device=w.device)], 0)
-
-
 def pack_prior_arena(hp: dict, sd: Dict[str, torch.Tensor], tdtype, device) -> Tuple[torch.Tensor, "OrderedDict[str, Tuple[int, int]]"]:
     f32 = torch.float32
     W, H = hp["xf_width"], hp["xf_heads"]
@@ -112,17 +106,7 @@ def pack_prior_arena(hp: dict, sd: Dict[str, torch.Tensor], tdtype, device) -> T
             ent[name] = _pad_rows(w).to(tdtype).contiguous()
         else:
             ent[name] = w.reshape(-1).contiguous() if name in ("positional_embedding", "prd_emb") else w.contiguous()
-    table: "OrderedDict[str, Tuple[int, int]]" = OrderedDict()
-    off = 0
-    for name, t in ent.items():
-        nb = t.numel() * t.element_size()
-        table[name] = (off, nb)
-        off += (nb + 255) // 256 * 256
-    arena = torch.zeros(off + 256, dtype=torch.uint8, device=device)
-    for name, t in ent.items():
-        o, nb = table[name]
-        arena[o:o + nb] = t.reshape(-1).view(torch.uint8)
-    return arena, table
+    return layout_arena(ent, device)
 
 
 class PriorSchedule:
@@ -163,75 +147,41 @@ class PriorSchedule:
         return tab
 
 
-class PriorDiffusionModelHIP(nn.Module):
+class PriorDiffusionModelHIP(NativeModule):
     """MI355X-native PriorDiffusionModel (kandinsky2/model/prior.py:273-384): holds PriorTransformer's parameters under
     `model.*` like the reference, plus the clip_mean / clip_std buffers."""
 
     def __init__(self, hparams: Optional[dict] = None, diffusion: Optional[dict] = None, clip_mean: Optional[torch.Tensor] = None,
                  clip_std: Optional[torch.Tensor] = None, backend_dtype: torch.dtype = torch.bfloat16):
-        super().__init__()
         self.hp = dict(hparams or PRIOR_HPARAMS_2_1)
+        super().__init__({"model." + k: v for k, v in prior_param_shapes(self.hp).items()}, backend_dtype)
         self.diffusion_kwargs = dict(diffusion or PRIOR_DIFFUSION_2_1)
-        self.backend_dtype = backend_dtype
         cd = self.hp["clip_dim"]
         self.register_buffer("clip_mean", (clip_mean if clip_mean is not None else torch.zeros(cd))[None, :].float(), persistent=False)
         self.register_buffer("clip_std", (clip_std if clip_std is not None else torch.ones(cd))[None, :].float(), persistent=False)
-        from .unet import _register
-        for name, shape in prior_param_shapes(self.hp).items():
-            _register(self, "model." + name, nn.Parameter(torch.zeros(shape), requires_grad=False))
-        self._handle = None
-        self._arena = self._ws = self._plan_key = None
-
-    def _release(self):
-        if self._handle is not None:
-            _lib.lib().k22_prior_destroy(self._handle)
-            self._handle = None
-        self._arena = self._ws = self._plan_key = None
-
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass
 
     def load_state_dict(self, state_dict, strict: bool = True, **kw):
         if state_dict and not any(k.startswith("model.") for k in state_dict):
             state_dict = {"model." + k: v for k, v in state_dict.items()}
-        r = super().load_state_dict(state_dict, strict=strict, **kw)
-        self._release()
-        return r
-
-    def _apply(self, fn, *args, **kwargs):
-        r = super()._apply(fn, *args, **kwargs)
-        self._release()
-        return r
+        return super().load_state_dict(state_dict, strict=strict, **kw)
 
     def prepare(self):
-        dev = next(self.parameters()).device
-        if dev.type != "cuda":
-            raise RuntimeError("PriorDiffusionModelHIP runs on the GPU only (no CPU fallback): move it with .to('cuda')")
+        dev = self._device()
         self._release()
         sd = {k[len("model."):]: v for k, v in self.state_dict().items() if k.startswith("model.")}
-        self._arena, table = pack_prior_arena(self.hp, sd, self.backend_dtype, dev)
+        arena, table = pack_prior_arena(self.hp, sd, self.backend_dtype, dev)
         cfg = _lib.K22PriorConfig()
         cfg.dtype = _lib.dtype_code(self.backend_dtype)
         for k in ("text_ctx", "xf_width", "xf_layers", "xf_heads", "clip_dim", "clip_xf_width"):
             setattr(cfg, k, int(self.hp[k]))
         cfg.xf_final_ln = 1 if self.hp["xf_final_ln"] else 0
-        arr, self._names = _lib.weight_array(self._arena, table)
-        h = C.c_void_p()
-        _lib.check(_lib.lib().k22_prior_create(C.byref(cfg), arr, len(table), C.byref(h)))
-        self._handle = h
+        self._engines["prior"] = NativeEngine("prior", cfg, arena, table)
         return self
 
     def _ensure_plan(self, B):
-        if self._handle is None:
+        if not self._engines:
             self.prepare()
-        if self._plan_key != B:
-            self._plan_key = None   # a failed plan / bind leaves the native engine without a plan: never skip re-planning after it
-            L = _lib.lib()
-            self._ws = _lib.plan_and_bind(L.k22_prior_plan, L.k22_prior_bind, self._handle, self._arena.device, B)
-            self._plan_key = B
+        self._engines["prior"].ensure_plan(B)
 
     def tuning_report(self) -> str:
         buf = C.create_string_buffer(1 << 14)

@@ -14,24 +14,14 @@ import os
 from typing import Optional
 
 import torch
-import torch.nn as nn
 
 from . import _lib
 from .arch import UNetArch, make_arch, param_shapes
+from .native import NativeEngine, NativeModule, arena_size
 from .pack import pack_arena
 
 
-def _register(root: nn.Module, dotted: str, param: nn.Parameter) -> None:
-    parts = dotted.split(".")
-    m = root
-    for p in parts[:-1]:
-        if p not in m._modules:
-            m.add_module(p, nn.Module())
-        m = m._modules[p]
-    m.register_parameter(parts[-1], param)
-
-
-class Text2ImUNetHIP(nn.Module):
+class Text2ImUNetHIP(NativeModule):
     """MI355X-native Text2ImUNet (kandinsky2/model/text2im_model2_1.py:13-103).
 
     backend_dtype: torch.bfloat16 (BASELINE's dtype, bf16 MFMA), torch.float16 (the reference's own use_fp16 mode: same MFMA rate,
@@ -48,30 +38,19 @@ class Text2ImUNetHIP(nn.Module):
 
     def __init__(self, arch: UNetArch, backend_dtype: torch.dtype = torch.bfloat16, use_graph: bool = True,
                  cache_text_emb: bool = True, meta_params: bool = False, chains: Optional[int] = None):
-        super().__init__()
         if backend_dtype not in (torch.bfloat16, torch.float16, torch.float32, _lib.F16X3, _lib.F16X2):
             raise ValueError('backend_dtype must be torch.bfloat16, torch.float16, torch.float32, "f16x3" (split precision) or "f16x2" '
                              '(asymmetric split: per-op precision plan)')
+        super().__init__(param_shapes(arch), backend_dtype, meta_params)
         self.arch = arch
-        self.backend_dtype = backend_dtype
         self.use_graph = use_graph
         self.cache_text_emb = cache_text_emb
-        self.dtype = torch.float32  # public tensors are fp32, like the reference's x / output
         self.model_channels = arch.model_channels
-        for name, shape in param_shapes(arch).items():
-            t = torch.empty(shape, device="meta") if meta_params else torch.zeros(shape)
-            _register(self, name, nn.Parameter(t, requires_grad=False))
         self.chains = int(os.environ.get("K22_CHAINS", "1")) if chains is None else int(chains)
         if self.chains not in (1, 2):
             raise ValueError("chains must be 1 or 2")
-        self._handle: Optional[C.c_void_p] = None
-        self._handle2: Optional[C.c_void_p] = None      # second half-batch engine of the two-chain mode
-        self._ws2 = None
-        self._side = None                               # its stream
-        self._arena = None
-        self._weights_keepalive = None
-        self._ws = None
-        self._plan_key = None
+        self._side = None                               # stream of the second half-batch engine of the two-chain mode
+        self._plan_key = None                           # (B, H, W) of the whole batch, which two chains split between their engines
         self._cond_key = None
         self.cache = None  # mirrors the reference attribute; holds the key of the cached conditioning
 
@@ -109,35 +88,8 @@ class Text2ImUNetHIP(nn.Module):
 
     # ---- engine management -------------------------------------------------------------------------
     def _release(self):
-        if self._handle is not None:
-            _lib.lib().k22_unet_destroy(self._handle)
-            self._handle = None
-        if getattr(self, "_handle2", None) is not None:
-            _lib.lib().k22_unet_destroy(self._handle2)
-            self._handle2 = None
-        self._arena = None
-        self._ws = None
-        self._ws2 = None
-        self._loop_bufs = None
-        self._ddim_bufs = None
-        self._plan_key = None
-        self._cond_key = None
-
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass
-
-    def load_state_dict(self, *args, **kwargs):
-        r = super().load_state_dict(*args, **kwargs)
-        self._release()  # weights changed: re-pack lazily
-        return r
-
-    def _apply(self, fn, *args, **kwargs):
-        r = super()._apply(fn, *args, **kwargs)
-        self._release()  # device move: re-pack lazily
-        return r
+        super()._release()
+        self._loop_bufs = self._ddim_bufs = self._plan_key = self._cond_key = None
 
     def arena_table(self):
         """name -> (byte offset, byte size) of the packed arena, derived from shapes only."""
@@ -145,9 +97,7 @@ class Text2ImUNetHIP(nn.Module):
         return pack_arena(self.arch, meta_sd, self.backend_dtype, "meta")[1]
 
     def arena_bytes(self) -> int:
-        t = self.arena_table()
-        last_off, last_n = list(t.values())[-1]
-        return (last_off + (last_n + 255) // 256 * 256) + 256
+        return arena_size(self.arena_table())
 
     def _engine_config(self):
         """K22UNetConfig of this architecture / dtype (host-side only: no device is touched)"""
@@ -177,30 +127,21 @@ class Text2ImUNetHIP(nn.Module):
 
     def prepare(self, arena: Optional[torch.Tensor] = None, free_params: bool = False):
         """Packs the weights (or adopts a broadcast arena) and creates the native engine."""
-        dev = arena.device if arena is not None else next(self.parameters()).device
-        if dev.type != "cuda":
-            raise RuntimeError("Text2ImUNetHIP runs on the GPU only (no CPU fallback): move it with .to('cuda')")
-        L = _lib.lib()
+        dev = self._device(None if arena is None else arena.device)
         self._release()
         self._arena_adopted = arena is not None
         if arena is None:
             arena, table = pack_arena(self.arch, self.state_dict(), self.backend_dtype, dev)
         else:
             table = self.arena_table()
-            if arena.numel() < self.arena_bytes() or arena.dtype != torch.uint8:
+            if arena.numel() < arena_size(table) or arena.dtype != torch.uint8:
                 raise ValueError("arena does not match this architecture/dtype")
-        self._arena = arena
         cfg = self._engine_config()
-        arr, _names = _lib.weight_array(arena, table)
-        h = C.c_void_p()
-        _lib.check(L.k22_unet_create(C.byref(cfg), arr, len(table), C.byref(h)))
-        self._handle = h
+        self._engines[0] = NativeEngine("unet", cfg, arena, table)
         if self.chains == 2:
-            if L.k22_build_flags() & 1:
+            if _lib.lib().k22_build_flags() & 1:
                 raise RuntimeError("chains=2 overlaps two engines on one device: this libk22hip.so was built with packed-fp32 instructions (NOPK=0)")
-            h2 = C.c_void_p()
-            _lib.check(L.k22_unet_create(C.byref(cfg), arr, len(table), C.byref(h2)))
-            self._handle2 = h2
+            self._engines[1] = NativeEngine("unet", cfg, arena, table)      # second half-batch engine: same arena, own workspace and graphs
         if free_params:
             for p in self.parameters():
                 p.data = torch.empty(0, device=dev)
@@ -208,24 +149,19 @@ class Text2ImUNetHIP(nn.Module):
         return self
 
     def _ensure_plan(self, B: int, H: int, W: int):
-        if self._handle is None:
+        if not self._engines:
             self.prepare()
-        key = (B, H, W)
-        if self._plan_key != key:
-            self._plan_key = None   # a failed plan / bind leaves the native engine without a plan: never skip re-planning after it
-            self._cond_key = None
-            L = _lib.lib()
-            pb = B // 2 if self._chained(B) else B
-            self._ws = _lib.plan_and_bind(L.k22_unet_plan, L.k22_unet_bind, self._handle, self._arena.device, pb, H, W)
-            if self._chained(B):
-                self._ws2 = _lib.plan_and_bind(L.k22_unet_plan, L.k22_unet_bind, self._handle2, self._arena.device, pb, H, W)
-                if self._side is None:
-                    self._side = torch.cuda.Stream(device=self._arena.device)
-            self._plan_key = key
-            self._cond_key = None
+        if self._plan_key != (B, H, W):
+            self._plan_key = self._cond_key = None   # no batch key until every engine of the batch has its plan
+            n = 2 if self._chained(B) else 1
+            for e in list(self._engines.values())[:n]:      # the first engine's workspace before the second's
+                e.plan(B // n, H, W)
+            if n == 2 and self._side is None:
+                self._side = torch.cuda.Stream(device=self._arena.device)
+            self._plan_key = (B, H, W)
 
     def _chained(self, B: int) -> bool:
-        return self.chains == 2 and self._handle2 is not None and B >= 2 and B % 2 == 0
+        return len(self._engines) == 2 and B >= 2 and B % 2 == 0
 
     def _parts(self, B: int):
         """(handle, first row, rows, stream handle) of every chain of a batch of B; the side stream is ordered behind the caller's first"""
@@ -233,7 +169,7 @@ class Text2ImUNetHIP(nn.Module):
         if not self._chained(B):
             return [(self._handle, 0, B, cur.cuda_stream)]
         self._side.wait_stream(cur)
-        return [(self._handle, 0, B // 2, cur.cuda_stream), (self._handle2, B // 2, B // 2, self._side.cuda_stream)]
+        return [(self._handle, 0, B // 2, cur.cuda_stream), (self._engines[1].handle, B // 2, B // 2, self._side.cuda_stream)]
 
     def _join(self, B: int):
         if self._chained(B):
@@ -248,7 +184,7 @@ class Text2ImUNetHIP(nn.Module):
         tot = {k: dict(ms=0.0, flops=0.0, bytes=0.0, launches=0) for k in kinds}
         # two chains: the halves are timed one after the other, op by op - ISOLATED device times of both, summed (the step itself overlaps
         # them, so the class times then add up to more than the step)
-        handles = [self._handle] + ([self._handle2] if self._plan_key is not None and self._chained(self._plan_key[0]) else [])
+        handles = [self._handle] + ([self._engines[1].handle] if self._plan_key is not None and self._chained(self._plan_key[0]) else [])
         for h in handles:
             ms, fl, by = (C.c_double * 5)(), (C.c_double * 5)(), (C.c_double * 5)()
             ln = (C.c_int * 5)()

@@ -1,7 +1,8 @@
-"""The plan / bind life cycle that the four native engines share (csrc/plan.h), exercised through ordinary use: run at shape A, re-plan to
-shape B and run, re-plan back to A; bind the same plan to a second workspace; for the UNet, a plan call with a rejected shape.  Every
-comparison is bit-for-bit (torch.equal): a plan is a pure function of (configuration, weights, shape, tile table), a workspace holds no
-state that outlives a forward, and a cached graph never survives the plan or the binding it was captured for."""
+"""The plan / bind life cycle that the four native engines share (csrc/plan.h), exercised through ordinary use of the six Python mirrors
+(kandinsky2_amd/native.py): run at shape A, re-plan to shape B and run, re-plan back to A; bind the same plan to a second workspace; for
+the UNet, a plan call with a rejected shape.  Every comparison is bit-for-bit (torch.equal): a plan is a pure function of (configuration,
+weights, shape, tile table), a workspace holds no state that outlives a forward, and a cached graph never survives the plan or the
+binding it was captured for."""
 import ctypes as C
 
 import pytest
@@ -104,12 +105,48 @@ def _tower():
 
     def rebind():
         e = m._engine_for(77)
-        e._ws = _rebind(_lib.lib().k22_encoder_bind, e.handle, e._ws)
+        e.ws = _rebind(_lib.lib().k22_encoder_bind, e.handle, e.ws)
 
     return run, 2, 1, rebind, None
 
 
-@pytest.mark.parametrize("engine", [_unet, _movq, _prior, _tower], ids=["unet", "movq", "prior", "tower"])
+def _movq_encoder():
+    arch = k22.MoVQArch(k22.MOVQ_CONFIG_2_1["ddconfig"])
+    m = k22.MoVQEncoderHIP(backend_dtype=BACKEND)
+    m.load_state_dict(k22.init_movq_encoder_state_dict(arch, seed=0), strict=True)
+    m = m.to("cuda")
+    g = torch.Generator().manual_seed(13)
+    # the smallest images that keep every level's height and width at least 8
+    imgs = {2: torch.rand(2, 3, 64, 64, generator=g).cuda() * 2 - 1, 1: torch.rand(1, 3, 64, 128, generator=g).cuda() * 2 - 1}
+
+    def rebind():
+        m._ws = _rebind(_lib.lib().k22_movq_bind, m._handle, m._ws)
+
+    return (lambda B: m.encode(imgs[B]).clone()), 2, 1, rebind, None
+
+
+def _clip_text():
+    cfg = k22.tiny_clip_config()
+    m = k22.CLIPModelHIP(cfg, backend_dtype=BACKEND)
+    m.load_state_dict(k22.init_clip_state_dict(cfg, seed=0))
+    m = m.to("cuda")
+    g = torch.Generator().manual_seed(17)
+    tokens = torch.randint(1, cfg["vocab_size"] - 1, (2, cfg["context_length"]), generator=g)
+    tokens[0, 9] = tokens[1, 30] = cfg["vocab_size"] - 1      # the end-of-text token: the largest id, where the pooled row is read
+
+    def run(B):
+        pooled, seq = m.encode_text_with_sequence(tokens[:B].cuda())
+        return torch.cat([pooled.reshape(-1), seq.reshape(-1)]).clone()
+
+    def rebind():
+        e = m._engine("text")
+        e.ws = _rebind(_lib.lib().k22_encoder_bind, e.handle, e.ws)
+
+    return run, 2, 1, rebind, None
+
+
+@pytest.mark.parametrize("engine", [_unet, _movq, _prior, _tower, _movq_encoder, _clip_text],
+                         ids=["unet", "movq", "prior", "tower", "movq_encoder", "clip_text"])
 def test_replan_and_rebind_reproduce_the_first_result_bit_for_bit(engine):
     run, A, B, rebind, rejected_plan = engine()
     first = run(A)
