@@ -21,7 +21,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib
+from . import sampling
 
 
 def named_betas(schedule: str, steps: int, linear_start: float, linear_end: float) -> np.ndarray:
@@ -69,6 +69,16 @@ def percentile_index(n: int, p: float = 99.5):
     if lo >= n - 1:
         lo, gamma = n - 1, np.float32(0)
     return lo, float(gamma)
+
+
+def _model_fn_call(model_fn, ts_rows, **kw):
+    """model_call of the drop-in form of p_sample_loop: the reference's model_fn closure on the latent itself, at row c of ts_rows"""
+    def call(x, c):
+        out = model_fn(x, ts_rows[c], **kw)   # already guided: [N, 8, H, W]
+        if tuple(out.shape) != (x.shape[0], 8) + tuple(x.shape[2:]):
+            raise ValueError(f"model_fn must return [N, 8, H, W] (eps | learned variance); got {tuple(out.shape)}")
+        return out.float().contiguous()
+    return call
 
 
 class SpacedDiffusionHIP:
@@ -194,11 +204,9 @@ class SpacedDiffusionHIP:
         `shape` = (2*bs, 4, h, w) with halves [cond | uncond].  noise_seq[k] (optional, [n_iters, *shape]) replaces
         randn_like at the k-th executed step (parity tests inject the reference's noise).
         """
-        L = _lib.lib()
         N, Cc, H, W = shape
         if Cc != 4 or N % 2:
             raise ValueError("shape must be (2*bs, 4, h, w)")
-        bs = N // 2
         dev = torch.device("cuda" if device is None else device)
         if dev.type != "cuda":
             raise RuntimeError("p_sample_loop runs on the GPU only (no CPU fallback)")
@@ -211,13 +219,10 @@ class SpacedDiffusionHIP:
         if noise is not None and tuple(noise.shape) != tuple(shape):
             raise ValueError(f"noise must have shape {tuple(shape)}")
         x = noise.to(dev).float().contiguous().clone() if noise is not None else torch.randn(*shape, device=dev)
-        x_next = torch.empty_like(x)
         table = torch.from_numpy(self.step_table()).to(dev)
         ts = torch.from_numpy(self.model_timesteps()).to(dev)
         ts_rows = ts[:, None].expand(-1, N).contiguous()  # [T][N]
-        HW = H * W
-        scratch = torch.empty(L.k22_sampler_scratch_bytes(N, HW), dtype=torch.uint8, device=dev)
-        pct_lo, pct_gamma = percentile_index(4 * HW) if clip_denoised else (-1, 0.0)
+        pct = percentile_index(4 * H * W) if clip_denoised else (-1, 0.0)
         if fused:
             if denoised_fn is not None:
                 raise ValueError("fused call: denoised_fn is implied (clamp +-2 and the init_img / img_mask blend)")
@@ -236,45 +241,21 @@ class SpacedDiffusionHIP:
                 raise ValueError(f"init_img / img_mask do not broadcast to {(N, 4, H, W)} / {(N, 1, H, W)}: {e}") from None
         if noise_seq is not None and tuple(noise_seq.shape[1:]) != tuple(shape):
             raise ValueError(f"noise_seq must have shape [n_steps, {tuple(shape)}]")
-        x0 = torch.empty_like(x) if return_pred_xstart else None
         indices = list(range(self.num_timesteps))[::-1] if init_step is None else list(range(self.num_timesteps))[:init_step][::-1]
+        # the noise of every step up front, by the randn_like calls a draw per step would make (same generator draws)
+        nzs = sampling.step_noise(x, len(indices), noise_seq)
+        ts_exec = ts_rows[torch.as_tensor(indices, dtype=torch.long, device=dev)].contiguous()      # timesteps, like the schedule rows, in execution order
+        if fused and whole_loop_graph and hasattr(model, "sample_loop") and not return_pred_xstart and not progress and len(indices) > 0:
+            # the whole loop as ONE hipGraph replay
+            return model.sample_loop(x, ts_exec, nzs, table, indices, guidance_scale, (lo, hi), pct, init_img=init, img_mask=mask, **model_kwargs)
+        model_call = (sampling.fused_call if fused else _model_fn_call)(model, ts_exec, **model_kwargs)
         if progress:
             from tqdm.auto import tqdm
             indices = tqdm(indices)
-        stream = _lib.current_stream()
-        if fused and whole_loop_graph and hasattr(model, "sample_loop") and not return_pred_xstart and not progress and len(indices) > 0:
-            # the whole loop as ONE hipGraph replay: noise of every step drawn up front by the same sequence of randn_like calls the
-            # per-step path makes (same generator draws), timesteps and schedule rows in execution order
-            n = len(indices)
-            if noise_seq is not None:
-                nzs = noise_seq[:n].to(dev).float().contiguous()
-            else:
-                nzs = torch.empty(n, *x.shape, device=dev)
-                for k in range(n):
-                    nzs[k] = torch.randn_like(x)
-            rows = torch.as_tensor(indices, device=dev)
-            kw = {k_: v for k_, v in model_kwargs.items()}
-            return model.sample_loop(x, ts_rows[rows].contiguous(), nzs, table, list(indices), guidance_scale, (lo, hi), (pct_lo, pct_gamma),
-                                     init_img=init, img_mask=mask, **kw)
-        for k, i in enumerate(indices):
-            if fused:
-                half = x[:bs]
-                combined = torch.cat([half, half], dim=0)  # model_fn: the second half of x is never fed to the UNet
-                out = model(combined, ts_rows[i], **model_kwargs)
-            else:
-                out = model(x, ts_rows[i], **model_kwargs)   # already guided: [N, 8, H, W]
-                if tuple(out.shape) != (N, 8, H, W):
-                    raise ValueError(f"model_fn must return [N, 8, H, W] (eps | learned variance); got {tuple(out.shape)}")
-                out = out.float().contiguous()
-            nz = noise_seq[k].to(dev).float().contiguous() if noise_seq is not None else torch.randn_like(x)
-            _lib.check(L.k22_sampler_step(
-                x.data_ptr(), out.data_ptr(), nz.data_ptr(), _lib.ptr(init), _lib.ptr(mask), table.data_ptr(), i,
-                float(guidance_scale) if fused else 1.0, 1 if fused else 0, lo, hi, pct_lo, pct_gamma, scratch.data_ptr(),
-                x_next.data_ptr(), _lib.ptr(x0), N, HW, stream))
-            x, x_next = x_next, x
-        if return_pred_xstart:
-            return x, x0
-        return x
+        x, x0 = sampling.step_loop(model_call, x, indices, nzs, torch.empty_like(x) if return_pred_xstart else None, sampling.sampler_step,
+                                   table=table, guidance=guidance_scale if fused else 1.0, use_cfg=fused, clamp=(lo, hi), pct=pct, init=init,
+                                   mask=mask, scratch=sampling.sampler_scratch(x))
+        return (x, x0) if return_pred_xstart else x
 
 
 class DDIMSamplerHIP:
@@ -311,18 +292,28 @@ class DDIMSamplerHIP:
 
     def _ddim_step(self, x, model_out, noise, table_row, x_out, x0_out):
         """One fused k22_ddim_step launch."""
-        N, HW = x.shape[0], x.shape[2] * x.shape[3]
-        _lib.check(_lib.lib().k22_ddim_step(x.data_ptr(), model_out.data_ptr(), _lib.ptr(noise), table_row.data_ptr(), self.guidance_scale, 1,
-                                            x_out.data_ptr(), x0_out.data_ptr(), N, HW, _lib.current_stream()))
+        sampling.ddim_step(x, model_out, noise, table_row, x_out, x0_out, guidance=self.guidance_scale)
 
-    @torch.no_grad()
-    def _whole_loop(self, kind, x, calls, noise_seq, conditioning):
-        """The loop as ONE hipGraph replay (Text2ImUNetHIP.ddim_loop -> k22_unet_ddim_loop): `calls` = the raw ddim timestep of every model
-        call in execution order, the table rows flipped into execution order."""
-        dev = x.device
-        ts_rows = torch.tensor([float(c) for c in calls], dtype=torch.float32, device=dev)[:, None].expand(-1, x.shape[0]).contiguous()
-        table = torch.from_numpy(self.table[::-1].copy()).to(dev)
-        x, x0 = self.model.ddim_loop(kind, x, ts_rows, table, self.guidance_scale, noise_seq, **(conditioning or {}))
+    def _x_T(self, batch_size, shape, x_T, device):
+        C, H, W = shape
+        if C != 4 or batch_size % 2:
+            raise ValueError("shape must be (4, h, w) and batch_size = 2*bs")
+        dev = torch.device(device)
+        return x_T.to(dev).float().contiguous().clone() if x_T is not None else torch.randn(batch_size, C, H, W, device=dev)
+
+    def _loop(self, kind, x, calls, noise, conditioning, whole_loop_graph):
+        """The loop over self.table from x = x_T.  `calls` = the raw ddim timestep of every model call in execution order; the table rows
+        flipped into execution order.  whole_loop_graph: ONE hipGraph replay (Text2ImUNetHIP.ddim_loop -> k22_unet_ddim_loop) where the
+        model has it, else the host-driven loop - same kernels, same bits."""
+        ts_rows = torch.tensor([float(c) for c in calls], dtype=torch.float32, device=x.device)[:, None].expand(-1, x.shape[0]).contiguous()
+        table = torch.from_numpy(self.table[::-1].copy()).to(x.device)
+        kw = conditioning or {}
+        if whole_loop_graph and hasattr(self.model, "ddim_loop") and len(table) > 0:
+            x, x0 = self.model.ddim_loop(kind, x, ts_rows, table, self.guidance_scale, noise, **kw)
+        elif kind == "plms":
+            x, x0 = sampling.plms_loop(sampling.fused_call(self.model, ts_rows, **kw), x, table, self._step)
+        else:
+            x, x0 = sampling.step_loop(sampling.fused_call(self.model, ts_rows, **kw), x, table, noise, torch.empty_like(x), self._ddim_step)
         return x, {"pred_x0": [x0]}
 
     @torch.no_grad()
@@ -330,37 +321,10 @@ class DDIMSamplerHIP:
                whole_loop_graph: bool = False, **_unused):
         """whole_loop_graph=True: the whole loop as one hipGraph (no host work between steps; same kernels, same bits)."""
         self.make_schedule(S, ddim_eta=eta, init_step=init_step)
-        C, H, W = shape
-        if C != 4 or batch_size % 2:
-            raise ValueError("shape must be (4, h, w) and batch_size = 2*bs")
-        dev = torch.device(device)
-        N, HW, bs = batch_size, H * W, batch_size // 2
-        x = x_T.to(dev).float().contiguous().clone() if x_T is not None else torch.randn(N, C, H, W, device=dev)
-        x_next, x0 = torch.empty_like(x), torch.empty_like(x)
-        table = torch.from_numpy(self.table).to(dev)
-        total = len(self.ddim_timesteps)
-        if whole_loop_graph and hasattr(self.model, "ddim_loop") and total > 0:
-            # the noise of every step drawn up front by the same sequence of randn_like calls the per-step path makes (same generator draws)
-            nzs = None
-            if self.eta > 0.0:
-                if noise_seq is not None:
-                    nzs = noise_seq[:total].to(dev).float().contiguous()
-                else:
-                    nzs = torch.empty(total, *x.shape, device=dev)
-                    for k in range(total):
-                        nzs[k] = torch.randn_like(x)
-            return self._whole_loop("ddim", x, np.flip(self.ddim_timesteps), nzs, conditioning)
-        for i, step in enumerate(np.flip(self.ddim_timesteps)):
-            index = total - i - 1
-            ts = torch.full((N,), float(step), device=dev)
-            half = x[:bs]
-            out = self.model(torch.cat([half, half], 0), ts, **(conditioning or {}))
-            nz = None
-            if self.eta > 0.0:
-                nz = noise_seq[i].to(dev).float().contiguous() if noise_seq is not None else torch.randn_like(x)
-            self._ddim_step(x, out, nz, table[index], x_next, x0)
-            x, x_next = x_next, x
-        return x, {"pred_x0": [x0]}
+        x = self._x_T(batch_size, shape, x_T, device)
+        # eta > 0: the noise of every step up front, by the randn_like calls a draw per step would make (same generator draws)
+        nzs = sampling.step_noise(x, len(self.ddim_timesteps), noise_seq) if self.eta > 0.0 else None
+        return self._loop("ddim", x, self.ddim_timesteps[::-1].tolist(), nzs, conditioning, whole_loop_graph)
 
 
 class PLMSSamplerHIP(DDIMSamplerHIP):
@@ -373,11 +337,7 @@ class PLMSSamplerHIP(DDIMSamplerHIP):
 
     def _step(self, x, model_out, hist, order, table_row, x_out, eps_out, x0_out):
         """One fused k22_plms_step launch; hist = eps history, newest first (as many tensors as `order` needs)."""
-        N, HW = x.shape[0], x.shape[2] * x.shape[3]
-        h = [t.data_ptr() for t in hist] + [None, None, None]
-        _lib.check(_lib.lib().k22_plms_step(x.data_ptr(), model_out.data_ptr(), h[0], h[1], h[2], order, table_row.data_ptr(),
-                                            self.guidance_scale, 1, x_out.data_ptr(), _lib.ptr(eps_out), _lib.ptr(x0_out), N, HW,
-                                            _lib.current_stream()))
+        sampling.plms_step(x, model_out, hist, order, table_row, x_out, eps_out, x0_out, guidance=self.guidance_scale)
 
     @torch.no_grad()
     def sample(self, S, batch_size, shape, conditioning=None, eta=0.0, x_T=None, init_step=None, device="cuda",
@@ -385,46 +345,8 @@ class PLMSSamplerHIP(DDIMSamplerHIP):
         if eta != 0:
             raise ValueError("ddim_eta must be 0 for PLMS")   # samplers.py:355-356
         self.make_schedule(S, ddim_eta=0.0, init_step=init_step)
-        C, H, W = shape
-        if C != 4 or batch_size % 2:
-            raise ValueError("shape must be (4, h, w) and batch_size = 2*bs")
-        dev = torch.device(device)
-        N, HW, bs = batch_size, H * W, batch_size // 2
-        x = x_T.to(dev).float().contiguous().clone() if x_T is not None else torch.randn(N, C, H, W, device=dev)
-        if whole_loop_graph and hasattr(self.model, "ddim_loop") and len(self.ddim_timesteps) > 0:
-            # model calls in execution order: the first step calls the model twice, the second time at the next step's timestep (its own when
-            # it is the only step)
-            tr = list(np.flip(self.ddim_timesteps))
-            return self._whole_loop("plms", x, [tr[0], tr[min(1, len(tr) - 1)]] + tr[1:], None, conditioning)
-        x_next, x0 = torch.empty_like(x), torch.empty_like(x)
-        hist = [torch.empty_like(x) for _ in range(4)]   # ring of guided eps tensors: 3 of history + the one being written
-        old = []                                          # newest last, like the reference's old_eps
-        table = torch.from_numpy(self.table).to(dev)
-        kw = conditioning or {}
-        time_range = np.flip(self.ddim_timesteps)
-        total = len(time_range)
-
-        def model(xx, step):
-            half = xx[:bs]
-            return self.model(torch.cat([half, half], 0), torch.full((N,), float(step), device=dev), **kw)
-
-        for i, step in enumerate(time_range):
-            index = total - i - 1
-            row = table[index]
-            e_buf = next(b for b in hist if all(b is not o for o in old))
-            out = model(x, step)
-            if len(old) == 0:
-                # stage one: e_t -> e_buf, provisional x_prev -> x_next; stage two: model at t_next, e' = (e_t + e_next) / 2
-                self._step(x, out, [], 0, row, x_next, e_buf, None)
-                out2 = model(x_next, time_range[min(i + 1, total - 1)])
-                self._step(x, out2, [e_buf], 4, row, x_next, None, x0)
-            else:
-                self._step(x, out, list(reversed(old)), len(old), row, x_next, e_buf, x0)
-            old.append(e_buf)
-            if len(old) >= 4:
-                old.pop(0)
-            x, x_next = x_next, x
-        return x, {"pred_x0": [x0]}
+        x = self._x_T(batch_size, shape, x_T, device)
+        return self._loop("plms", x, sampling.plms_calls(self.ddim_timesteps[::-1].tolist()), None, conditioning, whole_loop_graph)
 
 
 def create_gaussian_diffusion(**kw) -> SpacedDiffusionHIP:

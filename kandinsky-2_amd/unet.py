@@ -15,7 +15,7 @@ from typing import Optional
 
 import torch
 
-from . import _lib
+from . import _lib, sampling
 from .arch import UNetArch, make_arch, param_shapes
 from .native import NativeEngine, NativeModule, arena_size
 from .pack import pack_arena
@@ -50,9 +50,8 @@ class Text2ImUNetHIP(NativeModule):
         if self.chains not in (1, 2):
             raise ValueError("chains must be 1 or 2")
         self._side = None                               # stream of the second half-batch engine of the two-chain mode
-        self._plan_key = None                           # (B, H, W) of the whole batch, which two chains split between their engines
-        self._cond_key = None
         self.cache = None  # mirrors the reference attribute; holds the key of the cached conditioning
+        self._release()
 
     # ---- reference-compatible no-ops -------------------------------------------------------------
     def convert_to_fp16(self):
@@ -89,7 +88,9 @@ class Text2ImUNetHIP(NativeModule):
     # ---- engine management -------------------------------------------------------------------------
     def _release(self):
         super()._release()
-        self._loop_bufs = self._ddim_bufs = self._plan_key = self._cond_key = None
+        self._plan_key = self._cond_key = None          # _plan_key: (B, H, W) of the whole batch, which two chains split between their engines
+        # operand buffers of sample_loop and of ddim_loop: one set each, never shared (the engine's captured loop holds their addresses)
+        self._loop_bufs, self._ddim_bufs = sampling.OwnedBuffers(), sampling.OwnedBuffers()
 
     def arena_table(self):
         """name -> (byte offset, byte size) of the packed arena, derived from shapes only."""
@@ -232,6 +233,20 @@ class Text2ImUNetHIP(NativeModule):
             self._cond_key = True
             self.cache = {"cached": True}
 
+    def _inpaint_operands(self, x, inpaint_image, inpaint_mask):
+        """(inpaint_image, inpaint_mask) as fp32 views on x's device, broadcast the way the reference's torch.cat([x, inpaint_image *
+        inpaint_mask, inpaint_mask], dim=1) would need them ([B,4,H,W], [B,1,H,W]); None = not given, which on the 9-channel UNet means
+        zeros (InpaintText2ImUNet.forward defaults, text2im_model2_1.py:146-150).  A text2img UNet takes neither."""
+        if not self.arch.inpainting:
+            if inpaint_image is not None or inpaint_mask is not None:
+                raise ValueError("inpaint_image / inpaint_mask given to a text2img UNet (create it with inpainting=True)")
+            return None, None
+        B, _, H, W = x.shape
+        try:
+            return tuple(None if t is None else t.detach().float().to(x.device).expand(B, c, H, W) for t, c in ((inpaint_image, 4), (inpaint_mask, 1)))
+        except RuntimeError as e:
+            raise ValueError(f"inpaint_image / inpaint_mask do not match x {tuple(x.shape)}: {e}") from None
+
     @torch.no_grad()
     def forward(self, x, timesteps, full_emb=None, pooled_emb=None, image_emb=None, inpaint_image=None, inpaint_mask=None):
         if x.device.type != "cuda":
@@ -245,17 +260,10 @@ class Text2ImUNetHIP(NativeModule):
             raise ValueError(f"timesteps must hold one value per batch element ({B}); got {tuple(timesteps.shape)}")
         xf = x.detach().float().contiguous()
         tf = timesteps.detach().float().reshape(B).contiguous().to(x.device)
-        img = msk = None
+        img, msk = self._inpaint_operands(xf, inpaint_image, inpaint_mask)
         if self.arch.inpainting:
-            # InpaintText2ImUNet.forward defaults (text2im_model2_1.py:146-150); operands are broadcast the way the
-            # reference's torch.cat([x, inpaint_image * inpaint_mask, inpaint_mask], dim=1) would need them ([B,4,H,W], [B,1,H,W])
-            try:
-                img = torch.zeros_like(xf) if inpaint_image is None else inpaint_image.detach().float().to(x.device).expand(B, 4, H, W).contiguous()
-                msk = torch.zeros_like(xf[:, :1]) if inpaint_mask is None else inpaint_mask.detach().float().to(x.device).expand(B, 1, H, W).contiguous()
-            except RuntimeError as e:
-                raise ValueError(f"inpaint_image / inpaint_mask do not match x {tuple(x.shape)}: {e}") from None
-        elif inpaint_image is not None or inpaint_mask is not None:
-            raise ValueError("inpaint_image / inpaint_mask given to a text2img UNet (create it with inpainting=True)")
+            img = torch.zeros_like(xf) if img is None else img.contiguous()
+            msk = torch.zeros_like(xf[:, :1]) if msk is None else msk.contiguous()
         out = torch.empty(B, self.arch.out_channels, H, W, dtype=torch.float32, device=x.device)
         for h, r0, n, st in self._parts(B):      # one chain, or the two half-batch chains side by side (each replays its own graph on its stream)
             _lib.check(_lib.lib().k22_unet_forward(
@@ -263,7 +271,6 @@ class Text2ImUNetHIP(NativeModule):
                 _lib.ptr(None if msk is None else msk[r0:r0 + n]), out[r0:r0 + n].data_ptr(), 1 if self.use_graph else 0, st))
         self._join(B)
         return out
-
 
     @torch.no_grad()
     def sample_loop(self, x, ts_rows, noise_seq, table, table_rows, guidance_scale, clamp, pct, *, full_emb=None, pooled_emb=None,
@@ -280,48 +287,28 @@ class Text2ImUNetHIP(NativeModule):
             raise ValueError("sample_loop: ts_rows must be [n_steps, N] and noise_seq [n_steps, N, 4, h, w]")
         self._ensure_plan(B, H, W)
         self._ensure_condition(full_emb, pooled_emb, image_emb)
-        if not self.arch.inpainting and (inpaint_image is not None or inpaint_mask is not None):
-            raise ValueError("inpaint_image / inpaint_mask given to a text2img UNet (create it with inpainting=True)")
-        dev = x.device
+        img, msk = self._inpaint_operands(x, inpaint_image, inpaint_mask)
+        ii = None if init_img is None else init_img.float().expand(B, 4, H, W)
+        mm = None if init_img is None else img_mask.float().expand(B, 1, H, W)
+        dev, g, rows = x.device, float(guidance_scale), [int(r) for r in table_rows]
         if self._chained(B):
             # two chains: the loop is driven from the host - per step the two half-batch graphs side by side, a join, the sampler kernels (one
             # captured graph with two branches runs them back to back: measured in round 4).  Same step arithmetic as k22_unet_sample_loop.
-            L = _lib.lib()
-            cur, nxt = x.detach().float().clone(), torch.empty(B, 4, H, W, dtype=torch.float32, device=dev)
-            scratch = torch.empty(L.k22_sampler_scratch_bytes(B, H * W), dtype=torch.uint8, device=dev)
-            tbl = table.float().contiguous()
-            ii = None if init_img is None else init_img.float().expand(B, 4, H, W).contiguous()
-            mm = None if init_img is None else img_mask.float().expand(B, 1, H, W).contiguous()
-            for k in range(n_steps):
-                half = cur[: B // 2]
-                out = self.forward(torch.cat([half, half], 0), ts_rows[k], inpaint_image=inpaint_image, inpaint_mask=inpaint_mask)
-                _lib.check(L.k22_sampler_step(cur.data_ptr(), out.data_ptr(), noise_seq[k].contiguous().data_ptr(), _lib.ptr(ii), _lib.ptr(mm), tbl.data_ptr(),
-                                              int(table_rows[k]), float(guidance_scale), 1, float(clamp[0]), float(clamp[1]), int(pct[0]), float(pct[1]),
-                                              scratch.data_ptr(), nxt.data_ptr(), None, B, H * W, _lib.current_stream()))
-                cur, nxt = nxt, cur
-            return cur
-        key = (B, H, W, n_steps, tuple(table.shape), init_img is not None, str(dev))
-        bufs = getattr(self, "_loop_bufs", None)
-        if bufs is None or bufs["key"] != key:
-            f32 = dict(dtype=torch.float32, device=dev)
-            bufs = {"key": key, "x": torch.empty(B, 4, H, W, **f32), "tmp": torch.empty(B, 4, H, W, **f32), "ts": torch.empty(n_steps, B, **f32),
-                    "noise": torch.empty(n_steps, B, 4, H, W, **f32), "table": torch.empty(tuple(table.shape), **f32),
-                    "scratch": torch.empty(_lib.lib().k22_sampler_scratch_bytes(B, H * W), dtype=torch.uint8, device=dev),
-                    "init": torch.empty(B, 4, H, W, **f32) if init_img is not None else None,
-                    "mask": torch.empty(B, 1, H, W, **f32) if init_img is not None else None,
-                    "img": torch.zeros(B, 4, H, W, **f32) if self.arch.inpainting else None,
-                    "msk": torch.zeros(B, 1, H, W, **f32) if self.arch.inpainting else None}
-            self._loop_bufs = bufs
-        bufs["x"].copy_(x); bufs["ts"].copy_(ts_rows); bufs["noise"].copy_(noise_seq); bufs["table"].copy_(table)
-        if init_img is not None:
-            bufs["init"].copy_(init_img.float().expand(B, 4, H, W)); bufs["mask"].copy_(img_mask.float().expand(B, 1, H, W))
-        if self.arch.inpainting:
-            bufs["img"].zero_() if inpaint_image is None else bufs["img"].copy_(inpaint_image.float().expand(B, 4, H, W))
-            bufs["msk"].zero_() if inpaint_mask is None else bufs["msk"].copy_(inpaint_mask.float().expand(B, 1, H, W))
-        rows = (C.c_int * n_steps)(*[int(r) for r in table_rows])
+            x = x.detach().float().clone()
+            return sampling.step_loop(sampling.fused_call(self.forward, ts_rows, inpaint_image=img, inpaint_mask=msk), x, rows, noise_seq.contiguous(),
+                                      None, sampling.sampler_step, table=table.float().contiguous(), guidance=g, use_cfg=1, clamp=clamp, pct=pct,
+                                      init=None if ii is None else ii.contiguous(), mask=None if mm is None else mm.contiguous(),
+                                      scratch=sampling.sampler_scratch(x))[0]
+        box, img9 = (B, 4, H, W), self.arch.inpainting
+        bufs = self._loop_bufs.stage(
+            (B, H, W, n_steps, tuple(table.shape), init_img is not None, str(dev)), dev,
+            lambda: dict(x=box, tmp=box, ts=(n_steps, B), noise=(n_steps,) + box, table=tuple(table.shape),
+                         scratch=_lib.lib().k22_sampler_scratch_bytes(B, H * W), init=box if ii is not None else None,
+                         mask=(B, 1, H, W) if ii is not None else None, img=box if img9 else None, msk=(B, 1, H, W) if img9 else None),
+            dict(x=x, ts=ts_rows, noise=noise_seq, table=table, init=ii, mask=mm, img=img, msk=msk))
         _lib.check(_lib.lib().k22_unet_sample_loop(
             self._handle, bufs["x"].data_ptr(), bufs["tmp"].data_ptr(), bufs["ts"].data_ptr(), bufs["noise"].data_ptr(), _lib.ptr(bufs["init"]),
-            _lib.ptr(bufs["mask"]), _lib.ptr(bufs["img"]), _lib.ptr(bufs["msk"]), bufs["table"].data_ptr(), rows, n_steps, float(guidance_scale),
+            _lib.ptr(bufs["mask"]), _lib.ptr(bufs["img"]), _lib.ptr(bufs["msk"]), bufs["table"].data_ptr(), (C.c_int * n_steps)(*rows), n_steps, g,
             float(clamp[0]), float(clamp[1]), int(pct[0]), float(pct[1]), bufs["scratch"].data_ptr(), 1 if self.use_graph else 0,
             _lib.current_stream()))
         return bufs["x"].clone()
@@ -348,64 +335,26 @@ class Text2ImUNetHIP(NativeModule):
             raise ValueError("ddim_loop: noise_seq is [n_steps, N, 4, h, w], for DDIM only (PLMS is eta = 0)")
         self._ensure_plan(B, H, W)
         self._ensure_condition(full_emb, pooled_emb, image_emb)
-        if not self.arch.inpainting and (inpaint_image is not None or inpaint_mask is not None):
-            raise ValueError("inpaint_image / inpaint_mask given to a text2img UNet (create it with inpainting=True)")
-        L, dev = _lib.lib(), x.device
-        f32 = dict(dtype=torch.float32, device=dev)
+        img, msk = self._inpaint_operands(x, inpaint_image, inpaint_mask)
+        dev, g = x.device, float(guidance_scale)
         if self._chained(B):
             # two chains: host-driven, per model call the two half-batch graphs side by side (see sample_loop).  The steps of k22_unet_ddim_loop.
-            cur, nxt, x0 = x.detach().float().clone(), torch.empty(B, 4, H, W, **f32), torch.empty(B, 4, H, W, **f32)
-            tbl, g, st = table.float().contiguous(), float(guidance_scale), _lib.current_stream
-            ring, old, call = [torch.empty(B, 4, H, W, **f32) for _ in range(4)] if plms else [], [], 0
-
-            def model(xx, c):
-                half = xx[: B // 2]
-                return self.forward(torch.cat([half, half], 0), ts_rows[c], inpaint_image=inpaint_image, inpaint_mask=inpaint_mask)
-
-            def plms_step(out, hist, order, row, eps_out, x0_out):
-                h = [t.data_ptr() for t in hist] + [None, None, None]
-                _lib.check(L.k22_plms_step(cur.data_ptr(), out.data_ptr(), h[0], h[1], h[2], order, row.data_ptr(), g, 1, nxt.data_ptr(),
-                                           _lib.ptr(eps_out), _lib.ptr(x0_out), B, H * W, st()))
-
-            for k in range(n_steps):
-                out = model(cur, call)
-                call += 1
-                if not plms:
-                    nz = None if noise_seq is None else noise_seq[k].float().contiguous()
-                    _lib.check(L.k22_ddim_step(cur.data_ptr(), out.data_ptr(), _lib.ptr(nz), tbl[k].data_ptr(), g, 1, nxt.data_ptr(), x0.data_ptr(),
-                                               B, H * W, st()))
-                else:
-                    e_buf = next(b for b in ring if all(b is not o for o in old))
-                    if not old:
-                        plms_step(out, [], 0, tbl[k], e_buf, None)
-                        out = model(nxt, call)
-                        call += 1
-                        plms_step(out, [e_buf], 4, tbl[k], None, x0)
-                    else:
-                        plms_step(out, old, len(old), tbl[k], e_buf, x0)
-                    old = [e_buf] + old[:2]   # newest first
-                cur, nxt = nxt, cur
-            return cur, x0
-        key = (kind, B, H, W, n_steps, noise_seq is not None, str(dev))
-        bufs = getattr(self, "_ddim_bufs", None)
-        if bufs is None or bufs["key"] != key:
-            bufs = {"key": key, "x": torch.empty(B, 4, H, W, **f32), "tmp": torch.empty(B, 4, H, W, **f32), "x0": torch.empty(B, 4, H, W, **f32),
-                    "ts": torch.empty(n_calls, B, **f32), "table": torch.empty(n_steps, 4, **f32),
-                    "noise": torch.empty(n_steps, B, 4, H, W, **f32) if noise_seq is not None else None,
-                    "hist": torch.empty(4, B, 4, H, W, **f32) if plms else None,
-                    "img": torch.zeros(B, 4, H, W, **f32) if self.arch.inpainting else None,
-                    "msk": torch.zeros(B, 1, H, W, **f32) if self.arch.inpainting else None}
-            self._ddim_bufs = bufs
-        bufs["x"].copy_(x); bufs["ts"].copy_(ts_rows); bufs["table"].copy_(table)
-        if noise_seq is not None:
-            bufs["noise"].copy_(noise_seq)
-        if self.arch.inpainting:
-            bufs["img"].zero_() if inpaint_image is None else bufs["img"].copy_(inpaint_image.float().expand(B, 4, H, W))
-            bufs["msk"].zero_() if inpaint_mask is None else bufs["msk"].copy_(inpaint_mask.float().expand(B, 1, H, W))
-        _lib.check(L.k22_unet_ddim_loop(
+            call = sampling.fused_call(self.forward, ts_rows, inpaint_image=img, inpaint_mask=msk)
+            x, tbl = x.detach().float().clone(), table.float().contiguous()
+            if plms:
+                return sampling.plms_loop(call, x, tbl, sampling.plms_step, guidance=g)
+            nzs = None if noise_seq is None else noise_seq.float().contiguous()
+            return sampling.step_loop(call, x, tbl, nzs, torch.empty_like(x), sampling.ddim_step, guidance=g)
+        box, img9 = (B, 4, H, W), self.arch.inpainting
+        bufs = self._ddim_bufs.stage(
+            (kind, B, H, W, n_steps, noise_seq is not None, str(dev)), dev,
+            lambda: dict(x=box, tmp=box, x0=box, ts=(n_calls, B), table=(n_steps, 4), noise=(n_steps,) + box if noise_seq is not None else None,
+                         hist=(4,) + box if plms else None, img=box if img9 else None, msk=(B, 1, H, W) if img9 else None),
+            dict(x=x, ts=ts_rows, table=table, noise=noise_seq, img=img, msk=msk))
+        _lib.check(_lib.lib().k22_unet_ddim_loop(
             self._handle, _lib.K22_LOOP_PLMS if plms else _lib.K22_LOOP_DDIM, bufs["x"].data_ptr(), bufs["tmp"].data_ptr(), bufs["x0"].data_ptr(),
             bufs["ts"].data_ptr(), bufs["table"].data_ptr(), _lib.ptr(bufs["noise"]), _lib.ptr(bufs["img"]), _lib.ptr(bufs["msk"]),
-            _lib.ptr(bufs["hist"]), n_steps, float(guidance_scale), 1 if self.use_graph else 0, _lib.current_stream()))
+            _lib.ptr(bufs["hist"]), n_steps, g, 1 if self.use_graph else 0, _lib.current_stream()))
         return bufs["x"].clone(), bufs["x0"].clone()
 
 

@@ -32,7 +32,7 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, sampling
 from .arch import UNetArch, _walk
 from .unet import Text2ImUNetHIP
 
@@ -543,8 +543,7 @@ class DDPMSchedulerHIP:
             nz = torch.randn(sample.shape, generator=generator, device=gdev).to(sample.device)
         x, mo = sample.detach().float().contiguous(), model_output.detach().float().contiguous()
         out = torch.empty_like(x)
-        fused = guidance_scale is not None
-        _lib.check(L.k22_sampler_step(x.data_ptr(), mo.data_ptr(), nz.float().contiguous().data_ptr(), None, None, self._table.data_ptr(), row,
-                                      float(guidance_scale) if fused else 1.0, 1 if fused else 0, -min(self.clip, 3.0e38), min(self.clip, 3.0e38), -1, 0.0,
-                                      self._scratch.data_ptr(), out.data_ptr(), None, N, HW, _lib.current_stream()))
+        fused, clip = guidance_scale is not None, min(self.clip, 3.0e38)
+        sampling.sampler_step(x, mo, nz.float().contiguous(), row, out, None, table=self._table, guidance=guidance_scale if fused else 1.0, use_cfg=fused,
+                              clamp=(-clip, clip), pct=(-1, 0.0), init=None, mask=None, scratch=self._scratch)
         return SimpleNamespace(prev_sample=out) if return_dict else (out,)

@@ -420,3 +420,29 @@ def test_two_chains_p_sampler_final_latent_vs_reference_golden(golden_dir, name)
     print(f"{name}: fp32 engine, two chains, vs reference p_sampler final latent max|d| = {err:.3e}")
     assert err <= 1e-3
     assert torch.equal(finals[0], finals[1]) and torch.equal(finals[1], finals[2])
+
+
+@pytest.mark.parametrize("name", ["tiny_text2img", "tiny_inpaint"])
+def test_two_chains_p_sampler_whole_loop_is_the_stepwise_loop(golden_dir, name):
+    """Under two chains whole_loop_graph=True runs the host-driven loop that whole_loop_graph=False runs: equal final latents, and no
+    single-graph loop is captured or launched."""
+    from kandinsky2_amd import _lib
+    fx = _load(golden_dir, name)
+    assert (fx["B"], fx["h"], fx["w"]) == ((2, 16, 16) if name == "tiny_text2img" else (4, 16, 24))
+    arch = k22.make_arch(fx["model_config"], inpainting=fx["inpainting"])
+    _a, sd, _m, _x, img, mask, kw = _setup(fx, torch.float32, use_graph=True)
+    m = k22.Text2ImUNetHIP(arch, backend_dtype=torch.float32, use_graph=True, chains=2)
+    m.load_state_dict(sd)
+    m = m.to("cuda").eval()
+    g = torch.Generator().manual_seed(42)
+    shape = (fx["B"], 4, fx["h"], fx["w"])
+    x_T, noise_seq = torch.randn(*shape, generator=g).cuda(), torch.randn(fx["steps"], *shape, generator=g).cuda()
+    d = k22.create_gaussian_diffusion(**dict(k22.DIFFUSION_CONFIG_2_1, timestep_respacing=str(fx["steps"])))
+    ii, mm = (img.cuda(), mask.cuda()) if fx["inpainting"] else (None, None)
+    counters = lambda: tuple(_lib.lib().k22_debug_counter(c) for c in (b"loop_captures", b"loop_launches"))
+    before, finals = counters(), []
+    for whole in (False, True):
+        m.del_cache()
+        finals.append(d.p_sample_loop(m, shape, model_kwargs=kw, guidance_scale=fx["guidance"], noise=x_T, noise_seq=noise_seq, init_img=ii,
+                                      img_mask=mm, whole_loop_graph=whole))
+    assert torch.equal(finals[0], finals[1]) and counters() == before

@@ -69,6 +69,7 @@ def main(argv=None):
 
     def generation(sampler, whole):
         pipe.whole_loop_graph = whole
+        torch.manual_seed(17)                         # p_sampler draws its per-step noise: every generation of a configuration the same one
         return pipe.generate_img(prompt, image_emb, batch_size=a.bs, diffusion=diffusions[sampler], guidance_scale=4, noise=x_T, h=a.size, w=a.size,
                                  sampler=sampler, num_steps=a.steps, text_embs=text_embs, decode=False)
 
