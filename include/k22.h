@@ -608,6 +608,26 @@ int k22_prior_finish_input(float* inp, const float* pos, const float* prd, int B
  * without one is 0 * inf. */
 int k22_attention_masked(const void* qkv, const void* ctxkv, void* kall, void* vtall, void* out, int B, int H, int T, int S, int causal,
                          const float* key_valid, int kv_n, int out_x3, int dtype, void* stream);
+/* GroupNorm32 of the UNet, one kernel per entry (csrc/elementwise.hip; tests/test_gn_parity_gpu.py, tests/gn_ref.py), each through the
+ * launcher K22UNet::op_gn calls.  x0 [B][H][W][C0] (+ x1 [B][H][W][C1], C1 = 0 and x1 null without a concat) are NHWC tensors of the
+ * storage type (fp32 for the split dtypes); 32 groups over C = C0 + C1.
+ *   gn_stats   per-channel (sum, sum of squares) of each of nsplit pixel ranges of ceil(HW / nsplit) pixels: partial [B][nsplit][C][2]
+ *              fp32, *nsplit_out receives nsplit (a function of B and HW; at most 128).  A range past the end of the image gives zero
+ *              rows.  K22_EINVAL: C % 128 != 0, C0 % 4 != 0, C > 3072.
+ *   gn_coeff   coeff [B][C][2] = (A, Bc) with GroupNorm(x) [* (1 + scale) + shift] = x * A + Bc, from the partial sums of up to two sources
+ *              as their producers left them: image b owns rows [b * rpi_k, (b + 1) * rpi_k) of st_k [rows][C_k][2] (gn_stats: rpi = nsplit,
+ *              one source with C_k = C; k22_conv3x3_gnstats / k22_gemm_gnstats: their *rows_per_image).  A group may straddle the two
+ *              sources.  film (optional): row b at film + b * film_ld holds scale at [c] and shift at [C + c]; film_ld >= 2 C.
+ *              K22_EINVAL, nothing launched: C % 32 != 0, more than 256 channels per group, rpi <= 0 on a used source, C1 > 0 with a
+ *              null st1, film with film_ld < 2 C, null gamma / beta / coeff.
+ *   gn_apply   out [B][Ho + 2 pad][Wo + 2 pad][C] = zero-bordered resample(act(x * A + Bc)); mode 0 same size, 1 = 2x2 average (floor of
+ *              H / 2, W / 2), 2 = nearest x2; act 0 | K22_ACT_SILU.  K22_F16X3 / K22_F16X2: the fp32 kernel writing x3 chunks, as k22_groupnorm.
+ *              C and C0 must be multiples of 8 (16-bit types) / 4 (fp32). */
+int k22_gn_stats(const void* x0, const void* x1, int C0, int C1, int B, int HW, float* partial, int* nsplit_out, int dtype, void* stream);
+int k22_gn_coeff(const float* st0, int rpi0, int C0, const float* st1, int rpi1, int C1, int B, int HW, const float* gamma, const float* beta,
+                 const float* film, long film_ld, float eps, float* coeff, void* stream);
+int k22_gn_apply(const void* x0, const void* x1, int C0, int C1, int B, int H, int W, const float* coeff, int act, int mode, int pad, void* out,
+                 int dtype, void* stream);
 
 #ifdef __cplusplus
 }

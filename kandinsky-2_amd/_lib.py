@@ -184,6 +184,10 @@ SIGNATURES = {
     "k22_prior_layernorm": (_I, [_P, _L, _P, _P, _P, _I, _I, _I, _I, _P]),
     "k22_prior_finish_input": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "k22_attention_masked": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _P]),
+    # GroupNorm, one kernel per entry (tests/test_gn_parity_gpu.py)
+    "k22_gn_stats": (_I, [_P, _P, _I, _I, _I, _I, _P, C.POINTER(_I), _I, _P]),
+    "k22_gn_coeff": (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _P, _P, _P, _L, _F, _P, _P]),
+    "k22_gn_apply": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _P, _I, _P]),
 }
 
 _lib = None

@@ -538,6 +538,44 @@ int k22_attention_masked(const void* qkv, const void* ctxkv, void* kall, void* v
   return attention_seq(qkv, ctxkv, kall, vtall, out, B, H, T, S, causal, key_valid, kv_n, out_x3, dtype, reinterpret_cast<hipStream_t>(stream));
 }
 
+// ---- GroupNorm32, one kernel per entry (tests/test_gn_parity_gpu.py): the three launchers K22UNet::op_gn calls, with the fields it fills ----
+int k22_gn_stats(const void* x0, const void* x1, int C0, int C1, int B, int HW, float* partial, int* nsplit_out, int dtype, void* stream) {
+  if (nsplit_out) *nsplit_out = 0;
+  if (!x0 || !partial || C0 < 1 || C1 < 0 || (C1 > 0 && !x1) || B < 1 || B > 65535 || HW < 1 || !(aux_dtype_ok(dtype) || k22_is_split(dtype)))
+    return k22_set_error(K22_EINVAL, "gn_stats: bad argument");
+  GnStatsParams sp = {};
+  sp.x0 = x0; sp.x1 = C1 > 0 ? x1 : nullptr; sp.C0 = C0; sp.C1 = C1; sp.HW = HW; sp.B = B; sp.groups = 32; sp.nsplit = gn_nsplit(B, HW); sp.partial = partial;
+  if (nsplit_out) *nsplit_out = sp.nsplit;
+  return launch_gn_stats(sp, k22_storage_dtype(dtype), reinterpret_cast<hipStream_t>(stream));
+}
+int k22_gn_coeff(const float* st0, int rpi0, int C0, const float* st1, int rpi1, int C1, int B, int HW, const float* gamma, const float* beta,
+                 const float* film, long film_ld, float eps, float* coeff, void* stream) {
+  // (the engine's plan cannot trip any of these: its channel counts are multiples of 128, op_gn refuses rpi <= 0 itself and film_ld is the
+  // whole FiLM row - so they live here and launch_gn_coeff stays as it is)
+  if (!gamma || !beta || !coeff) return k22_set_error(K22_EINVAL, "gn_coeff: gamma, beta and coeff are required");
+  if (!st0 || C0 < 1 || C1 < 0 || B < 1 || B > 65535 || HW < 1) return k22_set_error(K22_EINVAL, "gn_coeff: bad argument");
+  if (rpi0 <= 0 || (C1 > 0 && rpi1 <= 0)) return k22_set_error(K22_EINVAL, "gn_coeff: rows per image of a used source must be positive");
+  if (C1 > 0 && !st1) return k22_set_error(K22_EINVAL, "gn_coeff: second source without partial sums");
+  const int C = C0 + C1;
+  if (C % 32 != 0) return k22_set_error(K22_EINVAL, "gn_coeff: 32 groups need C % 32 == 0");
+  if (film && film_ld < 2L * C) return k22_set_error(K22_EINVAL, "gn_coeff: film_ld < 2 C");
+  GnCoeffParams cp = {};
+  cp.src[0].st = st0; cp.src[0].rpi = rpi0; cp.src[0].C = C0;
+  if (C1 > 0) { cp.src[1].st = st1; cp.src[1].rpi = rpi1; cp.src[1].C = C1; }
+  cp.HW = HW; cp.C = C; cp.groups = 32; cp.eps = eps; cp.gamma = gamma; cp.beta = beta; cp.film = film; cp.film_ld = film_ld; cp.coeff = coeff;
+  return launch_gn_coeff(cp, B, reinterpret_cast<hipStream_t>(stream));
+}
+int k22_gn_apply(const void* x0, const void* x1, int C0, int C1, int B, int H, int W, const float* coeff, int act, int mode, int pad, void* out,
+                 int dtype, void* stream) {
+  if (!x0 || !coeff || !out || C0 < 1 || C1 < 0 || (C1 > 0 && !x1) || B < 1 || H < 1 || W < 1 || mode < 0 || mode > 2 || (mode == 1 && (H < 2 || W < 2)) ||
+      (pad != 0 && pad != 1) || (act != K22_ACT_NONE && act != K22_ACT_SILU) || !(aux_dtype_ok(dtype) || k22_is_split(dtype)))
+    return k22_set_error(K22_EINVAL, "gn_apply: bad argument");
+  GnApplyParams ap = {};
+  ap.x0 = x0; ap.x1 = C1 > 0 ? x1 : nullptr; ap.C0 = C0; ap.C1 = C1; ap.B = B; ap.H = H; ap.W = W; ap.mode = mode; ap.pad = pad; ap.act = act;
+  ap.coeff = coeff; ap.out = out; ap.out_x3 = k22_is_split(dtype) ? 1 : 0;   // as k22_groupnorm: fp32 in, x3 chunks out
+  return launch_gn_apply(ap, k22_storage_dtype(dtype), reinterpret_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"
 
 // ---- debug: LDS sentinel (tools/lds_victim_probe.py) -------------------------------------------------------------
