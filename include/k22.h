@@ -76,7 +76,7 @@ const char* k22_last_error(void);
  * "att_pipe" = -1 as K22_ATT_PIPE says (default), 0 / 1: the unmasked 16-bit attention through attention_kernel / attention_pipe_kernel. */
 int k22_set_option(const char* name, int value);
 /* Host counters for tests, since the library was loaded: "stream_launches" = launches of the weight-streaming kernel;
- * "loop_captures" = whole-loop graphs captured by any loop entry (k22_unet_sample_loop, k22_unet_ddim_loop); "loop_launches" = whole-loop
+ * "loop_captures" = whole-loop graphs captured by any loop entry (k22_unet_sample_loop, k22_unet_ddim_loop, k22_prior_sample_loop); "loop_launches" = whole-loop
  * replays or eager loop runs.  -1 for an unknown name. */
 long k22_debug_counter(const char* name);
 /* Fragment-major copy of a 16-bit weight matrix [Npad][taps * Kc] for the weight-streaming kernel (1 KB contiguous per MFMA B
@@ -442,6 +442,35 @@ int k22_prior_forward(K22Prior* m, const float* x, const float* timesteps, const
  * posterior_log_variance_clipped, t != 0); x / model_out / noise / x_out: [2*bs][D]; scales [bs]. */
 int k22_prior_sampler_step(const float* x, const float* model_out, const float* noise, const float* scales, const float* table_row,
                            float clamp, float* x_out, int bs, int D, void* stream);
+/* One DDIM step (gaussian_diffusion.py:477-519 as the prior runs it: START_X, clip_denoised off, denoised_fn = clamp):
+ *   x0 = clamp(uncond + scales[j]*(cond - uncond), +-clamp);  eps = (sqrt_recip_ac*x - x0) / sqrt_recipm1_ac;
+ *   x_out = sqrt(ab_prev)*x0 + sqrt(1 - ab_prev - sigma^2)*eps + (i != 0)*sigma*noise.
+ * table_row: device fp32[8] = (sqrt_recip_alphas_cumprod[i], sqrt_recipm1_alphas_cumprod[i], sqrt(alphas_cumprod_prev[i]), sigma,
+ * sqrt(1 - alphas_cumprod_prev[i] - sigma^2), i != 0, 0, 0), computed in float64 and rounded once;
+ * sigma = eta * sqrt((1 - ab_prev)/(1 - ab)) * sqrt(1 - ab/ab_prev).  Layout as k22_prior_sampler_step.  noise may be NULL and then reads
+ * as 0: valid for an eta = 0 table only.  x0_out [2*bs][D] (the clamped guided prediction) may be NULL.  Every operation is rounded once
+ * (no contraction).  K22_EINVAL for a null required argument or bs, D < 1. */
+int k22_prior_ddim_step(const float* x, const float* model_out, const float* noise, const float* scales, const float* table_row,
+                        float clamp, float* x_out, float* x0_out, int bs, int D, void* stream);
+/* The whole sampling loop of PriorDiffusionModel.forward (prior.py:336-384) on a bound handle, B = 2*bs rows [cond | uncond]:
+ * the conditioning (text_emb, text_enc, key_valid as k22_prior_forward takes them) is copied into the plan once; then for
+ * k = 0 .. n_steps-1:  transformer([x[:bs] | x[:bs]], timesteps[k]) -> k22_prior_sampler_step (kind ANCESTRAL, table rows fp32[4]) or
+ * k22_prior_ddim_step (kind DDIM, table rows fp32[8]), alternating between x and x_tmp; the final latent ends up in x.
+ *   timesteps [n_steps][B], table [n_steps][4 | 8], noise_seq [n_steps][B][D]: all in EXECUTION order (schedule index T-1 first).
+ *   noise_seq may be NULL for kind DDIM only (eta = 0).  x0_out [B][D] (DDIM: the last step's x0) may be NULL.
+ *   n_steps is the schedule's own count: "ddimN" keeps the timesteps 1, 1 + 1000//N, ... below 1000, which is 3 steps for "ddim3" (the
+ *   stride formula's 1000 is no timestep) and 31 for "ddim30" (stride 33).
+ * use_graph != 0: the loop is ONE captured graph, a single chain on the handle's capture stream, launched on `stream`.  The handle
+ * keeps one such loop, keyed by kind, n_steps, clamp and every pointer argument: a call with the same key replays it (the caller
+ * refills its buffers), anything else captures again; k22_prior_bind drops it.  use_graph == 0 issues the same launches eagerly.
+ * Both count into k22_debug_counter("loop_captures" / "loop_launches").  The first use of a plan measures its tile configurations and
+ * runs one eager pass of the launch list, as k22_prior_forward does.
+ * K22_EINVAL (with a k22_last_error text) for a null required argument, an unknown kind, n_steps < 1, ANCESTRAL without noise_seq, or
+ * no bound workspace; a refused call leaves the handle and its captured loop as they were. */
+enum { K22_PRIOR_LOOP_ANCESTRAL = 0, K22_PRIOR_LOOP_DDIM = 1 };
+int k22_prior_sample_loop(K22Prior* m, int kind, float* x, float* x_tmp, float* x0_out, const float* timesteps, const float* table,
+                          const float* noise_seq, const float* scales, const float* text_emb, const float* text_enc,
+                          const float* key_valid, float clamp, int n_steps, int use_graph, void* stream);
 
 /* ---- MoVQ decoder ---------------------------------------------------------------------------
  * Replaces MOVQ.decode (kandinsky2/vqgan/autoencoder.py:182-185: post_quant_conv + MOVQDecoder.forward,

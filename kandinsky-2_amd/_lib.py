@@ -17,6 +17,7 @@ TILE_TABLE_PATH = os.path.join(_HERE, "tiles_gfx950.txt")
 
 K22_BF16, K22_F32, K22_F16, K22_F16X3, K22_F16X2 = 0, 1, 2, 3, 4
 K22_LOOP_DDIM, K22_LOOP_PLMS = 0, 1   # include/k22.h: kind of k22_unet_ddim_loop
+K22_PRIOR_LOOP_ANCESTRAL, K22_PRIOR_LOOP_DDIM = 0, 1   # include/k22.h: kind of k22_prior_sample_loop
 # backend_dtype of the split-precision UNet engine (no torch dtype names it): fp32 tensors, MFMA operands as fp16 (hi, lo) pairs, three
 # fp16 MFMAs per product - the arithmetic that meets the 1e-3 final-latent gate at 16-bit MFMA rate (include/k22.h: K22_F16X3)
 F16X3 = "f16x3"
@@ -122,6 +123,8 @@ SIGNATURES = {
     "k22_prior_tuning_report": (_I, [_P, C.c_char_p, _Z]),
     "k22_prior_forward": (_I, [_P, _P, _P, _P, _P, _P, _P, _P]),
     "k22_prior_sampler_step": (_I, [_P, _P, _P, _P, _P, _F, _P, _I, _I, _P]),
+    "k22_prior_ddim_step": (_I, [_P, _P, _P, _P, _P, _F, _P, _P, _I, _I, _P]),
+    "k22_prior_sample_loop": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _I, _P]),
     "k22_encoder_create": (_I, [C.POINTER(K22EncoderConfig), C.POINTER(K22Weight), _I, C.POINTER(_P)]),
     "k22_encoder_destroy": (None, [_P]),
     "k22_encoder_plan": (_I, [_P, _I, C.POINTER(_Z)]),

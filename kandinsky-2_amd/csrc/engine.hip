@@ -35,12 +35,10 @@ int launch_step_advance(int* step, int delta, hipStream_t s);
 static std::atomic<long> g_loop_captures{0}, g_loop_launches{0};
 long loop_capture_count() { return g_loop_captures.load(); }
 long loop_launch_count() { return g_loop_launches.load(); }
-static void loop_count_capture() { g_loop_captures.fetch_add(1); }
-static void loop_count_launch() { g_loop_launches.fetch_add(1); }
+void loop_count_capture() { g_loop_captures.fetch_add(1); }
+void loop_count_launch() { g_loop_launches.fetch_add(1); }
 // first word of a captured loop's key: which entry's nodes the graph holds
 enum : unsigned long long { K22_LOOP_KIND_P = 0, K22_LOOP_KIND_DDIM = 1, K22_LOOP_KIND_PLMS = 2 };
-static unsigned long long loop_key_ptr(const void* p) { return (unsigned long long)(uintptr_t)p; }
-static unsigned long long loop_key_bits(double v) { unsigned long long b; memcpy(&b, &v, 8); return b; }
 
 namespace {
 

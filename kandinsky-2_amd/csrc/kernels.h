@@ -4,6 +4,8 @@
 #include "common.h"
 
 #include <atomic>
+#include <stdint.h>
+#include <string.h>
 #include <type_traits>
 
 #define K22_OK 0
@@ -205,6 +207,11 @@ long stream_launch_count();
 // engine.hip: whole-loop graphs captured / whole-loop replays or eager loop runs since the library was loaded
 long loop_capture_count();
 long loop_launch_count();
+void loop_count_capture();   // called by every loop entry (engine.hip, prior.hip)
+void loop_count_launch();
+// what a captured loop's key is made of: every pointer and scalar baked into its nodes
+inline unsigned long long loop_key_ptr(const void* p) { return (unsigned long long)(uintptr_t)p; }
+inline unsigned long long loop_key_bits(double v) { unsigned long long b; memcpy(&b, &v, 8); return b; }
 // bytes of the fragment-major copy of a [Npad][taps * Kc] weight matrix, and the one-time repack (any 16-bit dtype)
 size_t stream_frag_bytes(int Npad, int taps, int Kc, int dtype);
 int launch_stream_repack(const void* W, void* out, int Npad, int taps, int Kc, int dtype, hipStream_t stream);

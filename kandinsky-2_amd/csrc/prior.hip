@@ -71,6 +71,25 @@ __global__ void prior_sampler_step_kernel(const float* x, const float* model_out
   x_out[i] = mean + tab[3] * expf(0.5f * tab[2]) * noise[i];
 }
 
+// ---- one DDIM step of the prior (gaussian_diffusion.py:477-519 with START_X, clip_denoised off, denoised_fn = clamp) with
+// classifier-free guidance applied to the x0 prediction.  Layout as above; tab = (sqrt_recip_ac, sqrt_recipm1_ac, sqrt(ab_prev), sigma,
+// sqrt(1 - ab_prev - sigma^2), i != 0, 0, 0).  noise == nullptr reads as 0 (an eta = 0 table: sigma = 0); x0_out may be nullptr.
+// Every product, sum and quotient is rounded once, explicitly: the result does not depend on the compiler's contraction.
+__global__ void prior_ddim_step_kernel(const float* x, const float* model_out, const float* noise, const float* scales,
+                                       const float* tab, float clamp, float* x_out, float* x0_out, int bs, int D) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= 2 * bs * D) return;
+  const int d = i % D, n = i / D, j = n % bs;
+  const float c = model_out[(int64_t)j * D + d], u = model_out[(int64_t)(j + bs) * D + d];
+  float x0 = __fadd_rn(u, __fmul_rn(scales[j], __fsub_rn(c, u)));
+  x0 = fminf(fmaxf(x0, -clamp), clamp);
+  const float eps = __fdiv_rn(__fsub_rn(__fmul_rn(tab[0], x[i]), x0), tab[1]);
+  const float mean = __fadd_rn(__fmul_rn(tab[2], x0), __fmul_rn(tab[4], eps));
+  const float nz = noise ? noise[i] : 0.f;
+  x_out[i] = __fadd_rn(mean, __fmul_rn(tab[5], __fmul_rn(tab[3], nz)));
+  if (x0_out) x0_out[i] = x0;
+}
+
 // ---- launchers: the plan's ops and the single-kernel entry points (include/k22.h) go through the same code ------------------
 static int launch_prior_layernorm(const float* x, int64_t ldx, const float* g, const float* b, void* y, int rows, int D, bool to_f32, int dt,
                                   hipStream_t st) {
@@ -92,6 +111,12 @@ static int launch_prior_sampler_step(const float* x, const float* model_out, con
   K22_CHECK_LAUNCH();
   return K22_OK;
 }
+static int launch_prior_ddim_step(const float* x, const float* model_out, const float* noise, const float* scales, const float* tab, float clamp,
+                                  float* x_out, float* x0_out, int bs, int D, hipStream_t st) {
+  hipLaunchKernelGGL(prior_ddim_step_kernel, dim3((2 * bs * D + 255) / 256), dim3(256), 0, st, x, model_out, noise, scales, tab, clamp, x_out, x0_out, bs, D);
+  K22_CHECK_LAUNCH();
+  return K22_OK;
+}
 
 namespace {
 typedef std::function<int(hipStream_t)> POp;
@@ -109,6 +134,20 @@ struct K22Prior : GraphPlan {   // tuned: every transformer Linear; graph: the ~
   bool wfrag_done = false;
   struct WFrag { const void* src; Slot* dst; int Npad, K; };
   std::vector<WFrag> wfrags;   // fragment-major copies of the transformer weights, written into the workspace once per bind
+  // the ONE captured sampling loop of this handle (k22_prior_sample_loop), valid for loop_key: kind, n_steps, clamp and every pointer
+  GraphCache loop;
+  std::vector<unsigned long long> loop_key;
+
+  // fragment-major weight copies of the skinny path: once per binding, before the first launch list that reads them
+  int repack_once(hipStream_t st) {
+    if (!skinny || wfrag_done) return K22_OK;
+    for (auto& wf : wfrags) {
+      int rc = launch_stream_repack(wf.src, ptr(wf.dst), wf.Npad, 1, wf.K, dtype, st);
+      if (rc) return rc;
+    }
+    wfrag_done = true;
+    return K22_OK;
+  }
 
   int run_ops(hipStream_t st) const {
     for (auto& op : ops) { int rc = op(st); if (rc) return rc; }
@@ -171,7 +210,7 @@ struct K22Prior : GraphPlan {   // tuned: every transformer Linear; graph: the ~
     if (D % 64 || D / cfg.xf_heads != 64) return k22_set_error(K22_EINVAL, "prior: 64 channels per head");
     begin_plan();
     B = nB;
-    ops.clear(); wfrags.clear(); wfrag_done = false;
+    ops.clear(); wfrags.clear(); wfrag_done = false; loop.drop();
     s_x = new_slot((size_t)B * cd * 4); s_t = new_slot((size_t)B * 4 + 64);
     s_temb = new_slot((size_t)B * D * 4); s_te1 = new_slot((size_t)B * D * 4);
     s_txtemb = new_slot((size_t)B * cd * 4); s_txtenc = new_slot((size_t)B * nt * cw * 4); s_txtencT = new_slot((size_t)B * nt * cw * esz);
@@ -335,6 +374,7 @@ int k22_prior_bind(K22Prior* m, void* workspace, size_t workspace_bytes) {
   if (!m) return k22_set_error(K22_EINVAL, "prior_bind: null argument");
   if (int rc = m->bind(workspace, workspace_bytes, "prior_bind")) return rc;
   m->wfrag_done = false;
+  m->loop.drop();   // its nodes hold the old workspace's addresses
   return K22_OK;
 }
 int k22_prior_forward(K22Prior* m, const float* x, const float* timesteps, const float* text_emb, const float* text_enc,
@@ -348,13 +388,7 @@ int k22_prior_forward(K22Prior* m, const float* x, const float* timesteps, const
   if (int rc = copy_d2d(m->ptr(m->s_txtemb), text_emb, (size_t)m->B * c.clip_dim * 4, st)) return rc;
   if (int rc = copy_d2d(m->ptr(m->s_txtenc), text_enc, (size_t)m->B * c.text_ctx * c.clip_xf_width * 4, st)) return rc;
   if (int rc = copy_d2d(m->ptr(m->s_valid), key_valid, (size_t)m->B * c.text_ctx * 4, st)) return rc;
-  if (m->skinny && !m->wfrag_done) {
-    for (auto& wf : m->wfrags) {
-      int rc = launch_stream_repack(wf.src, m->ptr(wf.dst), wf.Npad, 1, wf.K, m->dtype, st);
-      if (rc) return rc;
-    }
-    m->wfrag_done = true;
-  }
+  if (int rc = m->repack_once(st)) return rc;
   if (int rc = m->tune_once(m->s_flush, st)) return rc;
   if (int rc = m->replay(m->graph, st, [m](hipStream_t s) { return m->run_ops(s); })) return rc;
   return copy_d2d(out, m->ptr(m->s_out), (size_t)m->B * c.clip_dim * 4, st);
@@ -364,6 +398,82 @@ int k22_prior_sampler_step(const float* x, const float* model_out, const float* 
                            float clamp, float* x_out, int bs, int D, void* stream) {
   if (!x || !model_out || !noise || !scales || !table_row || !x_out || bs < 1 || D < 1) return k22_set_error(K22_EINVAL, "prior_sampler_step: bad argument");
   return launch_prior_sampler_step(x, model_out, noise, scales, table_row, clamp, x_out, bs, D, reinterpret_cast<hipStream_t>(stream));
+}
+
+int k22_prior_ddim_step(const float* x, const float* model_out, const float* noise, const float* scales, const float* table_row, float clamp,
+                        float* x_out, float* x0_out, int bs, int D, void* stream) {
+  if (!x || !model_out || !scales || !table_row || !x_out || bs < 1 || D < 1) return k22_set_error(K22_EINVAL, "prior_ddim_step: bad argument");
+  return launch_prior_ddim_step(x, model_out, noise, scales, table_row, clamp, x_out, x0_out, bs, D, reinterpret_cast<hipStream_t>(stream));
+}
+
+// The whole sampling loop of PriorDiffusionModel.forward (prior.py:336-384 -> p_sample_loop / ddim_sample_loop) on this handle's plan: the
+// conditioning goes into the plan's slots once, then per step  [x_half | x_half] -> s_x, timesteps[k] -> s_t, the launch list, the step
+// kernel of `kind` from s_out into the other of x / x_tmp.  Eagerly, or as ONE captured graph (a single chain on the capture stream).
+int k22_prior_sample_loop(K22Prior* m, int kind, float* x, float* x_tmp, float* x0_out, const float* timesteps, const float* table,
+                          const float* noise_seq, const float* scales, const float* text_emb, const float* text_enc, const float* key_valid,
+                          float clamp, int n_steps, int use_graph, void* stream) {
+  // arguments first, the handle's state after them: a refused call names its own mistake, and leaves the handle and its captured loop alone
+  if (!m || !x || !x_tmp || !timesteps || !table || !scales || !text_emb || !text_enc || !key_valid) return k22_set_error(K22_EINVAL, "prior_sample_loop: null argument");
+  if (kind != K22_PRIOR_LOOP_ANCESTRAL && kind != K22_PRIOR_LOOP_DDIM)
+    return k22_set_error(K22_EINVAL, "prior_sample_loop: kind must be K22_PRIOR_LOOP_ANCESTRAL or K22_PRIOR_LOOP_DDIM");
+  if (n_steps < 1) return k22_set_error(K22_EINVAL, "prior_sample_loop: n_steps must be >= 1");
+  if (kind == K22_PRIOR_LOOP_ANCESTRAL && !noise_seq) return k22_set_error(K22_EINVAL, "prior_sample_loop: the ancestral loop needs noise_seq (NULL is the DDIM loop at eta = 0)");
+  if (!m->ws) return k22_set_error(K22_EINVAL, "prior_sample_loop: bind a workspace first");
+  if (m->B % 2) return k22_set_error(K22_EINVAL, "prior_sample_loop: the batch is the CFG batch [cond | uncond] (even)");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const K22PriorConfig& c = m->cfg;
+  const int B = m->B, bs = B / 2, D = c.clip_dim;
+  const size_t lat = (size_t)B * D, half = (size_t)bs * D * sizeof(float);
+  auto conditioning = [&](hipStream_t s) -> int {
+    if (int rc = copy_d2d(m->ptr(m->s_txtemb), text_emb, (size_t)B * D * 4, s)) return rc;
+    if (int rc = copy_d2d(m->ptr(m->s_txtenc), text_enc, (size_t)B * c.text_ctx * c.clip_xf_width * 4, s)) return rc;
+    return copy_d2d(m->ptr(m->s_valid), key_valid, (size_t)B * c.text_ctx * 4, s);
+  };
+  auto model_input = [&](const float* cur, int k, hipStream_t s) -> int {   // guided_model_fn: the transformer sees the first half twice
+    if (int rc = copy_d2d(m->ptr(m->s_x), cur, half, s)) return rc;
+    if (int rc = copy_d2d(m->ptr(m->s_x) + half, cur, half, s)) return rc;
+    return copy_d2d(m->ptr(m->s_t), timesteps + (size_t)k * B, (size_t)B * 4, s);
+  };
+  if (int rc = m->repack_once(st)) return rc;
+  if ((m->autotune && !m->tuned_done) || !m->warmed) {   // first use of this plan: measure, then one eager pass of the launch list (as k22_prior_forward)
+    if (int rc = conditioning(st)) return rc;
+    if (int rc = model_input(x, 0, st)) return rc;
+    if (int rc = m->tune_once(m->s_flush, st)) return rc;
+    if (!m->warmed) { if (int rc = m->run_eager(st, [m](hipStream_t s) { return m->run_ops(s); })) return rc; }
+  }
+  auto body = [&](hipStream_t s) -> int {
+    if (int rc = conditioning(s)) return rc;
+    float* cur = x; float* nxt = x_tmp;
+    for (int k = 0; k < n_steps; ++k) {
+      if (int rc = model_input(cur, k, s)) return rc;
+      if (int rc = m->run_ops(s)) return rc;
+      const float* out = m->ptr<float>(m->s_out);
+      const float* nz = noise_seq ? noise_seq + (size_t)k * lat : nullptr;
+      int rc;
+      if (kind == K22_PRIOR_LOOP_DDIM) rc = launch_prior_ddim_step(cur, out, nz, scales, table + (size_t)k * 8, clamp, nxt, x0_out, bs, D, s);
+      else rc = launch_prior_sampler_step(cur, out, nz, scales, table + (size_t)k * 4, clamp, nxt, bs, D, s);
+      if (rc) return rc;
+      float* t_ = cur; cur = nxt; nxt = t_;
+    }
+    if (cur != x) return copy_d2d(x, cur, lat * sizeof(float), s);
+    return K22_OK;
+  };
+  if (!use_graph) {
+    const int rc = body(st);
+    if (rc == K22_OK) loop_count_launch();
+    return rc;
+  }
+  const std::vector<unsigned long long> key = {(unsigned long long)kind, (unsigned long long)n_steps, loop_key_bits(clamp), loop_key_ptr(x), loop_key_ptr(x_tmp),
+      loop_key_ptr(x0_out), loop_key_ptr(timesteps), loop_key_ptr(table), loop_key_ptr(noise_seq), loop_key_ptr(scales), loop_key_ptr(text_emb),
+      loop_key_ptr(text_enc), loop_key_ptr(key_valid)};
+  if (!m->loop || key != m->loop_key) {
+    if (int rc = m->loop.capture(m->cap, body)) return rc;
+    m->loop_key = key;
+    loop_count_capture();
+  }
+  const int rc = m->loop.launch(st);
+  if (rc == K22_OK) loop_count_launch();
+  return rc;
 }
 
 // ---- single-kernel entry points for the parity tests (include/k22.h); no product code calls them -------------------------
