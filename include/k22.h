@@ -392,9 +392,10 @@ int k22_conv3x3_direct(const float* x, const float* w, const float* bias, float*
  * k22_finish_ln, by k22_skinny_gemm with epi = 1, or by k22_small_attention with out_frag = 1.  dtype: K22_BF16 / K22_F16.
  *   k22_skinny_gemm: epi 0 -> out[m*ldo + n] = act(A.W^T + bias) in T;  epi 1 -> the same values in the A-fragment order of a consumer
  *     whose K is this N;  epi 2 -> fp32 partial[z][m][n], z < splitk (no bias / activation);  (mt, nb) = m-atoms x n-atoms of 32 per
- *     workgroup, one of (6,1) (3,2) (3,1) (2,2) (2,1) (1,2); 0,0 = default.
+ *     workgroup, one of (6,1) (3,4) (3,2) (3,1) (2,2) (2,1) (1,2); 0,0 = default.  nb = 4 needs Npad % 128 == 0.
  *   k22_finish_ln: x[m][:] += bias + sum_z partial[z][m][:] (skipped when partial == NULL), then yfrag = LayerNorm(x[m][:]) * gain +
- *     beta in T, A-fragment order (skipped when gain == NULL).  N <= 2048.
+ *     beta in T, A-fragment order (skipped when gain == NULL).  N <= 2048, N % 8 == 0, and N % 64 == 0 where the LayerNorm output is
+ *     written; 1 <= splitk <= 8 with partials.
  *   k22_small_attention: qkv [B*T][3*H*64] = [Q | K | V] x [H][64] row-major T -> softmax(q.k / 8 + mask) v, T <= 128 tokens;
  *     mask = causal (key <= query) and key_valid [B][kv_n] (0 = padding key; keys >= kv_n are valid), as prior.py:262-263.
  *     qkv_partial != NULL: qkv is instead T(qkv_bias + sum_s qkv_partial[s][B*T][3*H*64]), s < nsplit <= 4 - the finish of a split-K

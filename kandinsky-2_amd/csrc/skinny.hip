@@ -352,8 +352,11 @@ int launch_skinny(const SkinnyParams& p, int dtype, int mt, int nb, hipStream_t 
 }
 
 int launch_finish_ln(const FinishLnParams& p, int dtype, hipStream_t st) {
-  if ((dtype != K22_BF16 && dtype != K22_F16) || p.N > 2048 || p.N % 8 || p.M < 1 || (p.ldx & 3) || p.splitk > 8 || (p.g != nullptr && (p.b == nullptr || p.yfrag == nullptr)))
-    return k22_set_error(K22_EINVAL, "finish_ln: unsupported problem (16-bit types, N <= 2048, N % 8 == 0)");
+  // partials with splitk < 1 would make the kernel's clamp (splitk - 1) read in front of the buffer; a fragment-major output whose N is
+  // no multiple of 64 ends past afrag_bytes(M, N) from the second m-atom on
+  if ((dtype != K22_BF16 && dtype != K22_F16) || p.N > 2048 || p.N % 8 || p.M < 1 || (p.ldx & 3) || p.splitk > 8 || (p.partial != nullptr && p.splitk < 1) ||
+      (p.g != nullptr && (p.b == nullptr || p.yfrag == nullptr || p.N % 64)))
+    return k22_set_error(K22_EINVAL, "finish_ln: unsupported problem (16-bit types, N <= 2048, N % 8 == 0, N % 64 == 0 with a LayerNorm output, 1 <= splitk <= 8 with partials)");
   if (dtype == K22_BF16) hipLaunchKernelGGL(finish_ln_kernel<bf16_t>, dim3(p.M), dim3(256), 0, st, p);
   else hipLaunchKernelGGL(finish_ln_kernel<f16_t>, dim3(p.M), dim3(256), 0, st, p);
   K22_CHECK_LAUNCH();

@@ -10,23 +10,12 @@ import torch
 
 import helpers as hp
 from kandinsky2_amd import _lib
+from skinny_ref import afrag_index, from_afrag   # noqa: F401  (the index helpers live with the float64 restatements)
 from test_kernels_gpu import rnd
 
 pytestmark = pytest.mark.gpu
 DT = [_lib.K22_BF16, _lib.K22_F16]
 TOL = {_lib.K22_BF16: 1.2e-2, _lib.K22_F16: 1.5e-3}
-
-
-def afrag_index(M, K, device="cpu"):
-    """flat element offset of (m, k) in the A-fragment tensor [K/64][MA][4][64][8] (skinny.hip: afrag_off)"""
-    MA = (M + 31) // 32
-    m = torch.arange(M, device=device)[:, None]
-    k = torch.arange(K, device=device)[None, :]
-    return ((((k >> 6) * MA + (m >> 5)) * 4 + ((k >> 4) & 3)) * 64 + (m & 31) + 32 * ((k >> 3) & 1)) * 8 + (k & 7)
-
-
-def from_afrag(buf, M, K):
-    return buf.reshape(-1)[afrag_index(M, K, buf.device).reshape(-1)].reshape(M, K)
 
 
 def pack_a(a):
