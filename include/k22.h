@@ -76,7 +76,7 @@ const char* k22_last_error(void);
  * "att_pipe" = -1 as K22_ATT_PIPE says (default), 0 / 1: the unmasked 16-bit attention through attention_kernel / attention_pipe_kernel. */
 int k22_set_option(const char* name, int value);
 /* Host counters for tests, since the library was loaded: "stream_launches" = launches of the weight-streaming kernel;
- * "loop_captures" = whole-loop graphs captured by any loop entry (k22_unet_sample_loop, k22_unet_ddim_loop, k22_prior_sample_loop); "loop_launches" = whole-loop
+ * "loop_captures" = whole-loop graphs captured by any loop entry (k22_unet_sample_loop[_keep], k22_unet_ddim_loop, k22_prior_sample_loop); "loop_launches" = whole-loop
  * replays or eager loop runs.  -1 for an unknown name. */
 long k22_debug_counter(const char* name);
 /* Fragment-major copy of a 16-bit weight matrix [Npad][taps * Kc] for the weight-streaming kernel (1 KB contiguous per MFMA B
@@ -183,6 +183,22 @@ int k22_unet_sample_loop(K22UNet* u, float* x, float* x_tmp, const float* timest
                          const float* mask, const float* inpaint_image, const float* inpaint_mask, const float* table,
                          const int* table_rows, int n_steps, float guidance, float clamp_lo, float clamp_hi, int pct_index,
                          double pct_gamma, void* scratch, int use_graph, void* stream);
+/* k22_unet_sample_loop with one more stage per step: the known region of the Kandinsky 2.2 inpainting pipeline (diffusers
+ * KandinskyV22InpaintPipeline loop, used by kandinsky2/kandinsky2_2_model.py:150-173) is re-imposed on the freshly written latent,
+ *   per step k:  UNet([x_half | x_half], timesteps[k]) -> k22_sampler_step -> k22_keep_region(sa, sb = keep_coef[k])
+ * as one chain on the capture stream.  keep_init [4][HW], keep_mask [HW] (image 0's, 1 = keep) and keep_noise [B / 2][4][HW] (each
+ * sample's own initial noise) are device buffers; keep_coef [n_steps][2] is a HOST array: row k = (sqrt(alphas_cumprod[t_{k+1}]),
+ * sqrt(1 - alphas_cumprod[t_{k+1}])), the last row (1, 0).  pct_index = -1 switches the percentile threshold off (DDPMScheduler does
+ * not threshold).  The engine's ONE cached loop serves this entry too: its key holds a kind of its own, the three keep pointers and the
+ * bits of every keep_coef value besides k22_unet_sample_loop's; use_graph = 0 issues the same launches eagerly; both count into
+ * k22_debug_counter("loop_captures" / "loop_launches").  With all four keep arguments NULL it IS k22_unet_sample_loop (same kind, same key).
+ * K22_EINVAL (with a k22_last_error text) for keep arguments given only in part, an odd B, missing 9-channel operands on the inpainting
+ * UNet, and whatever else k22_unet_sample_loop refuses; a refused call leaves the handle and its captured loop as they were. */
+int k22_unet_sample_loop_keep(K22UNet* u, float* x, float* x_tmp, const float* timesteps, const float* noise_seq, const float* init_img,
+                              const float* mask, const float* inpaint_image, const float* inpaint_mask, const float* table,
+                              const int* table_rows, int n_steps, float guidance, float clamp_lo, float clamp_hi, int pct_index,
+                              double pct_gamma, void* scratch, const float* keep_init, const float* keep_noise, const float* keep_mask,
+                              const float* keep_coef, int use_graph, void* stream);
 /* The whole classifier-free-guided DDIM or PLMS loop - generate_img's default sampler and its documented alternative - as ONE hipGraph
  * replay (kandinsky2/kandinsky2_1_model.py:222-233, the non-p_sampler model_fn, driving kandinsky2/model/samplers.py:206-331 for
  * kind = K22_LOOP_DDIM and samplers.py:475-637 for kind = K22_LOOP_PLMS): per step  UNet([x_half | x_half], t) -> k22_ddim_step or
@@ -598,6 +614,13 @@ int k22_movq_prepare(const float* z, const float* wpq, const float* bpq, float* 
 int k22_movq_enc_prepare(const float* image, void* xin, int B, int H, int W, int Cpad, int dtype, void* stream);
 int k22_movq_quant_conv(const float* h, const float* wq, const float* bq, float* out, int B, int HW, void* stream);
 int k22_to_uint8_nhwc(const float* x, unsigned char* y, int B, int C, int H, int W, void* stream);
+/* 2.2 inpainting loop (csrc/prestep.hip; tests/test_decoder22_loop_gpu.py, tests/decoder22_ref.py): the stage k22_unet_sample_loop_keep adds.
+ *   keep_region        out[n][c][p] = m[p] * (sa * init[c][p] + sb * noise0[n % (B / 2)][c][p]) + (1 - m[p]) * x[n][c][p] over the CFG batch
+ *                      x / out [B][4][HW] (out == x allowed); init [4][HW] and mask m [HW] of image 0 serve every row, noise0 [B / 2][4][HW]
+ *                      is each sample's own; every operation rounded once: |out - exact| <= 4 * 2^-24 * (|m| (|sa init| + |sb noise|) +
+ *                      |1 - m| |x|).  K22_EINVAL: a null argument, B odd or < 2, HW < 1. */
+int k22_keep_region(const float* x, const float* init, const float* noise0, const float* mask, float sa, float sb, float* out, int B, int HW,
+                    void* stream);
 /* Encoder towers.
  *   enc_layernorm      `rows` fp32 rows x + r * ldx of D <= 2048 values (K22_EINVAL above: 8 x 256 values per row) -> fp32 rows
  *                      out_f32 + r * ld_out (optional; may be x itself) and / or T rows out_t + r * D (optional)

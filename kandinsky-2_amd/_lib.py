@@ -106,6 +106,8 @@ SIGNATURES = {
     "k22_unet_set_hint": (_I, [_P, _P, _P]),
     "k22_unet_forward": (_I, [_P, _P, _P, _P, _P, _P, _I, _P]),
     "k22_unet_sample_loop": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(_I), _I, _F, _F, _F, _I, _D, _P, _I, _P]),
+    "k22_unet_sample_loop_keep": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(_I), _I, _F, _F, _F, _I, _D, _P, _P, _P, _P, C.POINTER(_F), _I,
+                                       _P]),
     "k22_unet_ddim_loop": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _F, _I, _P]),
     "k22_unet_num_ops": (_I, [_P]),
     "k22_unet_set_autotune": (_I, [_P, _I]),
@@ -187,6 +189,7 @@ SIGNATURES = {
     "k22_prior_layernorm": (_I, [_P, _L, _P, _P, _P, _I, _I, _I, _I, _P]),
     "k22_prior_finish_input": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "k22_attention_masked": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _P]),
+    "k22_keep_region": (_I, [_P, _P, _P, _P, _F, _F, _P, _I, _I, _P]),     # tests/test_decoder22_loop_gpu.py
     # GroupNorm, one kernel per entry (tests/test_gn_parity_gpu.py)
     "k22_gn_stats": (_I, [_P, _P, _I, _I, _I, _I, _P, C.POINTER(_I), _I, _P]),
     "k22_gn_coeff": (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _P, _P, _P, _L, _F, _P, _P]),

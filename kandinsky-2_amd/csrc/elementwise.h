@@ -130,6 +130,10 @@ int launch_sampler_step(const SamplerParams& p, hipStream_t s);
 int launch_plms_step(const float* x, const float* model_out, const float* h1, const float* h2, const float* h3, int order, const float* tab,
                      float guidance, int use_cfg, float* x_out, float* e_store, float* x0_out, int N, int HW, hipStream_t s);
 int launch_prepare_mask(const float* old_mask, float* out, int C, int H, int W, hipStream_t s);
+// prestep.hip: out[n] = mask * (sa * init + sb * noise0[n % (B / 2)]) + (1 - mask) * x[n] over the CFG batch x [B][4][HW]; init [4][HW] and
+// mask [HW] of image 0 serve every row, noise0 [B / 2][4][HW]; out == x allowed
+int launch_keep_region(const float* x, const float* init, const float* noise0, const float* mask, float sa, float sb, float* out, int B,
+                       int HW, hipStream_t s);
 int launch_ddim_step(const float* x, const float* model_out, const float* noise, const float* tab, float guidance, int use_cfg,
                      float* x_out, float* x0_out, int N, int HW, hipStream_t s);
 

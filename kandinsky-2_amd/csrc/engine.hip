@@ -38,7 +38,7 @@ long loop_launch_count() { return g_loop_launches.load(); }
 void loop_count_capture() { g_loop_captures.fetch_add(1); }
 void loop_count_launch() { g_loop_launches.fetch_add(1); }
 // first word of a captured loop's key: which entry's nodes the graph holds
-enum : unsigned long long { K22_LOOP_KIND_P = 0, K22_LOOP_KIND_DDIM = 1, K22_LOOP_KIND_PLMS = 2 };
+enum : unsigned long long { K22_LOOP_KIND_P = 0, K22_LOOP_KIND_DDIM = 1, K22_LOOP_KIND_PLMS = 2, K22_LOOP_KIND_P_KEEP = 3 };
 
 namespace {
 
@@ -839,6 +839,69 @@ struct K22UNet : GraphPlan {   // dtype: arithmetic type of the MFMA kernels (K2
   }
 };
 
+// The whole classifier-free-guided p_sampler loop of Kandinsky2_1.generate_img (kandinsky2_1_model.py:222-257 ->
+// gaussian_diffusion.py:384-475) as ONE hipGraph: for every step  UNet([x_half | x_half], t_k) -> k22_sampler_step  with no host work
+// between steps (the reference returns to Python - and to the CPU for np.percentile - at every step).  All inputs are device buffers
+// the caller fills BEFORE the call: timesteps [n_steps][B] (the values the UNet receives, in execution order), noise_seq
+// [n_steps][B][4][HW] (the ancestral noise of every step, drawn up front), table [T][8] + table_rows[k] (host array: the schedule row
+// of step k).  x [B][4][HW] is updated in place (x_tmp: scratch of the same size).  The captured graph is replayed as long as the
+// same buffers and scalars are passed (a generation service re-uses its buffers); anything else re-captures.
+// keep_* (all four or none): after every step the known region of the 2.2 inpainting pipeline is re-imposed on the freshly written latent
+// (launch_keep_region, prestep.hip) with keep_coef[k] = (sa, sb) of step k, a HOST array; none = the loop k22_unet_sample_loop has always run.
+static int unet_sample_loop_body(K22UNet* u, float* x, float* x_tmp, const float* timesteps, const float* noise_seq, const float* init_img,
+                                 const float* mask, const float* inpaint_image, const float* inpaint_mask, const float* table,
+                                 const int* table_rows, int n_steps, float guidance, float clamp_lo, float clamp_hi, int pct_index,
+                                 double pct_gamma, void* scratch, const float* keep_init, const float* keep_noise, const float* keep_mask,
+                                 const float* keep_coef, int use_graph, void* stream) {
+  if (!u || !u->ws) return k22_set_error(K22_EINVAL, "unet_sample_loop: bind a workspace first");
+  if (!u->cond_set) return k22_set_error(K22_EINVAL, "unet_sample_loop: call k22_unet_set_condition first");
+  if (!x || !x_tmp || !timesteps || !noise_seq || !table || !table_rows || !scratch || n_steps < 1)
+    return k22_set_error(K22_EINVAL, "unet_sample_loop: null argument");
+  if (u->B % 2) return k22_set_error(K22_EINVAL, "unet_sample_loop: the batch is the CFG batch [cond | uncond] (even)");
+  if (u->cfg.out_channels != 8) return k22_set_error(K22_EINVAL, "unet_sample_loop: the UNet must predict eps and variance (8 channels)");
+  if (u->cfg.in_channels == 9 && (!inpaint_image || !inpaint_mask)) return k22_set_error(K22_EINVAL, "unet_sample_loop: inpainting UNet needs inpaint_image and inpaint_mask");
+  if (u->cfg.hint_channels && !u->hint_set) return k22_set_error(K22_EINVAL, "unet_sample_loop: call k22_unet_set_hint first");
+  const int B = u->B, HW = u->H * u->W;
+  if (pct_index >= 4 * HW) return k22_set_error(K22_EINVAL, "unet_sample_loop: percentile index out of range");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  K22UNet::LoopRows lr;
+  if (int rc = u->loop_begin(n_steps, st, &lr)) return rc;
+  auto body = [&](hipStream_t s) -> int {
+    if (int rc = u->loop_prologue(lr, timesteps, n_steps, inpaint_image, inpaint_mask, s)) return rc;
+    float* cur = x; float* nxt = x_tmp;
+    for (int k = 0; k < n_steps; ++k) {
+      int rc = u->loop_model(lr, cur, timesteps, k, s);
+      if (rc) return rc;
+      SamplerParams p = {};
+      p.x = cur; p.model_out = u->model_out(); p.noise = noise_seq + (size_t)k * B * 4 * HW; p.init_img = init_img; p.mask = mask;
+      p.table = table; p.step = nullptr; p.step_host = table_rows[k]; p.guidance = guidance; p.clamp_lo = clamp_lo; p.clamp_hi = clamp_hi;
+      p.use_cfg = 1; p.n_lo = pct_index; p.gamma = pct_gamma;
+      p.s_buf = reinterpret_cast<float*>(scratch); p.x0_buf = reinterpret_cast<float*>(scratch) + 64;
+      p.x_out = nxt; p.x0_out = nullptr; p.N = B; p.HW = HW;
+      rc = launch_sampler_step(p, s);
+      if (rc) return rc;
+      if (keep_init) {
+        rc = launch_keep_region(nxt, keep_init, keep_noise, keep_mask, keep_coef[2 * k], keep_coef[2 * k + 1], nxt, B, HW, s);
+        if (rc) return rc;
+      }
+      float* t_ = cur; cur = nxt; nxt = t_;
+    }
+    if (cur != x) return copy_d2d(x, cur, (size_t)B * 4 * HW * sizeof(float), s);
+    return K22_OK;
+  };
+  std::vector<unsigned long long> key = {K22_LOOP_KIND_P, loop_key_ptr(x), loop_key_ptr(x_tmp), loop_key_ptr(timesteps), loop_key_ptr(noise_seq),
+      loop_key_ptr(init_img), loop_key_ptr(mask), loop_key_ptr(inpaint_image), loop_key_ptr(inpaint_mask), loop_key_ptr(table), loop_key_ptr(scratch),
+      (unsigned long long)n_steps, (unsigned long long)pct_index, (unsigned long long)(lr.hoist ? 1 : 0),
+      loop_key_bits(guidance), loop_key_bits(clamp_lo), loop_key_bits(clamp_hi), loop_key_bits(pct_gamma)};
+  for (int k = 0; k < n_steps; ++k) key.push_back((unsigned long long)table_rows[k]);
+  if (keep_init) {   // a kind of its own, the three device operands and the bits of every coefficient baked into the keep-region nodes
+    key[0] = K22_LOOP_KIND_P_KEEP;
+    key.push_back(loop_key_ptr(keep_init)); key.push_back(loop_key_ptr(keep_noise)); key.push_back(loop_key_ptr(keep_mask));
+    for (int k = 0; k < 2 * n_steps; ++k) key.push_back(loop_key_bits(keep_coef[k]));
+  }
+  return u->loop_run(key, timesteps, inpaint_image, inpaint_mask, use_graph, st, body);
+}
+
 // ---------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------
@@ -939,55 +1002,28 @@ int k22_unet_forward(K22UNet* u, const float* x, const float* timesteps, const f
   return copy_d2d(out, u->ptr(u->s_out), pb * u->cfg.out_channels * hw * 4, st);
 }
 
-// The whole classifier-free-guided p_sampler loop of Kandinsky2_1.generate_img (kandinsky2_1_model.py:222-257 ->
-// gaussian_diffusion.py:384-475) as ONE hipGraph: for every step  UNet([x_half | x_half], t_k) -> k22_sampler_step  with no host work
-// between steps (the reference returns to Python - and to the CPU for np.percentile - at every step).  All inputs are device buffers
-// the caller fills BEFORE the call: timesteps [n_steps][B] (the values the UNet receives, in execution order), noise_seq
-// [n_steps][B][4][HW] (the ancestral noise of every step, drawn up front), table [T][8] + table_rows[k] (host array: the schedule row
-// of step k).  x [B][4][HW] is updated in place (x_tmp: scratch of the same size).  The captured graph is replayed as long as the
-// same buffers and scalars are passed (a generation service re-uses its buffers); anything else re-captures.
 int k22_unet_sample_loop(K22UNet* u, float* x, float* x_tmp, const float* timesteps, const float* noise_seq, const float* init_img,
                          const float* mask, const float* inpaint_image, const float* inpaint_mask, const float* table,
                          const int* table_rows, int n_steps, float guidance, float clamp_lo, float clamp_hi, int pct_index,
                          double pct_gamma, void* scratch, int use_graph, void* stream) {
-  if (!u || !u->ws) return k22_set_error(K22_EINVAL, "unet_sample_loop: bind a workspace first");
-  if (!u->cond_set) return k22_set_error(K22_EINVAL, "unet_sample_loop: call k22_unet_set_condition first");
-  if (!x || !x_tmp || !timesteps || !noise_seq || !table || !table_rows || !scratch || n_steps < 1)
-    return k22_set_error(K22_EINVAL, "unet_sample_loop: null argument");
-  if (u->B % 2) return k22_set_error(K22_EINVAL, "unet_sample_loop: the batch is the CFG batch [cond | uncond] (even)");
-  if (u->cfg.out_channels != 8) return k22_set_error(K22_EINVAL, "unet_sample_loop: the UNet must predict eps and variance (8 channels)");
-  if (u->cfg.in_channels == 9 && (!inpaint_image || !inpaint_mask)) return k22_set_error(K22_EINVAL, "unet_sample_loop: inpainting UNet needs inpaint_image and inpaint_mask");
-  if (u->cfg.hint_channels && !u->hint_set) return k22_set_error(K22_EINVAL, "unet_sample_loop: call k22_unet_set_hint first");
-  const int B = u->B, HW = u->H * u->W;
-  if (pct_index >= 4 * HW) return k22_set_error(K22_EINVAL, "unet_sample_loop: percentile index out of range");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  K22UNet::LoopRows lr;
-  if (int rc = u->loop_begin(n_steps, st, &lr)) return rc;
-  auto body = [&](hipStream_t s) -> int {
-    if (int rc = u->loop_prologue(lr, timesteps, n_steps, inpaint_image, inpaint_mask, s)) return rc;
-    float* cur = x; float* nxt = x_tmp;
-    for (int k = 0; k < n_steps; ++k) {
-      int rc = u->loop_model(lr, cur, timesteps, k, s);
-      if (rc) return rc;
-      SamplerParams p = {};
-      p.x = cur; p.model_out = u->model_out(); p.noise = noise_seq + (size_t)k * B * 4 * HW; p.init_img = init_img; p.mask = mask;
-      p.table = table; p.step = nullptr; p.step_host = table_rows[k]; p.guidance = guidance; p.clamp_lo = clamp_lo; p.clamp_hi = clamp_hi;
-      p.use_cfg = 1; p.n_lo = pct_index; p.gamma = pct_gamma;
-      p.s_buf = reinterpret_cast<float*>(scratch); p.x0_buf = reinterpret_cast<float*>(scratch) + 64;
-      p.x_out = nxt; p.x0_out = nullptr; p.N = B; p.HW = HW;
-      rc = launch_sampler_step(p, s);
-      if (rc) return rc;
-      float* t_ = cur; cur = nxt; nxt = t_;
-    }
-    if (cur != x) return copy_d2d(x, cur, (size_t)B * 4 * HW * sizeof(float), s);
-    return K22_OK;
-  };
-  std::vector<unsigned long long> key = {K22_LOOP_KIND_P, loop_key_ptr(x), loop_key_ptr(x_tmp), loop_key_ptr(timesteps), loop_key_ptr(noise_seq),
-      loop_key_ptr(init_img), loop_key_ptr(mask), loop_key_ptr(inpaint_image), loop_key_ptr(inpaint_mask), loop_key_ptr(table), loop_key_ptr(scratch),
-      (unsigned long long)n_steps, (unsigned long long)pct_index, (unsigned long long)(lr.hoist ? 1 : 0),
-      loop_key_bits(guidance), loop_key_bits(clamp_lo), loop_key_bits(clamp_hi), loop_key_bits(pct_gamma)};
-  for (int k = 0; k < n_steps; ++k) key.push_back((unsigned long long)table_rows[k]);
-  return u->loop_run(key, timesteps, inpaint_image, inpaint_mask, use_graph, st, body);
+  return unet_sample_loop_body(u, x, x_tmp, timesteps, noise_seq, init_img, mask, inpaint_image, inpaint_mask, table, table_rows, n_steps,
+                               guidance, clamp_lo, clamp_hi, pct_index, pct_gamma, scratch, nullptr, nullptr, nullptr, nullptr, use_graph, stream);
+}
+
+// k22_unet_sample_loop with the known region of the Kandinsky 2.2 inpainting pipeline re-imposed after every step (diffusers
+// KandinskyV22InpaintPipeline loop, driven by kandinsky2_2_model.py:150-173): per step  UNet -> k22_sampler_step -> k22_keep_region on the
+// freshly written latent, one chain on the capture stream.  All four keep arguments NULL: k22_unet_sample_loop itself.
+int k22_unet_sample_loop_keep(K22UNet* u, float* x, float* x_tmp, const float* timesteps, const float* noise_seq, const float* init_img,
+                              const float* mask, const float* inpaint_image, const float* inpaint_mask, const float* table,
+                              const int* table_rows, int n_steps, float guidance, float clamp_lo, float clamp_hi, int pct_index,
+                              double pct_gamma, void* scratch, const float* keep_init, const float* keep_noise, const float* keep_mask,
+                              const float* keep_coef, int use_graph, void* stream) {
+  const int n_keep = (keep_init != nullptr) + (keep_noise != nullptr) + (keep_mask != nullptr) + (keep_coef != nullptr);
+  if (n_keep != 0 && n_keep != 4)
+    return k22_set_error(K22_EINVAL, "unet_sample_loop_keep: keep_init, keep_noise, keep_mask and keep_coef go together (all four or none)");
+  return unet_sample_loop_body(u, x, x_tmp, timesteps, noise_seq, init_img, mask, inpaint_image, inpaint_mask, table, table_rows, n_steps,
+                               guidance, clamp_lo, clamp_hi, pct_index, pct_gamma, scratch, keep_init, keep_noise, keep_mask, keep_coef, use_graph,
+                               stream);
 }
 
 // The whole classifier-free-guided DDIM or PLMS loop of Kandinsky2_1.generate_img (kandinsky2_1_model.py:222-233 -> samplers.py:206-331,

@@ -16,7 +16,7 @@ from typing import Optional
 
 import torch
 
-from . import _lib, prestep
+from . import _lib, prestep, sampling
 from .movq import MoVQDecoderHIP, MoVQEncoderHIP
 from .pipeline import prepare_image, process_images
 from .unet22 import SCHEDULER_CONFIG_2_2, DDPMSchedulerHIP, UNet2DConditionHIP, make_arch22
@@ -50,16 +50,46 @@ def _downscale(height, width, f=8):
     return (height // f ** 2 + (1 if height % f ** 2 else 0)) * f, (width // f ** 2 + (1 if width % f ** 2 else 0)) * f
 
 
+MAX_LOOP_GRAPH_STEPS = 100     # the largest default step count of either pipeline; a captured loop of a few hundred steps crashed the runtime
+
+
+class KnownRegion:
+    """after_step of the inpainting decoder: the known region re-imposed at the NEXT timestep's noise level, un-noised after the last
+    step.  Called (the stepwise route) it launches k22_blend_noised once per sample; the one-graph route reads its operands and runs
+    k22_keep_region over the whole CFG batch inside the captured loop instead."""
+
+    def __init__(self, lat0, noise0, mask, scheduler, timesteps):
+        self.lat0, self.noise0, self.mask, self.ac, self.ts = lat0, noise0, mask, scheduler.alphas_cumprod, list(timesteps)
+
+    def __call__(self, k, cur):
+        L, bs, hw = _lib.lib(), cur.shape[0], cur.shape[2] * cur.shape[3]
+        out = torch.empty_like(cur)
+        a = float(self.ac[self.ts[k + 1]]) if k + 1 < len(self.ts) else 1.0
+        # image 0's latents / mask serve the whole batch; the noise is each sample's own initial noise
+        for j in range(bs):
+            _lib.check(L.k22_blend_noised(cur[j].contiguous().data_ptr(), self.lat0.data_ptr(), self.noise0[j].contiguous().data_ptr(),
+                                          self.mask.data_ptr(), a ** 0.5, (1.0 - a) ** 0.5, out[j].data_ptr(), 1, 4, hw, 0, _lib.current_stream()))
+        return out
+
+
 class KandinskyV22DecoderHIP:
     """The decoder call of the reference (kandinsky2_2_model.py:77-80; ControlNet: notebooks/kandinsky2_2_controlnet.ipynb:9235):
         decoder(image_embeds=, negative_image_embeds=, num_inference_steps=, height=, width=, guidance_scale= [, hint=]).images
     One step = UNet on the CFG batch + k22_sampler_step (guidance, learned-range variance, clip +-2, ancestral noise), fused.
     The CFG batch is laid out [cond | uncond] inside (the engine's sampler step expects that order; batch elements are independent,
-    so the order is an internal convention: diffusers uses [uncond | cond])."""
+    so the order is an internal convention: diffusers uses [uncond | cond]).
+    whole_loop_graph (None = follow unet.use_graph): the denoising loop of 1 .. MAX_LOOP_GRAPH_STEPS steps as ONE captured graph
+    (UNet2DConditionHIP.sample_loop -> k22_unet_sample_loop_keep) instead of one UNet replay and one scheduler step per step driven from
+    Python.  Same kernels on the same operands: text2img, ControlNet-depth and img2img give the stepwise route's bits, also with
+    generator-drawn noise (sampling.ddpm_step_noise makes the stepwise loop's draws).  Inpainting re-imposes the known region with
+    k22_keep_region in place of the per-sample k22_blend_noised launches: equal to rounding, not bit for bit.  Longer loops and loops with
+    an arbitrary after_step callback stay stepwise."""
 
-    def __init__(self, unet: UNet2DConditionHIP, movq: MoVQDecoderHIP, scheduler: Optional[DDPMSchedulerHIP] = None, movq_scale_factor: int = 8):
+    def __init__(self, unet: UNet2DConditionHIP, movq: MoVQDecoderHIP, scheduler: Optional[DDPMSchedulerHIP] = None, movq_scale_factor: int = 8,
+                 whole_loop_graph: Optional[bool] = None):
         self.unet, self.movq, self.scheduler = unet, movq, scheduler or DDPMSchedulerHIP.from_config(SCHEDULER_CONFIG_2_2)
         self.movq_scale_factor = movq_scale_factor
+        self.whole_loop_graph = whole_loop_graph
 
     def _check(self, image_embeds):
         if image_embeds.device.type != "cuda":
@@ -67,11 +97,32 @@ class KandinskyV22DecoderHIP:
         if 2 * image_embeds.shape[0] > 8:
             raise ValueError("at most 4 images per call (CFG batch <= 8); shard larger batches over calls / ranks")
 
+    def _one_graph(self, n_steps, after_step) -> bool:
+        on = bool(getattr(self.unet, "use_graph", False)) if self.whole_loop_graph is None else bool(self.whole_loop_graph)
+        return on and 1 <= n_steps <= MAX_LOOP_GRAPH_STEPS and (after_step is None or isinstance(after_step, KnownRegion))
+
     def _denoise(self, x, emb, timesteps, guidance_scale, noise_seq, generator, hint2=None, extra=None, after_step=None):
         """x [bs,4,h,w]; emb [2bs,D] = [cond | uncond]; extra [2bs,5,h,w]: channels appended to every UNet input (inpainting);
-        after_step(k, latents [bs,4,h,w]) -> latents"""
+        after_step(k, latents [bs,4,h,w]) -> latents: a KnownRegion or none goes with the one-graph route, any other callable is
+        called step by step"""
         bs = x.shape[0]
         x = torch.cat([x, x], 0).contiguous()
+        if self._one_graph(len(timesteps), after_step):
+            n, dev = len(timesteps), x.device
+            ts_rows, rows, coef = sampling.ddpm_loop_operands(self.scheduler, timesteps, 2 * bs, keep=after_step is not None)
+            if noise_seq is not None:
+                ns = (noise_seq[:n] if torch.is_tensor(noise_seq) else torch.stack([noise_seq[k] for k in range(n)])).to(dev).float()
+                nzs = torch.cat([ns, ns], 1)
+            else:
+                nzs = sampling.ddpm_step_noise(n, x.shape, generator, dev)
+            clip = min(self.scheduler.clip, 3.0e38)
+            keep = None if after_step is None else (after_step.lat0, after_step.noise0, after_step.mask, coef)
+            with self.unet.fixed_conditioning():
+                x = self.unet.sample_loop(x, ts_rows, nzs, self.scheduler._table, rows, guidance_scale, (-clip, clip), image_embeds=emb, hint=hint2,
+                                          inpaint_image=None if extra is None else extra[:, :4], inpaint_mask=None if extra is None else extra[:, 4:5],
+                                          keep=keep)
+            self.last_latent = x[:bs]
+            return self.last_latent
         ack = {"image_embeds": emb} if hint2 is None else {"image_embeds": emb, "hint": hint2}
         with self.unet.fixed_conditioning():          # emb / hint2 are this call's own and do not change during the loop
             for k, t in enumerate(timesteps):
@@ -116,8 +167,9 @@ class KandinskyV22Img2ImgDecoderHIP(KandinskyV22DecoderHIP):
     movq.encode(image) -> add_noise at the first retained timestep -> the text2img loop over timesteps[t_start:]
     (get_timesteps: t_start = steps - min(int(steps * strength), steps)).  PARITY UNPINNED (diffusers, recalled)."""
 
-    def __init__(self, unet, movq, movq_encoder: MoVQEncoderHIP, scheduler=None, movq_scale_factor: int = 8):
-        super().__init__(unet, movq, scheduler, movq_scale_factor)
+    def __init__(self, unet, movq, movq_encoder: MoVQEncoderHIP, scheduler=None, movq_scale_factor: int = 8,
+                 whole_loop_graph: Optional[bool] = None):
+        super().__init__(unet, movq, scheduler, movq_scale_factor, whole_loop_graph)
         self.movq_encoder = movq_encoder
 
     def get_timesteps(self, num_inference_steps, strength, device="cuda"):
@@ -160,7 +212,9 @@ class KandinskyV22InpaintDecoderHIP(KandinskyV22Img2ImgDecoderHIP):
     timestep's noise level, x = mask * add_noise(image_latents, initial_noise, t_next) + (1 - mask) * x, and un-noised after the last.
     mask_image: [H, W] / [1,1,H,W] array or tensor, 1 = keep, 0 = repaint - the convention of the reference's 2.1 `img_mask` and of the
     diffusers commit the reference's notebooks install (before diffusers 0.19 inverted it); pass repaint_white=True for the later
-    convention.  The latent-resolution mask goes through the same 1-pixel erosion as 2.1 (prepare_mask).  PARITY UNPINNED."""
+    convention.  The latent-resolution mask goes through the same 1-pixel erosion as 2.1 (prepare_mask).  PARITY UNPINNED.
+    The one-graph route (whole_loop_graph) re-imposes with k22_keep_region, every operation rounded once, the stepwise route with
+    k22_blend_noised, whose multiply-adds the compiler may contract: the two routes agree to rounding, not bit for bit."""
 
     @torch.no_grad()
     def __call__(self, image_embeds, negative_image_embeds, image, mask_image, height=512, width=512, num_inference_steps=100,
@@ -185,17 +239,7 @@ class KandinskyV22InpaintDecoderHIP(KandinskyV22Img2ImgDecoderHIP):
         noise0 = x.clone()
         self.scheduler.set_timesteps(num_inference_steps, device=dev)
         ts = self.scheduler.timesteps.tolist()
-        ac, L = self.scheduler.alphas_cumprod, _lib.lib()
-
-        def reimpose(k, cur):
-            out = torch.empty_like(cur)
-            a = float(ac[ts[k + 1]]) if k + 1 < len(ts) else 1.0
-            # image 0's latents / mask serve the whole batch; the noise is each sample's own initial noise
-            for j in range(bs):
-                _lib.check(L.k22_blend_noised(cur[j].contiguous().data_ptr(), lat0.data_ptr(), noise0[j].contiguous().data_ptr(), m.data_ptr(),
-                                              a ** 0.5, (1.0 - a) ** 0.5, out[j].data_ptr(), 1, 4, h * w, 0, _lib.current_stream()))
-            return out
-
+        reimpose = KnownRegion(lat0, noise0, m, self.scheduler, ts)
         x = self._denoise(x, emb, ts, guidance_scale, noise_seq, generator, extra=extra, after_step=reimpose)
         return self._images(x, height, width, output_type)
 
@@ -215,11 +259,12 @@ def _load_weights(folder):
     return sd, (json.load(open(cfg)) if os.path.exists(cfg) else None)
 
 
-def load_decoder22_from_cache_dir(cache_dir, task_type="text2img", controlnet=False):
+def load_decoder22_from_cache_dir(cache_dir, task_type="text2img", controlnet=False, whole_loop_graph: Optional[bool] = None):
     """What `from_pretrained('kandinsky-community/kandinsky-2-2-<repo>', subfolder='unet' | 'movq' | 'scheduler')` reads
     (kandinsky2_2_model.py:26-41), from a local copy `cache_dir/<repo>/{unet,movq,scheduler}/`: the UNet and MoVQ state dicts plus
     unet/config.json and scheduler/scheduler_config.json, which DRIVE the architecture and the scheduler (make_arch22,
-    DDPMSchedulerHIP.from_config) - nothing about the checkpoint is assumed.  Raises when a folder is missing (no download path)."""
+    DDPMSchedulerHIP.from_config) - nothing about the checkpoint is assumed.  Raises when a folder is missing (no download path).
+    whole_loop_graph is handed through under its own key: the decoders' route switch (KandinskyV22DecoderHIP), not read from any file."""
     import json
     repo = "kandinsky-2-2-controlnet-depth" if controlnet else ("kandinsky-2-2-decoder-inpaint" if task_type == "inpainting" else "kandinsky-2-2-decoder")
     root = os.path.join(cache_dir, repo)
@@ -228,7 +273,8 @@ def load_decoder22_from_cache_dir(cache_dir, task_type="text2img", controlnet=Fa
     unet_sd, unet_cfg = _load_weights(os.path.join(root, "unet"))
     movq_sd, _ = _load_weights(os.path.join(root, "movq"))
     sc = os.path.join(root, "scheduler", "scheduler_config.json")
-    return {"unet": unet_sd, "unet_config": unet_cfg, "movq": movq_sd, "scheduler_config": json.load(open(sc)) if os.path.exists(sc) else None}
+    return {"unet": unet_sd, "unet_config": unet_cfg, "movq": movq_sd, "scheduler_config": json.load(open(sc)) if os.path.exists(sc) else None,
+            "whole_loop_graph": whole_loop_graph}
 
 
 class Kandinsky2_2HIP:
@@ -237,12 +283,13 @@ class Kandinsky2_2HIP:
 
     def __init__(self, device="cuda", task_type="text2img", *, unet_state_dict=None, movq_state_dict=None, conditioner=None,
                  cache_dir=None, backend_dtype: torch.dtype = torch.bfloat16, use_graph: bool = True, unet_config=None, controlnet=None,
-                 scheduler_config=None, movq_dtype: Optional[torch.dtype] = None):
+                 scheduler_config=None, movq_dtype: Optional[torch.dtype] = None, whole_loop_graph: Optional[bool] = None):
         if task_type not in ("text2img", "img2img", "inpainting"):
             raise ValueError("Only text2img, img2img, inpainting is available")
         if (unet_state_dict is None or movq_state_dict is None) and cache_dir is not None:
             # the files from_pretrained('kandinsky-community/kandinsky-2-2-decoder[-inpaint]', subfolder=...) caches (kandinsky2_2_model.py:26-41)
-            loaded = load_decoder22_from_cache_dir(cache_dir, task_type, bool(controlnet))
+            loaded = load_decoder22_from_cache_dir(cache_dir, task_type, bool(controlnet), whole_loop_graph)
+            whole_loop_graph = loaded["whole_loop_graph"]
             unet_state_dict = unet_state_dict if unet_state_dict is not None else loaded["unet"]
             movq_state_dict = movq_state_dict if movq_state_dict is not None else loaded["movq"]
             unet_config = unet_config if unet_config is not None else loaded["unet_config"]
@@ -277,12 +324,12 @@ class Kandinsky2_2HIP:
         movq.load_state_dict(movq_state_dict, strict=True)          # decoder keys; a full MOVQ checkpoint's other keys are skipped
         movq = movq.to(device)
         if task_type == "text2img":
-            self.decoder = KandinskyV22DecoderHIP(self.unet, movq, scheduler())
+            self.decoder = KandinskyV22DecoderHIP(self.unet, movq, scheduler(), whole_loop_graph=whole_loop_graph)
         else:
             enc = MoVQEncoderHIP(backend_dtype=mdt)
             enc.load_state_dict(movq_state_dict, strict=True)
             cls = KandinskyV22Img2ImgDecoderHIP if task_type == "img2img" else KandinskyV22InpaintDecoderHIP
-            self.decoder = cls(self.unet, movq, enc.to(device), scheduler())
+            self.decoder = cls(self.unet, movq, enc.to(device), scheduler(), whole_loop_graph=whole_loop_graph)
 
     def get_new_h_w(self, h, w):
         return (h // 64 + (1 if h % 64 else 0)) * 64, (w // 64 + (1 if w % 64 else 0)) * 64

@@ -6,6 +6,7 @@ and a step launcher, to which it hands its keywords (guidance, clamp, ...) throu
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -31,6 +32,45 @@ def step_noise(x: torch.Tensor, n: int, noise_seq=None) -> torch.Tensor:
     for k in range(n):
         nzs[k] = torch.randn_like(x)
     return nzs
+
+
+def ddpm_loop_operands(scheduler, timesteps, B: int, keep: bool = False):
+    """Host side of the one-graph 2.2 decoder loop (UNet2DConditionHIP.sample_loop): a DDPMSchedulerHIP after set_timesteps and the
+    retained timesteps in execution order (all of scheduler.timesteps, or img2img's tail) -> (ts_rows [n, B] fp32: the value every row
+    of the UNet receives at step k, as the stepwise loop's `unet(inp, t)`; table_rows: the row of scheduler's step table of every step,
+    as `scheduler.step(out, t, ...)` looks it up; keep_coef).  keep_coef (keep=True, the inpainting re-imposition; else None) is
+    [n, 2] fp32: row k = (sqrt(ac[ts[k + 1]]), sqrt(1 - ac[ts[k + 1]])), the last row (1, 0) - computed in float64 and rounded to fp32 the
+    way the stepwise route's `a ** 0.5` is when it crosses the C ABI as a float.  No GPU is touched."""
+    ts = [int(t) for t in timesteps]
+    n = len(ts)
+    ts_rows = torch.tensor(ts, dtype=torch.float32).reshape(n, 1).expand(n, B).contiguous()
+    rows = [scheduler._row[t] for t in ts]
+    coef = None
+    if keep:
+        ac = scheduler.alphas_cumprod
+        coef = np.zeros((n, 2), dtype=np.float32)
+        for k in range(n):
+            a = float(ac[ts[k + 1]]) if k + 1 < n else 1.0
+            coef[k] = (a ** 0.5, (1.0 - a) ** 0.5)
+    return ts_rows, rows, coef
+
+
+def ddpm_step_noise(n_steps: int, shape, generator=None, device="cuda") -> torch.Tensor:
+    """[n_steps, *shape]: the ancestral noise of a whole DDPM loop by the very draws DDPMSchedulerHIP.step makes when it is given no
+    noise - one torch.randn(shape) per step, in step order (the caller has drawn the initial latent before); a CPU generator draws on
+    the CPU and the noise moves over (diffusers' randn_tensor).  shape is the sample the scheduler steps: the CFG batch [2 bs, 4, h, w].
+    So a seed gives the same image whether the loop is driven step by step or replayed as one graph."""
+    gdev = generator.device if generator is not None else device
+    out = torch.empty((n_steps,) + tuple(shape), dtype=torch.float32, device=device)
+    for k in range(n_steps):
+        out[k] = torch.randn(tuple(shape), generator=generator, device=gdev).to(device)
+    return out
+
+
+def keep_region(x, init, noise0, mask, sa, sb, out):
+    """One k22_keep_region launch over the CFG batch x [B,4,h,w] (out may be x)."""
+    _lib.check(_lib.lib().k22_keep_region(x.data_ptr(), init.data_ptr(), noise0.data_ptr(), mask.data_ptr(), float(sa), float(sb), out.data_ptr(),
+                                          x.shape[0], x.shape[2] * x.shape[3], _lib.current_stream()))
 
 
 def plms_calls(steps: list) -> list:

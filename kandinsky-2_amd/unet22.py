@@ -24,6 +24,7 @@ So the engine runs the same kernels; this file maps the diffusers state_dict key
 from __future__ import annotations
 
 import contextlib
+import ctypes as C
 import math
 from collections import OrderedDict
 from types import SimpleNamespace
@@ -302,6 +303,10 @@ class UNet2DConditionHIP(Text2ImUNetHIP):
         super().del_cache()
         self._cond_emb = self._cond_hint = None
 
+    def _release(self):
+        super()._release()
+        self._loop22_bufs = sampling.OwnedBuffers()      # operand buffers of sample_loop: the engine's captured loop holds their addresses
+
     @contextlib.contextmanager
     def fixed_conditioning(self):
         """Inside the block the conditioning the first forward computes is reused without comparing its inputs again: for callers that
@@ -346,6 +351,82 @@ class UNet2DConditionHIP(Text2ImUNetHIP):
             raise ValueError("this UNet has no hint input (build it with make_arch22(controlnet=True))")
         return self
 
+    def _ensure_condition22(self, emb, hint):
+        if self._cond_key is None or not (self._cond_fixed or self._same_condition(emb, hint)):
+            if emb is None:
+                raise ValueError("added_cond_kwargs['image_embeds'] is required")
+            self.set_condition(emb, hint)
+            self._cond_key = True
+            if not self._cond_fixed:
+                self._cond_emb = emb.detach().float().clone()
+                self._cond_hint = None if hint is None else hint.detach().float().clone()
+            self.cache = {"cached": True}
+
+    @torch.no_grad()
+    def sample_loop(self, x, ts_rows, noise_seq, table, table_rows, guidance_scale, clamp, *, image_embeds=None, hint=None,
+                    inpaint_image=None, inpaint_mask=None, keep=None):
+        """The whole guided DDPM loop of the 2.2 decoders as ONE hipGraph replay (k22_unet_sample_loop_keep, percentile threshold off);
+        returns the final latent [B,4,h,w].  x [B,4,h,w] = the CFG batch [x_T | x_T]; ts_rows [n, B], table_rows and keep's coefficients:
+        sampling.ddpm_loop_operands; noise_seq [n, B,4,h,w]; table: the scheduler's [T,8] step table; image_embeds [B,D] = [cond | uncond]
+        (hint [B,3,8h,8w] for the ControlNet-depth UNet) as forward's added_cond_kwargs; inpaint_image [.,4,h,w] (the already masked image
+        latents) / inpaint_mask [.,1,h,w]: channels 4-8 of the 9-channel UNet's input.  keep=(init [1,4,h,w], noise0 [B/2,4,h,w], mask
+        [1,1,h,w], coef [n,2] host array): the known region re-imposed after every step by k22_keep_region, which rounds every operation
+        once - equal to the stepwise route's k22_blend_noised launches to rounding, not bit for bit; without keep the loop equals the
+        stepwise calls bit for bit.  The operands are copied into buffers this module OWNS, so a second generation of the same shape and
+        step count replays the capture.  Two chains: the host-driven loop, as Text2ImUNetHIP.sample_loop."""
+        B, Cx, H, W = x.shape
+        if Cx != 4 or x.device.type != "cuda" or B % 2:
+            raise ValueError("sample_loop: x must be the CFG batch [2 bs,4,h,w] on the GPU")
+        n_steps, a, bs = len(table_rows), self.arch, B // 2
+        if n_steps < 1 or tuple(ts_rows.shape) != (n_steps, B) or tuple(noise_seq.shape) != (n_steps, B, 4, H, W):
+            raise ValueError("sample_loop: ts_rows must be [n_steps, B] and noise_seq [n_steps, B, 4, h, w], n_steps >= 1")
+        if a.inpainting != (inpaint_image is not None) or a.inpainting != (inpaint_mask is not None):
+            raise ValueError("sample_loop: inpaint_image / inpaint_mask go with the 9-channel UNet, and only with it")
+        self._ensure_plan(B, H, W)
+        self._ensure_condition22(image_embeds, hint)
+        img = None if inpaint_image is None else inpaint_image.detach().float().expand(B, 4, H, W)
+        msk = None if inpaint_mask is None else inpaint_mask.detach().float().expand(B, 1, H, W)
+        k_init = k_noise = k_mask = coef = None
+        if keep is not None:
+            k_init, k_noise, k_mask, coef = keep
+            coef = np.ascontiguousarray(coef, dtype=np.float32)
+            if k_init.numel() != 4 * H * W or tuple(k_noise.shape) != (bs, 4, H, W) or k_mask.numel() != H * W or coef.shape != (n_steps, 2):
+                raise ValueError("sample_loop: keep = (init [1,4,h,w], noise0 [bs,4,h,w], mask [1,1,h,w], coef [n_steps,2])")
+            k_init, k_mask = k_init.reshape(4, H, W), k_mask.reshape(H, W)
+        dev, g, rows, clip = x.device, float(guidance_scale), [int(r) for r in table_rows], (float(clamp[0]), float(clamp[1]))
+        if self._chained(B):
+            ack = {"image_embeds": image_embeds} if hint is None else {"image_embeds": image_embeds, "hint": hint}
+            extra = None if img is None else torch.cat([img, msk], 1)
+
+            def call(xc, c):
+                inp = sampling.cfg_input(xc)
+                return self.forward(inp if extra is None else torch.cat([inp, extra], 1), ts_rows[c], added_cond_kwargs=ack, return_dict=False)[0]
+
+            def step(xc, mo, nz, krow, x_out, x0, **kw):
+                sampling.sampler_step(xc, mo, nz, krow[1], x_out, x0, **kw)
+                if keep is not None:
+                    sampling.keep_region(x_out, k_init.float().contiguous(), k_noise.float().contiguous(), k_mask.float().contiguous(),
+                                         coef[krow[0], 0], coef[krow[0], 1], x_out)
+
+            xc = x.detach().float().clone()
+            return sampling.step_loop(call, xc, list(enumerate(rows)), noise_seq.float().contiguous(), None, step, table=table.float().contiguous(),
+                                      guidance=g, use_cfg=1, clamp=clip, pct=(-1, 0.0), init=None, mask=None, scratch=sampling.sampler_scratch(xc))[0]
+        box, lat = (B, 4, H, W), (4, H, W)
+        bufs = self._loop22_bufs.stage(
+            (B, H, W, n_steps, tuple(table.shape), keep is not None, str(dev)), dev,
+            lambda: dict(x=box, tmp=box, ts=(n_steps, B), noise=(n_steps,) + box, table=tuple(table.shape),
+                         scratch=_lib.lib().k22_sampler_scratch_bytes(B, H * W), img=box if a.inpainting else None,
+                         msk=(B, 1, H, W) if a.inpainting else None, kinit=lat if keep is not None else None,
+                         knoise=(bs,) + lat if keep is not None else None, kmask=(H, W) if keep is not None else None),
+            dict(x=x, ts=ts_rows, noise=noise_seq, table=table, img=img, msk=msk, kinit=k_init, knoise=k_noise, kmask=k_mask))
+        ccoef = None if coef is None else coef.ctypes.data_as(C.POINTER(C.c_float))
+        _lib.check(_lib.lib().k22_unet_sample_loop_keep(
+            self._handle, bufs["x"].data_ptr(), bufs["tmp"].data_ptr(), bufs["ts"].data_ptr(), bufs["noise"].data_ptr(), None, None,
+            _lib.ptr(bufs["img"]), _lib.ptr(bufs["msk"]), bufs["table"].data_ptr(), (C.c_int * n_steps)(*rows), n_steps, g, clip[0], clip[1], -1, 0.0,
+            bufs["scratch"].data_ptr(), _lib.ptr(bufs["kinit"]), _lib.ptr(bufs["knoise"]), _lib.ptr(bufs["kmask"]), ccoef,
+            1 if self.use_graph else 0, _lib.current_stream()))
+        return bufs["x"].clone()
+
     @torch.no_grad()
     def forward(self, sample, timestep, encoder_hidden_states=None, added_cond_kwargs=None, return_dict: bool = True, **_unused):
         if sample.device.type != "cuda":
@@ -362,15 +443,7 @@ class UNet2DConditionHIP(Text2ImUNetHIP):
         emb, hint = ack.get("image_embeds"), ack.get("hint")
         # the conditioning head (and the hint stack) is re-run whenever the tensors passed hold other VALUES than the ones it was
         # computed from (_same_condition); inside fixed_conditioning() the caller guarantees they do not change
-        if self._cond_key is None or not (self._cond_fixed or self._same_condition(emb, hint)):
-            if emb is None:
-                raise ValueError("added_cond_kwargs['image_embeds'] is required")
-            self.set_condition(emb, hint)
-            self._cond_key = True
-            if not self._cond_fixed:
-                self._cond_emb = emb.detach().float().clone()
-                self._cond_hint = None if hint is None else hint.detach().float().clone()
-            self.cache = {"cached": True}
+        self._ensure_condition22(emb, hint)
         t = torch.as_tensor(timestep, device=sample.device).float().reshape(-1)
         if t.numel() == 1:
             t = t.expand(B)
