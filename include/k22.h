@@ -565,6 +565,11 @@ typedef struct K22EncoderConfig {
   float ln_eps;    /* 1e-5 */
   int mlp_dim;     /* 0 = 4 * width (OpenAI CLIP, XLM-R); CLIP ViT-bigG/14: 8192 at width 1664 */
   int hidden_act;  /* CLIP towers: 0 = QuickGELU (OpenAI CLIP), 1 = exact erf GELU (open_clip bigG: "hidden_act": "gelu") */
+  int key_mask;    /* CLIP text: 0 = causal mask only (OpenAI clip; transformers without attention_mask); 1 = key_valid of k22_encoder_forward
+                      masks padded keys in addition to the causal triangle (transformers' CLIPTextModel called with attention_mask).  A plan-time
+                      switch: with 1 every forward needs key_valid */
+  int eos_id;      /* CLIP text, the pooled row: 0 = argmax(tokens) (OpenAI clip; transformers when config.eos_token_id == 2); > 0 = the FIRST
+                      position whose id equals eos_id (transformers otherwise), position 0 when the row holds none */
 } K22EncoderConfig;
 typedef struct K22Encoder K22Encoder;
 int k22_encoder_create(const K22EncoderConfig* cfg, const K22Weight* weights, int n_weights, K22Encoder** out);
@@ -572,6 +577,7 @@ void k22_encoder_destroy(K22Encoder* m);
 int k22_encoder_plan(K22Encoder* m, int B, size_t* workspace_bytes);     /* B sequences / images per call, <= 8 */
 int k22_encoder_bind(K22Encoder* m, void* workspace, size_t workspace_bytes);
 /* tokens: int32 [B][n_ctx] (text towers); key_valid: fp32 [B][n_ctx], 1 = token, 0 = padding (xlmr: the attention_mask);
+ * CLIP text with cfg.key_mask: required as well - transformers' attention_mask, padded keys masked under the causal triangle);
  * image: fp32 [B][3][S][S] (vision); seq_out: fp32 [B][n_ctx][width] or null; pooled_out: fp32 [B][out_dim].  Device buffers. */
 int k22_encoder_forward(K22Encoder* m, const int* tokens, const float* key_valid, const float* image, float* seq_out, float* pooled_out,
                         void* stream);

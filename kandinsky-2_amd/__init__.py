@@ -19,10 +19,14 @@ from .unet22 import (DDPM_SCHEDULER_DEFAULTS, SCHEDULER_CONFIG_2_2, SCHEDULER_CO
                      tiny_unet22_config)
 from .pipeline import (CONFIG_2_1, Kandinsky2_1HIP, ReferenceConditioner, SeededConditioner, get_kandinsky2, prepare_image,
                        process_images)
-from .encoders import (CLIP_BIGG_VISION, CLIP_VITL14, XLMR_LARGE, CLIPModelHIP, CLIPVisionModelWithProjectionHIP, HIPConditioner,
+from .encoders import (CLIP_BIGG_TEXT, CLIP_BIGG_VISION, CLIP_VITL14, XLMR_LARGE, CLIPModelHIP, CLIPTextModelWithProjectionHIP,
+                       CLIPVisionModelWithProjectionHIP, HIPConditioner, clip_text_hf_param_shapes, init_clip_text_hf_state_dict,
+                       tiny_clip_text_hf_config,
                        MultilingualCLIPHIP, TextEncoderHIP, clip_param_shapes, clip_vision_hf_param_shapes, init_clip_state_dict,
                        init_clip_vision_hf_state_dict, init_multiclip_state_dict, multiclip_param_shapes, tiny_clip_config,
                        tiny_clip_vision_hf_config, tiny_xlmr_config)
+from .prior22 import (PRIOR_TRANSFORMER_2_2, SCHEDULER_CONFIG_PRIOR_2_2, KandinskyV22PriorHIP, PriorTransformerHIP, UnCLIPSchedulerHIP,
+                      init_prior22_state_dict, load_prior22_from_cache_dir, prior22_param_shapes, rekey_prior22, tiny_prior22_config)
 from .movq import (MOVQ_CONFIG_2_1, MoVQArch, MoVQDecoderHIP, MoVQEncoderHIP, movq_param_shapes, init_movq_state_dict,
                    movq_encoder_param_shapes, init_movq_encoder_state_dict)
 
@@ -42,5 +46,8 @@ __all__ = [
     "CLIP_VITL14", "CLIP_BIGG_VISION", "CLIPVisionModelWithProjectionHIP", "clip_vision_hf_param_shapes", "init_clip_vision_hf_state_dict",
     "tiny_clip_vision_hf_config", "XLMR_LARGE", "CLIPModelHIP", "HIPConditioner", "MultilingualCLIPHIP", "TextEncoderHIP", "clip_param_shapes",
     "init_clip_state_dict", "init_multiclip_state_dict", "multiclip_param_shapes", "tiny_clip_config", "tiny_xlmr_config",
+    "CLIP_BIGG_TEXT", "CLIPTextModelWithProjectionHIP", "clip_text_hf_param_shapes", "init_clip_text_hf_state_dict", "tiny_clip_text_hf_config",
+    "PRIOR_TRANSFORMER_2_2", "SCHEDULER_CONFIG_PRIOR_2_2", "KandinskyV22PriorHIP", "PriorTransformerHIP", "UnCLIPSchedulerHIP",
+    "init_prior22_state_dict", "load_prior22_from_cache_dir", "prior22_param_shapes", "rekey_prior22", "tiny_prior22_config",
     "CONFIG_2_1", "Kandinsky2_1HIP", "ReferenceConditioner", "SeededConditioner", "get_kandinsky2", "prepare_image", "process_images",
 ]

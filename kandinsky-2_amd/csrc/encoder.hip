@@ -4,6 +4,9 @@
 //   K22_ENC_CLIP_TEXT    OpenAI CLIP ViT-L/14 text tower as Kandinsky2_1.generate_clip_emb walks it
 //                        (kandinsky2/kandinsky2_1_model.py:159-168): token + positional embedding, 12 pre-LN causal blocks with
 //                        QuickGELU MLPs, ln_final -> txt_feat_seq [B,77,768]; row argmax(tokens) @ text_projection -> txt_feat
+//                        Also transformers' CLIPTextModelWithProjection (the CLIP-bigG text tower of the Kandinsky 2.2 prior): erf GELU,
+//                        cfg.key_mask = the attention_mask's padded keys masked under the causal triangle, cfg.eos_id = the pooled row
+//                        is the first position holding that id.  Both are plan-time switches; zero = the OpenAI tower above
 //   K22_ENC_CLIP_VISION  clip_model.encode_image (kandinsky2_1_model.py:177-181): 14x14 patch embedding, class token,
 //                        positional embedding, ln_pre, 24 pre-LN blocks, ln_post(class token) @ proj -> [B,768]
 //   K22_ENC_XLMR         MultilingualCLIP.forward (kandinsky2/model/text_encoders.py:108-122): transformers' XLMRobertaModel
@@ -87,12 +90,19 @@ __global__ __launch_bounds__(256) void enc_embed_kernel(const int* tok, const fl
   for (int i = tid; i < D; i += 256) xr[i] = te[i] + pe[i] + (type_emb != nullptr ? type_emb[i] : 0.f);
 }
 
-// ---- CLIP text: the row of every sequence at its highest token id (the end-of-text token), torch.argmax semantics (first) --------
-__global__ __launch_bounds__(256) void enc_gather_eot_kernel(const int* tok, const float* x, float* out, int n_ctx, int D) {
+// ---- CLIP text: the row of every sequence at its highest token id (the end-of-text token), torch.argmax semantics (first);
+// eos_id > 0: at the FIRST position whose id equals eos_id instead (transformers' CLIPTextTransformer when config.eos_token_id != 2:
+// (input_ids == eos_token_id).int().argmax(-1), so position 0 when the row holds no such id) ---------------------------------------
+__global__ __launch_bounds__(256) void enc_gather_eot_kernel(const int* tok, const float* x, float* out, int n_ctx, int D, int eos_id) {
   const int b = blockIdx.x, tid = threadIdx.x;
   const int* tb = tok + (int64_t)b * n_ctx;
-  int best = 0, bv = tb[0];
-  for (int j = 1; j < n_ctx; ++j) if (tb[j] > bv) { bv = tb[j]; best = j; }
+  int best = 0;
+  if (eos_id > 0) {
+    for (int j = n_ctx - 1; j >= 0; --j) if (tb[j] == eos_id) best = j;
+  } else {
+    int bv = tb[0];
+    for (int j = 1; j < n_ctx; ++j) if (tb[j] > bv) { bv = tb[j]; best = j; }
+  }
   const float* xr = x + ((int64_t)b * n_ctx + best) * D;
   for (int i = tid; i < D; i += 256) out[(int64_t)b * D + i] = xr[i];
 }
@@ -239,8 +249,8 @@ int launch_enc_embed(const int* tok, const float* te, const float* pe, const flo
   K22_CHECK_LAUNCH();
   return K22_OK;
 }
-int launch_enc_gather_eot(const int* tok, const float* x, float* out, int B, int n, int D, hipStream_t st) {
-  hipLaunchKernelGGL(enc_gather_eot_kernel, dim3(B), dim3(256), 0, st, tok, x, out, n, D);
+int launch_enc_gather_eot(const int* tok, const float* x, float* out, int B, int n, int D, int eos_id, hipStream_t st) {
+  hipLaunchKernelGGL(enc_gather_eot_kernel, dim3(B), dim3(256), 0, st, tok, x, out, n, D, eos_id);
   K22_CHECK_LAUNCH();
   return K22_OK;
 }
@@ -341,6 +351,9 @@ struct K22Encoder : GraphPlan {   // tuned: every transformer Linear; graph: the
     const int Kraw = 3 * cfg.patch * cfg.patch, Kp = (Kraw + 63) / 64 * 64;
     if (vision && (cfg.image_size % cfg.patch || P + 1 != n)) return k22_set_error(K22_EINVAL, "encoder: n_ctx must be (image_size/patch)^2 + 1");
     if (!vision && cfg.vocab < 1) return k22_set_error(K22_EINVAL, "encoder: vocab");
+    if ((cfg.key_mask || cfg.eos_id) && kind != K22_ENC_CLIP_TEXT) return k22_set_error(K22_EINVAL, "encoder: key_mask / eos_id belong to the CLIP text tower");
+    if (cfg.eos_id < 0 || (cfg.eos_id > 0 && cfg.eos_id >= cfg.vocab)) return k22_set_error(K22_EINVAL, "encoder: eos_id outside the vocabulary");
+    if (cfg.key_mask && !flash) return k22_set_error(K22_EINVAL, "encoder: the key-padding mask runs on the 64-channel flash kernel");
     // validated: only now drop the previous plan
     begin_plan();
     B = nB;
@@ -393,6 +406,7 @@ struct K22Encoder : GraphPlan {   // tuned: every transformer Linear; graph: the
       if (!xlmr) op_ln(s_inp, 0, D, M, pfx + ".ln_1", nullptr, 0, s_ln);
       op_linear(s_ln, M, 3 * D, D, pfx + ".qkv", K22_ACT_NONE, s_qkv, 3 * D, 0);
       const int causal = kind == K22_ENC_CLIP_TEXT ? 1 : 0;
+      const bool masked = xlmr || cfg.key_mask != 0;   // the attention_mask: XLM-R always, CLIP text (under the causal triangle) by config
       if (!flash) {
         ops.push_back([=](hipStream_t st) { return launch_enc_attention_generic(ptr(s_qkv), ptr(s_att), Bn, heads, n, hd, dt, st); });
       } else
@@ -406,7 +420,7 @@ struct K22Encoder : GraphPlan {   // tuned: every transformer Linear; graph: the
         ap.q = ptr(s_qkv); ap.ldq = 3 * D; ap.kall = ptr(s_kall); ap.vtall = ptr(s_vtall); ap.out = ptr(s_att); ap.ldo = D;
         ap.B = Bn; ap.H = heads; ap.T = n; ap.Tk = n; ap.Tkp = Tkp; ap.scale = 0.125f;
         ap.causal = causal;
-        if (xlmr) { ap.key_valid = ptr<float>(s_valid); ap.kv_ld = n; ap.kv_n = n; }
+        if (masked) { ap.key_valid = ptr<float>(s_valid); ap.kv_ld = n; ap.kv_n = n; }
         return launch_attention(ap, dt, st);
       });
       op_linear(s_att, M, D, D, pfx + ".proj", K22_ACT_NONE, s_inp, D, 2);
@@ -430,7 +444,8 @@ struct K22Encoder : GraphPlan {   // tuned: every transformer Linear; graph: the
     const float* hb = xlmr ? Wf("head.bias") : nullptr;
     if (kind == K22_ENC_CLIP_TEXT) {
       op_ln(s_inp, 0, D, M, "ln_final", s_seq, D, nullptr);
-      ops.push_back([=](hipStream_t st) { return launch_enc_gather_eot(ptr<int>(s_tok), ptr<float>(s_seq), ptr<float>(s_pool_in), Bn, n, D, st); });
+      const int eos = cfg.eos_id;
+      ops.push_back([=](hipStream_t st) { return launch_enc_gather_eot(ptr<int>(s_tok), ptr<float>(s_seq), ptr<float>(s_pool_in), Bn, n, D, eos, st); });
     } else if (vision) {
       op_ln(s_inp, 0, (int64_t)n * D, B, "ln_post", s_pool_in, D, nullptr);      // class-token rows only
     } else {
@@ -479,16 +494,16 @@ int k22_encoder_forward(K22Encoder* m, const int* tokens, const float* key_valid
                         void* stream) {
   if (!m || !m->ws) return k22_set_error(K22_EINVAL, "encoder_forward: bind a workspace first");
   const K22EncoderConfig& c = m->cfg;
-  const bool vision = c.kind == K22_ENC_CLIP_VISION, xlmr = c.kind == K22_ENC_XLMR;
+  const bool vision = c.kind == K22_ENC_CLIP_VISION, xlmr = c.kind == K22_ENC_XLMR, masked = xlmr || c.key_mask != 0;
   if (vision ? !image : !tokens) return k22_set_error(K22_EINVAL, "encoder_forward: tokens (text towers) / image (vision tower) is null");
-  if (xlmr && !key_valid) return k22_set_error(K22_EINVAL, "encoder_forward: the XLM-R tower needs the attention mask");
+  if (masked && !key_valid) return k22_set_error(K22_EINVAL, "encoder_forward: this tower (XLM-R, or CLIP text with key_mask) needs the attention mask");
   if (vision && seq_out) return k22_set_error(K22_EINVAL, "encoder_forward: the vision tower has no sequence output");
   if (!pooled_out) return k22_set_error(K22_EINVAL, "encoder_forward: pooled_out is null");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const size_t M = (size_t)m->B * c.n_ctx;
   if (vision) { if (int rc = copy_d2d(m->ptr(m->s_img), image, (size_t)m->B * 3 * c.image_size * c.image_size * 4, st)) return rc; }
   else { if (int rc = copy_d2d(m->ptr(m->s_tok), tokens, M * 4, st)) return rc; }
-  if (xlmr) { if (int rc = copy_d2d(m->ptr(m->s_valid), key_valid, M * 4, st)) return rc; }
+  if (masked) { if (int rc = copy_d2d(m->ptr(m->s_valid), key_valid, M * 4, st)) return rc; }
   if (int rc = m->tune_once(m->s_flush, st)) return rc;
   if (int rc = m->replay(m->graph, st, [m](hipStream_t s) { return m->run_ops(s); })) return rc;
   if (seq_out) { if (int rc = copy_d2d(seq_out, m->ptr(m->s_seq), M * c.width * 4, st)) return rc; }
@@ -514,7 +529,7 @@ int k22_enc_embed(const int* tokens, const float* tok_emb, const float* pos_emb,
 }
 int k22_enc_gather_eot(const int* tokens, const float* x, float* out, int B, int n_ctx, int D, void* stream) {
   if (!tokens || !x || !out || B < 1 || n_ctx < 1 || D < 1) return k22_set_error(K22_EINVAL, "enc_gather_eot: bad argument");
-  return launch_enc_gather_eot(tokens, x, out, B, n_ctx, D, reinterpret_cast<hipStream_t>(stream));
+  return launch_enc_gather_eot(tokens, x, out, B, n_ctx, D, 0, reinterpret_cast<hipStream_t>(stream));
 }
 int k22_enc_masked_mean(const float* x, const float* mask, float* out, int B, int n_ctx, int D, void* stream) {
   if (!x || !mask || !out || B < 1 || n_ctx < 1 || D < 1) return k22_set_error(K22_EINVAL, "enc_masked_mean: bad argument");

@@ -3,6 +3,9 @@ Kandinsky 2.1 runs once per prompt / image before the prior and the denoising lo
 
     CLIPVisionModelWithProjectionHIP   transformers' class of that name under its own keys: the CLIP ViT-bigG/14 image encoder Kandinsky 2.2 loads
                           (kandinsky2/kandinsky2_2_model.py:24) - 48 layers x 1664, 16 heads of 104 channels, 1280-d embedding.
+    CLIPTextModelWithProjectionHIP     transformers' class of that name under its own keys: the CLIP ViT-bigG/14 text tower of the 2.2 prior
+                          (the `text_encoder` folder of kandinsky-2-2-prior) - 32 layers x 1280, 20 heads of 64, erf GELU; optional
+                          key-padding mask under the causal mask, pooled token by eos id (prior22.py drives it).
     CLIPModelHIP          clip.load("ViT-L/14") as the reference uses it: the text tower walked by generate_clip_emb
                           (kandinsky2/kandinsky2_1_model.py:159-168) and encode_image (:177-181).  Parameters under the OpenAI
                           `clip.model.CLIP` state_dict keys, so that checkpoint loads unchanged.
@@ -43,6 +46,21 @@ XLMR_LARGE = {"vocab_size": 250002, "hidden_size": 1024, "num_hidden_layers": 24
 # layout [published architecture: 48 layers x 1664 wide, 16 heads of 104, MLP 8192, erf GELU, 14-px patches of a 224-px image, 1280-d output]
 CLIP_BIGG_VISION = {"hidden_size": 1664, "intermediate_size": 8192, "num_hidden_layers": 48, "num_attention_heads": 16, "image_size": 224,
                     "patch_size": 14, "projection_dim": 1280, "hidden_act": "gelu", "layer_norm_eps": 1e-5}
+
+
+# config.json of the `text_encoder` sub-folder of kandinsky-community/kandinsky-2-2-prior (transformers' CLIPTextModelWithProjection: open_clip
+# ViT-bigG/14's text tower) [published architecture; eos_token_id 2 is what the configs converted before transformers 4.3x carry - the
+# argmax pooling - and is recalled, not read: prior22.load_prior22_from_cache_dir prefers the folder's own config.json]
+CLIP_BIGG_TEXT = {"hidden_size": 1280, "intermediate_size": 5120, "num_hidden_layers": 32, "num_attention_heads": 20,
+                  "max_position_embeddings": 77, "vocab_size": 49408, "projection_dim": 1280, "hidden_act": "gelu", "layer_norm_eps": 1e-5,
+                  "eos_token_id": 2}
+
+
+def tiny_clip_text_hf_config() -> dict:
+    """Same structure at 2 layers x 128 wide (two heads of 64), vocabulary 1000; projection_dim 96 != width, so that a transposed
+    projection cannot pass."""
+    return dict(CLIP_BIGG_TEXT, hidden_size=128, intermediate_size=512, num_hidden_layers=2, num_attention_heads=2, vocab_size=1000,
+                projection_dim=96)
 
 
 def tiny_clip_vision_hf_config() -> dict:
@@ -144,6 +162,26 @@ def clip_vision_hf_param_shapes(cfg: dict) -> "OrderedDict[str, tuple]":
     return s
 
 
+def clip_text_hf_param_shapes(cfg: dict) -> "OrderedDict[str, tuple]":
+    """state_dict of transformers' CLIPTextModelWithProjection (models/clip/modeling_clip.py); position_ids is no parameter."""
+    H, I = cfg["hidden_size"], cfg["intermediate_size"]
+    s: "OrderedDict[str, tuple]" = OrderedDict()
+    e = "text_model.embeddings."
+    s[e + "token_embedding.weight"] = (cfg["vocab_size"], H)
+    s[e + "position_embedding.weight"] = (cfg["max_position_embeddings"], H)
+    for l in range(cfg["num_hidden_layers"]):
+        q = f"text_model.encoder.layers.{l}."
+        for nm in ("q_proj", "k_proj", "v_proj", "out_proj"):
+            s[q + f"self_attn.{nm}.weight"] = (H, H); s[q + f"self_attn.{nm}.bias"] = (H,)
+        s[q + "layer_norm1.weight"] = (H,); s[q + "layer_norm1.bias"] = (H,)
+        s[q + "mlp.fc1.weight"] = (I, H); s[q + "mlp.fc1.bias"] = (I,)
+        s[q + "mlp.fc2.weight"] = (H, I); s[q + "mlp.fc2.bias"] = (H,)
+        s[q + "layer_norm2.weight"] = (H,); s[q + "layer_norm2.bias"] = (H,)
+    s["text_model.final_layer_norm.weight"] = (H,); s["text_model.final_layer_norm.bias"] = (H,)
+    s["text_projection.weight"] = (cfg["projection_dim"], H)
+    return s
+
+
 def _init(shapes, seed):
     g = torch.Generator(device="cpu").manual_seed(seed)
     sd: "OrderedDict[str, torch.Tensor]" = OrderedDict()
@@ -174,6 +212,10 @@ def init_clip_state_dict(cfg: dict, seed: int = 0):
 
 def init_clip_vision_hf_state_dict(cfg: dict, seed: int = 0):
     return _init(clip_vision_hf_param_shapes(cfg), seed)
+
+
+def init_clip_text_hf_state_dict(cfg: dict, seed: int = 0):
+    return _init(clip_text_hf_param_shapes(cfg), seed)
 
 
 def init_multiclip_state_dict(cfg: dict, in_features=1024, out_features=768, seed: int = 0):
@@ -226,6 +268,39 @@ def pack_clip_vision_arena(cfg, sd, tdtype, device):
     return layout_arena(ent, device)
 
 
+def _hf_layers(ent, sd, src, n_layers, tdtype, f):
+    """transformers' CLIPEncoderLayer keys under `src`.<l>. -> the engine's layers.<l>.* (q / k / v rows stacked [q | k | v], heads contiguous
+    inside each, exactly as the separate q_proj / k_proj / v_proj weights already are)"""
+    for l in range(n_layers):
+        s_, q = f"{src}.{l}.", f"layers.{l}"
+        a = s_ + "self_attn."
+        ent[q + ".qkv.weight"] = _pad_rows(torch.cat([f(sd[a + "q_proj.weight"]), f(sd[a + "k_proj.weight"]), f(sd[a + "v_proj.weight"])], 0)).to(tdtype).contiguous()
+        ent[q + ".qkv.bias"] = torch.cat([f(sd[a + "q_proj.bias"]), f(sd[a + "k_proj.bias"]), f(sd[a + "v_proj.bias"])], 0).contiguous()
+        ent[q + ".proj.weight"] = _pad_rows(f(sd[a + "out_proj.weight"])).to(tdtype).contiguous()
+        ent[q + ".proj.bias"] = f(sd[a + "out_proj.bias"]).contiguous()
+        ent[q + ".fc.weight"] = _pad_rows(f(sd[s_ + "mlp.fc1.weight"])).to(tdtype).contiguous()
+        ent[q + ".fc.bias"] = f(sd[s_ + "mlp.fc1.bias"]).contiguous()
+        ent[q + ".out.weight"] = _pad_rows(f(sd[s_ + "mlp.fc2.weight"])).to(tdtype).contiguous()
+        ent[q + ".out.bias"] = f(sd[s_ + "mlp.fc2.bias"]).contiguous()
+        ent[q + ".ln_1.weight"] = f(sd[s_ + "layer_norm1.weight"]).contiguous(); ent[q + ".ln_1.bias"] = f(sd[s_ + "layer_norm1.bias"]).contiguous()
+        ent[q + ".ln_2.weight"] = f(sd[s_ + "layer_norm2.weight"]).contiguous(); ent[q + ".ln_2.bias"] = f(sd[s_ + "layer_norm2.bias"]).contiguous()
+
+
+def pack_clip_text_hf_arena(cfg, sd, tdtype, device):
+    """transformers CLIPTextModelWithProjection keys -> the encoder engine's names; text_projection.weight [proj, width] is a Linear weight
+    already (no transpose, unlike OpenAI clip's text_projection [width, embed])."""
+    f = lambda t: t.detach().to(device=device, dtype=torch.float32)  # noqa: E731
+    e = "text_model.embeddings."
+    ent: "OrderedDict[str, torch.Tensor]" = OrderedDict()
+    ent["token_embedding"] = f(sd[e + "token_embedding.weight"]).contiguous()
+    ent["positional_embedding"] = f(sd[e + "position_embedding.weight"]).contiguous()
+    _hf_layers(ent, sd, "text_model.encoder.layers", cfg["num_hidden_layers"], tdtype, f)
+    ent["ln_final.weight"] = f(sd["text_model.final_layer_norm.weight"]).contiguous()
+    ent["ln_final.bias"] = f(sd["text_model.final_layer_norm.bias"]).contiguous()
+    ent["head.weight"] = f(sd["text_projection.weight"]).contiguous()
+    return layout_arena(ent, device)
+
+
 def pack_clip_vision_hf_arena(cfg, sd, tdtype, device):
     """transformers CLIPVisionModelWithProjection keys -> the encoder engine's names (q / k / v rows stacked [q | k | v], heads
     contiguous inside each, exactly as the separate q_proj / k_proj / v_proj weights already are)."""
@@ -242,19 +317,7 @@ def pack_clip_vision_hf_arena(cfg, sd, tdtype, device):
     ent["positional_embedding"] = f(sd[e + "position_embedding.weight"]).contiguous()
     ent["ln_pre.weight"] = f(sd["vision_model.pre_layrnorm.weight"]).contiguous(); ent["ln_pre.bias"] = f(sd["vision_model.pre_layrnorm.bias"]).contiguous()
     ent["ln_post.weight"] = f(sd["vision_model.post_layernorm.weight"]).contiguous(); ent["ln_post.bias"] = f(sd["vision_model.post_layernorm.bias"]).contiguous()
-    for l in range(cfg["num_hidden_layers"]):
-        s_, q = f"vision_model.encoder.layers.{l}.", f"layers.{l}"
-        a = s_ + "self_attn."
-        ent[q + ".qkv.weight"] = _pad_rows(torch.cat([f(sd[a + "q_proj.weight"]), f(sd[a + "k_proj.weight"]), f(sd[a + "v_proj.weight"])], 0)).to(tdtype).contiguous()
-        ent[q + ".qkv.bias"] = torch.cat([f(sd[a + "q_proj.bias"]), f(sd[a + "k_proj.bias"]), f(sd[a + "v_proj.bias"])], 0).contiguous()
-        ent[q + ".proj.weight"] = _pad_rows(f(sd[a + "out_proj.weight"])).to(tdtype).contiguous()
-        ent[q + ".proj.bias"] = f(sd[a + "out_proj.bias"]).contiguous()
-        ent[q + ".fc.weight"] = _pad_rows(f(sd[s_ + "mlp.fc1.weight"])).to(tdtype).contiguous()
-        ent[q + ".fc.bias"] = f(sd[s_ + "mlp.fc1.bias"]).contiguous()
-        ent[q + ".out.weight"] = _pad_rows(f(sd[s_ + "mlp.fc2.weight"])).to(tdtype).contiguous()
-        ent[q + ".out.bias"] = f(sd[s_ + "mlp.fc2.bias"]).contiguous()
-        ent[q + ".ln_1.weight"] = f(sd[s_ + "layer_norm1.weight"]).contiguous(); ent[q + ".ln_1.bias"] = f(sd[s_ + "layer_norm1.bias"]).contiguous()
-        ent[q + ".ln_2.weight"] = f(sd[s_ + "layer_norm2.weight"]).contiguous(); ent[q + ".ln_2.bias"] = f(sd[s_ + "layer_norm2.bias"]).contiguous()
+    _hf_layers(ent, sd, "vision_model.encoder.layers", cfg["num_hidden_layers"], tdtype, f)
     ent["head.weight"] = f(sd["visual_projection.weight"]).contiguous()
     return layout_arena(ent, device)
 
@@ -364,6 +427,67 @@ class CLIPModelHIP(NativeModule):
         if image.dim() != 4 or tuple(image.shape[1:]) != (3, r, r):
             raise ValueError(f"CLIP image batch must be [n, 3, {r}, {r}] (preprocessed), got {tuple(image.shape)}")
         return _run_tower(self._engine("vision"), image=image)[1]
+
+
+class CLIPTextModelWithProjectionHIP(NativeModule):
+    """transformers' `CLIPTextModelWithProjection` - the `text_encoder` of the Kandinsky 2.2 prior repository (CLIP ViT-bigG/14's text
+    tower), which diffusers' prior pipeline calls as `text_encoder(input_ids)` and reads `.text_embeds` / `.last_hidden_state` of - on
+    the K22_ENC_CLIP_TEXT engine.  Parameters under transformers' own state_dict keys.  Two things of transformers' class the OpenAI tower
+    does not have, both plan-time switches of the engine (include/k22.h: key_mask, eos_id): with `attention_mask` padded keys are masked
+    under the causal triangle (a second engine on the same arena; valid rows and the pooled output do not change, padded rows do), and
+    the pooled row is the first position holding `eos_token_id` unless that id is 2, the legacy configs' argmax(input_ids)."""
+
+    def __init__(self, config: Optional[dict] = None, backend_dtype: torch.dtype = torch.bfloat16):
+        self.config_dict = dict(config or CLIP_BIGG_TEXT)
+        c = self.config_dict
+        if c["hidden_size"] != 64 * c["num_attention_heads"] or c["intermediate_size"] % 64:
+            raise ValueError("CLIPTextModelWithProjectionHIP: 64 channels per attention head (bigG: 1280 / 20), intermediate_size % 64 == 0")
+        if c.get("hidden_act", "quick_gelu") not in ("gelu", "quick_gelu"):
+            raise NotImplementedError("hidden_act: gelu (bigG) or quick_gelu (OpenAI CLIP)")
+        if not 0 < int(c.get("eos_token_id", 2)) < c["vocab_size"]:
+            raise ValueError("eos_token_id outside the vocabulary")
+        self._arena_table = None
+        super().__init__(clip_text_hf_param_shapes(c), backend_dtype)
+        self.config = type("Config", (), {"projection_dim": c["projection_dim"], "hidden_size": c["hidden_size"],
+                                          "max_position_embeddings": c["max_position_embeddings"], "eos_token_id": c.get("eos_token_id", 2)})()
+
+    def load_state_dict(self, state_dict, strict: bool = True, **kw):
+        sd = {k: v for k, v in state_dict.items() if not k.endswith("position_ids")}        # buffer of older transformers versions
+        return super().load_state_dict(sd, strict=strict, **kw)
+
+    def _engine(self, masked: bool):
+        """the causal-only engine or the one that also masks padded keys, both on one packed arena"""
+        if self._arena_table is None:
+            self._arena_table = pack_clip_text_hf_arena(self.config_dict, self.state_dict(), self.backend_dtype, self._device())
+        key = "text_masked" if masked else "text"
+        if key not in self._engines:
+            c = self.config_dict
+            eos = int(c.get("eos_token_id", 2))
+            ecfg = dict(kind=ENC_CLIP_TEXT, width=c["hidden_size"], layers=c["num_hidden_layers"], heads=c["num_attention_heads"],
+                        n_ctx=c["max_position_embeddings"], vocab=c["vocab_size"], out_dim=c["projection_dim"], image_size=0, patch=0, max_pos=0,
+                        pad_id=0, ln_eps=float(c.get("layer_norm_eps", 1e-5)), mlp_dim=c["intermediate_size"],
+                        hidden_act=1 if c.get("hidden_act", "quick_gelu") == "gelu" else 0, key_mask=1 if masked else 0,
+                        eos_id=0 if eos == 2 else eos)
+            self._engines[key] = _tower_engine(ecfg, *self._arena_table, self.backend_dtype)
+        return self._engines[key]
+
+    def _release(self):
+        super()._release()
+        self._arena_table = None
+
+    @torch.no_grad()
+    def forward(self, input_ids, attention_mask=None, **_unused):
+        c = self.config_dict
+        n = c["max_position_embeddings"]
+        if input_ids.dim() != 2 or input_ids.shape[1] != n:
+            raise ValueError(f"input_ids must be [n, {n}] (padded to max_length), got {tuple(input_ids.shape)}")
+        if attention_mask is not None and attention_mask.shape != input_ids.shape:
+            raise ValueError("attention_mask must have the shape of input_ids")
+        if input_ids.numel() and (int(input_ids.min()) < 0 or int(input_ids.max()) >= c["vocab_size"]):
+            raise ValueError("CLIP token id outside the vocabulary")
+        from types import SimpleNamespace
+        seq, pooled = _run_tower(self._engine(attention_mask is not None), tokens=input_ids, key_valid=attention_mask)
+        return SimpleNamespace(text_embeds=pooled, last_hidden_state=seq)
 
 
 class CLIPVisionModelWithProjectionHIP(NativeModule):

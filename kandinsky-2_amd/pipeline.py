@@ -563,11 +563,11 @@ def _conditioner_from_cache_dir(cache_dir, device, backend_dtype, tokenizer2=Non
 
 def get_kandinsky2(device, task_type="text2img", cache_dir="/tmp/kandinsky2", use_auth_token=None, model_version="2.1",
                    use_flash_attention=False, *, conditioner=None, backend_dtype: torch.dtype = torch.bfloat16, use_graph: bool = True,
-                   movq_dtype: Optional[torch.dtype] = None, tokenizer2=None):
+                   movq_dtype: Optional[torch.dtype] = None, tokenizer2=None, prior_cache_dir=None):
     """`get_kandinsky2` (kandinsky2/__init__.py:164-192) for the HIP engines.  The reference downloads the checkpoints into
     cache_dir (kandinsky2/__init__.py:100-160); this box-local variant reads the same file names from cache_dir and raises if
     they are not there (there is no download path).  use_flash_attention is accepted and ignored: attention always runs in the
-    engine's own fused kernel."""
+    engine's own fused kernel.  2.2: conditioner="native" with prior_cache_dir= builds the native prior (prior22.py)."""
     if model_version == "2.1":
         config = copy.deepcopy(CONFIG_2_1)
         model_name = {"text2img": "decoder_fp16.ckpt", "inpainting": "inpainting_fp16.ckpt"}.get(task_type)
@@ -586,5 +586,5 @@ def get_kandinsky2(device, task_type="text2img", cache_dir="/tmp/kandinsky2", us
     if model_version == "2.2":
         from .pipeline22 import Kandinsky2_2HIP
         return Kandinsky2_2HIP(device=device, task_type=task_type, cache_dir=cache_dir, conditioner=conditioner, backend_dtype=backend_dtype,
-                               use_graph=use_graph, movq_dtype=movq_dtype)
+                               use_graph=use_graph, movq_dtype=movq_dtype, prior_cache_dir=prior_cache_dir)
     raise ValueError("Only 2.1 and 2.2 are available on the HIP engines")

@@ -5,6 +5,7 @@ PARITY UNPINNED (see unet22.py / oracle/unet22_ref.py): the 2.2 arithmetic is di
 
 The 2.2 PRIOR (`KandinskyV22PriorPipeline`: CLIP-bigG text tower + diffusers' PriorTransformer + UnCLIPScheduler) is a
 conditioning encoder in the sense of SURVEY 8f-3 - it runs once per prompt and its network is not in the reference tree - and is
+native in prior22.py (KandinskyV22PriorHIP; conditioner="native" builds it from prior_cache_dir) and
 reached through the conditioner:  conditioner.prior22(prompt, negative_prompt | None, batch_size, steps, guidance, device) ->
 (image_embeds [bs,1280], negative_image_embeds [bs,1280]);  conditioner.encode_image22(image, device) -> [1,1280] (mix_images).
 """
@@ -283,7 +284,8 @@ class Kandinsky2_2HIP:
 
     def __init__(self, device="cuda", task_type="text2img", *, unet_state_dict=None, movq_state_dict=None, conditioner=None,
                  cache_dir=None, backend_dtype: torch.dtype = torch.bfloat16, use_graph: bool = True, unet_config=None, controlnet=None,
-                 scheduler_config=None, movq_dtype: Optional[torch.dtype] = None, whole_loop_graph: Optional[bool] = None):
+                 scheduler_config=None, movq_dtype: Optional[torch.dtype] = None, whole_loop_graph: Optional[bool] = None,
+                 prior_cache_dir=None):
         if task_type not in ("text2img", "img2img", "inpainting"):
             raise ValueError("Only text2img, img2img, inpainting is available")
         if (unet_state_dict is None or movq_state_dict is None) and cache_dir is not None:
@@ -299,15 +301,24 @@ class Kandinsky2_2HIP:
                                     "cache_dir= holding the decoder repository's unet/, movq/, scheduler/ folders (no download path in this build)")
         if controlnet and task_type != "text2img":
             raise ValueError("the ControlNet-depth UNet is a text2img decoder")
-        # The reference builds the CLIP-bigG image encoder and the prior pipeline here (kandinsky2_2_model.py:24-31).  Seeded stand-in
+        # The reference builds the CLIP-bigG image encoder and the prior pipeline here (kandinsky2_2_model.py:24-31): conditioner="native"
+        # does the same on the HIP engines (prior22.KandinskyV22PriorHIP from the prior repository under prior_cache_dir).  Seeded stand-in
         # embeddings would ignore the prompt, so they are an explicit opt-in (conditioner="seeded"), never a silent default.
         if conditioner is None:
             raise ValueError("Kandinsky2_2HIP: pass conditioner= (an object with prior22 / encode_image22: the 2.2 prior pipeline and its "
-                             "CLIP-bigG image encoder), or conditioner='seeded' for the offline benchmark stand-in")
+                             "CLIP-bigG image encoder), conditioner='native' with prior_cache_dir=, or conditioner='seeded' for the offline "
+                             "benchmark stand-in")
         if isinstance(conditioner, str):
-            if conditioner != "seeded":
-                raise ValueError("conditioner must be an object or the string 'seeded'")
-            conditioner = SeededPrior22()
+            if conditioner == "native":
+                if prior_cache_dir is None:
+                    raise ValueError("conditioner='native' needs prior_cache_dir= (the folder holding kandinsky-2-2-prior/)")
+                from .prior22 import load_prior22_from_cache_dir
+                conditioner = load_prior22_from_cache_dir(prior_cache_dir, backend_dtype if isinstance(backend_dtype, torch.dtype) else torch.float32,
+                                                          device)
+            elif conditioner == "seeded":
+                conditioner = SeededPrior22()
+            else:
+                raise ValueError("conditioner must be an object or one of the strings 'native', 'seeded'")
         self.device, self.task_type = device, task_type
         self.conditioner = conditioner
         arch = make_arch22(unet_config, controlnet=controlnet if controlnet else None, inpainting=True if task_type == "inpainting" else None)

@@ -85,7 +85,23 @@ def init_prior_state_dict(hp: dict, seed: int = 0) -> "OrderedDict[str, torch.Te
     return sd
 
 
-def pack_prior_arena(hp: dict, sd: Dict[str, torch.Tensor], tdtype, device) -> Tuple[torch.Tensor, "OrderedDict[str, Tuple[int, int]]"]:
+def qkv_planes(w: torch.Tensor, heads: int) -> torch.Tensor:
+    """c_qkv weight [3W, W] or bias [3W] in the reference's per-head [q|k|v] interleaving (prior.py:93-95) -> the Q | K | V planes x
+    [head][64] the engine reads.  Separate to_q / to_k / to_v matrices (diffusers) concatenated are those planes already."""
+    return w.reshape((heads, 3, 64) + tuple(w.shape[1:])).transpose(0, 1).reshape(w.shape)
+
+
+def qkv_heads(w: torch.Tensor, heads: int) -> torch.Tensor:
+    """the inverse of qkv_planes: Q | K | V planes -> the reference's per-head interleaving"""
+    return w.reshape((3, heads, 64) + tuple(w.shape[1:])).transpose(0, 1).reshape(w.shape)
+
+
+def pack_prior_arena(hp: dict, sd: Dict[str, torch.Tensor], tdtype, device,
+                     qkv_layout: str = "heads") -> Tuple[torch.Tensor, "OrderedDict[str, Tuple[int, int]]"]:
+    """sd under prior_param_shapes' keys -> the engine's arena.  qkv_layout: how the c_qkv rows of sd are ordered - "heads": the
+    reference's per-head [q|k|v] (2.1 checkpoints), "planes": Q | K | V (prior22: diffusers' to_q / to_k / to_v stacked)."""
+    if qkv_layout not in ("heads", "planes"):
+        raise ValueError('qkv_layout must be "heads" or "planes"')
     f32 = torch.float32
     W, H = hp["xf_width"], hp["xf_heads"]
     ent: "OrderedDict[str, torch.Tensor]" = OrderedDict()
@@ -94,12 +110,9 @@ def pack_prior_arena(hp: dict, sd: Dict[str, torch.Tensor], tdtype, device) -> T
     for name in prior_param_shapes(hp):
         w = sd[name].detach().to(device=device, dtype=f32)
         if ".attn.c_qkv." in name:
-            # per-head [q|k|v] interleaved (prior.py:93-95) -> Q | K | V planes x [head][64]
-            if name.endswith(".weight"):
-                w = w.reshape(H, 3, 64, W).permute(1, 0, 2, 3).reshape(3 * W, W)
-                ent[name] = _pad_rows(w).to(tdtype).contiguous()
-            else:
-                ent[name] = w.reshape(H, 3, 64).permute(1, 0, 2).reshape(-1).contiguous()
+            if qkv_layout == "heads":
+                w = qkv_planes(w, H)
+            ent[name] = _pad_rows(w).to(tdtype).contiguous() if name.endswith(".weight") else w.contiguous()
         elif name.startswith("transformer.") and name.endswith(".weight") and ".ln_" not in name:
             ent[name] = _pad_rows(w).to(tdtype).contiguous()
         elif name == "text_enc_proj.weight":
@@ -180,31 +193,24 @@ class PriorSchedule:
         return tab
 
 
-class PriorDiffusionModelHIP(NativeModule):
-    """MI355X-native PriorDiffusionModel (kandinsky2/model/prior.py:273-384): holds PriorTransformer's parameters under
-    `model.*` like the reference, plus the clip_mean / clip_std buffers."""
+class PriorEngineModule(NativeModule):
+    """What the two mirrors of the K22Prior engine share (PriorDiffusionModelHIP here, prior22.PriorTransformerHIP): the engine built
+    from `self.hp` and `_engine_weights()`, one transformer forward, and the sampling loop - k22_prior_sample_loop on the module's own
+    buffers, or the same launches step by step."""
 
-    def __init__(self, hparams: Optional[dict] = None, diffusion: Optional[dict] = None, clip_mean: Optional[torch.Tensor] = None,
-                 clip_std: Optional[torch.Tensor] = None, backend_dtype: torch.dtype = torch.bfloat16):
-        self.hp = dict(hparams or PRIOR_HPARAMS_2_1)
-        super().__init__({"model." + k: v for k, v in prior_param_shapes(self.hp).items()}, backend_dtype)
-        self.diffusion_kwargs = dict(diffusion or PRIOR_DIFFUSION_2_1)
+    def _init_engine(self):
         self.use_graph = True                   # k22_prior_sample_loop: one captured graph (False: the same launches eagerly)
         self._loop = sampling.OwnedBuffers()    # operands of k22_prior_sample_loop: stable addresses, so a second call replays
-        cd = self.hp["clip_dim"]
-        self.register_buffer("clip_mean", (clip_mean if clip_mean is not None else torch.zeros(cd))[None, :].float(), persistent=False)
-        self.register_buffer("clip_std", (clip_std if clip_std is not None else torch.ones(cd))[None, :].float(), persistent=False)
 
-    def load_state_dict(self, state_dict, strict: bool = True, **kw):
-        if state_dict and not any(k.startswith("model.") for k in state_dict):
-            state_dict = {"model." + k: v for k, v in state_dict.items()}
-        return super().load_state_dict(state_dict, strict=strict, **kw)
+    def _engine_weights(self):
+        """-> (state dict under prior_param_shapes' keys, its qkv_layout for pack_prior_arena)"""
+        raise NotImplementedError
 
     def prepare(self):
         dev = self._device()
         self._release()
-        sd = {k[len("model."):]: v for k, v in self.state_dict().items() if k.startswith("model.")}
-        arena, table = pack_prior_arena(self.hp, sd, self.backend_dtype, dev)
+        sd, layout = self._engine_weights()
+        arena, table = pack_prior_arena(self.hp, sd, self.backend_dtype, dev, layout)
         cfg = _lib.K22PriorConfig()
         cfg.dtype = _lib.dtype_code(self.backend_dtype)
         for k in ("text_ctx", "xf_width", "xf_layers", "xf_heads", "clip_dim", "clip_xf_width"):
@@ -227,7 +233,7 @@ class PriorDiffusionModelHIP(NativeModule):
     def transformer(self, x, timesteps, text_emb, text_enc, mask):
         """PriorTransformer.forward (prior.py:226-270); mask [B, text_ctx] bool; the causal mask is built in."""
         if x.device.type != "cuda":
-            raise RuntimeError("PriorDiffusionModelHIP: inputs must be on the GPU (no CPU fallback)")
+            raise RuntimeError(f"{type(self).__name__}: inputs must be on the GPU (no CPU fallback)")
         B = x.shape[0]
         self._ensure_plan(B)
         f = lambda t: t.detach().float().contiguous()  # noqa: E731
@@ -236,6 +242,62 @@ class PriorDiffusionModelHIP(NativeModule):
         _lib.check(_lib.lib().k22_prior_forward(self._handle, xs.data_ptr(), ts.data_ptr(), te.data_ptr(), tq.data_ptr(), mk.data_ptr(),
                                                 out.data_ptr(), _lib.current_stream()))
         return out
+
+    def _run_loop(self, ddim, table, ts, x, nzs, scales, txt_feat, txt_feat_seq, mask, whole, clamp=10.0):
+        """T steps on x [N, D] = [cond | uncond] rows (its own buffer: overwritten): table [T, 8 | 4], ts [T, N] and nzs [T, N, D] (or
+        None: DDIM at eta = 0) in execution order.  `whole`: k22_prior_sample_loop on the module's own buffers, else step by step from
+        here (k22_prior_forward + the step kernel).  Same kernels on the same operands: the routes agree bit for bit.  -> x [N, D]"""
+        N, T = x.shape[0], table.shape[0]
+        bs, D, dev = N // 2, self.hp["clip_dim"], x.device
+        L = _lib.lib()
+        if whole:
+            self._ensure_plan(N)
+            f = lambda t: t.detach().float()  # noqa: E731
+            b = self._loop.stage(
+                (self._handle.value, ddim, T, N, nzs is not None), dev,
+                lambda: dict(x=(N, D), x_tmp=(N, D), timesteps=(T, N), table=tuple(table.shape), noise=None if nzs is None else (T, N, D),
+                             scales=(bs,), text_emb=(N, D), text_enc=tuple(txt_feat_seq.shape), key_valid=tuple(mask.shape)),
+                dict(x=x, timesteps=ts, table=table, noise=nzs, scales=scales, text_emb=f(txt_feat), text_enc=f(txt_feat_seq), key_valid=f(mask)))
+            _lib.check(L.k22_prior_sample_loop(
+                self._handle, _lib.K22_PRIOR_LOOP_DDIM if ddim else _lib.K22_PRIOR_LOOP_ANCESTRAL, b["x"].data_ptr(), b["x_tmp"].data_ptr(),
+                None, b["timesteps"].data_ptr(), b["table"].data_ptr(), _lib.ptr(b["noise"]), b["scales"].data_ptr(), b["text_emb"].data_ptr(),
+                b["text_enc"].data_ptr(), b["key_valid"].data_ptr(), float(clamp), T, int(bool(self.use_graph)), _lib.current_stream()))
+            return b["x"]
+        x_next = torch.empty_like(x)
+        for k in range(T):
+            half = x[:bs]
+            out = self.transformer(torch.cat([half, half], 0), ts[k], txt_feat, txt_feat_seq, mask)
+            if ddim:
+                _lib.check(L.k22_prior_ddim_step(x.data_ptr(), out.data_ptr(), None if nzs is None else nzs[k].data_ptr(), scales.data_ptr(),
+                                                 table[k].data_ptr(), float(clamp), x_next.data_ptr(), None, bs, D, _lib.current_stream()))
+            else:
+                _lib.check(L.k22_prior_sampler_step(x.data_ptr(), out.data_ptr(), nzs[k].data_ptr(), scales.data_ptr(), table[k].data_ptr(),
+                                                    float(clamp), x_next.data_ptr(), bs, D, _lib.current_stream()))
+            x, x_next = x_next, x
+        return x
+
+
+class PriorDiffusionModelHIP(PriorEngineModule):
+    """MI355X-native PriorDiffusionModel (kandinsky2/model/prior.py:273-384): holds PriorTransformer's parameters under
+    `model.*` like the reference, plus the clip_mean / clip_std buffers."""
+
+    def __init__(self, hparams: Optional[dict] = None, diffusion: Optional[dict] = None, clip_mean: Optional[torch.Tensor] = None,
+                 clip_std: Optional[torch.Tensor] = None, backend_dtype: torch.dtype = torch.bfloat16):
+        self.hp = dict(hparams or PRIOR_HPARAMS_2_1)
+        super().__init__({"model." + k: v for k, v in prior_param_shapes(self.hp).items()}, backend_dtype)
+        self.diffusion_kwargs = dict(diffusion or PRIOR_DIFFUSION_2_1)
+        self._init_engine()
+        cd = self.hp["clip_dim"]
+        self.register_buffer("clip_mean", (clip_mean if clip_mean is not None else torch.zeros(cd))[None, :].float(), persistent=False)
+        self.register_buffer("clip_std", (clip_std if clip_std is not None else torch.ones(cd))[None, :].float(), persistent=False)
+
+    def load_state_dict(self, state_dict, strict: bool = True, **kw):
+        if state_dict and not any(k.startswith("model.") for k in state_dict):
+            state_dict = {"model." + k: v for k, v in state_dict.items()}
+        return super().load_state_dict(state_dict, strict=strict, **kw)
+
+    def _engine_weights(self):
+        return {k[len("model."):]: v for k, v in self.state_dict().items() if k.startswith("model.")}, "heads"
 
     @torch.no_grad()
     def forward(self, txt_feat, txt_feat_seq, mask, cf_guidance_scales=None, timestep_respacing=None, denoised_fn=True,
@@ -289,31 +351,6 @@ class PriorDiffusionModelHIP(NativeModule):
         x = noise.to(dev).float().contiguous().clone() if noise is not None else torch.randn(N, D, device=dev)
         # eta = 0 multiplies the noise by sigma = 0: none is drawn, the kernel reads a null pointer as zeros
         nzs = sampling.step_noise(x, T, noise_seq) if (not sched.ddim or sched.eta > 0.0 or noise_seq is not None) else None
-        L = _lib.lib()
-        if whole:
-            self._ensure_plan(N)
-            f = lambda t: t.detach().float()  # noqa: E731
-            b = self._loop.stage(
-                (self._handle.value, sched.ddim, T, N, nzs is not None), dev,
-                lambda: dict(x=(N, D), x_tmp=(N, D), timesteps=(T, N), table=tuple(table.shape), noise=None if nzs is None else (T, N, D),
-                             scales=(bs,), text_emb=(N, D), text_enc=tuple(txt_feat_seq.shape), key_valid=tuple(mask.shape)),
-                dict(x=x, timesteps=ts, table=table, noise=nzs, scales=scales, text_emb=f(txt_feat), text_enc=f(txt_feat_seq), key_valid=f(mask)))
-            _lib.check(L.k22_prior_sample_loop(
-                self._handle, _lib.K22_PRIOR_LOOP_DDIM if sched.ddim else _lib.K22_PRIOR_LOOP_ANCESTRAL, b["x"].data_ptr(), b["x_tmp"].data_ptr(),
-                None, b["timesteps"].data_ptr(), b["table"].data_ptr(), _lib.ptr(b["noise"]), b["scales"].data_ptr(), b["text_emb"].data_ptr(),
-                b["text_enc"].data_ptr(), b["key_valid"].data_ptr(), 10.0, T, int(bool(self.use_graph)), _lib.current_stream()))
-            x = b["x"]
-        else:
-            x_next = torch.empty_like(x)
-            for k in range(T):
-                half = x[:bs]
-                out = self.transformer(torch.cat([half, half], 0), ts[k], txt_feat, txt_feat_seq, mask)
-                if sched.ddim:
-                    _lib.check(L.k22_prior_ddim_step(x.data_ptr(), out.data_ptr(), None if nzs is None else nzs[k].data_ptr(), scales.data_ptr(),
-                                                     table[k].data_ptr(), 10.0, x_next.data_ptr(), None, bs, D, _lib.current_stream()))
-                else:
-                    _lib.check(L.k22_prior_sampler_step(x.data_ptr(), out.data_ptr(), nzs[k].data_ptr(), scales.data_ptr(), table[k].data_ptr(),
-                                                        10.0, x_next.data_ptr(), bs, D, _lib.current_stream()))
-                x, x_next = x_next, x
+        x = self._run_loop(sched.ddim, table, ts, x, nzs, scales, txt_feat, txt_feat_seq, mask, whole)
         sample = x * self.clip_std.to(dev) + self.clip_mean.to(dev)
         return sample[:bs]

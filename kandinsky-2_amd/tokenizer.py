@@ -13,7 +13,8 @@ un-pinned dependency that is not installed here, so the published algorithm of i
   vocabulary = 256 byte symbols, the same 256 with "</w>", the first 48 894 merges of the file, <|startoftext|>, <|endoftext|> (49 408).
 
 `ClipBPETokenizer(path)` reads the merges from `bpe_simple_vocab_16e6.txt.gz` (or the same list as a plain-text `merges.txt`, the
-form the HF CLIP repositories carry); `find_bpe_file(cache_dir)` is where `get_kandinsky2(cache_dir=...)` looks for it.  Checked in
+form the HF CLIP repositories carry, the `tokenizer/` folder of the Kandinsky 2.2 prior among them, whose pipeline pads with
+`padded_ids_and_mask`); `find_bpe_file(cache_dir)` is where `get_kandinsky2(cache_dir=...)` looks for it.  Checked in
 tests/test_host_cpu.py against transformers' independent implementation of the same algorithm (`CLIPTokenizer`) on a generated
 merges list.
 """
@@ -183,3 +184,32 @@ class ClipBPETokenizer:
                 r[-1] = self.eot_token          # a truncated prompt still ends in <|endoftext|>
             out[i, : len(r)] = torch.tensor(r)
         return out, mask
+
+    # -- transformers' CLIPTokenizer(texts, padding="max_length", max_length=77, truncation=True) as the 2.2 prior pipeline calls it ----
+    def padded_ids_and_mask(self, texts, max_length: int = 77, pad_id: int = 0):
+        """-> (input_ids [n, max_length] int64, attention_mask [n, max_length] bool): [sot] + ids[:max_length - 2] + [eot], padded with
+        pad_id; the mask is True on the tokens, the two specials included"""
+        if isinstance(texts, str):
+            texts = [texts]
+        ids = torch.full((len(texts), max_length), int(pad_id), dtype=torch.long)
+        mask = torch.zeros(len(texts), max_length, dtype=torch.bool)
+        for i, t in enumerate(texts):
+            r = [self.sot_token] + self.encode(t)[: max_length - 2] + [self.eot_token]
+            ids[i, : len(r)] = torch.tensor(r)
+            mask[i, : len(r)] = True
+        return ids, mask
+
+    def pad_id_from_folder(self, folder: str, default: int = 0) -> int:
+        """the padding id a transformers tokenizer folder names: pad_token of tokenizer_config.json looked up in vocab.json (else in this
+        vocabulary); `default` when the folder does not say"""
+        import json
+        cfg = os.path.join(folder, "tokenizer_config.json")
+        if not os.path.exists(cfg):
+            return default
+        tok = json.load(open(cfg)).get("pad_token")
+        tok = tok.get("content") if isinstance(tok, dict) else tok
+        if tok is None:
+            return default
+        voc = os.path.join(folder, "vocab.json")
+        table = json.load(open(voc)) if os.path.exists(voc) else self.encoder
+        return int(table.get(tok, default))
