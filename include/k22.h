@@ -76,7 +76,7 @@ const char* k22_last_error(void);
  * "att_pipe" = -1 as K22_ATT_PIPE says (default), 0 / 1: the unmasked 16-bit attention through attention_kernel / attention_pipe_kernel. */
 int k22_set_option(const char* name, int value);
 /* Host counters for tests, since the library was loaded: "stream_launches" = launches of the weight-streaming kernel;
- * "loop_captures" = whole-loop graphs captured by any loop entry (k22_unet_sample_loop[_keep], k22_unet_ddim_loop, k22_prior_sample_loop); "loop_launches" = whole-loop
+ * "loop_captures" = whole-loop graphs captured by any loop entry (k22_unet_sample_loop[_keep], k22_unet_ddim_loop, k22_unet_dpmpp_loop, k22_prior_sample_loop); "loop_launches" = whole-loop
  * replays or eager loop runs.  -1 for an unknown name. */
 long k22_debug_counter(const char* name);
 /* Fragment-major copy of a 16-bit weight matrix [Npad][taps * Kc] for the weight-streaming kernel (1 KB contiguous per MFMA B
@@ -222,6 +222,23 @@ enum { K22_LOOP_DDIM = 0, K22_LOOP_PLMS = 1 };
 int k22_unet_ddim_loop(K22UNet* u, int kind, float* x, float* x_tmp, float* x0_out, const float* timesteps, const float* table,
                        const float* noise_seq, const float* inpaint_image, const float* inpaint_mask, float* eps_hist, int n_steps,
                        float guidance, int use_graph, void* stream);
+/* The whole classifier-free-guided DPM-Solver++ loop (multistep, data-prediction form, orders 1 and 2M; Lu et al. 2022 - the reference has
+ * no such sampler) as ONE hipGraph replay: per step  UNet([x_half | x_half], t) -> k22_dpmpp_step on all B rows (use_cfg = 1).  The
+ * machinery, the counters and the guarantees are k22_unet_ddim_loop's: one captured loop per engine, equal bits with the stepwise calls,
+ * also with use_graph = 0 and under K22_HOIST_TIME=0.  Device buffers, filled by the caller before the call:
+ *   x [B][4][HW]: in x_T, out the final latent;  x_tmp: same-size scratch;
+ *   x0_hist: 2 x [B][4][HW] floats.  Step k writes its data prediction to slot k % 2 and reads slot (k - 1) % 2 when orders[k] == 2; after
+ *     the call slot (n_steps - 1) % 2 holds the predicted x0 of the last step;
+ *   timesteps [n_steps][B]: the raw integer timestep of every model call in execution order;
+ *   table [n_steps][5]: the k22_dpmpp_step rows in execution order;
+ *   inpaint_image / inpaint_mask: 9-channel UNet inputs (required for it), else NULL.
+ * orders is a HOST array of n_steps ints (1 or 2, orders[0] = 1): which rows read the history is resolved when the loop is captured, and
+ * every value is part of the captured loop's key (other orders re-capture).
+ * K22_EINVAL (with a k22_last_error text) for a null argument, an odd B, n_steps < 1, an order outside {1, 2}, orders[0] != 1, a missing
+ * condition / hint, missing inpaint operands or a UNet with out_channels != 8; a refused call leaves the handle and its captured loop as
+ * they were. */
+int k22_unet_dpmpp_loop(K22UNet* u, float* x, float* x_tmp, float* x0_hist, const float* timesteps, const float* table, const int* orders,
+                        const float* inpaint_image, const float* inpaint_mask, int n_steps, float guidance, int use_graph, void* stream);
 int k22_unet_num_ops(const K22UNet* u);
 /* Tile configurations of the convolutions / GEMMs are chosen by measurement during the first k22_unet_forward
  * after k22_unet_plan (default on; env K22_AUTOTUNE=0 or k22_unet_set_autotune(u, 0) before planning = heuristics).
@@ -278,6 +295,14 @@ int k22_ddim_step(const float* x, const float* model_out, const float* noise, co
  * whose ORIGINAL value is not 1 zeroes its up / left / up-left / down / right / down-right neighbours.  mask, out: device fp32
  * [C][H][W], out of place (channel 0 decides, every channel is written). */
 int k22_prepare_mask(const float* mask, float* out, int C, int H, int W, void* stream);
+/* DPM-Solver++ step (multistep, data-prediction form; Lu et al. 2022, "DPM-Solver++", eq. of Algorithm 2 at orders 1 and 2) with the same
+ * guidance fold as k22_ddim_step: e = u + g (c - u) on channels 0-3 of model_out [N][8][HW];
+ *   x0 = (x - sigma_s e) / alpha_s;      x_out = c_x x + c_0 x0 + c_1 x0_prev      (the last term only when x0_prev != NULL)
+ * table_row: device fp32[5] = (alpha_s, sigma_s, c_x, c_0, c_1), the float64 coefficients of kandinsky2_amd.sampling.dpmpp_table rounded
+ * once.  x0_out (required) receives x0: the next step's x0_prev.  Every operation is rounded once.  Out of place: x, x_out, x0_out and
+ * x0_prev are distinct buffers (K22_EINVAL otherwise, and for a null argument or an odd N with use_cfg). */
+int k22_dpmpp_step(const float* x, const float* model_out, const float* x0_prev, const float* table_row, float guidance, int use_cfg,
+                   float* x_out, float* x0_out, int N, int HW, void* stream);
 /* PLMS step (PLMSSampler.p_sample_plms, kandinsky2/model/samplers.py:566-637; eta = 0) with model_fn's guidance folded in:
  * e_t = u + g (c - u) of this model call; e' = Adams-Bashforth combination of e_t and the eps history by `order`
  * (0: e_t; 1: (3 e_t - h1)/2; 2: (23 e_t - 16 h1 + 5 h2)/12; 3: (55 e_t - 59 h1 + 37 h2 - 9 h3)/24; 4: (h1 + e_t)/2, the second

@@ -38,7 +38,7 @@ long loop_launch_count() { return g_loop_launches.load(); }
 void loop_count_capture() { g_loop_captures.fetch_add(1); }
 void loop_count_launch() { g_loop_launches.fetch_add(1); }
 // first word of a captured loop's key: which entry's nodes the graph holds
-enum : unsigned long long { K22_LOOP_KIND_P = 0, K22_LOOP_KIND_DDIM = 1, K22_LOOP_KIND_PLMS = 2, K22_LOOP_KIND_P_KEEP = 3 };
+enum : unsigned long long { K22_LOOP_KIND_P = 0, K22_LOOP_KIND_DDIM = 1, K22_LOOP_KIND_PLMS = 2, K22_LOOP_KIND_P_KEEP = 3, K22_LOOP_KIND_DPMPP = 4 };
 
 namespace {
 
@@ -1089,6 +1089,47 @@ int k22_unet_ddim_loop(K22UNet* u, int kind, float* x, float* x_tmp, float* x0_o
   const std::vector<unsigned long long> key = {kind == K22_LOOP_DDIM ? K22_LOOP_KIND_DDIM : K22_LOOP_KIND_PLMS, loop_key_ptr(x), loop_key_ptr(x_tmp),
       loop_key_ptr(x0_out), loop_key_ptr(timesteps), loop_key_ptr(table), loop_key_ptr(noise_seq), loop_key_ptr(inpaint_image), loop_key_ptr(inpaint_mask),
       loop_key_ptr(eps_hist), (unsigned long long)n_steps, (unsigned long long)(lr.hoist ? 1 : 0), loop_key_bits(guidance)};
+  return u->loop_run(key, timesteps, inpaint_image, inpaint_mask, use_graph, st, body);
+}
+
+// The whole classifier-free-guided DPM-Solver++ loop (multistep, data prediction, orders 1 / 2M; no counterpart in the reference) as ONE
+// hipGraph: the k22_unet_ddim_loop machinery with k22_dpmpp_step as the step.  Step k writes its x0 to slot k % 2 of x0_hist and, when
+// orders[k] == 2, reads slot (k - 1) % 2: the rotation is resolved here, at capture time, like the PLMS ring - so every order is in the key.
+int k22_unet_dpmpp_loop(K22UNet* u, float* x, float* x_tmp, float* x0_hist, const float* timesteps, const float* table, const int* orders,
+                        const float* inpaint_image, const float* inpaint_mask, int n_steps, float guidance, int use_graph, void* stream) {
+  if (!u || !u->ws) return k22_set_error(K22_EINVAL, "unet_dpmpp_loop: bind a workspace first");
+  if (!u->cond_set) return k22_set_error(K22_EINVAL, "unet_dpmpp_loop: call k22_unet_set_condition first");
+  if (!x || !x_tmp || !x0_hist || !timesteps || !table || !orders) return k22_set_error(K22_EINVAL, "unet_dpmpp_loop: null argument");
+  if (n_steps < 1) return k22_set_error(K22_EINVAL, "unet_dpmpp_loop: n_steps must be >= 1");
+  for (int k = 0; k < n_steps; ++k)
+    if (orders[k] != 1 && orders[k] != 2) return k22_set_error(K22_EINVAL, "unet_dpmpp_loop: every order is 1 or 2");
+  if (orders[0] != 1) return k22_set_error(K22_EINVAL, "unet_dpmpp_loop: the first step has no history (orders[0] must be 1)");
+  if (u->B % 2) return k22_set_error(K22_EINVAL, "unet_dpmpp_loop: the batch is the CFG batch [cond | uncond] (even)");
+  if (u->cfg.out_channels != 8) return k22_set_error(K22_EINVAL, "unet_dpmpp_loop: the UNet must predict eps and variance (8 channels)");
+  if (u->cfg.in_channels == 9 && (!inpaint_image || !inpaint_mask)) return k22_set_error(K22_EINVAL, "unet_dpmpp_loop: inpainting UNet needs inpaint_image and inpaint_mask");
+  if (u->cfg.hint_channels && !u->hint_set) return k22_set_error(K22_EINVAL, "unet_dpmpp_loop: call k22_unet_set_hint first");
+  const int B = u->B, HW = u->H * u->W;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  K22UNet::LoopRows lr;
+  if (int rc = u->loop_begin(n_steps, st, &lr)) return rc;
+  const size_t lat = (size_t)B * 4 * HW;
+  auto body = [&](hipStream_t s) -> int {
+    if (int rc = u->loop_prologue(lr, timesteps, n_steps, inpaint_image, inpaint_mask, s)) return rc;
+    float* cur = x; float* nxt = x_tmp;
+    for (int k = 0; k < n_steps; ++k) {
+      if (int rc = u->loop_model(lr, cur, timesteps, k, s)) return rc;
+      float* x0_new = x0_hist + (size_t)(k % 2) * lat;
+      const float* x0_old = orders[k] == 2 ? x0_hist + (size_t)((k + 1) % 2) * lat : nullptr;
+      if (int rc = launch_dpmpp_step(cur, u->model_out(), x0_old, table + (size_t)k * 5, guidance, 1, nxt, x0_new, B, HW, s)) return rc;
+      float* t_ = cur; cur = nxt; nxt = t_;
+    }
+    if (cur != x) return copy_d2d(x, cur, lat * sizeof(float), s);
+    return K22_OK;
+  };
+  std::vector<unsigned long long> key = {K22_LOOP_KIND_DPMPP, loop_key_ptr(x), loop_key_ptr(x_tmp), loop_key_ptr(x0_hist), loop_key_ptr(timesteps),
+      loop_key_ptr(table), loop_key_ptr(inpaint_image), loop_key_ptr(inpaint_mask), (unsigned long long)n_steps,
+      (unsigned long long)(lr.hoist ? 1 : 0), loop_key_bits(guidance)};
+  for (int k = 0; k < n_steps; ++k) key.push_back((unsigned long long)orders[k]);
   return u->loop_run(key, timesteps, inpaint_image, inpaint_mask, use_graph, st, body);
 }
 

@@ -338,6 +338,62 @@ int launch_plms_step(const float* x, const float* model_out, const float* h1, co
   return K22_OK;
 }
 
+// ---- DPM-Solver++ step (multistep, data prediction; orders 1 and 2M) with the same classifier-free guidance fold -----------------------
+// tab = (alpha_s, sigma_s, c_x, c_0, c_1) as fp32: the float64 coefficients of sampling.dpmpp_table, rounded once.
+//   e = u + g (c - u)         x0 = (x - sigma_s e) / alpha_s         x_out = c_x x + c_0 x0 [+ c_1 x0_prev]
+// x0_out always receives x0: it is the next step's history.  x0_prev == NULL is an order-1 step (c_1 is not read).  Out of place.
+// One rounding per operation, in this order: c - u, g *, u +, sigma_s *, x -, / alpha_s, c_x * x, c_0 * x0, their sum, c_1 * x0_prev, the
+// last sum - nine on the longest path (tests/dpmpp_ref.py counts them).  Contraction is switched off for the body and the operations are
+// plain operators: the __f*_rn intrinsics are inline functions compiled under the headers' contraction mode and were fused after inlining
+// (see keep_region_kernel, prestep.hip).
+__global__ __launch_bounds__(256) void dpmpp_step_kernel(const float* x, const float* model_out, const float* x0_prev, const float* tab,
+                                                         float guidance, int use_cfg, float* x_out, float* x0_out, int N, int HW) {
+#pragma clang fp contract(off)
+  const float a_s = tab[0], s_s = tab[1], c_x = tab[2], c_0 = tab[3];
+  const float c_1 = x0_prev != nullptr ? tab[4] : 0.0f;
+  const int64_t total = (int64_t)N * 4 * HW;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int pix = (int)(i % HW);
+    const int c = (int)((i / HW) % 4), n = (int)(i / (4 * (int64_t)HW));
+    float e;
+    if (use_cfg) {
+      const int bs = N / 2, j = n % bs;
+      const float ce = model_out[((int64_t)j * 8 + c) * HW + pix], ue = model_out[((int64_t)(j + bs) * 8 + c) * HW + pix];
+      const float d = ce - ue;
+      const float gd = guidance * d;
+      e = ue + gd;
+    } else {
+      e = model_out[((int64_t)n * 8 + c) * HW + pix];
+    }
+    const float xi = x[i];
+    const float se = s_s * e;
+    const float num = xi - se;
+    const float x0 = num / a_s;
+    const float t_x = c_x * xi, t_0 = c_0 * x0;
+    float out = t_x + t_0;
+    if (x0_prev != nullptr) {
+      const float t_1 = c_1 * x0_prev[i];
+      out = out + t_1;
+    }
+    x_out[i] = out;
+    x0_out[i] = x0;
+  }
+}
+
+int launch_dpmpp_step(const float* x, const float* model_out, const float* x0_prev, const float* tab, float guidance, int use_cfg,
+                      float* x_out, float* x0_out, int N, int HW, hipStream_t s) {
+  if (!x || !model_out || !tab || !x_out || !x0_out) return k22_set_error(K22_EINVAL, "dpmpp_step: null argument");
+  if (N <= 0 || HW <= 0 || (use_cfg && (N & 1))) return k22_set_error(K22_EINVAL, "dpmpp_step: bad batch");
+  if (x_out == x || x0_out == x || x0_out == x_out || (x0_prev && (x0_prev == x0_out || x0_prev == x_out)))
+    return k22_set_error(K22_EINVAL, "dpmpp_step: out of place only (x, x_out, x0_out and x0_prev are four buffers)");
+  const int64_t total = (int64_t)N * 4 * HW;
+  int nb = (int)((total + 255) / 256);
+  if (nb > 2048) nb = 2048;
+  hipLaunchKernelGGL(dpmpp_step_kernel, dim3(nb), dim3(256), 0, s, x, model_out, x0_prev, tab, guidance, use_cfg, x_out, x0_out, N, HW);
+  K22_CHECK_LAUNCH();
+  return K22_OK;
+}
+
 // ---- inpainting mask pre-step (prepare_mask, kandinsky2/utils.py:11-31) ----------------------------------------------------
 // The reference walks the latent-resolution mask in a Python double loop and, for every pixel whose ORIGINAL value is not 1,
 // zeroes six neighbours: up, left, up-left, down, right, down-right (not the anti-diagonal ones).  As a gather: a pixel

@@ -349,6 +349,54 @@ class PLMSSamplerHIP(DDIMSamplerHIP):
         return self._loop("plms", x, sampling.plms_calls(self.ddim_timesteps[::-1].tolist()), None, conditioning, whole_loop_graph)
 
 
+class DPMSolverSamplerHIP(DDIMSamplerHIP):
+    """DPM-Solver++ (multistep, data-prediction form, orders 1 and 2M; Lu et al. 2022) for the decoder UNet - a second-order solver the
+    reference does not have, for generations of fewer model calls.  The step arithmetic and model_fn's guidance are fused into
+    k22_dpmpp_step; coefficients and grid come from sampling.dpmpp_table / sampling.dpmpp_grid in float64.
+
+        sampler = DPMSolverSamplerHIP(model, old_diffusion, guidance_scale)
+        samples, aux = sampler.sample(20, batch_size * 2, (4, h, w), conditioning=model_kwargs, x_T=noise)
+
+    discretize="logsnr" (the default) places the steps uniformly in log-SNR, which is what the second order needs: on the reference's
+    uniform-in-t grid ("uniform") the solver gains next to nothing.  It may run FEWER than S steps (sampling.dpmpp_grid); the count is
+    len(sampler.timesteps).  With solver_order=1 and discretize="uniform" it is the eta = 0 DDIM sampler in another arrangement."""
+
+    def _dpm_step(self, x, model_out, x0_prev, table_row, x_out, x0_out):
+        """One fused k22_dpmpp_step launch."""
+        sampling.dpmpp_step(x, model_out, x0_prev, table_row, x_out, x0_out, guidance=self.guidance_scale)
+
+    def make_dpm_schedule(self, S, solver_order=2, lower_order_final=True, discretize="logsnr", init_step=None):
+        """self.timesteps (execution order), self.dpm_table (float64 [n,5]) and self.orders of a generation"""
+        ac = self.old_diffusion.alphas_cumprod
+        self.timesteps = sampling.dpmpp_grid(ac, S, discretize, init_step)
+        ac_t = np.asarray(ac[self.timesteps[1:]].tolist() + [ac[0]])[: len(self.timesteps)]
+        self.dpm_table, self.orders = sampling.dpmpp_table(ac[self.timesteps], ac_t, solver_order, lower_order_final)
+
+    @torch.no_grad()
+    def sample(self, S, batch_size, shape, conditioning=None, eta=0.0, x_T=None, init_step=None, device="cuda",
+               whole_loop_graph: bool = False, solver_order: int = 2, lower_order_final: bool = True, discretize: str = "logsnr", **_unused):
+        """whole_loop_graph=True: the whole loop as one hipGraph (Text2ImUNetHIP.dpmpp_loop -> k22_unet_dpmpp_loop); same kernels, same bits."""
+        if eta != 0:
+            raise ValueError("DPM-Solver++ here is the deterministic (ODE) solver: eta must be 0")
+        if solver_order not in (1, 2):
+            raise ValueError("solver_order must be 1 or 2")
+        if discretize not in ("logsnr", "uniform"):
+            raise ValueError('discretize must be "logsnr" or "uniform"')
+        self.make_dpm_schedule(S, solver_order, lower_order_final, discretize, init_step)
+        x = self._x_T(batch_size, shape, x_T, device)
+        n = len(self.timesteps)
+        ts_rows = torch.tensor(self.timesteps.astype(np.float32), device=x.device).reshape(n, 1).expand(n, x.shape[0]).contiguous()
+        table = torch.from_numpy(self.dpm_table.astype(np.float32)).to(x.device)      # the one rounding of the coefficients
+        kw = conditioning or {}
+        if n == 0:
+            x0 = x.clone()
+        elif whole_loop_graph and hasattr(self.model, "dpmpp_loop"):
+            x, x0 = self.model.dpmpp_loop(x, ts_rows, table, self.orders, self.guidance_scale, **kw)
+        else:
+            x, x0 = sampling.dpmpp_loop(sampling.fused_call(self.model, ts_rows, **kw), x, table, self.orders, self._dpm_step)
+        return x, {"pred_x0": [x0]}
+
+
 def create_gaussian_diffusion(**kw) -> SpacedDiffusionHIP:
     """Keyword-compatible with the reference's create_gaussian_diffusion (model_creation.py:86-128)."""
     return SpacedDiffusionHIP(**kw)

@@ -33,7 +33,7 @@ import torch
 
 from . import _lib
 from .arch import DIFFUSION_CONFIG_2_1, MODEL_CONFIG_2_1, make_arch
-from .diffusion import DDIMSamplerHIP, PLMSSamplerHIP, create_gaussian_diffusion
+from .diffusion import DDIMSamplerHIP, DPMSolverSamplerHIP, PLMSSamplerHIP, create_gaussian_diffusion
 from .movq import MOVQ_CONFIG_2_1, MoVQDecoderHIP, MoVQEncoderHIP
 from .prior import PRIOR_DIFFUSION_2_1, PRIOR_HPARAMS_2_1, PriorDiffusionModelHIP
 from .unet import Text2ImUNetHIP
@@ -182,7 +182,7 @@ class Kandinsky2_1HIP:
         self.task_type = task_type
         self.backend_dtype = backend_dtype
         # every sampler: the whole denoising loop as ONE hipGraph replay (p_sampler: k22_unet_sample_loop; ddim_sampler / plms_sampler:
-        # k22_unet_ddim_loop) - on whenever graphs are
+        # k22_unet_ddim_loop; dpm_sampler: k22_unet_dpmpp_loop) - on whenever graphs are
         self.whole_loop_graph = use_graph if whole_loop_graph is None else bool(whole_loop_graph)
         self.use_fp16 = False                       # public tensors are fp32; engine precision is backend_dtype
         self.model_dtype = torch.float32
@@ -292,8 +292,9 @@ class Kandinsky2_1HIP:
                 self.model, (full_batch_size, 4, new_h, new_w), device=self.device, noise=noise, model_kwargs=model_kwargs,
                 init_step=init_step, guidance_scale=guidance_scale, init_img=init_img, img_mask=img_mask, noise_seq=noise_seq,
                 whole_loop_graph=self.whole_loop_graph)[:batch_size]
-        elif sampler in ("ddim_sampler", "plms_sampler"):
-            cls = DDIMSamplerHIP if sampler == "ddim_sampler" else PLMSSamplerHIP
+        elif sampler in ("ddim_sampler", "plms_sampler", "dpm_sampler"):
+            # dpm_sampler: DPM-Solver++ 2M on the log-SNR grid (not in the reference; for generations of ~20 model calls)
+            cls = {"ddim_sampler": DDIMSamplerHIP, "plms_sampler": PLMSSamplerHIP, "dpm_sampler": DPMSolverSamplerHIP}[sampler]
             samples, _ = cls(self.model, diffusion, guidance_scale).sample(
                 num_steps, batch_size * 2, (4, new_h, new_w), conditioning=model_kwargs, x_T=noise, init_step=init_step, device=self.device,
                 whole_loop_graph=self.whole_loop_graph)

@@ -1,5 +1,5 @@
 """The host-driven step loops of the three decoder samplers, each written once, and the only ctypes callers of their step kernels
-(k22_sampler_step, k22_ddim_step, k22_plms_step).  SpacedDiffusionHIP.p_sample_loop, DDIMSamplerHIP / PLMSSamplerHIP.sample (diffusion.py)
+(k22_sampler_step, k22_ddim_step, k22_plms_step, k22_dpmpp_step).  SpacedDiffusionHIP.p_sample_loop, DDIMSamplerHIP / PLMSSamplerHIP.sample (diffusion.py)
 and the two-chain branches of Text2ImUNetHIP.sample_loop / ddim_loop (unet.py) run them; the captured single-chain loops are the same
 sequences in C++ (csrc/engine.hip).  A loop takes `model_call(latent, call_index) -> [N,8,H,W]`, the schedule rows in execution order
 and a step launcher, to which it hands its keywords (guidance, clamp, ...) through: the host tests pass recording launchers.
@@ -79,6 +79,72 @@ def plms_calls(steps: list) -> list:
     return [steps[0], steps[min(1, len(steps) - 1)]] + steps[1:] if steps else []
 
 
+# ---- DPM-Solver++ (2M, data prediction): grid and coefficient table, float64, no GPU -----------------------------------------------------
+def log_snr(ac) -> np.ndarray:
+    """lambda = ln(alpha / sigma) of alphas_cumprod values, alpha = sqrt(ac), sigma = sqrt(1 - ac)"""
+    ac = np.asarray(ac, dtype=np.float64)
+    return 0.5 * (np.log(ac) - np.log1p(-ac))
+
+
+def dpmpp_grid(ac, S: int, discretize: str = "logsnr", init_step=None) -> np.ndarray:
+    """The integer timesteps of a DPM-Solver++ generation in EXECUTION order (noisy first) on the float64 alphas_cumprod `ac` of the
+    un-respaced schedule; the last step targets ac[0].
+      "uniform": DDIMSamplerHIP.make_schedule's grid (1, 1 + T // S, ...), flipped.
+      "logsnr":  S + 1 targets uniform in lambda from lambda(ac[T - 1]) to lambda(ac[0]); for each of the first S the integer t in
+                 1 .. T - 1 whose lambda(ac[t]) is nearest, duplicates dropped - so the result may hold FEWER than S steps (the 2.1
+                 schedule: S = 20 gives 20, S = 50 gives 48: near t = T the schedule itself is coarser in lambda than the targets).
+    init_step keeps the timesteps t <= init_step (apply_init_step)."""
+    ac = np.asarray(ac, dtype=np.float64)
+    T, S = len(ac), int(S)
+    if S < 1:
+        raise ValueError("dpmpp_grid: S must be >= 1")
+    if discretize == "uniform":
+        steps = (np.asarray(list(range(0, T, T // S))) + 1)[::-1]
+    elif discretize == "logsnr":
+        lam = log_snr(ac)
+        cand = np.arange(1, T)
+        steps = []
+        for target in np.linspace(lam[T - 1], lam[0], S + 1)[:S]:
+            t = int(cand[np.argmin(np.abs(lam[cand] - target))])
+            if t not in steps:
+                steps.append(t)
+        steps = np.asarray(steps)
+    else:
+        raise ValueError(f'dpmpp_grid: discretize must be "logsnr" or "uniform"; got {discretize!r}')
+    if init_step is not None:
+        steps = np.array([i for i in steps if i <= init_step])
+    return steps.astype(np.int64)
+
+
+def dpmpp_table(ac_s, ac_t, solver_order: int = 2, lower_order_final: bool = True):
+    """DPM-Solver++ multistep coefficients, data-prediction form.  ac_s / ac_t: float64 alphas_cumprod of every step's current and target
+    point, in execution order.  Returns (table float64 [n][5], orders int [n]); row k = (alpha_s, sigma_s, c_x, c_0, c_1) with
+
+        x0_s = (x - sigma_s e) / alpha_s            x_t = c_x x + c_0 x0_s + c_1 x0_prev
+
+    h = lambda_t - lambda_s > 0, phi = -expm1(-h).  Order 1: c_x = sigma_t / sigma_s, c_0 = alpha_t phi, c_1 = 0 exactly (the eta = 0 DDIM
+    update).  Order 2 (2M), r = h_prev / h: c_0 = alpha_t phi (1 + 1 / (2 r)), c_1 = -alpha_t phi / (2 r).  orders[k] = 1 for k = 0, for
+    solver_order 1 and, with lower_order_final, for the last step; else 2.  Everything in float64; the caller rounds to fp32 once."""
+    if solver_order not in (1, 2):
+        raise ValueError("dpmpp_table: solver_order must be 1 or 2")
+    ac_s, ac_t = np.asarray(ac_s, dtype=np.float64), np.asarray(ac_t, dtype=np.float64)
+    if ac_s.shape != ac_t.shape or ac_s.ndim != 1:
+        raise ValueError("dpmpp_table: ac_s and ac_t are 1-D arrays of one length")
+    n = len(ac_s)
+    a_s, s_s, a_t, s_t = np.sqrt(ac_s), np.sqrt(1.0 - ac_s), np.sqrt(ac_t), np.sqrt(1.0 - ac_t)
+    h = log_snr(ac_t) - log_snr(ac_s)
+    phi = -np.expm1(-h)
+    table, orders = np.zeros((n, 5), dtype=np.float64), np.ones(n, dtype=np.int32)
+    table[:, 0], table[:, 1], table[:, 2], table[:, 3] = a_s, s_s, s_t / s_s, a_t * phi
+    for k in range(1, n):
+        if solver_order == 2 and not (lower_order_final and k == n - 1):
+            inv2r = h[k] / (2.0 * h[k - 1])          # 1 / (2 r), r = h_prev / h
+            orders[k] = 2
+            table[k, 3] = a_t[k] * phi[k] * (1.0 + inv2r)
+            table[k, 4] = -a_t[k] * phi[k] * inv2r
+    return table, orders
+
+
 def sampler_scratch(x: torch.Tensor) -> torch.Tensor:
     return torch.empty(_lib.lib().k22_sampler_scratch_bytes(x.shape[0], x.shape[2] * x.shape[3]), dtype=torch.uint8, device=x.device)
 
@@ -104,6 +170,13 @@ def plms_step(x, model_out, hist, order, row, x_out, eps_out, x0_out, *, guidanc
     _lib.check(_lib.lib().k22_plms_step(x.data_ptr(), model_out.data_ptr(), h[0], h[1], h[2], order, row.data_ptr(), float(guidance), 1,
                                         x_out.data_ptr(), _lib.ptr(eps_out), _lib.ptr(x0_out), x.shape[0], x.shape[2] * x.shape[3],
                                         _lib.current_stream()))
+
+
+def dpmpp_step(x, model_out, x0_prev, row, x_out, x0_out, *, guidance):
+    """One k22_dpmpp_step launch: `row` = the step's [5] table row (dpmpp_table); x0_prev = the previous step's x0_out for an order-2 row,
+    None for an order-1 row; x0_out always receives this step's data prediction."""
+    _lib.check(_lib.lib().k22_dpmpp_step(x.data_ptr(), model_out.data_ptr(), _lib.ptr(x0_prev), row.data_ptr(), float(guidance), 1,
+                                         x_out.data_ptr(), x0_out.data_ptr(), x.shape[0], x.shape[2] * x.shape[3], _lib.current_stream()))
 
 
 # ---- the loops -------------------------------------------------------------------------------------------------------------------------
@@ -135,6 +208,22 @@ def plms_loop(model_call, x, rows, step, **operands):
             step(x, out, hist, len(hist), row, x_next, eps, x0, **operands)
         call += 1
         hist = [eps] + hist[:2]
+        x, x_next = x_next, x
+    return x, x0
+
+
+def dpmpp_loop(model_call, x, rows, orders, step, **operands):
+    """DPM-Solver++ over the [n,5] table `rows` (dpmpp_table) and the host ints `orders`: per step k one model call and
+    step(x, model_out, x0_prev, rows[k], x_next, x0_out).  Step k writes its x0 to slot k % 2 of a ring of two and, when orders[k] == 2,
+    reads slot (k - 1) % 2 - the launches of k22_unet_dpmpp_loop.  Returns (final latent, x0 of the last step)."""
+    x_next, hist = torch.empty_like(x), [torch.empty_like(x), torch.empty_like(x)]
+    x0 = hist[0]
+    for k, row in enumerate(rows):
+        order = int(orders[k])
+        if order not in (1, 2) or (k == 0 and order != 1):
+            raise ValueError("dpmpp_loop: orders are 1 or 2, and the first step is order 1 (it has no history)")
+        x0 = hist[k % 2]
+        step(x, model_call(x, k), hist[(k - 1) % 2] if order == 2 else None, row, x_next, x0, **operands)
         x, x_next = x_next, x
     return x, x0
 

@@ -89,8 +89,8 @@ class Text2ImUNetHIP(NativeModule):
     def _release(self):
         super()._release()
         self._plan_key = self._cond_key = None          # _plan_key: (B, H, W) of the whole batch, which two chains split between their engines
-        # operand buffers of sample_loop and of ddim_loop: one set each, never shared (the engine's captured loop holds their addresses)
-        self._loop_bufs, self._ddim_bufs = sampling.OwnedBuffers(), sampling.OwnedBuffers()
+        # operand buffers of sample_loop, ddim_loop and dpmpp_loop: one set each, never shared (the engine's captured loop holds their addresses)
+        self._loop_bufs, self._ddim_bufs, self._dpmpp_bufs = sampling.OwnedBuffers(), sampling.OwnedBuffers(), sampling.OwnedBuffers()
 
     def arena_table(self):
         """name -> (byte offset, byte size) of the packed arena, derived from shapes only."""
@@ -356,6 +356,40 @@ class Text2ImUNetHIP(NativeModule):
             bufs["ts"].data_ptr(), bufs["table"].data_ptr(), _lib.ptr(bufs["noise"]), _lib.ptr(bufs["img"]), _lib.ptr(bufs["msk"]),
             _lib.ptr(bufs["hist"]), n_steps, g, 1 if self.use_graph else 0, _lib.current_stream()))
         return bufs["x"].clone(), bufs["x0"].clone()
+
+    @torch.no_grad()
+    def dpmpp_loop(self, x, ts_rows, table, orders, guidance_scale, *, full_emb=None, pooled_emb=None, image_emb=None, inpaint_image=None,
+                   inpaint_mask=None):
+        """The whole guided DPM-Solver++ loop as ONE hipGraph replay (k22_unet_dpmpp_loop); returns (final latent, predicted x0 of the last
+        step), both [N,4,h,w].  x = x_T; table [n_steps, 5]: the k22_dpmpp_step rows and orders (host ints, 1 or 2): sampling.dpmpp_table's
+        pair, in execution order; ts_rows [n_steps, N]: the timestep of every model call.  As in ddim_loop the operands are copied into
+        buffers this module OWNS: a second generation of the same shape, step count and orders replays the capture."""
+        B, Cx, H, W = x.shape
+        if Cx != 4 or x.device.type != "cuda":
+            raise ValueError("dpmpp_loop: x must be [N,4,h,w] on the GPU")
+        n_steps = table.shape[0]
+        orders = [int(o) for o in orders]
+        if n_steps < 1 or tuple(table.shape) != (n_steps, 5) or tuple(ts_rows.shape) != (n_steps, B) or len(orders) != n_steps:
+            raise ValueError("dpmpp_loop: table must be [n_steps, 5], ts_rows [n_steps, N] and orders n_steps ints")
+        self._ensure_plan(B, H, W)
+        self._ensure_condition(full_emb, pooled_emb, image_emb)
+        img, msk = self._inpaint_operands(x, inpaint_image, inpaint_mask)
+        dev, g = x.device, float(guidance_scale)
+        if self._chained(B):
+            # two chains: host-driven, per model call the two half-batch graphs side by side (see sample_loop).  The steps of k22_unet_dpmpp_loop.
+            call = sampling.fused_call(self.forward, ts_rows, inpaint_image=img, inpaint_mask=msk)
+            return sampling.dpmpp_loop(call, x.detach().float().clone(), table.float().contiguous(), orders, sampling.dpmpp_step, guidance=g)
+        box, img9 = (B, 4, H, W), self.arch.inpainting
+        bufs = self._dpmpp_bufs.stage(
+            (B, H, W, n_steps, str(dev)), dev,
+            lambda: dict(x=box, tmp=box, hist=(2,) + box, ts=(n_steps, B), table=(n_steps, 5), img=box if img9 else None,
+                         msk=(B, 1, H, W) if img9 else None),
+            dict(x=x, ts=ts_rows, table=table, img=img, msk=msk))
+        _lib.check(_lib.lib().k22_unet_dpmpp_loop(
+            self._handle, bufs["x"].data_ptr(), bufs["tmp"].data_ptr(), bufs["hist"].data_ptr(), bufs["ts"].data_ptr(), bufs["table"].data_ptr(),
+            (C.c_int * n_steps)(*orders), _lib.ptr(bufs["img"]), _lib.ptr(bufs["msk"]), n_steps, g, 1 if self.use_graph else 0,
+            _lib.current_stream()))
+        return bufs["x"].clone(), bufs["hist"][(n_steps - 1) % 2].clone()
 
 
 def create_model(backend_dtype: torch.dtype = torch.bfloat16, use_graph: bool = True, inpainting: bool = False,
