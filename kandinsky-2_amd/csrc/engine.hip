@@ -104,9 +104,9 @@ struct K22UNet : GraphPlan {   // dtype: arithmetic type of the MFMA kernels (K2
     return K22_OK;
   }
   bool cond_set = false;
-  // the whole denoising loop as ONE graph (k22_unet_sample_loop): valid for exactly the buffers / scalars it was captured with
-  GraphCache loop;
-  std::vector<unsigned long long> loop_key;
+  // the whole denoising loop as ONE graph (any of the k22_unet_*_loop entries, unet_loop below): valid for exactly the buffers / scalars
+  // it was captured with
+  LoopCache loop;
 
   // persistent slots
   Slot *s_xin, *s_img, *s_mask, *s_t, *s_out;
@@ -149,9 +149,9 @@ struct K22UNet : GraphPlan {   // dtype: arithmetic type of the MFMA kernels (K2
     return launch_linear_smallm(le, tw.dt, st);
   }
 
-  // (Round 4's "two half-batch chains" mode - the CFG pair as two engines on two streams, +3.9 % - is gone: it rested on a work-around for
-  // a kernel pair whose co-resident victim returned wrong elements.  Round 5 narrowed that to the victim's packed-fp32 instructions
-  // (profiles/r05_two_stream_probe.txt; `make NOPK=1` builds the library without them): INTEGRATION.md G.)
+  // (The "two half-batch chains" mode - the CFG pair as two engines on two streams - lives above this file: Text2ImUNetHIP(chains=2) drives
+  // two handles of this engine from the host (unet.py, K22_CHAINS in INTEGRATION.md, bench.py --chains) and needs a library built without
+  // packed-fp32 instructions, the Makefile's default NOPK=1.  No whole-loop graph runs under it.)
   // the [B][out_channels][HW] model output
   float* model_out() { return ptr<float>(s_out); }
   int exec(hipStream_t st) { return run_ops(st); }
@@ -166,7 +166,16 @@ struct K22UNet : GraphPlan {   // dtype: arithmetic type of the MFMA kernels (K2
     if (film_all) (void)hipFree(film_all);
   }
 
-  // ---- shared body of the whole-loop entries (k22_unet_sample_loop, k22_unet_ddim_loop) -------------------------------------------
+  // ---- what k22_unet_forward and the whole-loop entries share ----------------------------------------------------------------------
+  // the 9-channel UNet's constant inputs into their slots
+  int stage_inpaint(const float* inpaint_image, const float* inpaint_mask, hipStream_t s) {
+    if (cfg.in_channels != 9) return K22_OK;
+    const size_t pb = (size_t)B, hw = (size_t)H * W;
+    if (int rc = copy_d2d(ptr(s_img), inpaint_image, pb * 4 * hw * 4, s)) return rc;
+    return copy_d2d(ptr(s_mask), inpaint_mask, pb * hw * 4, s);
+  }
+
+  // ---- the whole-loop entries (k22_unet_sample_loop[_keep], k22_unet_ddim_loop, k22_unet_dpmpp_loop): pieces of unet_loop below -------
   // A loop is n_calls model calls, each  UNet([x_half | x_half], timesteps[call])  followed by the entry's own sampler kernels.
   struct LoopRows {   // hoisted time / FiLM rows of all model calls (null members: per-call launches)
     bool hoist = false;
@@ -204,12 +213,7 @@ struct K22UNet : GraphPlan {   // dtype: arithmetic type of the MFMA kernels (K2
         if (rc) return rc;
       }
     }
-    if (cfg.in_channels == 9) {
-      const size_t pb = (size_t)B, hw = (size_t)H * W;
-      if (int rc = copy_d2d(ptr(s_img), inpaint_image, pb * 4 * hw * 4, s)) return rc;
-      if (int rc = copy_d2d(ptr(s_mask), inpaint_mask, pb * hw * 4, s)) return rc;
-    }
-    return K22_OK;
+    return stage_inpaint(inpaint_image, inpaint_mask, s);
   }
   // model call number `call` of the loop on the latent `cur` [B][4][HW]; the output is model_out()
   int loop_model(const LoopRows& lr, const float* cur, const float* timesteps, int call, hipStream_t s) {
@@ -224,38 +228,16 @@ struct K22UNet : GraphPlan {   // dtype: arithmetic type of the MFMA kernels (K2
     }
     return exec(s);
   }
-  // `body` (one pass over the whole loop on a stream: what is captured is exactly what an eager call runs) eagerly, or as the ONE captured loop
-  // of this engine, valid for `key`: every pointer and scalar baked into its nodes, the entry's kind first.
-  template <typename F> int loop_run(const std::vector<unsigned long long>& key, const float* timesteps, const float* inpaint_image,
-                                     const float* inpaint_mask, int use_graph, hipStream_t st, F body) {
-    auto run_loop = [&](hipStream_t s) -> int { const int rc = body(s); film_cur = nullptr; return rc; };
-    if (!use_graph) {
-      const int rc = run_loop(st);
-      if (rc == K22_OK) loop_count_launch();
-      return rc;
-    }
-    if (!loop || key != loop_key) {
-      if (!warmed) {   // first forward of this plan: run one step's ops eagerly (function attributes, code load) on a scratch input; a re-capture
-                       // for other scalars / buffers (guidance, step count: they are baked into the graph's nodes) does not repeat it
-        const size_t pb = (size_t)B, hw = (size_t)H * W;
-        hipError_t e = hipMemsetAsync(ptr(s_xin), 0, pb * 4 * hw * 4, st);
-        if (e != hipSuccess) return k22_set_error_hip(e, __FILE__, __LINE__);
-        if (int rc = copy_d2d(ptr(s_t), timesteps, pb * 4, st)) return rc;
-        if (cfg.in_channels == 9) {
-          if (int rc = copy_d2d(ptr(s_img), inpaint_image, pb * 4 * hw * 4, st)) return rc;
-          if (int rc = copy_d2d(ptr(s_mask), inpaint_mask, pb * hw * 4, st)) return rc;
-        }
-        if (int rc = exec_eager(st)) return rc;
-        e = hipStreamSynchronize(st);
-        if (e != hipSuccess) return k22_set_error_hip(e, __FILE__, __LINE__);
-      }
-      if (int rc = loop.capture(cap, run_loop)) return rc;
-      loop_key = key;
-      loop_count_capture();
-    }
-    const int rc = loop.launch(st);
-    if (rc == K22_OK) loop_count_launch();
-    return rc;
+  // before the first capture of a plan: one step's ops eagerly (function attributes, code load) on a scratch input.  A re-capture for other
+  // scalars / buffers (guidance, step count: they are baked into the graph's nodes) does not repeat it.
+  int loop_warm(const float* timesteps, const float* inpaint_image, const float* inpaint_mask, hipStream_t st) {
+    hipError_t e = hipMemsetAsync(ptr(s_xin), 0, (size_t)B * 4 * H * W * 4, st);
+    if (e != hipSuccess) return k22_set_error_hip(e, __FILE__, __LINE__);
+    if (int rc = copy_d2d(ptr(s_t), timesteps, (size_t)B * 4, st)) return rc;
+    if (int rc = stage_inpaint(inpaint_image, inpaint_mask, st)) return rc;
+    if (int rc = exec_eager(st)) return rc;
+    e = hipStreamSynchronize(st);
+    return e == hipSuccess ? (int)K22_OK : k22_set_error_hip(e, __FILE__, __LINE__);
   }
 
   // One forward on `st`: the op list in order.  (A variant that forked the time-embedding / FiLM GEMV onto a second stream,
@@ -839,13 +821,73 @@ struct K22UNet : GraphPlan {   // dtype: arithmetic type of the MFMA kernels (K2
   }
 };
 
+static int refuse(const char* who, const char* what) { return k22_set_error(K22_EINVAL, (std::string(who) + ": " + what).c_str()); }
+
+// what a forward needs of the handle, asked by k22_unet_forward and every loop entry; `who`: the entry's name, the prefix of its messages
+static int unet_ready(const K22UNet* u, const char* who, const float* inpaint_image, const float* inpaint_mask) {
+  if (!u || !u->ws) return refuse(who, "bind a workspace first");
+  if (!u->cond_set) return refuse(who, "call k22_unet_set_condition first");
+  if (u->cfg.in_channels == 9 && (!inpaint_image || !inpaint_mask)) return refuse(who, "inpainting UNet needs inpaint_image and inpaint_mask");
+  if (u->cfg.hint_channels && !u->hint_set) return refuse(who, "call k22_unet_set_hint first");
+  return K22_OK;
+}
+
+// ---- the one driver of the whole-loop entries ---------------------------------------------------------------------------------------------
+// A loop updates x [B][4][HW] in place over n_steps steps (x_tmp: scratch of the same size, the other end of the ping-pong) with n_calls model
+// calls in all, on device buffers the caller filled BEFORE the call (timesteps [n_calls][B]: the values the UNet receives, in execution
+// order).  Eagerly, or as the engine's ONE captured graph, replayed as long as the same buffers and scalars are passed (a generation service
+// re-uses its buffers); anything else, another kind included, re-captures.
+struct UNetLoop {
+  const char* who;           // the entry's name: prefix of the refusals
+  unsigned long long kind;   // K22_LOOP_KIND_*: first word of the key
+  float *x, *x_tmp;
+  const float *timesteps, *inpaint_image, *inpaint_mask;
+  int n_steps, n_calls, use_graph;
+  void* stream;
+};
+// The entry supplies
+//   own_fault()                   its own argument checks, asked once the handle is known to be bound: the message of the first one that fails, or null
+//   step(k, cur, nxt, model, s)   the launches of step k behind its first model call (done: model_out() holds UNet(cur)), writing the next latent to
+//                                 nxt; model(latent) runs the loop's next model call on another latent (PLMS: its first step calls it on nxt)
+//   key_tail(key)                 appends every pointer and scalar the step bakes into its nodes (the operands above are the driver's to add);
+//                                 asked after the checks, so it may read the host arrays they vouch for
+// Everything is validated before loop_begin, which may drop the captured loop: a refused call leaves the handle as it was.
+template <typename Fault, typename Step, typename Tail>
+static int unet_loop(K22UNet* u, const UNetLoop& a, Fault own_fault, Step step, Tail key_tail) {
+  if (int rc = unet_ready(u, a.who, a.inpaint_image, a.inpaint_mask)) return rc;
+  if (const char* what = own_fault()) return refuse(a.who, what);
+  if (u->B % 2) return refuse(a.who, "the batch is the CFG batch [cond | uncond] (even)");
+  if (u->cfg.out_channels != 8) return refuse(a.who, "the UNet must predict eps and variance (8 channels)");
+  hipStream_t st = reinterpret_cast<hipStream_t>(a.stream);
+  K22UNet::LoopRows lr;
+  if (int rc = u->loop_begin(a.n_calls, st, &lr)) return rc;
+  auto steps = [&](hipStream_t s) -> int {
+    if (int rc = u->loop_prologue(lr, a.timesteps, a.n_calls, a.inpaint_image, a.inpaint_mask, s)) return rc;
+    float* cur = a.x; float* nxt = a.x_tmp;
+    int call = 0;
+    auto model = [&](const float* latent) { return u->loop_model(lr, latent, a.timesteps, call++, s); };
+    for (int k = 0; k < a.n_steps; ++k) {
+      if (int rc = model(cur)) return rc;
+      if (int rc = step(k, cur, nxt, model, s)) return rc;
+      float* t_ = cur; cur = nxt; nxt = t_;
+    }
+    if (cur != a.x) return copy_d2d(a.x, cur, (size_t)u->B * 4 * u->H * u->W * sizeof(float), s);
+    return K22_OK;
+  };
+  auto body = [&](hipStream_t s) -> int { const int rc = steps(s); u->film_cur = nullptr; return rc; };
+  std::vector<unsigned long long> key = {a.kind, loop_key_ptr(a.x), loop_key_ptr(a.x_tmp), loop_key_ptr(a.timesteps), loop_key_ptr(a.inpaint_image),
+      loop_key_ptr(a.inpaint_mask), (unsigned long long)a.n_steps, (unsigned long long)(lr.hoist ? 1 : 0)};
+  key_tail(key);
+  // a plan that has not run a forward has no captured loop either (begin_plan drops both): this is the warm-up before a first capture
+  if (a.use_graph && !u->warmed) { if (int rc = u->loop_warm(a.timesteps, a.inpaint_image, a.inpaint_mask, st)) return rc; }
+  return u->loop.run(u->cap, key, a.use_graph, st, body);
+}
+
 // The whole classifier-free-guided p_sampler loop of Kandinsky2_1.generate_img (kandinsky2_1_model.py:222-257 ->
 // gaussian_diffusion.py:384-475) as ONE hipGraph: for every step  UNet([x_half | x_half], t_k) -> k22_sampler_step  with no host work
-// between steps (the reference returns to Python - and to the CPU for np.percentile - at every step).  All inputs are device buffers
-// the caller fills BEFORE the call: timesteps [n_steps][B] (the values the UNet receives, in execution order), noise_seq
-// [n_steps][B][4][HW] (the ancestral noise of every step, drawn up front), table [T][8] + table_rows[k] (host array: the schedule row
-// of step k).  x [B][4][HW] is updated in place (x_tmp: scratch of the same size).  The captured graph is replayed as long as the
-// same buffers and scalars are passed (a generation service re-uses its buffers); anything else re-captures.
+// between steps (the reference returns to Python - and to the CPU for np.percentile - at every step).  Beside the driver's operands:
+// noise_seq [n_steps][B][4][HW] (the ancestral noise of every step, drawn up front), table [T][8] + table_rows[k] (host array: the
+// schedule row of step k).
 // keep_* (all four or none): after every step the known region of the 2.2 inpainting pipeline is re-imposed on the freshly written latent
 // (launch_keep_region, prestep.hip) with keep_coef[k] = (sa, sb) of step k, a HOST array; none = the loop k22_unet_sample_loop has always run.
 static int unet_sample_loop_body(K22UNet* u, float* x, float* x_tmp, const float* timesteps, const float* noise_seq, const float* init_img,
@@ -853,53 +895,35 @@ static int unet_sample_loop_body(K22UNet* u, float* x, float* x_tmp, const float
                                  const int* table_rows, int n_steps, float guidance, float clamp_lo, float clamp_hi, int pct_index,
                                  double pct_gamma, void* scratch, const float* keep_init, const float* keep_noise, const float* keep_mask,
                                  const float* keep_coef, int use_graph, void* stream) {
-  if (!u || !u->ws) return k22_set_error(K22_EINVAL, "unet_sample_loop: bind a workspace first");
-  if (!u->cond_set) return k22_set_error(K22_EINVAL, "unet_sample_loop: call k22_unet_set_condition first");
-  if (!x || !x_tmp || !timesteps || !noise_seq || !table || !table_rows || !scratch || n_steps < 1)
-    return k22_set_error(K22_EINVAL, "unet_sample_loop: null argument");
-  if (u->B % 2) return k22_set_error(K22_EINVAL, "unet_sample_loop: the batch is the CFG batch [cond | uncond] (even)");
-  if (u->cfg.out_channels != 8) return k22_set_error(K22_EINVAL, "unet_sample_loop: the UNet must predict eps and variance (8 channels)");
-  if (u->cfg.in_channels == 9 && (!inpaint_image || !inpaint_mask)) return k22_set_error(K22_EINVAL, "unet_sample_loop: inpainting UNet needs inpaint_image and inpaint_mask");
-  if (u->cfg.hint_channels && !u->hint_set) return k22_set_error(K22_EINVAL, "unet_sample_loop: call k22_unet_set_hint first");
-  const int B = u->B, HW = u->H * u->W;
-  if (pct_index >= 4 * HW) return k22_set_error(K22_EINVAL, "unet_sample_loop: percentile index out of range");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  K22UNet::LoopRows lr;
-  if (int rc = u->loop_begin(n_steps, st, &lr)) return rc;
-  auto body = [&](hipStream_t s) -> int {
-    if (int rc = u->loop_prologue(lr, timesteps, n_steps, inpaint_image, inpaint_mask, s)) return rc;
-    float* cur = x; float* nxt = x_tmp;
-    for (int k = 0; k < n_steps; ++k) {
-      int rc = u->loop_model(lr, cur, timesteps, k, s);
-      if (rc) return rc;
-      SamplerParams p = {};
-      p.x = cur; p.model_out = u->model_out(); p.noise = noise_seq + (size_t)k * B * 4 * HW; p.init_img = init_img; p.mask = mask;
-      p.table = table; p.step = nullptr; p.step_host = table_rows[k]; p.guidance = guidance; p.clamp_lo = clamp_lo; p.clamp_hi = clamp_hi;
-      p.use_cfg = 1; p.n_lo = pct_index; p.gamma = pct_gamma;
-      p.s_buf = reinterpret_cast<float*>(scratch); p.x0_buf = reinterpret_cast<float*>(scratch) + 64;
-      p.x_out = nxt; p.x0_out = nullptr; p.N = B; p.HW = HW;
-      rc = launch_sampler_step(p, s);
-      if (rc) return rc;
-      if (keep_init) {
-        rc = launch_keep_region(nxt, keep_init, keep_noise, keep_mask, keep_coef[2 * k], keep_coef[2 * k + 1], nxt, B, HW, s);
-        if (rc) return rc;
-      }
-      float* t_ = cur; cur = nxt; nxt = t_;
-    }
-    if (cur != x) return copy_d2d(x, cur, (size_t)B * 4 * HW * sizeof(float), s);
-    return K22_OK;
+  auto own_fault = [&]() -> const char* {
+    if (!x || !x_tmp || !timesteps || !noise_seq || !table || !table_rows || !scratch || n_steps < 1) return "null argument";
+    if (pct_index >= 4 * u->H * u->W) return "percentile index out of range";
+    return nullptr;
   };
-  std::vector<unsigned long long> key = {K22_LOOP_KIND_P, loop_key_ptr(x), loop_key_ptr(x_tmp), loop_key_ptr(timesteps), loop_key_ptr(noise_seq),
-      loop_key_ptr(init_img), loop_key_ptr(mask), loop_key_ptr(inpaint_image), loop_key_ptr(inpaint_mask), loop_key_ptr(table), loop_key_ptr(scratch),
-      (unsigned long long)n_steps, (unsigned long long)pct_index, (unsigned long long)(lr.hoist ? 1 : 0),
-      loop_key_bits(guidance), loop_key_bits(clamp_lo), loop_key_bits(clamp_hi), loop_key_bits(pct_gamma)};
-  for (int k = 0; k < n_steps; ++k) key.push_back((unsigned long long)table_rows[k]);
-  if (keep_init) {   // a kind of its own, the three device operands and the bits of every coefficient baked into the keep-region nodes
-    key[0] = K22_LOOP_KIND_P_KEEP;
-    key.push_back(loop_key_ptr(keep_init)); key.push_back(loop_key_ptr(keep_noise)); key.push_back(loop_key_ptr(keep_mask));
+  auto step = [&](int k, float* cur, float* nxt, auto&, hipStream_t s) -> int {
+    const int B = u->B, HW = u->H * u->W;
+    SamplerParams p = {};
+    p.x = cur; p.model_out = u->model_out(); p.noise = noise_seq + (size_t)k * B * 4 * HW; p.init_img = init_img; p.mask = mask;
+    p.table = table; p.step = nullptr; p.step_host = table_rows[k]; p.guidance = guidance; p.clamp_lo = clamp_lo; p.clamp_hi = clamp_hi;
+    p.use_cfg = 1; p.n_lo = pct_index; p.gamma = pct_gamma;
+    p.s_buf = reinterpret_cast<float*>(scratch); p.x0_buf = reinterpret_cast<float*>(scratch) + 64;
+    p.x_out = nxt; p.x0_out = nullptr; p.N = B; p.HW = HW;
+    if (int rc = launch_sampler_step(p, s)) return rc;
+    if (!keep_init) return K22_OK;
+    return launch_keep_region(nxt, keep_init, keep_noise, keep_mask, keep_coef[2 * k], keep_coef[2 * k + 1], nxt, B, HW, s);
+  };
+  auto key_tail = [&](std::vector<unsigned long long>& key) {
+    key.insert(key.end(), {loop_key_ptr(noise_seq), loop_key_ptr(init_img), loop_key_ptr(mask), loop_key_ptr(table), loop_key_ptr(scratch),
+                           (unsigned long long)pct_index, loop_key_bits(guidance), loop_key_bits(clamp_lo), loop_key_bits(clamp_hi), loop_key_bits(pct_gamma)});
+    for (int k = 0; k < n_steps; ++k) key.push_back((unsigned long long)table_rows[k]);
+    if (!keep_init) return;
+    // the three device operands and the bits of every coefficient baked into the keep-region nodes
+    key.insert(key.end(), {loop_key_ptr(keep_init), loop_key_ptr(keep_noise), loop_key_ptr(keep_mask)});
     for (int k = 0; k < 2 * n_steps; ++k) key.push_back(loop_key_bits(keep_coef[k]));
-  }
-  return u->loop_run(key, timesteps, inpaint_image, inpaint_mask, use_graph, st, body);
+  };
+  const UNetLoop a = {"unet_sample_loop", keep_init ? K22_LOOP_KIND_P_KEEP : K22_LOOP_KIND_P, x, x_tmp, timesteps, inpaint_image, inpaint_mask,
+                      n_steps, n_steps, use_graph, stream};
+  return unet_loop(u, a, own_fault, step, key_tail);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -981,19 +1005,13 @@ int k22_unet_set_hint(K22UNet* u, const float* hint, void* stream) {
 
 int k22_unet_forward(K22UNet* u, const float* x, const float* timesteps, const float* inpaint_image,
                      const float* inpaint_mask, float* out, int use_graph, void* stream) {
-  if (!u || !u->ws) return k22_set_error(K22_EINVAL, "unet_forward: bind a workspace first");
-  if (!u->cond_set) return k22_set_error(K22_EINVAL, "unet_forward: call k22_unet_set_condition first");
-  if (u->cfg.in_channels == 9 && (!inpaint_image || !inpaint_mask)) return k22_set_error(K22_EINVAL, "unet_forward: inpainting UNet needs inpaint_image and inpaint_mask");
-  if (u->cfg.hint_channels && !u->hint_set) return k22_set_error(K22_EINVAL, "unet_forward: call k22_unet_set_hint first");
+  if (int rc = unet_ready(u, "unet_forward", inpaint_image, inpaint_mask)) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const size_t hw = (size_t)u->H * u->W;
   const size_t pb = (size_t)u->B;
   if (int rc = copy_d2d(u->ptr(u->s_xin), x, pb * 4 * hw * 4, st)) return rc;
   if (int rc = copy_d2d(u->ptr(u->s_t), timesteps, pb * 4, st)) return rc;
-  if (u->cfg.in_channels == 9) {
-    if (int rc = copy_d2d(u->ptr(u->s_img), inpaint_image, pb * 4 * hw * 4, st)) return rc;
-    if (int rc = copy_d2d(u->ptr(u->s_mask), inpaint_mask, pb * hw * 4, st)) return rc;
-  }
+  if (int rc = u->stage_inpaint(inpaint_image, inpaint_mask, st)) return rc;
   // first forward on this plan: fragment-major weight copies; conv / GEMM problems the tile table does not know are measured on the device
   { int rc = u->prepare_run(st); if (rc) return rc; }
   // graph: warm-up eagerly once per plan (sets function attributes), then capture and replay
@@ -1027,110 +1045,82 @@ int k22_unet_sample_loop_keep(K22UNet* u, float* x, float* x_tmp, const float* t
 }
 
 // The whole classifier-free-guided DDIM or PLMS loop of Kandinsky2_1.generate_img (kandinsky2_1_model.py:222-233 -> samplers.py:206-331,
-// 475-637) as ONE hipGraph: the k22_unet_sample_loop machinery with k22_ddim_step / k22_plms_step as the step.  PLMS: the rotation of the
+// 475-637) as ONE hipGraph: unet_loop with k22_ddim_step / k22_plms_step as the step.  PLMS: the rotation of the
 // eps ring is resolved here, at capture time - every captured plms_step node holds fixed h1 / h2 / h3 / eps_out pointers.
 int k22_unet_ddim_loop(K22UNet* u, int kind, float* x, float* x_tmp, float* x0_out, const float* timesteps, const float* table,
                        const float* noise_seq, const float* inpaint_image, const float* inpaint_mask, float* eps_hist, int n_steps,
                        float guidance, int use_graph, void* stream) {
-  if (!u || !u->ws) return k22_set_error(K22_EINVAL, "unet_ddim_loop: bind a workspace first");
-  if (kind != K22_LOOP_DDIM && kind != K22_LOOP_PLMS) return k22_set_error(K22_EINVAL, "unet_ddim_loop: kind must be K22_LOOP_DDIM or K22_LOOP_PLMS");
-  if (!u->cond_set) return k22_set_error(K22_EINVAL, "unet_ddim_loop: call k22_unet_set_condition first");
-  if (!x || !x_tmp || !timesteps || !table) return k22_set_error(K22_EINVAL, "unet_ddim_loop: null argument");
-  if (n_steps < 1) return k22_set_error(K22_EINVAL, "unet_ddim_loop: n_steps must be >= 1");
-  if (kind == K22_LOOP_PLMS && noise_seq) return k22_set_error(K22_EINVAL, "unet_ddim_loop: PLMS is eta = 0 (samplers.py:355-356): noise_seq must be NULL");
-  if (kind == K22_LOOP_PLMS && !eps_hist) return k22_set_error(K22_EINVAL, "unet_ddim_loop: PLMS needs the eps-history workspace (4 x [B][4][HW] floats)");
-  if (u->B % 2) return k22_set_error(K22_EINVAL, "unet_ddim_loop: the batch is the CFG batch [cond | uncond] (even)");
-  if (u->cfg.out_channels != 8) return k22_set_error(K22_EINVAL, "unet_ddim_loop: the UNet must predict eps and variance (8 channels)");
-  if (u->cfg.in_channels == 9 && (!inpaint_image || !inpaint_mask)) return k22_set_error(K22_EINVAL, "unet_ddim_loop: inpainting UNet needs inpaint_image and inpaint_mask");
-  if (u->cfg.hint_channels && !u->hint_set) return k22_set_error(K22_EINVAL, "unet_ddim_loop: call k22_unet_set_hint first");
-  const int B = u->B, HW = u->H * u->W;
-  const int n_calls = kind == K22_LOOP_PLMS ? n_steps + 1 : n_steps;   // PLMS: the pseudo improved-Euler start calls the model twice
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  K22UNet::LoopRows lr;
-  if (int rc = u->loop_begin(n_calls, st, &lr)) return rc;
-  const size_t lat = (size_t)B * 4 * HW;
-  auto body = [&](hipStream_t s) -> int {
-    if (int rc = u->loop_prologue(lr, timesteps, n_calls, inpaint_image, inpaint_mask, s)) return rc;
-    float* cur = x; float* nxt = x_tmp;
-    float* old[3] = {nullptr, nullptr, nullptr};   // PLMS: guided eps of earlier steps, newest first
-    int n_old = 0, call = 0;
-    for (int k = 0; k < n_steps; ++k) {
-      const float* row = table + (size_t)k * 4;
-      int rc = u->loop_model(lr, cur, timesteps, call++, s);
-      if (rc) return rc;
-      if (kind == K22_LOOP_DDIM) {
-        rc = launch_ddim_step(cur, u->model_out(), noise_seq ? noise_seq + (size_t)k * lat : nullptr, row, guidance, 1, nxt, x0_out, B, HW, s);
-        if (rc) return rc;
-      } else {
-        float* e_buf = nullptr;   // the slot of the ring of four that holds none of the (at most three) live history tensors
-        for (int j = 0; j < 4 && !e_buf; ++j) {
-          float* c = eps_hist + (size_t)j * lat;
-          if (c != old[0] && c != old[1] && c != old[2]) e_buf = c;
-        }
-        if (n_old == 0) {
-          // stage one: e_t -> e_buf, provisional x_prev -> nxt; stage two: the model on it at the NEXT timestep, e' = (e_t + e_next) / 2
-          rc = launch_plms_step(cur, u->model_out(), nullptr, nullptr, nullptr, 0, row, guidance, 1, nxt, e_buf, nullptr, B, HW, s);
-          if (rc) return rc;
-          rc = u->loop_model(lr, nxt, timesteps, call++, s);
-          if (rc) return rc;
-          rc = launch_plms_step(cur, u->model_out(), e_buf, nullptr, nullptr, 4, row, guidance, 1, nxt, nullptr, x0_out, B, HW, s);
-        } else {
-          rc = launch_plms_step(cur, u->model_out(), old[0], old[1], old[2], n_old, row, guidance, 1, nxt, e_buf, x0_out, B, HW, s);
-        }
-        if (rc) return rc;
-        old[2] = old[1]; old[1] = old[0]; old[0] = e_buf;
-        if (n_old < 3) ++n_old;
-      }
-      float* t_ = cur; cur = nxt; nxt = t_;
-    }
-    if (cur != x) return copy_d2d(x, cur, lat * sizeof(float), s);
-    return K22_OK;
+  auto own_fault = [&]() -> const char* {
+    if (kind != K22_LOOP_DDIM && kind != K22_LOOP_PLMS) return "kind must be K22_LOOP_DDIM or K22_LOOP_PLMS";
+    if (!x || !x_tmp || !timesteps || !table) return "null argument";
+    if (n_steps < 1) return "n_steps must be >= 1";
+    if (kind == K22_LOOP_PLMS && noise_seq) return "PLMS is eta = 0 (samplers.py:355-356): noise_seq must be NULL";
+    if (kind == K22_LOOP_PLMS && !eps_hist) return "PLMS needs the eps-history workspace (4 x [B][4][HW] floats)";
+    return nullptr;
   };
-  const std::vector<unsigned long long> key = {kind == K22_LOOP_DDIM ? K22_LOOP_KIND_DDIM : K22_LOOP_KIND_PLMS, loop_key_ptr(x), loop_key_ptr(x_tmp),
-      loop_key_ptr(x0_out), loop_key_ptr(timesteps), loop_key_ptr(table), loop_key_ptr(noise_seq), loop_key_ptr(inpaint_image), loop_key_ptr(inpaint_mask),
-      loop_key_ptr(eps_hist), (unsigned long long)n_steps, (unsigned long long)(lr.hoist ? 1 : 0), loop_key_bits(guidance)};
-  return u->loop_run(key, timesteps, inpaint_image, inpaint_mask, use_graph, st, body);
+  float* old[3] = {nullptr, nullptr, nullptr};   // PLMS: guided eps of earlier steps, newest first (the step runs once per call, if at all)
+  int n_old = 0;
+  auto step = [&](int k, float* cur, float* nxt, auto& model, hipStream_t s) -> int {
+    const int B = u->B, HW = u->H * u->W;
+    const size_t lat = (size_t)B * 4 * HW;
+    const float* row = table + (size_t)k * 4;
+    if (kind == K22_LOOP_DDIM)
+      return launch_ddim_step(cur, u->model_out(), noise_seq ? noise_seq + (size_t)k * lat : nullptr, row, guidance, 1, nxt, x0_out, B, HW, s);
+    float* e_buf = nullptr;   // the slot of the ring of four that holds none of the (at most three) live history tensors
+    for (int j = 0; j < 4 && !e_buf; ++j) {
+      float* c = eps_hist + (size_t)j * lat;
+      if (c != old[0] && c != old[1] && c != old[2]) e_buf = c;
+    }
+    int rc;
+    if (n_old == 0) {
+      // stage one: e_t -> e_buf, provisional x_prev -> nxt; stage two: the model on it at the NEXT timestep, e' = (e_t + e_next) / 2
+      rc = launch_plms_step(cur, u->model_out(), nullptr, nullptr, nullptr, 0, row, guidance, 1, nxt, e_buf, nullptr, B, HW, s);
+      if (rc) return rc;
+      rc = model(nxt);
+      if (rc) return rc;
+      rc = launch_plms_step(cur, u->model_out(), e_buf, nullptr, nullptr, 4, row, guidance, 1, nxt, nullptr, x0_out, B, HW, s);
+    } else {
+      rc = launch_plms_step(cur, u->model_out(), old[0], old[1], old[2], n_old, row, guidance, 1, nxt, e_buf, x0_out, B, HW, s);
+    }
+    old[2] = old[1]; old[1] = old[0]; old[0] = e_buf;
+    if (n_old < 3) ++n_old;
+    return rc;
+  };
+  auto key_tail = [&](std::vector<unsigned long long>& key) {
+    key.insert(key.end(), {loop_key_ptr(x0_out), loop_key_ptr(table), loop_key_ptr(noise_seq), loop_key_ptr(eps_hist), loop_key_bits(guidance)});
+  };
+  // PLMS: the pseudo improved-Euler start calls the model twice
+  const UNetLoop a = {"unet_ddim_loop", kind == K22_LOOP_PLMS ? K22_LOOP_KIND_PLMS : K22_LOOP_KIND_DDIM, x, x_tmp, timesteps, inpaint_image,
+                      inpaint_mask, n_steps, kind == K22_LOOP_PLMS ? n_steps + 1 : n_steps, use_graph, stream};
+  return unet_loop(u, a, own_fault, step, key_tail);
 }
 
 // The whole classifier-free-guided DPM-Solver++ loop (multistep, data prediction, orders 1 / 2M; no counterpart in the reference) as ONE
-// hipGraph: the k22_unet_ddim_loop machinery with k22_dpmpp_step as the step.  Step k writes its x0 to slot k % 2 of x0_hist and, when
+// hipGraph: unet_loop with k22_dpmpp_step as the step.  Step k writes its x0 to slot k % 2 of x0_hist and, when
 // orders[k] == 2, reads slot (k - 1) % 2: the rotation is resolved here, at capture time, like the PLMS ring - so every order is in the key.
 int k22_unet_dpmpp_loop(K22UNet* u, float* x, float* x_tmp, float* x0_hist, const float* timesteps, const float* table, const int* orders,
                         const float* inpaint_image, const float* inpaint_mask, int n_steps, float guidance, int use_graph, void* stream) {
-  if (!u || !u->ws) return k22_set_error(K22_EINVAL, "unet_dpmpp_loop: bind a workspace first");
-  if (!u->cond_set) return k22_set_error(K22_EINVAL, "unet_dpmpp_loop: call k22_unet_set_condition first");
-  if (!x || !x_tmp || !x0_hist || !timesteps || !table || !orders) return k22_set_error(K22_EINVAL, "unet_dpmpp_loop: null argument");
-  if (n_steps < 1) return k22_set_error(K22_EINVAL, "unet_dpmpp_loop: n_steps must be >= 1");
-  for (int k = 0; k < n_steps; ++k)
-    if (orders[k] != 1 && orders[k] != 2) return k22_set_error(K22_EINVAL, "unet_dpmpp_loop: every order is 1 or 2");
-  if (orders[0] != 1) return k22_set_error(K22_EINVAL, "unet_dpmpp_loop: the first step has no history (orders[0] must be 1)");
-  if (u->B % 2) return k22_set_error(K22_EINVAL, "unet_dpmpp_loop: the batch is the CFG batch [cond | uncond] (even)");
-  if (u->cfg.out_channels != 8) return k22_set_error(K22_EINVAL, "unet_dpmpp_loop: the UNet must predict eps and variance (8 channels)");
-  if (u->cfg.in_channels == 9 && (!inpaint_image || !inpaint_mask)) return k22_set_error(K22_EINVAL, "unet_dpmpp_loop: inpainting UNet needs inpaint_image and inpaint_mask");
-  if (u->cfg.hint_channels && !u->hint_set) return k22_set_error(K22_EINVAL, "unet_dpmpp_loop: call k22_unet_set_hint first");
-  const int B = u->B, HW = u->H * u->W;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  K22UNet::LoopRows lr;
-  if (int rc = u->loop_begin(n_steps, st, &lr)) return rc;
-  const size_t lat = (size_t)B * 4 * HW;
-  auto body = [&](hipStream_t s) -> int {
-    if (int rc = u->loop_prologue(lr, timesteps, n_steps, inpaint_image, inpaint_mask, s)) return rc;
-    float* cur = x; float* nxt = x_tmp;
-    for (int k = 0; k < n_steps; ++k) {
-      if (int rc = u->loop_model(lr, cur, timesteps, k, s)) return rc;
-      float* x0_new = x0_hist + (size_t)(k % 2) * lat;
-      const float* x0_old = orders[k] == 2 ? x0_hist + (size_t)((k + 1) % 2) * lat : nullptr;
-      if (int rc = launch_dpmpp_step(cur, u->model_out(), x0_old, table + (size_t)k * 5, guidance, 1, nxt, x0_new, B, HW, s)) return rc;
-      float* t_ = cur; cur = nxt; nxt = t_;
-    }
-    if (cur != x) return copy_d2d(x, cur, lat * sizeof(float), s);
-    return K22_OK;
+  auto own_fault = [&]() -> const char* {
+    if (!x || !x_tmp || !x0_hist || !timesteps || !table || !orders) return "null argument";
+    if (n_steps < 1) return "n_steps must be >= 1";
+    for (int k = 0; k < n_steps; ++k)
+      if (orders[k] != 1 && orders[k] != 2) return "every order is 1 or 2";
+    if (orders[0] != 1) return "the first step has no history (orders[0] must be 1)";
+    return nullptr;
   };
-  std::vector<unsigned long long> key = {K22_LOOP_KIND_DPMPP, loop_key_ptr(x), loop_key_ptr(x_tmp), loop_key_ptr(x0_hist), loop_key_ptr(timesteps),
-      loop_key_ptr(table), loop_key_ptr(inpaint_image), loop_key_ptr(inpaint_mask), (unsigned long long)n_steps,
-      (unsigned long long)(lr.hoist ? 1 : 0), loop_key_bits(guidance)};
-  for (int k = 0; k < n_steps; ++k) key.push_back((unsigned long long)orders[k]);
-  return u->loop_run(key, timesteps, inpaint_image, inpaint_mask, use_graph, st, body);
+  auto step = [&](int k, float* cur, float* nxt, auto&, hipStream_t s) -> int {
+    const int B = u->B, HW = u->H * u->W;
+    const size_t lat = (size_t)B * 4 * HW;
+    float* x0_new = x0_hist + (size_t)(k % 2) * lat;
+    const float* x0_old = orders[k] == 2 ? x0_hist + (size_t)((k + 1) % 2) * lat : nullptr;
+    return launch_dpmpp_step(cur, u->model_out(), x0_old, table + (size_t)k * 5, guidance, 1, nxt, x0_new, B, HW, s);
+  };
+  auto key_tail = [&](std::vector<unsigned long long>& key) {
+    key.insert(key.end(), {loop_key_ptr(x0_hist), loop_key_ptr(table), loop_key_bits(guidance)});
+    for (int k = 0; k < n_steps; ++k) key.push_back((unsigned long long)orders[k]);
+  };
+  const UNetLoop a = {"unet_dpmpp_loop", K22_LOOP_KIND_DPMPP, x, x_tmp, timesteps, inpaint_image, inpaint_mask, n_steps, n_steps, use_graph, stream};
+  return unet_loop(u, a, own_fault, step, key_tail);
 }
 
 int k22_unet_num_ops(const K22UNet* u) {

@@ -1,5 +1,6 @@
 // k22 — host-side substrate shared by the four native engines (UNet engine.hip, MoVQ movq.hip, prior prior.hip, conditioning towers
-// encoder.hip): workspace slots, the weight table, the plan / bind life cycle, and the cached hipGraph of a launch list.  Host-only.
+// encoder.hip): workspace slots, the weight table, the plan / bind life cycle, the cached hipGraph of a launch list, and the keyed
+// graph of a whole sampling loop.  Host-only.
 //
 // Life cycle of a handle (include/k22.h):  create -> plan -> bind -> run.
 //   plan   begin_plan() drops everything of the previous plan; the engine sizes its slots and builds its launch list; finish_plan() lays the
@@ -15,6 +16,7 @@
 #include <deque>
 #include <string>
 #include <unordered_map>
+#include <vector>
 #include <stdint.h>
 #include <stdlib.h>
 
@@ -115,6 +117,26 @@ struct GraphCache {
   int launch(hipStream_t st) const {
     const hipError_t e = hipGraphLaunch(exec, st);
     return e == hipSuccess ? (int)K22_OK : k22_set_error_hip(e, __FILE__, __LINE__);
+  }
+};
+
+// The ONE captured whole loop of an engine (a sampling loop: many passes of the launch list with step kernels between them) and the key
+// it is valid for: every pointer and scalar baked into its nodes, the loop's kind first.  A word missing from the key is a stale replay.
+struct LoopCache {
+  GraphCache graph;
+  std::vector<unsigned long long> key;
+  void drop() { graph.drop(); key.clear(); }
+  // `body` (one pass over the whole loop on a stream) eagerly on `st`, or as the captured loop valid for `k`, captured on a miss: what a
+  // capture records is exactly what an eager call runs.  Whatever has to run before a first capture (warm-up) the caller has run.
+  template <typename F> int run(CaptureStream& cs, const std::vector<unsigned long long>& k, int use_graph, hipStream_t st, F body) {
+    if (use_graph && (!graph || k != key)) {
+      if (int rc = graph.capture(cs, body)) { drop(); return rc; }
+      key = k;
+      loop_count_capture();
+    }
+    const int rc = use_graph ? graph.launch(st) : body(st);
+    if (rc == K22_OK) loop_count_launch();
+    return rc;
   }
 };
 

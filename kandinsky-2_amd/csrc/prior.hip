@@ -134,9 +134,8 @@ struct K22Prior : GraphPlan {   // tuned: every transformer Linear; graph: the ~
   bool wfrag_done = false;
   struct WFrag { const void* src; Slot* dst; int Npad, K; };
   std::vector<WFrag> wfrags;   // fragment-major copies of the transformer weights, written into the workspace once per bind
-  // the ONE captured sampling loop of this handle (k22_prior_sample_loop), valid for loop_key: kind, n_steps, clamp and every pointer
-  GraphCache loop;
-  std::vector<unsigned long long> loop_key;
+  // the ONE captured sampling loop of this handle (k22_prior_sample_loop); its key: kind, n_steps, clamp and every pointer
+  LoopCache loop;
 
   // fragment-major weight copies of the skinny path: once per binding, before the first launch list that reads them
   int repack_once(hipStream_t st) {
@@ -458,22 +457,9 @@ int k22_prior_sample_loop(K22Prior* m, int kind, float* x, float* x_tmp, float* 
     if (cur != x) return copy_d2d(x, cur, lat * sizeof(float), s);
     return K22_OK;
   };
-  if (!use_graph) {
-    const int rc = body(st);
-    if (rc == K22_OK) loop_count_launch();
-    return rc;
-  }
-  const std::vector<unsigned long long> key = {(unsigned long long)kind, (unsigned long long)n_steps, loop_key_bits(clamp), loop_key_ptr(x), loop_key_ptr(x_tmp),
+  return m->loop.run(m->cap, {(unsigned long long)kind, (unsigned long long)n_steps, loop_key_bits(clamp), loop_key_ptr(x), loop_key_ptr(x_tmp),
       loop_key_ptr(x0_out), loop_key_ptr(timesteps), loop_key_ptr(table), loop_key_ptr(noise_seq), loop_key_ptr(scales), loop_key_ptr(text_emb),
-      loop_key_ptr(text_enc), loop_key_ptr(key_valid)};
-  if (!m->loop || key != m->loop_key) {
-    if (int rc = m->loop.capture(m->cap, body)) return rc;
-    m->loop_key = key;
-    loop_count_capture();
-  }
-  const int rc = m->loop.launch(st);
-  if (rc == K22_OK) loop_count_launch();
-  return rc;
+      loop_key_ptr(text_enc), loop_key_ptr(key_valid)}, use_graph, st, body);
 }
 
 // ---- single-kernel entry points for the parity tests (include/k22.h); no product code calls them -------------------------
