@@ -344,6 +344,18 @@ int k22_conv3x3_skip(const void* x_padded, const void* Wp, const float* bias, co
 int k22_conv3x3_gnstats(const void* x_padded, const void* Wp, const float* bias, const void* residual, void* out,
                         void* partial, int B, int H, int W, int Cin, int Cout, int Npad, int splitk, int bm, int bn,
                         float* stats, int stats_capacity_rows, int* rows_per_image, int dtype, void* stream);
+/* Nearest 2x upsample + conv3x3 (in_layers of an up-sampling ResBlock, unet.py:158-159, 204) as four 2x2 convolutions of the LOW-resolution
+ * tensor, one per output phase (py, px): x_padded = [B][H+2][W+2][Cin] zero-bordered low-resolution input, Wph = the folded weights
+ * [phase 2*py+px][Npad][tap 2x2][Cin] in the engine type (k22_up2_fold, rounded once), out = the unpadded row-major [B][2H][2W][Cout].
+ * splitk: 0 = the fixed rule, else as given (partial: fp32 [splitk][B*4HW][Cout]); bm: 0 = rule, 256, 128.  stats (optional, may be
+ * null): the GroupNorm partial sums of the stored output, image b owning rows [b*rpi, (b+1)*rpi); *rows_per_image receives rpi. */
+int k22_conv3x3_up2(const void* x_padded, const void* Wph, const float* bias, void* out, void* partial, int B, int H, int W, int Cin,
+                    int Cout, int Npad, int splitk, int bm, float* stats, int stats_capacity_rows, int* rows_per_image, int dtype,
+                    void* stream);
+/* The fold itself: w = fp32 3x3 weights in pack order [O][ky][kx][I] -> out = fp32 phase weights [4][Opad][2][2][I] (rows O .. Opad-1
+ * zero).  Phase py takes tap ky into row slot (py + ky + 1) / 2 - py (py = 0: {0 | 1, 2}; py = 1: {0, 1 | 2}), columns alike; the sums
+ * run in fp32, ky then kx ascending.  The caller rounds / splits to the engine type afterwards, once. */
+int k22_up2_fold(const float* w, float* out, int O, int Opad, int I, void* stream);
 /* Same for a 1x1 convolution over unpadded rows [B*H*W][K] (AttentionBlock proj_out, unet.py:244-268, whose output the
  * next ResBlock's GroupNorm32 normalises): out = A W^T + bias (+ residual) through the 8-wave BM x 128 GEMM kernel
  * (bm = 256 / 128 / 0 = auto), with the per-tile (sum, sum of squares) rows as above. */

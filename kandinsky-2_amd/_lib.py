@@ -154,6 +154,8 @@ SIGNATURES = {
     "k22_conv3x3_skip": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "k22_gemm_gnstats": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, C.POINTER(_I), _I, _P]),
     "k22_conv3x3_gnstats": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, C.POINTER(_I), _I, _P]),
+    "k22_conv3x3_up2": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, C.POINTER(_I), _I, _P]),
+    "k22_up2_fold": (_I, [_P, _P, _I, _I, _I, _P]),
     "k22_igemm_cfg_accepted": (_I, [C.POINTER(K22IgemmProblem)]),
     "k22_igemm_cfg": (_I, [C.POINTER(K22IgemmProblem), C.POINTER(K22IgemmOperands), C.POINTER(_I), _P]),
     "k22_conv3x3_gn": (_I, [_P, _P, _I, _I, _P, _P, _P, _L, _F, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),

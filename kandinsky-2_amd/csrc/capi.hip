@@ -198,6 +198,30 @@ int k22_conv3x3_gnstats(const void* x_padded, const void* Wp, const float* bias,
   return launch_igemm(p, dtype, reinterpret_cast<hipStream_t>(stream));
 }
 
+int k22_conv3x3_up2(const void* x_padded, const void* Wph, const float* bias, void* out, void* partial, int B, int H, int W, int Cin,
+                    int Cout, int Npad, int splitk, int bm, float* stats, int stats_capacity_rows, int* rows_per_image, int dtype,
+                    void* stream) {
+  if (!x_padded || !Wph || !out || B <= 0 || H <= 0 || W <= 0) return k22_set_error(K22_EINVAL, "conv3x3_up2: bad argument");
+  IgemmParams p = igemm_up2_problem(B, H, W, Cin, Cout);
+  p.A0 = x_padded; p.Wp = Wph; p.bias = bias; p.out = out; p.partial = reinterpret_cast<float*>(partial);
+  p.Npad = Npad; p.splitk = splitk; p.force_bm = bm;
+  if (p.splitk == 0) p.splitk = partial ? igemm_choose_splitk(p, dtype) : 1;
+  if (p.splitk > 1 && !partial) return k22_set_error(K22_EINVAL, "conv3x3_up2: split-K needs the partial buffer");
+  if (rows_per_image) *rows_per_image = 0;
+  if (stats) {
+    const int rpi = igemm_stats_rows_per_image(p, dtype);
+    if (rows_per_image) *rows_per_image = rpi;
+    if (rpi <= 0) return k22_set_error(K22_EINVAL, "conv3x3_up2: this configuration cannot produce GroupNorm partial sums");
+    if (rpi * B > stats_capacity_rows) return k22_set_error(K22_ENOMEM, "conv3x3_up2: stats buffer too small");
+    p.stats = stats;
+  }
+  return launch_igemm(p, dtype, reinterpret_cast<hipStream_t>(stream));
+}
+
+int k22_up2_fold(const float* w, float* out, int O, int Opad, int I, void* stream) {
+  return launch_up2_fold(w, out, O, Opad, I, reinterpret_cast<hipStream_t>(stream));
+}
+
 int k22_gemm_gnstats(const void* A, const void* Wp, const float* bias, const void* residual, void* out, void* partial,
                      int B, int H, int W, int N, int Npad, int K, int splitk, int bm, float* stats,
                      int stats_capacity_rows, int* rows_per_image, int dtype, void* stream) {

@@ -198,8 +198,11 @@ template <int NBST> constexpr int halo_count_a(int t) {
 // v < H*W of image `img` themselves (gemm8_kernel), and the qkv-projection output mode is available.
 // SPEC = true (conv3_halo_spec_kernel): only waves 0-3 hold accumulators, 2 x 2 over the tile with (BM/2) x 64 each; waves 4-7
 // were the producers of the main loop.  All eight waves issue the skip loop's LDS-DMA and run the store / statistics epilogue.
-template <typename T, int BM, bool PLAIN = false, bool SPEC = false>
-__device__ __forceinline__ void halo_tail(const IgemmParams& p, f32x16_t (&acc)[SPEC ? BM / 64 : BM / 128][2], char* smem, int bx, int bz, int img, int v0, int n0) {
+// UP2 = true (conv3_up2_kernel, conv3_up2.hip): rows are positions v of the LOW-resolution padded plane and row (y, x) of phase ph = 2*py + px
+// is stored at (2y + py, 2x + px) of the unpadded 2H x 2W output; p.M counts the output's rows; bx = the statistics row of this tile.
+template <typename T, int BM, bool PLAIN = false, bool SPEC = false, bool UP2 = false>
+__device__ __forceinline__ void halo_tail(const IgemmParams& p, f32x16_t (&acc)[SPEC ? BM / 64 : BM / 128][2], char* smem, int bx, int bz, int img, int v0, int n0,
+                                          int ph = 0) {
   using TR = TT<T>;
   constexpr int BK = TR::BK, EPC = TR::EPC, KSTEPS = TR::KSTEPS;
   constexpr int BN = HALO_BN, NW = HALO_NW, WM = SPEC ? 2 : 4, WN = 2;
@@ -396,7 +399,8 @@ __device__ __forceinline__ void halo_tail(const IgemmParams& p, f32x16_t (&acc)[
     } else {
       const int y = v / W2, x = v - y * W2;
       if (!n_ok || v >= VR || x >= p.W) continue;
-      m = ((int64_t)img * p.H + y) * p.W + x;
+      if constexpr (UP2) m = ((int64_t)img * 2 * p.H + 2 * y + (ph >> 1)) * (2 * p.W) + 2 * x + (ph & 1);
+      else m = ((int64_t)img * p.H + y) * p.W + x;
     }
     const float4 t0 = *reinterpret_cast<const float4*>(smem + row * TS + cs * 32);
     const float4 t1 = *reinterpret_cast<const float4*>(smem + row * TS + cs * 32 + 16);

@@ -103,6 +103,9 @@ struct K22UNet : GraphPlan {   // dtype: arithmetic type of the MFMA kernels (K2
     frag_done = true;
     return K22_OK;
   }
+  // in_layers of the up-sampling ResBlocks as four 2x2 convolutions of the low-resolution tensor (conv3_up2.hip) instead of GroupNorm-apply
+  // into the 4x larger padded tensor + a 9-tap convolution at the high resolution.  K22_UP_PHASE=0: the 9-tap route everywhere (A/B in one build).
+  int up_phase = env_flag("K22_UP_PHASE", 1);
   bool cond_set = false;
   // the whole denoising loop as ONE graph (any of the k22_unet_*_loop entries, unet_loop below): valid for exactly the buffers / scalars
   // it was captured with
@@ -407,6 +410,41 @@ struct K22UNet : GraphPlan {   // dtype: arithmetic type of the MFMA kernels (K2
     return t;
   }
 
+  // Does the up-sampling ResBlock with a low-resolution Hl x Wl input take the four-phase route?  The folded weights must be in the arena
+  // (pack.py writes them for every up-sampling block; an arena without them runs the 9-tap route) and the kernel must fit the problem.
+  bool up2_route(const std::string& wname, int Hl, int Wl, int Cin, int Cout) const {
+    if (!up_phase || w.find(wname) == w.end()) return false;
+    const IgemmParams q = igemm_up2_problem(B, Hl, Wl, Cin, Cout);
+    const int dt = conv_dt(CONV_IN, 2 * Hl);
+    return conv3_up2_supported(q, dt, 256) || conv3_up2_supported(q, dt, 128);
+  }
+  // nearest 2x upsample + conv3x3 in the four-phase form: `src` = the zero-bordered LOW-resolution slot [B][Hl+2][Wl+2][Cin], `dst` = the
+  // unpadded [B][2Hl][2Wl][Cout]; weights pfx.weight_up2 [4][roundup(Cout,64)][2x2][Cin].  Tile and split: igemm_resolve's fixed rule.
+  Tuned* op_conv_up2(OpList& L, Slot* src, int Hl, int Wl, int Cin, int Cout, const std::string& pfx, Slot* dst, Slot* stats) {
+    tuned.emplace_back();
+    Tuned* t = &tuned.back();
+    t->dt = conv_dt(CONV_IN, 2 * Hl);
+    IgemmParams& p = t->p;
+    p = igemm_up2_problem(B, Hl, Wl, Cin, Cout);
+    p.Wp = W_(pfx + ".weight_up2"); p.bias = Wf(pfx + ".bias");
+    t->want_stats = stats != nullptr;
+    make_candidates(*t);
+    default_cfg(*t);
+    need(s_splitk, max_splitk_bytes(*t));
+    if (t->want_stats) need(stats, (size_t)B * max_rpi(*t) * Cout * 2 * sizeof(float));
+    need(dst, (size_t)p.M * Cout * esz);
+    const int dt = t->dt;
+    t->run = [=](hipStream_t st) {
+      IgemmParams q = t->p;
+      apply_cfg(q, t->cfg);
+      q.A0 = ptr(src); q.out = ptr(dst); q.partial = ptr<float>(s_splitk);
+      q.stats = t->want_stats ? ptr<float>(stats) : nullptr;
+      return launch_igemm(q, dt, st);
+    };
+    L.push_back(Op([=](hipStream_t st) { return t->run(st); }, OP_CONV3, 2.0 * p.M * (double)p.N * 4.0 * p.Kc, 0.0, 1));
+    return t;
+  }
+
   // GEMM over unpadded rows (1x1 conv / linear); `in` may be a virtual concat.
   // `stats` (optional) receives the GroupNorm partial sums of the output (image-shaped inputs only: in.H * in.W rows
   // per image); whether a configuration that can deliver them exists is reported by the returned want_stats.
@@ -454,9 +492,17 @@ struct K22UNet : GraphPlan {   // dtype: arithmetic type of the MFMA kernels (K2
     // in_layers: GN + SiLU (+ resample) -> conv3x3
     GnLink* l1 = nullptr;
     if (fuse_gn && updown == 0) { gn_links.emplace_back(); l1 = &gn_links.back(); }   // (the resampling GroupNorms keep gn_apply)
-    op_gn(ops, in, pfx + ".in_layers.0", -1, K22_ACT_SILU, updown, 1, s_P1, l1);
-    Tuned* t1 = op_conv(ops, CONV_IN, s_P1, Ho, Wo, Cin, Cout, pfx + ".in_layers.2", nullptr, s_U1, IG_OUT_ROWMAJOR, s_U1st, nullptr, std::string(),
-                        l1 ? &in : nullptr, K22_ACT_SILU);
+    const bool up2 = updown == 2 && !in.s1 && up2_route(pfx + ".in_layers.2.weight_up2", in.H, in.W, Cin, Cout);
+    Tuned* t1;
+    if (up2) {
+      // GroupNorm + SiLU at the LOW resolution (zero border), then the four 2x2 phase convolutions write the high-resolution tensor
+      op_gn(ops, in, pfx + ".in_layers.0", -1, K22_ACT_SILU, 0, 1, s_P1, nullptr);
+      t1 = op_conv_up2(ops, s_P1, in.H, in.W, Cin, Cout, pfx + ".in_layers.2", s_U1, s_U1st);
+    } else {
+      op_gn(ops, in, pfx + ".in_layers.0", -1, K22_ACT_SILU, updown, 1, s_P1, l1);
+      t1 = op_conv(ops, CONV_IN, s_P1, Ho, Wo, Cin, Cout, pfx + ".in_layers.2", nullptr, s_U1, IG_OUT_ROWMAJOR, s_U1st, nullptr, std::string(),
+                   l1 ? &in : nullptr, K22_ACT_SILU);
+    }
     if (l1) l1->consumer = t1;
     // out_layers: GN * (1+scale) + shift -> SiLU -> conv3x3 (+ skip)
     Act u1; u1.s0 = s_U1; u1.C0 = Cout; u1.H = Ho; u1.W = Wo;

@@ -451,7 +451,7 @@ void igemm_set_default_stages(int v) { g_opts.stages = (v >= 2 && v <= 4) ? v : 
 void igemm_set_xcd_remap(int v) { g_opts.xcd_remap = v ? 1 : 0; }
 void igemm_set_gemm_algo(int v) { g_opts.gemm_algo = (v == IG_ALGO_GEMM8 || v == IG_ALGO_STREAM) ? v : 0; }
 void igemm_set_conv_algo(int v) {
-  bool ok = v == IG_ALGO_GENERIC || v == IG_ALGO_STREAM || (igemm_algo_is_halo(v) && !igemm_algo_is_debug(v));
+  bool ok = v == IG_ALGO_GENERIC || v == IG_ALGO_STREAM || v == IG_ALGO_UP2 || v == IG_ALGO_UP2_PIPE || (igemm_algo_is_halo(v) && !igemm_algo_is_debug(v));
 #ifdef K22_DEBUG_VARIANTS   // the measurement-only kernels (wrong results) are not reachable in a release build
   ok = ok || igemm_algo_is_debug(v);
 #endif
@@ -461,7 +461,7 @@ void igemm_set_conv_algo(int v) {
 // Can the split-K finish run row-tiled (splitk_reduce_rows_kernel: 16 rows of one image per workgroup, GroupNorm sums on request)?  3x3
 // convolutions always finish that way; plain GEMMs only when they owe GroupNorm sums.
 static bool reduce_rows_ok(const IgemmParams& p, bool stats) {
-  const int hw = (p.taps == 9 || stats) ? p.H * p.W : 0;
+  const int hw = p.taps == 4 ? 4 * p.H * p.W : ((p.taps == 9 || stats) ? p.H * p.W : 0);   // output rows per image
   return hw > 0 && hw % 16 == 0 && (p.N & 3) == 0 && (p.ldo & 3) == 0 && (p.ldr & 3) == 0 &&
          (p.out_mode == IG_OUT_ROWMAJOR || p.out_mode == IG_OUT_ROWMAJOR_F32);
 }
@@ -479,7 +479,7 @@ int igemm_resolve(const IgemmParams& p, int dtype, IgemmLaunch* out) {
   const int want = (p.stages < 2 && o.stages >= 0) ? o.stages : p.stages;
   auto blocks = [&](int bm, int bn) { return ((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn); };
   // ---- weight-streaming small-M kernel (stream_gemm.hip): the tuner's candidate or the conv_algo / gemm_algo option -----------
-  if (p.algo == IG_ALGO_STREAM || (p.algo == IG_ALGO_AUTO && (p.taps == 9 ? o.conv_algo : o.gemm_algo) == IG_ALGO_STREAM)) {
+  if (p.taps != 4 && (p.algo == IG_ALGO_STREAM || (p.algo == IG_ALGO_AUTO && (p.taps == 9 ? o.conv_algo : o.gemm_algo) == IG_ALGO_STREAM))) {
     const int mb = p.force_bm == 288 ? 9 : 5;
     if (stream_supported(p, dtype, mb)) {
       L.family = IG_FAM_STREAM; L.algo = IG_ALGO_STREAM; L.bm = mb * 32; L.bn = 64;
@@ -489,6 +489,32 @@ int igemm_resolve(const IgemmParams& p, int dtype, IgemmLaunch* out) {
       if (L.splitk < 1) L.splitk = 1;
       L.block = 256; L.grid = (unsigned)nb; L.lds = stream_lds_bytes(p, mb);
     }
+  }
+  // ---- upsample + 3x3 convolution in its four-phase form (conv3_up2.hip): one kernel; tile and split from a fixed rule ---------------------
+  if (p.taps == 4) {
+    const bool up2_opt = o.conv_algo == IG_ALGO_UP2 || o.conv_algo == IG_ALGO_UP2_PIPE;   // ("conv_algo" option: the A/B of the two forms)
+    const int algo = p.algo != IG_ALGO_AUTO ? p.algo : (up2_opt ? o.conv_algo : IG_ALGO_AUTO);
+    if (algo != IG_ALGO_AUTO && algo != IG_ALGO_UP2 && algo != IG_ALGO_UP2_PIPE)
+      return k22_set_error(K22_EINVAL, "igemm: the four-phase upsampling convolution runs conv3_up2_kernel only (algo 0 / 30 / 31)");
+    // The rule, from the measurements in profiles/up2_phase_ab.txt (bf16, C2's three up-block shapes): 256-row tiles wherever they fit - also
+    // where an image fills only part of one (12x12: half as many workgroups re-read each weight tile) - and a 2-way slab split where the
+    // four phases alone give fewer than 128 workgroups (12x12 at B = 2: 96); no deeper split: its partial round trip costs more than it hides.
+    int bm = p.force_bm;
+    if (bm == 0) bm = conv3_up2_supported(p, dtype, 256) ? 256 : 128;
+    if ((bm != 256 && bm != 128) || !conv3_up2_supported(p, dtype, bm))
+      return k22_set_error(K22_EINVAL, "igemm: this four-phase upsampling convolution is not supported (tile 256 / 128, N % 8, Kc % BK, LDS)");
+    L.family = IG_FAM_UP2; L.bm = bm; L.bn = 128;
+    L.pipe = (k22_esz(dtype) == 2 && algo != IG_ALGO_UP2) ? 1 : 0;
+    L.algo = L.pipe ? IG_ALGO_UP2_PIPE : IG_ALGO_UP2;
+    const int nslab = p.Kc / BK;
+    const int nb = (p.M / (4 * p.H * p.W)) * conv3_up2_tiles_per_image(p, bm) * ((p.N + 127) / 128) * 4;
+    L.splitk = p.splitk > 0 ? p.splitk : ((nb < 128 && nslab >= 4) ? 2 : 1);
+    if (L.splitk > nslab) L.splitk = nslab;
+    if (L.splitk < 1) L.splitk = 1;
+    L.grid = (unsigned)nb;
+    L.depth = conv3_up2_ring(p, bm);
+    if (want >= 2 && want < L.depth) L.depth = 2;   // shallower ring on request (instantiated: 4, 2)
+    L.lds = conv3_up2_lds_bytes(p, bm, L.depth);
   }
   // ---- 3x3 convolution: the LDS-resident halo kernels when they apply -----------------------------------------------------------
   const int conv_algo = (p.algo && p.algo != IG_ALGO_STREAM) ? p.algo : (o.conv_algo == IG_ALGO_STREAM ? 0 : o.conv_algo);
@@ -620,7 +646,8 @@ int igemm_resolve(const IgemmParams& p, int dtype, IgemmLaunch* out) {
   L.finish = !finishes ? IG_FINISH_NONE : (reduce_rows_ok(p, p.stats != nullptr) ? IG_FINISH_ROWS : IG_FINISH_FLAT);
   // GroupNorm partial sums the launch could write: the row-tiled finish's 16-row blocks, else the 8-wave kernels' own m-tiles
   if (p.taps == 1 && (generic || p.H <= 0 || qkv)) L.stats_rows_per_image = 0;
-  else if (finishes) L.stats_rows_per_image = reduce_rows_ok(p, true) ? p.H * p.W / 16 : 0;
+  else if (finishes) L.stats_rows_per_image = reduce_rows_ok(p, true) ? (p.taps == 4 ? 4 : 1) * p.H * p.W / 16 : 0;
+  else if (L.family == IG_FAM_UP2) L.stats_rows_per_image = 4 * conv3_up2_tiles_per_image(p, L.bm);
   else if (generic) L.stats_rows_per_image = 0;
   else L.stats_rows_per_image = p.taps == 1 ? gemm8_tiles_per_image(p, L.bm) : conv3_halo_tiles_per_image(p, L.bm);
   *out = L;
@@ -686,7 +713,7 @@ int launch_igemm(const IgemmParams& p, int dtype, hipStream_t stream) {
   const int BK = k22_bk(dtype);
   if (p.a_raw && !k22_is_split(dtype)) return k22_set_error(K22_EINVAL, "igemm: a_raw is an option of the split-precision arithmetics only");
   if (p.M <= 0 || p.N <= 0) return K22_OK;
-  if (p.taps != 1 && p.taps != 9) return k22_set_error(K22_EINVAL, "igemm: taps must be 1 or 9");
+  if (p.taps != 1 && p.taps != 9 && p.taps != 4) return k22_set_error(K22_EINVAL, "igemm: taps must be 1, 9 or 4 (four-phase upsampling convolution)");
   if (p.Kc % BK != 0 || p.K0 % BK != 0) return k22_set_error(K22_EINVAL, "igemm: K per tap must be a multiple of 64 (bf16) / 32 (fp32)");
   if (p.Npad % 64 != 0 || p.Npad < p.N) return k22_set_error(K22_EINVAL, "igemm: Npad must be roundup(N,64)");
   if (p.K0 < p.Kc && p.A1 == nullptr) return k22_set_error(K22_EINVAL, "igemm: A1 missing for concat operand");
@@ -711,6 +738,7 @@ int launch_igemm(const IgemmParams& p, int dtype, hipStream_t stream) {
     case IG_FAM_STREAM: rc = launch_stream(q, dtype, L, stream); break;
     case IG_FAM_GEMM8: case IG_FAM_GEMM8_SPEC: rc = launch_gemm8(q, dtype, L, stream); break;
     case IG_FAM_SPEC: rc = launch_conv3_halo_spec(q, dtype, L, stream); break;
+    case IG_FAM_UP2: rc = launch_conv3_up2(q, dtype, L, stream); break;
     case IG_FAM_GENERIC: rc = launch_generic(q, dtype, L, stream); break;
     default: rc = launch_conv3_halo(q, dtype, L, stream); break;
   }

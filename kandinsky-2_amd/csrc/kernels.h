@@ -33,6 +33,8 @@ inline int k22_ensure_lds_attr(LdsAttrGuard& g, const void* fn, int bytes, const
 //               ("virtual concat" of two row-major operands; A1 may be null when K0 == Kc).
 //   taps == 9 : 3x3 convolution, stride 1, pad 1 over a ZERO-BORDERED NHWC input
 //               A0 = [B][H+2][W+2][Kc]; m = (b*H + y)*W + x; k = tap*Kc + c, tap = ky*3+kx.
+//   taps == 4 : nearest 2x upsample + 3x3 convolution in its four-phase form (conv3_up2.hip): A0 = [B][H+2][W+2][Kc] is the zero-bordered
+//               LOW-resolution input, M = B*2H*2W rows of the unpadded 2H x 2W output, Wp = the folded weights [phase 4][Npad][tap 2x2][Kc].
 //   Wp is the packed weight [Npad][taps*Kc] (K contiguous), Npad = roundup(N, 64), zero rows.
 // ---------------------------------------------------------------------------------------
 enum IgemmOut { IG_OUT_ROWMAJOR = 0,  // T out[m*ldo + n]
@@ -53,7 +55,7 @@ struct IgemmParams {
   int M, N, Npad;
   int Kc;                // K elements per tap (K0 + K1 in concat mode)
   int K0;                // channels served by A0 (== Kc when A1 is null)
-  int taps;              // 1 or 9
+  int taps;              // 1, 9 or 4 (above)
   int H, W;              // conv geometry (taps == 9) and NCHW store geometry
   long lda0, lda1;       // row strides (elements) in GEMM mode
   int ldo, ldr;
@@ -109,11 +111,14 @@ enum IgemmAlgo {
   IG_ALGO_SPEC_PIPE = 12,       //   + explicit, interleaved fragment pipeline in the consumers
   IG_ALGO_DBG_SPEC_NO_DMA = 13, // measurement only: forms of 12 without the LDS-DMA in the tap loop /
   IG_ALGO_DBG_SPEC_NO_WAIT = 14,//   with LDS-DMA that is never waited for
-  IG_ALGO_STREAM = 20           // stream_kernel (stream_gemm.hip): weight streaming for small M
+  IG_ALGO_STREAM = 20,          // stream_kernel (stream_gemm.hip): weight streaming for small M
+  IG_ALGO_UP2 = 30,             // conv3_up2_kernel (conv3_up2.hip): the taps == 4 problems, and only they
+  IG_ALGO_UP2_PIPE = 31         //   + explicit fragment pipeline (16-bit types)
 };
 struct IgemmAlgoName { int algo; const char* name; };   // tuning_report_text's column
 constexpr IgemmAlgoName IGEMM_ALGO_NAMES[] = {{IG_ALGO_GENERIC, "gen"},   {IG_ALGO_HALO, "halo"},   {IG_ALGO_HALO3, "hal3"}, {IG_ALGO_HALO_PIPE, "hal6"},
-                                              {IG_ALGO_HALO_ASM, "hal7"}, {IG_ALGO_GEMM8, "gem8"}, {IG_ALGO_SPEC, "spec"},  {IG_ALGO_SPEC_PIPE, "spcp"}};
+                                              {IG_ALGO_HALO_ASM, "hal7"}, {IG_ALGO_GEMM8, "gem8"}, {IG_ALGO_SPEC, "spec"},  {IG_ALGO_SPEC_PIPE, "spcp"},
+                                              {IG_ALGO_UP2, "up2"}, {IG_ALGO_UP2_PIPE, "up2p"}};
 inline const char* igemm_algo_name(int algo) {
   for (const IgemmAlgoName& a : IGEMM_ALGO_NAMES) if (a.algo == algo) return a.name;
   return "auto";
@@ -136,10 +141,17 @@ inline IgemmParams igemm_conv3_problem(int B, int H, int W, int Cin, int Cout, i
   return p;
 }
 
+// nearest 2x upsample + conv3x3 over a LOW-resolution H x W input, four-phase form (taps == 4)
+inline IgemmParams igemm_up2_problem(int B, int H, int W, int Cin, int Cout, int out_mode = IG_OUT_ROWMAJOR) {
+  IgemmParams p = igemm_conv3_problem(B, H, W, Cin, Cout, out_mode);
+  p.M = B * 4 * H * W; p.taps = 4;
+  return p;
+}
+
 // ---- one resolved launch ----------------------------------------------------------------------------------------------------------
 // What launch_igemm runs for a problem: igemm_resolve is the ONE place that reads p.algo / p.force_bm / p.force_bn / p.splitk / p.stages and
 // the process-wide options; the plan-time questions (split-K scratch, GroupNorm stats rows) and the launch read the same result.
-enum IgemmFamily { IG_FAM_GENERIC, IG_FAM_HALO, IG_FAM_HALO3, IG_FAM_SPEC, IG_FAM_GEMM8, IG_FAM_GEMM8_SPEC, IG_FAM_STREAM };
+enum IgemmFamily { IG_FAM_GENERIC, IG_FAM_HALO, IG_FAM_HALO3, IG_FAM_SPEC, IG_FAM_GEMM8, IG_FAM_GEMM8_SPEC, IG_FAM_STREAM, IG_FAM_UP2 };
 enum IgemmFinish { IG_FINISH_NONE, IG_FINISH_FLAT, IG_FINISH_ROWS };   // split-K finish: none, splitk_reduce_kernel, splitk_reduce_rows_kernel
 struct IgemmLaunch {
   int family;                // IgemmFamily
@@ -191,6 +203,13 @@ size_t conv3_halo_lds_bytes(const IgemmParams& p, int bm, int depth);
 int launch_conv3_halo(const IgemmParams& p, int dtype, const IgemmLaunch& L, hipStream_t stream);
 int launch_conv3_halo_spec(const IgemmParams& p, int dtype, const IgemmLaunch& L, hipStream_t stream);   // conv3_spec.hip
 int launch_conv3_halo_trace(const IgemmParams& p, int dtype, hipStream_t stream);
+// conv3_up2.hip: the four-phase form of upsample + conv3x3 (taps == 4), and the one-time fold of its weights
+bool conv3_up2_supported(const IgemmParams& p, int dtype, int bm);
+int conv3_up2_tiles_per_image(const IgemmParams& p, int bm);
+int conv3_up2_ring(const IgemmParams& p, int bm);
+size_t conv3_up2_lds_bytes(const IgemmParams& p, int bm, int depth);
+int launch_conv3_up2(const IgemmParams& p, int dtype, const IgemmLaunch& L, hipStream_t stream);
+int launch_up2_fold(const float* w, float* out, int O, int Opad, int I, hipStream_t stream);   // [O][9][I] fp32 -> [4][Opad][4][I] fp32
 // gemm8.hip: 8-wave BM x 128 GEMM on the halo kernels' frame
 bool gemm8_supported(const IgemmParams& p, int dtype, int bm);
 bool gemm8_spec_supported(int dtype);   // gemm8_spec_kernel (producer / consumer waves, explicit fragment pipeline): 16-bit types

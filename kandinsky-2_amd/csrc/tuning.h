@@ -108,6 +108,8 @@ inline void tuned_make_candidates(Tuned& t, int dtype) {
   const int BK = k22_bk(dtype);
   const int nkt = p.taps * (p.Kc / BK);
   std::vector<Cfg> all;
+  // the four-phase upsampling convolution: one kernel, configured by igemm_resolve's fixed rule - nothing to measure, no table line
+  if (p.taps == 4) { t.cands.clear(); return; }
   if (p.taps == 9) {
     const int B = p.M / (p.H * p.W);
     // the lock-step halo kernel; its asm LDS-DMA form (exact lgkmcnt for the fragment reads, +1-3 %); that + the explicit fragment pipeline

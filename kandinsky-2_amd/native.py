@@ -57,6 +57,29 @@ def layout_arena(entries: "Dict[str, torch.Tensor]", device) -> Tuple[torch.Tens
     return arena, table
 
 
+def up2_fold(w9: torch.Tensor, opad: int) -> torch.Tensor:
+    """k22_up2_fold: fp32 3x3 weights in pack order [O][9 * I] on the GPU -> the fp32 phase weights [4][opad][4 * I] of the four-phase
+    upsampling convolution (csrc/conv3_up2.hip); the same sums, in the same order, as pack.fold_up2."""
+    o, i = w9.shape[0], w9.shape[1] // 9
+    w9 = w9.contiguous()
+    out = torch.empty(4, opad, 4 * i, dtype=torch.float32, device=w9.device)
+    _lib.check(_lib.lib().k22_up2_fold(w9.data_ptr(), out.data_ptr(), o, opad, i, _lib.current_stream()))
+    return out
+
+
+def conv3x3_up2(x_padded: torch.Tensor, wph: torch.Tensor, bias, out: torch.Tensor, B: int, H: int, W: int, Cin: int, Cout: int, dtype: int,
+                splitk: int = 0, bm: int = 0, stats: "torch.Tensor | None" = None):
+    """k22_conv3x3_up2: nearest 2x upsample + conv3x3 of the zero-bordered LOW-resolution x_padded [B][H+2][W+2][Cin] with the folded weights
+    wph [4][Npad][4 * Cin] into `out` (the unpadded [B][2H][2W][Cout] rows; the caller's buffer).  stats: optional fp32 [rows][Cout][2]
+    buffer for the GroupNorm partial sums.  Returns the stats rows per image (0 without stats)."""
+    partial = torch.empty(max(1, splitk if splitk else 4) * B * 4 * H * W * Cout + 64, dtype=torch.float32, device=out.device)
+    rpi = C.c_int(0)
+    _lib.check(_lib.lib().k22_conv3x3_up2(
+        x_padded.data_ptr(), wph.data_ptr(), _lib.ptr(bias), out.data_ptr(), partial.data_ptr(), B, H, W, Cin, Cout, wph.shape[1], splitk, bm,
+        _lib.ptr(stats), 0 if stats is None else stats.shape[0], C.byref(rpi), dtype, _lib.current_stream()))
+    return rpi.value
+
+
 class NativeEngine:
     """One native engine: the handle, the arena its weights live in, the workspace of its current plan and `plan_key` - None while
     there is no finished plan.  `family` names the four C entries (FAMILIES), `cfg` is the filled K22*Config of that family."""

@@ -4,6 +4,8 @@ Layouts (T = engine dtype: bf16, fp16 or fp32; for the split-precision engine "f
 linear, qkv, encoder_kv - are x3 chunks (to_x3 below: fp16 hi / lo pairs of the fp32 weight x 2^8, 4 bytes per element) and the
 emb_layers GEMV weights fp32; everything else fp32):
   conv3x3  [O,I,3,3] -> T [roundup(O,64)][ky][kx][I]   (K = tap-major then channel, contiguous)
+  in_layers.2 of an up-sampling ResBlock, additionally, as "<name>.weight_up2": the four 2x2 phase filters of upsample + conv3x3 (fold_up2),
+           summed in fp32 and cast once -> T [phase 2*py+px][roundup(O,64)][a][b][I]
   conv1x1 / conv1d k=1 / linear feeding the MFMA GEMM -> T [roundup(O,64)][I]
   AttentionBlock.qkv  rows re-ordered  head*192 + {q,k,v}*64 + d  ->  {q,k,v}*C + head*64 + d
   AttentionBlock.encoder_kv rows       head*128 + {k,v}*64 + d    ->  {k,v}*C + head*64 + d
@@ -41,6 +43,30 @@ def to_x3(w: torch.Tensor, scale: float = 256.0) -> torch.Tensor:
     return torch.stack([hi.reshape(g), lo.reshape(g)], dim=-2).reshape(sh[:-1] + (sh[-1] * 2,)).contiguous().view(torch.float32)
 
 
+# nearest 2x upsample + conv3x3 = four 2x2 convolutions of the low-resolution tensor (csrc/conv3_up2.hip): output pixel (2y+py, 2x+px) reads,
+# through tap ky, low-resolution row y + floor((py+ky-1)/2), i.e. row slot a of the phase's 2x2 window takes the taps UP2_TAPS[py][a]
+UP2_TAPS = (((0,), (1, 2)), ((0, 1), (2,)))
+
+
+def fold_up2(w: torch.Tensor) -> torch.Tensor:
+    """[O,I,3,3] -> the phase weights [phase 2*py+px][O][tap 2*a+b][I]: each the sum of 1, 2 or 4 of the original taps, added in w's own
+    precision in the order ky, kx ascending (what k22_up2_fold does on the device).  Fold the fp32 weights; round once, afterwards."""
+    wt = w.permute(0, 2, 3, 1)   # [O][ky][kx][I]
+    phases = []
+    for py in (0, 1):
+        for px in (0, 1):
+            taps = []
+            for a in (0, 1):
+                for b in (0, 1):
+                    acc = None
+                    for ky in UP2_TAPS[py][a]:
+                        for kx in UP2_TAPS[px][b]:
+                            acc = wt[:, ky, kx] if acc is None else acc + wt[:, ky, kx]
+                    taps.append(acc)
+            phases.append(torch.stack(taps, 1))
+    return torch.stack(phases, 0)
+
+
 def packed_entries(arch: UNetArch, sd: Dict[str, torch.Tensor], tdtype, device) -> "OrderedDict[str, torch.Tensor]":
     f32 = torch.float32
     out: "OrderedDict[str, torch.Tensor]" = OrderedDict()
@@ -62,6 +88,10 @@ def packed_entries(arch: UNetArch, sd: Dict[str, torch.Tensor], tdtype, device) 
     def conv3(name):
         w = get(name)  # [O,I,3,3]
         return cast(_pad_rows(w.permute(0, 2, 3, 1).reshape(w.shape[0], -1)))
+
+    def conv3_up2(name):
+        f = fold_up2(get(name))  # fp32 sums first; cast (one rounding, or the x3 split) afterwards
+        return cast(torch.stack([_pad_rows(f[ph].reshape(f.shape[1], -1)) for ph in range(4)], 0))
 
     def mat(name):
         w = get(name)
@@ -95,6 +125,8 @@ def packed_entries(arch: UNetArch, sd: Dict[str, torch.Tensor], tdtype, device) 
             for n in (".in_layers.2", ".out_layers.3"):
                 out[pfx + n + ".weight"] = conv3(pfx + n + ".weight")
                 out[pfx + n + ".bias"] = get(pfx + n + ".bias")
+            if _ud == 2:   # up-sampling block: in_layers.2 also in its four-phase form (the 9-tap weights stay: K22_UP_PHASE=0, unsupported shapes)
+                out[pfx + ".in_layers.2.weight_up2"] = conv3_up2(pfx + ".in_layers.2.weight")
             if cin != cout:
                 out[pfx + ".skip_connection.weight"] = mat(pfx + ".skip_connection.weight")
                 out[pfx + ".skip_connection.bias"] = get(pfx + ".skip_connection.bias")
