@@ -1,6 +1,7 @@
-// k22 - shared by the LDS-resident-halo convolution kernels (conv3_halo.hip: lock-step kernels; gemm8.hip; conv3_spec.hip: the
-// producer / consumer specialised kernel): fragment loaders, the LDS-DMA helper, the fused GroupNorm-apply rewrite, the common
-// epilogue halo_tail, and the LDS budget every launcher and kernel agrees on.
+// k22 - shared by the LDS-resident-halo convolution kernels (conv3_halo.hip: lock-step kernels; conv3_up2.hip; gemm8.hip; conv3_spec.hip:
+// the producer / consumer specialised kernel): fragment loaders, the LDS-DMA helper, the fused GroupNorm-apply rewrite, the one definition
+// of the 8-wave frame (block map, slab range, loader offsets and issues), of the tap body and of the tap step, the common epilogue
+// halo_tail, and the LDS budget and launch dispatch every launcher and kernel agrees on.
 #pragma once
 #include "kernels.h"
 #include <stdlib.h>
@@ -174,22 +175,261 @@ __device__ __forceinline__ void glds16w_asm(const void* g, unsigned lds_dst) {
 
 constexpr int HALO_BN = 128;
 constexpr int HALO_NW = 8;        // waves per workgroup
-constexpr int HALO_MAXA = 8;      // halo LDS-DMA slots per wave per slab: taps 0 .. 9-NBST carry one each
+constexpr int HALO_GM = 8;        // m-tiles per group of the block map
 
-// Each iteration issues [weight tile NBST-1 taps ahead (2 loads)] THEN [one halo piece]: the halo piece is the
+// Each iteration issues [weight tile NBST-1 taps ahead (2 loads)] THEN [the halo pieces of this tap]: the halo piece is the
 // youngest entry of the VMEM queue, so the counted wait for the weight tile can leave it in flight — it gets two
-// taps (~1.6 us at 96x96) to come back from the Infinity Cache / HBM instead of one.  This is the number of halo
-// pieces issued in the NBST-1 iterations before tap T, i.e. younger than the weight tile tap T needs; taps are
-// unrolled, so it is a compile-time constant.
-template <int NBST> constexpr int halo_count_a(int t) {
+// taps (~1.6 us at 96x96) to come back from the Infinity Cache / HBM instead of one.  Taps 0 .. TAPS-NBST of a slab issue halo
+// pieces; this is the number of such taps among the NBST-1 iterations before tap T, i.e. younger than the weight tile tap T
+// needs; taps are unrolled, so it is a compile-time constant.
+template <int TAPS, int NBST> constexpr int halo_count(int t) {
   int c = 0;
   for (int k = 1; k <= NBST - 1; ++k) {
     const int u = t - k;
-    if (u >= 0 && u <= 9 - NBST) ++c;
+    if (u >= 0 && u <= TAPS - NBST) ++c;
   }
   return c;
 }
+// (row, column) of tap t in its filter: 3x3, or the 2x2 filter of one up-sampling phase
+template <int TAPS> constexpr int halo_tap_dy(int t) { return TAPS == 9 ? t / 3 : t >> 1; }
+template <int TAPS> constexpr int halo_tap_dx(int t) { return TAPS == 9 ? t % 3 : t & 1; }
 
+// ---- the frame: 512 threads = 8 waves own one BM x 128 tile of a (gx m-tiles) x (gy n-tiles) x splitk grid -------------------
+// block -> (k-split bz, m-tile bx, n-tile by): XCD remap, then groups of HALO_GM m-tiles that walk the n-tiles together
+__device__ __forceinline__ void halo_block_map(const IgemmParams& p, int gx, int gy, int& bz, int& bx, int& by) {
+  constexpr int GM = HALO_GM;
+  int L = p.xcd_remap ? xcd_remap_h(blockIdx.x, gridDim.x) : (int)blockIdx.x;
+  const int per_z = gx * gy;
+  bz = L / per_z;
+  L -= bz * per_z;
+  const int grp = L / (GM * gy);
+  const int first_m = grp * GM;
+  const int gsz = gx - first_m < GM ? gx - first_m : GM;
+  const int lin = L - grp * GM * gy;
+  bx = first_m + lin % gsz;
+  by = lin / gsz;
+}
+// K slabs [s0, s1) of k-split bz
+__device__ __forceinline__ void halo_slab_range(const IgemmParams& p, int nslab, int bz, int& s0, int& s1) {
+  s0 = 0;
+  s1 = nslab;
+  if (p.splitk > 1) {
+    const int per = (nslab + p.splitk - 1) / p.splitk;
+    s0 = bz * per;
+    s1 = s0 + per < nslab ? s0 + per : nslab;
+  }
+}
+template <int MI, int NI> __device__ __forceinline__ void halo_zero_acc(f32x16_t (&acc)[MI][NI]) {
+#pragma unroll
+  for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < NI; ++ni)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
+}
+// LDS byte address of the dynamic shared segment (wave-uniform), for the asm LDS-DMA path
+__device__ __forceinline__ unsigned halo_lds_base(char* smem) {
+  return __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) char*)smem);
+}
+// one 16-byte-per-lane LDS-DMA: GASM = from inline asm (glds16_asm above; WEIGHT: glds16w_asm) to LDS byte address lds_addr, else the
+// compiler's builtin to the same place given as a pointer
+template <bool GASM, bool WEIGHT> __device__ __forceinline__ void halo_dma16(const void* g, unsigned lds_addr, char* lds_ptr) {
+  if constexpr (!GASM)
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g, (__attribute__((address_space(3))) void*)lds_ptr, 16, 0, 0);
+  else if constexpr (WEIGHT) glds16w_asm(g, __builtin_amdgcn_readfirstlane(lds_addr));
+  else glds16_asm(g, __builtin_amdgcn_readfirstlane(lds_addr));
+}
+
+}  // namespace
+
+// The macros below are the one text of the loaders, the tap body and the tap step of the kernels on this frame.  They are macros, not
+// functions: hipcc's schedule of the tap loop (address arithmetic, lgkmcnt waits) moves when the same text goes through a function
+// template, and does not when it is expanded in place (profiles/halo_frame_device_code.txt).  Names they take from the kernel:
+// smem, lds0 (halo_lds_base), GASM (constexpr bool, halo_dma16), h, KSTEPS, MI, NI, acc, and what each one lists.
+//
+// Row-tile LDS-DMA offsets (weight tiles; the A tile of the plain GEMM): loader wave LW of NWL issues rows [8 * (LW + NWL * i), + 8) in its
+// slot i; lane -> (row, 16-byte position lane % 8).  OFF[i] = ELEM, the element offset of row n = FIRST + row clamped to LAST (an
+// expression of n), plus the chunk the XOR swizzle of common.h assigns to this lane.
+#define K22_ROW_OFFSETS(OFF, SLOTS, LW, NWL, FIRST, LAST, ELEM)                                            \
+  _Pragma("unroll") for (int i = 0; i < (SLOTS); ++i) {                                                    \
+    const int row = 8 * ((LW) + (NWL) * i) + (lane >> 3);                                                  \
+    int n = (FIRST) + row;                                                                                 \
+    if (n > (LAST)) n = (LAST);                                                                            \
+    const int chunk = (lane & 7) ^ ((row >> 1) & 7);                                                       \
+    OFF[i] = (ELEM) + chunk * EPC;                                                                         \
+  }
+// Halo-piece LDS-DMA offsets: piece j (RP rows of 1024 / RP bytes: 8 x 128, or 16 x 64 in conv3_halo3_kernel) of the NP_ of a halo buffer is
+// issued by loader wave j % NWL in its slot j / NWL; lane -> (row RP * j + lane / (64 / RP), position lane % (64 / RP)).  FIRST = plane
+// position of the LDS image's row 0; PR_MAX = last position of the plane.
+#define K22_PIECE_OFFSETS(AOFF, SLOTS, LW, NWL, FIRST, NP_, RP)                                            \
+  _Pragma("unroll") for (int q = 0; q < (SLOTS); ++q) {                                                    \
+    int j = q * (NWL) + (LW);                                                                              \
+    if (j > (NP_) - 1) j = (NP_) - 1;  /* surplus slots re-load the last piece (same bytes, same place): uniform counting */ \
+    const int hr = (RP) * j + (lane >> ((RP) == 8 ? 3 : 2));                                               \
+    int pr = (FIRST) + hr;                                                                                 \
+    if (pr > PR_MAX) pr = PR_MAX;                                                                          \
+    const int chunk = (lane & (64 / (RP) - 1)) ^ ((hr >> ((RP) == 8 ? 1 : 2)) & (64 / (RP) - 1));          \
+    AOFF[q] = pr * p.Kc + chunk * EPC;                                                                     \
+  }
+// An LDS location (the DST of the macros below) is a pointer into smem unless a kernel says otherwise: the producer waves of
+// conv3_halo_spec_kernel name theirs by LDS byte address (lds0 + offset) and redefine these two.  (Both spellings of one place, and both
+// kept: hipcc's output follows the spelling.)
+#define K22_LDS_ADDR(AT) (lds0 + (unsigned)((AT) - smem))
+#define K22_LDS_PTR(AT) (AT)
+// Halo piece of slot Q of loader wave LW of NWL, K slab SLAB, into the halo buffer at LDS location DST.  Needs Aimg, aoff, NP, BK.
+#define K22_ISSUE_A(LW, NWL, Q, SLAB, DST)                                                                 \
+  {                                                                                                        \
+    int j_ = (Q) * (NWL) + (LW);                                                                           \
+    if (j_ > NP - 1) j_ = NP - 1;                                                                          \
+    halo_dma16<GASM, false>(Aimg + aoff[Q] + (SLAB) * BK, K22_LDS_ADDR(DST) + j_ * 1024, K22_LDS_PTR(DST) + j_ * 1024); \
+  }
+// Row tile (K22_ROW_OFFSETS: OFF[SLOTS]) of SRC at element offset KOFS, for a loader wave of NWL whose slot 0 lands at LDS byte address
+// DADDR = pointer DPTR (the wave's 1 KB of the tile; DPTR is read by the compiler-issued form only).
+#define K22_ISSUE_ROWS(WEIGHT, SRC, OFF, SLOTS, NWL, KOFS, DADDR, DPTR)                                    \
+  _Pragma("unroll") for (int i = 0; i < (SLOTS); ++i)                                                      \
+      halo_dma16<GASM, WEIGHT>((SRC) + OFF[i] + (KOFS), (DADDR) + i * (NWL) * 1024, (DPTR) + i * (NWL) * 1024);
+// The weight tile (Wp, boff) at element offset KOFS into the tile at LDS location DST, by loader wave LW of NWL
+#define K22_ISSUE_B(LW, NWL, KOFS, DST)                                                                    \
+  {                                                                                                        \
+    const int kofs_ = (KOFS);                                                                              \
+    const auto dst_ = (DST) + (LW) * 1024;                                                                 \
+    K22_ISSUE_ROWS(true, Wp, boff, B_SLOTS, NWL, kofs_, K22_LDS_ADDR(dst_), K22_LDS_PTR(dst_))             \
+  }
+
+// acc += B . A over the MI x NI atoms of a wave
+#define K22_MMA_ALL(B, A)                                                                                  \
+  _Pragma("unroll") for (int mi = 0; mi < MI; ++mi)                                                        \
+    _Pragma("unroll") for (int ni = 0; ni < NI; ++ni) mma_atom(acc[mi][ni], B[ni], A[mi]);
+// No fragment read of a tap's (slab's) LDS slot may be in flight when the slot is refilled after the next barrier: right behind barrier
+// TAP + 1 the loaders refill the weight slot THIS tap read, whatever the ring depth (and behind a slab's last tap the halo buffer of the
+// slab before).  Nothing is left to the DMA's latency.  (The MFMAs that use the fragments can still sink below the barrier: registers only.)
+#define K22_READS_DONE() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
+// The plain tap body: per k-step, the fragments (types FA / FB; activation rows AROW with swizzle key ASW as expressions of mi, loaded by
+// LDA; weight rows BROW of ni with key BSW), then MI x NI atoms; hipcc schedules it.
+#define K22_TAP_PLAIN(FA, FB, LDA, AROW, ASW, BROW, BSW)                                                   \
+  _Pragma("unroll") for (int ks = 0; ks < KSTEPS; ++ks) {                                                  \
+    FA a[MI];                                                                                              \
+    FB b[NI];                                                                                              \
+    _Pragma("unroll") for (int mi = 0; mi < MI; ++mi) LDA(a[mi], AROW, ASW, ks, h);                        \
+    _Pragma("unroll") for (int ni = 0; ni < NI; ++ni) ld_frag_at(b[ni], BROW, BSW, ks, h);                 \
+    K22_MMA_ALL(b, a)                                                                                      \
+  }
+// The explicit two-set fragment pipeline across the per-tap barrier.  The fragments of k-step ks + 1 are read from LDS BEFORE the MFMAs of
+// k-step ks are issued (two register sets: ca / cb here, pa / pb in the kernel - zero before the first tap, a no-op group), and the last
+// k-step of a tap is multiplied after the NEXT tap's barrier (K22_MMA_ALL(pb, pa) behind the loop for the last one).  MID stands between a
+// read group and the MFMA group of the set read before it, END behind that MFMA group: sched_barrier(0) twice where every wave also loads
+// (K22_PIPE_LOCKSTEP), nothing and the read-behind-every-MFMA interleave in the consumer waves (K22_PIPE_INTERLEAVED).
+#define K22_TAP_PIPE(...) K22_TAP_PIPE_(__VA_ARGS__)
+#define K22_TAP_PIPE_(FA, FB, AROW, ASW, BROW, BSW, MID, END)                                              \
+  {                                                                                                        \
+    FA ca[MI];                                                                                             \
+    FB cb[NI];                                                                                             \
+    _Pragma("unroll") for (int ks = 0; ks < KSTEPS; ks += 2) {                                             \
+      _Pragma("unroll") for (int mi = 0; mi < MI; ++mi) ld_frag_at(ca[mi], AROW, ASW, ks, h);              \
+      _Pragma("unroll") for (int ni = 0; ni < NI; ++ni) ld_frag_at(cb[ni], BROW, BSW, ks, h);              \
+      MID;                                                                                                 \
+      K22_MMA_ALL(pb, pa)                                                                                  \
+      END;                                                                                                 \
+      _Pragma("unroll") for (int mi = 0; mi < MI; ++mi) ld_frag_at(pa[mi], AROW, ASW, ks + 1, h);          \
+      _Pragma("unroll") for (int ni = 0; ni < NI; ++ni) ld_frag_at(pb[ni], BROW, BSW, ks + 1, h);          \
+      MID;                                                                                                 \
+      K22_MMA_ALL(cb, ca)                                                                                  \
+      END;                                                                                                 \
+    }                                                                                                      \
+  }
+#define K22_PIPE_LOCKSTEP __builtin_amdgcn_sched_barrier(0), __builtin_amdgcn_sched_barrier(0)
+// One block of the consumers' pipeline = NRD fragment reads (of the NEXT group) + NMF MFMAs (of the group read one block ago), which are
+// independent of each other: one read is scheduled behind every MPR MFMAs (0x008 = MFMA, 0x100 = DS read), so that each ds_read_b128
+// issues under the 32 cycles the MFMA before it occupies the pipe.  Needs NRD, NMF, MPR (halo_pipe_reads).
+#define K22_INTERLEAVE()                                                                                   \
+  {                                                                                                        \
+    _Pragma("unroll") for (int i_ = 0; i_ < NRD; ++i_) {                                                   \
+      __builtin_amdgcn_sched_group_barrier(0x008, MPR, 0);                                                 \
+      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                                                   \
+    }                                                                                                      \
+    if constexpr (NMF - MPR * NRD > 0) __builtin_amdgcn_sched_group_barrier(0x008, NMF - MPR * NRD, 0);    \
+    __builtin_amdgcn_sched_barrier(0);                                                                     \
+  }
+#define K22_PIPE_INTERLEAVED (void)0, K22_INTERLEAVE()
+
+// M(tap, ...) for every tap of the filter, with literal tap numbers: the vmcnt immediates and the (slab, tap) of the prefetched weight
+// tile are compile-time functions of the tap
+#define K22_TAPS_9(M, ...) M(0, __VA_ARGS__) M(1, __VA_ARGS__) M(2, __VA_ARGS__) M(3, __VA_ARGS__) M(4, __VA_ARGS__) M(5, __VA_ARGS__) M(6, __VA_ARGS__) M(7, __VA_ARGS__) M(8, __VA_ARGS__)
+#define K22_TAPS_4(M, ...) M(0, __VA_ARGS__) M(1, __VA_ARGS__) M(2, __VA_ARGS__) M(3, __VA_ARGS__)
+// A kernel may stand statements at four points of a tap: K22_TAP_HOOK(0 .. 3, TAP) = before the counted wait, behind it, behind the
+// barrier, behind the tap body (conv3_halo_kernel's TRACE stamps; the fused GroupNorm-apply producers' coefficient load)
+#define K22_TAP_HOOK(N, TAP)
+// The loaders' half of a tap, for loader wave LW of NWL in a TAPS-tap filter (weights [n][tap][Kc]) with an NBST-deep weight ring behind
+// the two halo buffers: the counted vmcnt wait for this tap's weight tile (VMEM queue of a wave per tap: [weight tile NBST-1 taps ahead,
+// B_SLOTS loads] then [PPT halo pieces, taps 0 .. TAPS-NBST]: at most the B_SLOTS * (NBST-2) younger weight loads and the halo pieces issued
+// since stay in flight; the last halo piece of a slab is followed by the weight loads of NBST-1 taps, so at tap 0 of the next slab it is
+// older than everything the wait leaves in flight), the ONE raw barrier of the tap, then the weight tile NBST-1 taps ahead into ring slot
+// `fill` and the next PPT pieces of the next slab's halo (ISSUE_HALO: K22_ISSUE_A or a macro of its signature) into the halo buffer at
+// LDS location ANEXT; RING = the LDS location of the weight ring (pasted as written: its sum with the slot offset is one expression).
+// Needs s, sn, fill, B_BYTES, B_SLOTS, NBST, p.
+#define K22_TAP_FRONT(TAP, TAPS, LW, NWL, PPT, WAITS, LOADS, ISSUE_HALO, ANEXT, RING)                      \
+  K22_TAP_HOOK(0, TAP)                                                                                     \
+  if (WAITS) wait_vmcnt<B_SLOTS * (NBST - 2) + (PPT) * halo_count<TAPS, NBST>(TAP)>();                     \
+  K22_TAP_HOOK(1, TAP)                                                                                     \
+  raw_barrier();                                                                                           \
+  K22_TAP_HOOK(2, TAP)                                                                                     \
+  if (LOADS) {                                                                                             \
+    constexpr int ta_ = ((TAP) + NBST - 1) % (TAPS);                                                       \
+    const int sa_ = ((TAP) + NBST - 1 >= (TAPS)) ? sn : s;                                                 \
+    K22_ISSUE_B(LW, NWL, ta_ * p.Kc + sa_ * BK, RING + fill * B_BYTES);                                    \
+    if constexpr ((TAP) <= (TAPS) - NBST) {                                                                \
+      _Pragma("unroll") for (int a_ = 0; a_ < (PPT); ++a_) {                                               \
+        constexpr int qb_ = ((TAP) <= (TAPS) - NBST ? (TAP) : 0) * (PPT);                                  \
+        ISSUE_HALO(LW, NWL, qb_ + a_, sn, ANEXT);                                                          \
+      }                                                                                                    \
+    }                                                                                                      \
+  }
+// The multiplying half of a tap: the fragment rows of the tap (A row = abase + mi*32 + tap shift in the current halo buffer Acur, B row =
+// brow[ni] in ring slot `cur`), the body (K22_TAP_PLAIN / K22_TAP_PIPE over arow, asw, Bcur), the read drain, the rotation of `cur`.
+#define K22_TAP_COMPUTE(TAP, TAPS, ...)                                                                    \
+  const char* Bcur = Bst + cur * B_BYTES;                                                                  \
+  constexpr int dy_ = halo_tap_dy<TAPS>(TAP), dx_ = halo_tap_dx<TAPS>(TAP);                                \
+  const int shift = dy_ * W2 + dx_;                                                                        \
+  const char* arow[MI];                                                                                    \
+  int asw[MI];                                                                                             \
+  _Pragma("unroll") for (int mi = 0; mi < MI; ++mi) {                                                      \
+    const int ar = abase + mi * 32 + shift;                                                                \
+    arow[mi] = Acur + ar * 128;                                                                            \
+    asw[mi] = (ar >> 1) & 7;                                                                               \
+  }                                                                                                        \
+  __VA_ARGS__                                                                                              \
+  K22_READS_DONE();                                                                                        \
+  K22_TAP_HOOK(3, TAP)                                                                                     \
+  cur = (cur + 1 == NBST) ? 0 : cur + 1;
+// One tap of a lock-step kernel: every wave loads, then multiplies
+#define K22_LOCKSTEP_TAP(TAP, TAPS, PPT, INLOOP, ...)                                                      \
+  {                                                                                                        \
+    K22_TAP_FRONT(TAP, TAPS, wave, NW, PPT, INLOOP, INLOOP, K22_ISSUE_A, Anext, Bst)                       \
+    K22_TAP_COMPUTE(TAP, TAPS, __VA_ARGS__)                                                                \
+    fill = (fill + 1 == NBST) ? 0 : fill + 1;                                                              \
+  }
+// The K loop of a lock-step kernel over slabs [s0, s1): prologue = the whole halo of the first slab (A_SLOTS pieces per wave), then the
+// weight tiles of taps 0 .. NBST-2; then TAPS taps per slab, the halo double-buffered across slabs.  LOADER: this wave issues LDS-DMA;
+// INLOOP: also inside the tap loop.
+#define K22_LOCKSTEP_LOOP(TAPS, A_SLOTS, PPT, LOADER, INLOOP, BODY)                                        \
+  if (s0 < s1) {                                                                                           \
+    if (LOADER) {                                                                                          \
+      _Pragma("unroll") for (int q = 0; q < (A_SLOTS); ++q) K22_ISSUE_A(wave, NW, q, s0, smem);            \
+      _Pragma("unroll") for (int t = 0; t < NBST - 1; ++t) K22_ISSUE_B(wave, NW, t * p.Kc + s0 * BK, Bst + t * B_BYTES); \
+    }                                                                                                      \
+    int cur = 0;               /* ring slot of the current tap's weights */                                \
+    int fill = NBST - 1;       /* ring slot the tile NBST-1 taps ahead goes into */                        \
+    for (int s = s0; s < s1; ++s) {                                                                        \
+      char* const Acur = smem + ((s - s0) & 1) * A_BYTES;                                                  \
+      char* const Anext = smem + (((s - s0) & 1) ^ 1) * A_BYTES;                                           \
+      const int sn = s + 1 < s1 ? s + 1 : s1 - 1;  /* past-the-end loads re-read the last slab (uniform counting) */ \
+      K22_TAPS_##TAPS(K22_LOCKSTEP_TAP, TAPS, PPT, INLOOP, BODY)                                           \
+    }                                                                                                      \
+  }
+
+namespace {
+// fragment reads of one block of the interleaved pipeline (x2: the activation fragment is ONE read, hi piece only)
+template <typename T, int MI, int NI> constexpr int halo_pipe_reads() { return is_x2<T>::value ? MI + 2 * NI : (MI + NI) * FragCost<T>::READS; }
 }  // namespace
 
 // Everything after the 3x3 K loop, shared by the halo kernels: optional fused 1x1 skip connection (a plain-GEMM K loop
@@ -247,13 +487,7 @@ __device__ __forceinline__ void halo_tail(const IgemmParams& p, f32x16_t (&acc)[
         schunk[i] = ((lane & 7) ^ ((row >> 1) & 7)) * EPC;
       }
       int wsoff[B_SLOTS];
-#pragma unroll
-      for (int i = 0; i < B_SLOTS; ++i) {
-        const int row = 8 * (wave + NW * i) + (lane >> 3);
-        int n = n0 + row;
-        if (n > p.Npad - 1) n = p.Npad - 1;
-        wsoff[i] = n * SK + ((lane & 7) ^ ((row >> 1) & 7)) * EPC;
-      }
+      K22_ROW_OFFSETS(wsoff, B_SLOTS, wave, NW, n0, p.Npad - 1, n * SK)
       const T* __restrict__ X0 = reinterpret_cast<const T*>(p.S0);
       const T* __restrict__ X1 = reinterpret_cast<const T*>(p.S1);
       const T* __restrict__ Ws = reinterpret_cast<const T*>(p.Ws);
@@ -265,7 +499,8 @@ __device__ __forceinline__ void halo_tail(const IgemmParams& p, f32x16_t (&acc)[
       // lgkmcnt(0); past-the-end issues re-load the last slab (uniform counting), drained by the vmcnt(0) below the loop.
       constexpr int NSK = BM == 256 ? 3 : 4;               // 3 x 48 KB / 4 x 32 KB of the 160 KB
       constexpr int SCH = SA_SLOTS + B_SLOTS;              // LDS-DMA instructions per wave per slab
-      const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) char*)smem);
+      constexpr bool GASM = true;
+      const unsigned lds0 = halo_lds_base(smem);
 #define K22_ISSUE_SKIP(Q, BUFI)                                                                            \
       {                                                                                                    \
         int q_ = (Q);                                                                                      \
@@ -278,8 +513,7 @@ __device__ __forceinline__ void halo_tail(const IgemmParams& p, f32x16_t (&acc)[
         const unsigned dA_ = lds0 + (BUFI) * SBUF + wave * 1024;                                           \
         _Pragma("unroll") for (int i = 0; i < SA_SLOTS; ++i)                                               \
             glds16_asm(xs_ + (int64_t)spix[i] * ldx_ + kk_ + schunk[i], __builtin_amdgcn_readfirstlane(dA_ + i * NW * 1024)); \
-        _Pragma("unroll") for (int i = 0; i < B_SLOTS; ++i)                                                \
-            glds16w_asm(Ws + wsoff[i] + k0_, __builtin_amdgcn_readfirstlane(dA_ + BM * 128 + i * NW * 1024)); \
+        K22_ISSUE_ROWS(true, Ws, wsoff, B_SLOTS, NW, k0_, dA_ + BM * 128, smem + (dA_ - lds0) + BM * 128)  \
       }
 #pragma unroll
       for (int t = 0; t < NSK - 1; ++t) K22_ISSUE_SKIP(q0 + t, t);
@@ -294,20 +528,9 @@ __device__ __forceinline__ void halo_tail(const IgemmParams& p, f32x16_t (&acc)[
         // (asymmetric split: the skip input is the un-normalised residual stream - its operand rounding alone costs as much as that of
         // every GroupNorm output together, tests/golden/drift_ablation_x2.json - so this K loop keeps all three MFMAs)
         using TSK = typename SkipT<T>::type;
-#pragma unroll
-        for (int ks = 0; ks < KSTEPS; ++ks) {
-          Frag<TSK> a[MI], b[NI];
-#pragma unroll
-          for (int mi = 0; mi < MI; ++mi) ld_frag_at_a<true, TSK>(a[mi], sA + (abase + mi * 32) * 128, bsw, ks, h);   // S0 / S1: plain T rows
-#pragma unroll
-          for (int ni = 0; ni < NI; ++ni) ld_frag_at(b[ni], sB + brow[ni], bsw, ks, h);
-#pragma unroll
-          for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-            for (int ni = 0; ni < NI; ++ni) mma_atom(acc[mi][ni], b[ni], a[mi]);
+        K22_TAP_PLAIN(Frag<TSK>, Frag<TSK>, (ld_frag_at_a<true, TSK>), sA + (abase + mi * 32) * 128, bsw, sB + brow[ni], bsw)   // S0 / S1: plain T rows
         }
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // no fragment read of this stage in flight when it is refilled after the next barrier
+        K22_READS_DONE();
         buf = (buf + 1 == NSK) ? 0 : buf + 1;
         fill = (fill + 1 == NSK) ? 0 : fill + 1;
       }
@@ -467,30 +690,63 @@ __device__ __forceinline__ void halo_tail(const IgemmParams& p, f32x16_t (&acc)[
 }
 
 // ---- host side ---------------------------------------------------------------------------------
-inline int halo_rows(const IgemmParams& p, int bm) { return (bm + 2 * (p.W + 2) + 2 + 7) & ~7; }
+constexpr int UP2_ASLOTS = 6;   // conv3_up2_kernel: halo LDS-DMA slots per wave per slab (48 pieces = 384 rows)
 
-inline size_t halo_smem_bytes(const IgemmParams& p, int bm, int nbst) {
-  // (+ 1 KB behind the weight ring for the fused GroupNorm-apply form: the landing place of its surplus DMA slots)
-  const size_t main_loop = (size_t)2 * halo_rows(p, bm) * 128 + (size_t)nbst * HALO_BN * 128 + (p.gn_coeff ? 1024 : 0);
+// rows of the LDS halo image of a BM tile, whole 8-row pieces: taps == 9 (3x3): BM + 2*(W+2) + 2; taps == 4 (one 2x2 phase): BM + (W+2) + 1
+inline int halo_rows(const IgemmParams& p, int bm, int taps) {
+  const int r = taps == 9 ? 2 : 1;
+  return (bm + r * (p.W + 2) + r + 7) & ~7;
+}
+// m-tiles per image: BM consecutive positions of the H x (W+2) plane each, whatever the filter
+inline int halo_tiles_per_image(const IgemmParams& p, int bm) { return (p.H * (p.W + 2) + bm - 1) / bm; }
+
+// LDS budget of a kernel on the frame: its main loop, or what halo_tail needs behind it - the fp32 epilogue tile, the statistics reduction,
+// the NSK stages of the fused skip's ring
+inline size_t halo_lds_budget(int bm, bool skip, size_t main_loop) {
   const size_t epi = (size_t)bm * (HALO_BN * 4 + 16);
   const size_t red = (size_t)32 * HALO_BN * 2 * 4;
-  const size_t skip = p.S0 ? (size_t)(bm == 256 ? 3 : 4) * (bm * 128 + HALO_BN * 128) : 0;   // halo_tail: NSK stages
+  const size_t sk = skip ? (size_t)(bm == 256 ? 3 : 4) * (bm * 128 + HALO_BN * 128) : 0;
   size_t m = main_loop > epi ? main_loop : epi;
-  m = m > skip ? m : skip;
+  m = m > sk ? m : sk;
   return m > red ? m : red;
 }
+// 128-byte-row kernels: two halo buffers + an nbst-deep weight ring (+ 1 KB behind the ring for the fused GroupNorm-apply form: the
+// landing place of its surplus DMA slots).  The four-phase problems have neither that form nor a fused skip.
+inline size_t halo_smem_bytes(const IgemmParams& p, int bm, int nbst, int taps = 9) {
+  const size_t main_loop = (size_t)2 * halo_rows(p, bm, taps) * 128 + (size_t)nbst * HALO_BN * 128 + (taps == 9 && p.gn_coeff ? 1024 : 0);
+  return halo_lds_budget(bm, taps == 9 && p.S0, main_loop);
+}
 
-// deepest weight ring (2, 3, 4 or 6 tiles) that fits the LDS next to the double-buffered halo and still leaves
-// enough halo slots (taps 0 .. 9-NBST, one 8-row piece per wave each); 0 = the problem does not fit at all.
-// Depth matters at the low-resolution levels: their weights stream from HBM (~2 us away) while a tap is
+// deepest instantiated weight ring (3x3: 6, 4, 3 or 2 tiles; four-phase: 4 or 2) that fits the LDS next to the double-buffered halo and
+// still leaves enough halo slots (3x3: taps 0 .. 9-NBST, one 8-row piece per wave each; four-phase: UP2_ASLOTS); 0 = the problem does
+// not fit at all.  Depth matters at the low-resolution levels: their weights stream from HBM (~2 us away) while a tap is
 // 0.2-0.4 us of MFMA work, so a workgroup must keep ~64+ KB of weight tiles in flight (Little's law).
-inline int halo_pick_nbst(const IgemmParams& p, int bm) {
-  const int np = halo_rows(p, bm) / 8;
+inline int halo_pick_nbst(const IgemmParams& p, int bm, int taps = 9) {
+  const int np = halo_rows(p, bm, taps) / 8;
   for (int nbst : {6, 4, 3, 2}) {
-    if (np > (10 - nbst) * HALO_NW) continue;
-    if (halo_smem_bytes(p, bm, nbst) > 160 * 1024) continue;
+    if (taps == 4 && nbst != 4 && nbst != 2) continue;
+    if (np > (taps == 9 ? 10 - nbst : UP2_ASLOTS) * HALO_NW) continue;
+    if (halo_smem_bytes(p, bm, nbst, taps) > 160 * 1024) continue;
     return nbst;
   }
   return 0;
 }
 
+// ---- launch: L.bm / L.depth -> the instantiation --------------------------------------------------
+// one launch of kernel K with dynamic LDS (its own per-device attribute guard)
+template <auto K> int halo_run(const IgemmParams& p, const IgemmLaunch& L, hipStream_t stream) {
+  static LdsAttrGuard guard;
+  return launch_lds_kernel(K, guard, L.grid, L.block, L.lds, 160 * 1024, stream, p);
+}
+// f(std::integral_constant<int, BM>): BM = 256 if bm says so and the form has it (HAS256), else 128
+template <bool HAS256 = true, typename F> int halo_with_bm(int bm, F&& f) {
+  if constexpr (HAS256) {
+    if (bm == 256) return f(std::integral_constant<int, 256>{});
+  }
+  return f(std::integral_constant<int, 128>{});
+}
+// f(std::integral_constant<int, D>): D = the first of the instantiated depths that `depth` equals, the last of them for any other
+template <int D0, int... DEPTHS, typename F> int halo_with_depth(int depth, F&& f) {
+  if constexpr (sizeof...(DEPTHS) == 0) return f(std::integral_constant<int, D0>{});
+  else return depth == D0 ? f(std::integral_constant<int, D0>{}) : halo_with_depth<DEPTHS...>(depth, f);
+}

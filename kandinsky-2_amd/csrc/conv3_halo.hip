@@ -51,7 +51,6 @@ __global__ __launch_bounds__(512) void conv3_halo_kernel(const IgemmParams p) {
   constexpr int B_BYTES = BN * 128;
   constexpr int APT = HALO_NW / LW;     // halo pieces per loader wave per tap
   constexpr int A_SLOTS = (10 - NBST) * APT;  // taps 0 .. 9-NBST issue APT halo pieces per loader wave
-  constexpr int GM = 8;
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
   const int tid = threadIdx.x, lane = tid & 63;
@@ -69,61 +68,21 @@ __global__ __launch_bounds__(512) void conv3_halo_kernel(const IgemmParams p) {
   const int PR_MAX = (p.H + 2) * W2 - 1;       // last pixel of one padded plane
   const int B = p.M / (p.H * p.W);
 
-  // ---- block -> (m-tile, n-tile, k-split) ------------------------------------------------------
-  const int gx = B * TPI, gy = (p.N + BN - 1) / BN;
-  int L = p.xcd_remap ? xcd_remap_h(blockIdx.x, gridDim.x) : (int)blockIdx.x;
-  const int per_z = gx * gy;
-  const int bz = L / per_z;
-  L -= bz * per_z;
-  const int grp = L / (GM * gy);
-  const int first_m = grp * GM;
-  const int gsz = gx - first_m < GM ? gx - first_m : GM;
-  const int lin = L - grp * GM * gy;
-  const int bx = first_m + lin % gsz, by = lin / gsz;
+  int bz, bx, by;
+  halo_block_map(p, B * TPI, (p.N + BN - 1) / BN, bz, bx, by);
   const int img = bx / TPI, v0 = (bx - img * TPI) * BM;
   const int n0 = by * BN;
 
   const T* __restrict__ Aimg = reinterpret_cast<const T*>(p.A0) + (int64_t)img * (p.H + 2) * W2 * p.Kc;
   const T* __restrict__ Wp = reinterpret_cast<const T*>(p.Wp);
-
-  // ---- loader geometry ---------------------------------------------------------------------------
-  // halo piece j (8 rows) is issued by wave j % NW in its slot j / NW; lane -> (row 8j + lane/8, position lane%8)
-  int aoff[A_SLOTS];
-#pragma unroll
-  for (int q = 0; q < A_SLOTS; ++q) {
-    int j = q * NW + wave;
-    if (j > NP - 1) j = NP - 1;  // surplus slots re-load the last piece (same bytes, same place): uniform counting
-    const int hr = 8 * j + (lane >> 3);
-    int pr = v0 + hr;
-    if (pr > PR_MAX) pr = PR_MAX;
-    const int chunk = (lane & 7) ^ ((hr >> 1) & 7);
-    aoff[q] = pr * p.Kc + chunk * EPC;
-  }
-  int boff[B_SLOTS];
-#pragma unroll
-  for (int i = 0; i < B_SLOTS; ++i) {
-    const int row = 8 * (wave + NW * i) + (lane >> 3);
-    int n = n0 + row;
-    if (n > p.Npad - 1) n = p.Npad - 1;
-    const int chunk = (lane & 7) ^ ((row >> 1) & 7);
-    boff[i] = n * 9 * p.Kc + chunk * EPC;
-  }
-  const int nslab = p.Kc / BK;
-  int s0 = 0, s1 = nslab;
-  if (p.splitk > 1) {
-    const int per = (nslab + p.splitk - 1) / p.splitk;
-    s0 = bz * per;
-    s1 = s0 + per < nslab ? s0 + per : nslab;
-  }
+  int aoff[A_SLOTS], boff[B_SLOTS];
+  K22_PIECE_OFFSETS(aoff, A_SLOTS, wave, NW, v0, NP, 8)
+  K22_ROW_OFFSETS(boff, B_SLOTS, wave, NW, n0, p.Npad - 1, n * 9 * p.Kc)
+  int s0, s1;
+  halo_slab_range(p, p.Kc / BK, bz, s0, s1);
 
   f32x16_t acc[MI][NI];
-#pragma unroll
-  for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
-
+  halo_zero_acc(acc);
   FragA<T> pa[MI];          // PIPE: fragments read but not yet multiplied (zero = a no-op group before the first tap)
   Frag<T> pb[NI];
   if constexpr (PIPE) {
@@ -139,140 +98,47 @@ __global__ __launch_bounds__(512) void conv3_halo_kernel(const IgemmParams p) {
 #pragma unroll
   for (int ni = 0; ni < NI; ++ni) brow[ni] = (wn * (BN / WN) + ni * 32 + l31) * 128;
   const int bsw = (l31 >> 1) & 7;  // (row >> 1) & 7 with row = multiple of 32 + l31
+  const unsigned lds0 = halo_lds_base(smem);
+  int trace_it = 0;
+  (void)trace_it;
 
-  // LDS byte address of the dynamic shared segment (wave-uniform), for the asm LDS-DMA path
-  const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) char*)smem);
-#define K22_ISSUE_A(Q, SLAB, DST)                                                                          \
-  {                                                                                                        \
-    int j_ = (Q) * NW + wave;                                                                              \
-    if (j_ > NP - 1) j_ = NP - 1;                                                                          \
-    if constexpr (GASM)                                                                                    \
-      glds16_asm(Aimg + aoff[Q] + (SLAB) * BK, __builtin_amdgcn_readfirstlane(lds0 + (unsigned)((DST) - smem) + j_ * 1024)); \
-    else                                                                                                   \
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(Aimg + aoff[Q] + (SLAB) * BK), \
-                                     (__attribute__((address_space(3))) void*)((DST) + j_ * 1024), 16, 0, 0); \
-  }
-#define K22_ISSUE_B(SLAB, TAP, STAGE)                                                                      \
-  {                                                                                                        \
-    const int kofs_ = (TAP) * p.Kc + (SLAB) * BK;                                                          \
-    char* dst_ = Bst + (STAGE) * B_BYTES + wave * 1024;                                                    \
-    _Pragma("unroll") for (int i = 0; i < B_SLOTS; ++i) {                                                  \
-      if constexpr (GASM)                                                                                  \
-        glds16w_asm(Wp + boff[i] + kofs_, __builtin_amdgcn_readfirstlane(lds0 + (unsigned)(dst_ - smem) + i * NW * 1024)); \
-      else                                                                                                 \
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(Wp + boff[i] + kofs_), \
-                                         (__attribute__((address_space(3))) void*)(dst_ + i * NW * 1024), 16, 0, 0); \
+  // TRACE: s_memtime stamps around the wait, the barrier and the tap body (launch_conv3_halo_trace below)
+#undef K22_TAP_HOOK
+#define K22_TAP_HOOK(N, TAP) K22_HALO_TRACE_##N
+#define K22_HALO_TRACE_0                                                                                   \
+  unsigned long long tr0_ = 0, tr1_ = 0, tr2_ = 0;                                                         \
+  if constexpr (TRACE) tr0_ = __builtin_amdgcn_s_memtime();
+#define K22_HALO_TRACE_1 if constexpr (TRACE) tr1_ = __builtin_amdgcn_s_memtime();
+#define K22_HALO_TRACE_2 if constexpr (TRACE) tr2_ = __builtin_amdgcn_s_memtime();
+#define K22_HALO_TRACE_3                                                                                   \
+  if constexpr (TRACE) {                                                                                   \
+    /* stamp after the last MFMA has been ISSUED (issue blocks while the pipe is busy) */                  \
+    asm volatile("" ::"v"(acc[0][0][0]), "v"(acc[MI - 1][NI - 1][15]));                                    \
+    const unsigned long long tr3_ = __builtin_amdgcn_s_memtime();                                          \
+    if (blockIdx.x == 0 && (wave == 0 || wave == 5) && lane == 0 && p.trace != nullptr) {                  \
+      unsigned long long* o_ = p.trace + ((size_t)(wave ? 1 : 0) * 4096 + (size_t)trace_it * 4);           \
+      if (trace_it < 1024) { o_[0] = tr0_; o_[1] = tr1_; o_[2] = tr2_; o_[3] = tr3_; }                      \
     }                                                                                                      \
+    ++trace_it;                                                                                            \
   }
-
-  if (s0 < s1) {
-    // prologue: the whole halo of the first slab, then the weight tiles of taps 0 .. NBST-2
-    if (loader) {
-#pragma unroll
-      for (int q = 0; q < A_SLOTS; ++q) K22_ISSUE_A(q, s0, smem);
-#pragma unroll
-      for (int t = 0; t < NBST - 1; ++t) K22_ISSUE_B(s0, t, t);
-    }
-    int trace_it = 0;
-    (void)trace_it;
-    int cur = 0;               // ring slot of the current tap's weights
-    int fill = NBST - 1;       // ring slot the tile NBST-1 taps ahead goes into
-    for (int s = s0; s < s1; ++s) {
-      char* const Acur = smem + ((s - s0) & 1) * A_BYTES;
-      char* const Anext = smem + (((s - s0) & 1) ^ 1) * A_BYTES;
-      const int sn = s + 1 < s1 ? s + 1 : s1 - 1;  // past-the-end loads re-read the last slab (uniform counting)
-      // the nine taps are expanded with literal tap numbers: the vmcnt immediates and the (slab, tap) of the
-      // prefetched weight tile are compile-time functions of the tap
-#define K22_TAP(TAP)                                                                                       \
-      {                                                                                                    \
-        unsigned long long tr0_ = 0, tr1_ = 0, tr2_ = 0;                                                   \
-        if constexpr (TRACE) tr0_ = __builtin_amdgcn_s_memtime();                                          \
-        if (loader && !DBG_NOLOAD) wait_vmcnt<B_SLOTS * (NBST - 2) + APT * halo_count_a<NBST>(TAP)>();     \
-        if constexpr (TRACE) tr1_ = __builtin_amdgcn_s_memtime();                                          \
-        raw_barrier();                                                                      \
-        if constexpr (TRACE) tr2_ = __builtin_amdgcn_s_memtime();                                          \
-        /* the weight tile NBST-1 taps ahead, then the next piece(s) of the next slab's halo */            \
-        if (loader && !DBG_NOLOAD) {                                                                       \
-          constexpr int ta_ = ((TAP) + NBST - 1) % 9;                                                      \
-          const int sa_ = ((TAP) + NBST - 1 >= 9) ? sn : s;                                                \
-          K22_ISSUE_B(sa_, ta_, fill);                                                                     \
-          if constexpr ((TAP) <= 9 - NBST) {                                                               \
-            _Pragma("unroll") for (int a_ = 0; a_ < APT; ++a_) {                                           \
-              constexpr int qb_ = ((TAP) <= 9 - NBST ? (TAP) : 0) * APT;                                   \
-              K22_ISSUE_A(qb_ + a_, sn, Anext);                                                            \
-            }                                                                                              \
-          }                                                                                                \
-        }                                                                                                  \
-        const char* Bcur = Bst + cur * B_BYTES;                                                            \
-        const int shift = ((TAP) / 3) * W2 + ((TAP) % 3);                                                  \
-        const char* arow[MI];                                                                              \
-        int asw[MI];                                                                                       \
-        _Pragma("unroll") for (int mi = 0; mi < MI; ++mi) {                                                \
-          const int ar = abase + mi * 32 + shift;                                                          \
-          arow[mi] = Acur + ar * 128;                                                                      \
-          asw[mi] = (ar >> 1) & 7;                                                                         \
-        }                                                                                                  \
-        if constexpr (PIPE) {                                                                              \
-          FragA<T> ca[MI];                                                                                 \
-          Frag<T> cb[NI];                                                                                  \
-          _Pragma("unroll") for (int ks = 0; ks < KSTEPS; ks += 2) {                                       \
-            _Pragma("unroll") for (int mi = 0; mi < MI; ++mi) ld_frag_at(ca[mi], arow[mi], asw[mi], ks, h); \
-            _Pragma("unroll") for (int ni = 0; ni < NI; ++ni) ld_frag_at(cb[ni], Bcur + brow[ni], bsw, ks, h); \
-            __builtin_amdgcn_sched_barrier(0);                                                             \
-            _Pragma("unroll") for (int mi = 0; mi < MI; ++mi)                                              \
-              _Pragma("unroll") for (int ni = 0; ni < NI; ++ni) mma_atom(acc[mi][ni], pb[ni], pa[mi]);     \
-            __builtin_amdgcn_sched_barrier(0);                                                             \
-            _Pragma("unroll") for (int mi = 0; mi < MI; ++mi) ld_frag_at(pa[mi], arow[mi], asw[mi], ks + 1, h); \
-            _Pragma("unroll") for (int ni = 0; ni < NI; ++ni) ld_frag_at(pb[ni], Bcur + brow[ni], bsw, ks + 1, h); \
-            __builtin_amdgcn_sched_barrier(0);                                                             \
-            _Pragma("unroll") for (int mi = 0; mi < MI; ++mi)                                              \
-              _Pragma("unroll") for (int ni = 0; ni < NI; ++ni) mma_atom(acc[mi][ni], cb[ni], ca[mi]);     \
-            __builtin_amdgcn_sched_barrier(0);                                                             \
-          }                                                                                                \
-          /* the reads of the last k-step are complete before the slot can be refilled (after the next barrier) */ \
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                               \
-        } else {                                                                                           \
-        _Pragma("unroll") for (int ks = 0; ks < KSTEPS; ++ks) {                                            \
-          FragA<T> a[MI];                                                                                  \
-          Frag<T> b[NI];                                                                                   \
-          _Pragma("unroll") for (int mi = 0; mi < MI; ++mi) ld_frag_at(a[mi], arow[mi], asw[mi], ks, h);   \
-          _Pragma("unroll") for (int ni = 0; ni < NI; ++ni) ld_frag_at(b[ni], Bcur + brow[ni], bsw, ks, h); \
-          if constexpr (DBG_NOMMA) {                                                                       \
-            _Pragma("unroll") for (int mi = 0; mi < MI; ++mi) asm volatile("" ::"v"(a[mi].v));             \
-            _Pragma("unroll") for (int ni = 0; ni < NI; ++ni) asm volatile("" ::"v"(b[ni].v));             \
-          } else {                                                                                         \
-          _Pragma("unroll") for (int mi = 0; mi < MI; ++mi)                                                \
-            _Pragma("unroll") for (int ni = 0; ni < NI; ++ni) mma_atom(acc[mi][ni], b[ni], a[mi]);         \
-          }                                                                                                \
-        }                                                                                                  \
-        /* no fragment read of this tap's weight slot in flight when the slot is refilled after the next barrier */ \
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                 \
-        }                                                                                                  \
-        if constexpr (TRACE) {                                                                             \
-          /* stamp after the last MFMA has been ISSUED (issue blocks while the pipe is busy) */            \
-          asm volatile("" ::"v"(acc[0][0][0]), "v"(acc[MI - 1][NI - 1][15]));                             \
-          const unsigned long long tr3_ = __builtin_amdgcn_s_memtime();                                    \
-          if (blockIdx.x == 0 && (wave == 0 || wave == 5) && lane == 0 && p.trace != nullptr) {            \
-            unsigned long long* o_ = p.trace + ((size_t)(wave ? 1 : 0) * 4096 + (size_t)trace_it * 4);     \
-            if (trace_it < 1024) { o_[0] = tr0_; o_[1] = tr1_; o_[2] = tr2_; o_[3] = tr3_; }                \
-          }                                                                                                \
-          ++trace_it;                                                                                      \
-        }                                                                                                  \
-        cur = (cur + 1 == NBST) ? 0 : cur + 1;                                                             \
-        fill = (fill + 1 == NBST) ? 0 : fill + 1;                                                          \
-      }
-      K22_TAP(0) K22_TAP(1) K22_TAP(2) K22_TAP(3) K22_TAP(4) K22_TAP(5) K22_TAP(6) K22_TAP(7) K22_TAP(8)
-#undef K22_TAP
-    }
-  }
-#undef K22_ISSUE_A
-#undef K22_ISSUE_B
-  if constexpr (PIPE) {
-#pragma unroll
-    for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-      for (int ni = 0; ni < NI; ++ni) mma_atom(acc[mi][ni], pb[ni], pa[mi]);
-  }
+  // DBG_NOMMA: the fragments are read and kept alive, nothing is multiplied
+#define K22_HALO_BODY                                                                                      \
+  if constexpr (PIPE) K22_TAP_PIPE(FragA<T>, Frag<T>, arow[mi], asw[mi], Bcur + brow[ni], bsw, K22_PIPE_LOCKSTEP) \
+  else if constexpr (DBG_NOMMA) {                                                                          \
+    _Pragma("unroll") for (int ks = 0; ks < KSTEPS; ++ks) {                                                \
+      FragA<T> a[MI];                                                                                      \
+      Frag<T> b[NI];                                                                                       \
+      _Pragma("unroll") for (int mi = 0; mi < MI; ++mi) ld_frag_at(a[mi], arow[mi], asw[mi], ks, h);       \
+      _Pragma("unroll") for (int ni = 0; ni < NI; ++ni) ld_frag_at(b[ni], Bcur + brow[ni], bsw, ks, h);    \
+      _Pragma("unroll") for (int mi = 0; mi < MI; ++mi) asm volatile("" ::"v"(a[mi].v));                   \
+      _Pragma("unroll") for (int ni = 0; ni < NI; ++ni) asm volatile("" ::"v"(b[ni].v));                   \
+    }                                                                                                      \
+  } else { K22_TAP_PLAIN(FragA<T>, Frag<T>, ld_frag_at, arow[mi], asw[mi], Bcur + brow[ni], bsw) }
+  K22_LOCKSTEP_LOOP(9, A_SLOTS, APT, loader, loader && !DBG_NOLOAD, K22_HALO_BODY)
+#undef K22_HALO_BODY
+#undef K22_TAP_HOOK
+#define K22_TAP_HOOK(N, TAP)
+  if constexpr (PIPE) { K22_MMA_ALL(pb, pa) }
   halo_tail<T, BM>(p, acc, smem, bx, bz, img, v0, n0);
 }
 
@@ -311,7 +177,6 @@ __global__ __launch_bounds__(512) void conv3_halo3_kernel(const IgemmParams p) {
   constexpr int BN = HALO_BN, NW = HALO_NW, WM = 4, WN = 2;
   constexpr int MI = BM / (WM * 32), NI = BN / (WN * 32);
   constexpr int BT_BYTES = 3 * BN * 64;      // weight tiles of one iteration (three taps)
-  constexpr int GM = 8;
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
   const int tid = threadIdx.x, lane = tid & 63;
@@ -328,16 +193,8 @@ __global__ __launch_bounds__(512) void conv3_halo3_kernel(const IgemmParams p) {
   const int PR_MAX = (p.H + 2) * W2 - 1;
   const int B = p.M / (p.H * p.W);
 
-  const int gx = B * TPI, gy = (p.N + BN - 1) / BN;
-  int L = p.xcd_remap ? xcd_remap_h(blockIdx.x, gridDim.x) : (int)blockIdx.x;
-  const int per_z = gx * gy;
-  const int bz = L / per_z;
-  L -= bz * per_z;
-  const int grp = L / (GM * gy);
-  const int first_m = grp * GM;
-  const int gsz = gx - first_m < GM ? gx - first_m : GM;
-  const int lin = L - grp * GM * gy;
-  const int bx = first_m + lin % gsz, by = lin / gsz;
+  int bz, bx, by;
+  halo_block_map(p, B * TPI, (p.N + BN - 1) / BN, bz, bx, by);
   const int img = bx / TPI, v0 = (bx - img * TPI) * BM;
   const int n0 = by * BN;
 
@@ -346,15 +203,7 @@ __global__ __launch_bounds__(512) void conv3_halo3_kernel(const IgemmParams p) {
 
   // loader geometry: a piece = 16 rows x 64 B; lane -> (row 16*piece + lane/4, position lane%4)
   int aoff[HALO3_ASLOTS];
-#pragma unroll
-  for (int q = 0; q < HALO3_ASLOTS; ++q) {
-    int j = q * NW + wave;
-    if (j > NPA - 1) j = NPA - 1;   // surplus slots re-load the last piece (same bytes, same place): uniform counting
-    const int hr = 16 * j + (lane >> 2);
-    int pr = v0 + hr;
-    if (pr > PR_MAX) pr = PR_MAX;
-    aoff[q] = pr * p.Kc + ((lane & 3) ^ ((hr >> 2) & 3)) * EPC;
-  }
+  K22_PIECE_OFFSETS(aoff, HALO3_ASLOTS, wave, NW, v0, NPA, 16)
   int boff;
   {
     const int row = 16 * wave + (lane >> 2);
@@ -362,21 +211,11 @@ __global__ __launch_bounds__(512) void conv3_halo3_kernel(const IgemmParams p) {
     if (n > p.Npad - 1) n = p.Npad - 1;
     boff = n * 9 * p.Kc + ((lane & 3) ^ ((row >> 2) & 3)) * EPC;
   }
-  const int nhs = p.Kc / EPH;
-  int h0 = 0, h1 = nhs;
-  if (p.splitk > 1) {
-    const int per = (nhs + p.splitk - 1) / p.splitk;
-    h0 = bz * per;
-    h1 = h0 + per < nhs ? h0 + per : nhs;
-  }
+  int h0, h1;
+  halo_slab_range(p, p.Kc / EPH, bz, h0, h1);
 
   f32x16_t acc[MI][NI];
-#pragma unroll
-  for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
+  halo_zero_acc(acc);
 
   char* const Bring = smem + 2 * A_BYTES;
   const int abase = wm * (BM / WM) + l31;
@@ -468,11 +307,7 @@ __global__ __launch_bounds__(512) void conv3_halo3_kernel(const IgemmParams p) {
 // ---- host side ---------------------------------------------------------------------------------
 static int halo3_rows(const IgemmParams& p, int bm) { return (bm + 2 * (p.W + 2) + 2 + 15) & ~15; }
 static size_t halo3_smem_bytes(const IgemmParams& p, int bm, int rb) {
-  const size_t main_loop = (size_t)2 * halo3_rows(p, bm) * 64 + (size_t)rb * 3 * HALO_BN * 64;
-  const size_t epi = (size_t)bm * (HALO_BN * 4 + 16);
-  const size_t skip = p.S0 ? (size_t)(bm == 256 ? 3 : 4) * (bm * 128 + HALO_BN * 128) : 0;   // halo_tail: NSK stages
-  size_t m = main_loop > epi ? main_loop : epi;
-  return m > skip ? m : skip;
+  return halo_lds_budget(bm, p.S0 != nullptr, (size_t)2 * halo3_rows(p, bm) * 64 + (size_t)rb * 3 * HALO_BN * 64);
 }
 static int halo3_pick_rb(const IgemmParams& p, int bm) {
   if (halo3_rows(p, bm) / 16 > HALO3_ASLOTS * HALO_NW) return 0;
@@ -505,36 +340,17 @@ bool conv3_halo_supported(const IgemmParams& p, int dtype, int bm) {
   return true;
 }
 
-int conv3_halo_tiles_per_image(const IgemmParams& p, int bm) { return (p.H * (p.W + 2) + bm - 1) / bm; }
+int conv3_halo_tiles_per_image(const IgemmParams& p, int bm) { return halo_tiles_per_image(p, bm); }
 size_t conv3_halo_lds_bytes(const IgemmParams& p, int bm, int depth) { return p.algo == IG_ALGO_HALO3 ? halo3_smem_bytes(p, bm, depth) : halo_smem_bytes(p, bm, depth); }
 
-template <typename T, int BM, int NBST, int MODE>
-static int run_halo(const IgemmParams& p, const IgemmLaunch& L, hipStream_t stream) {
-  static LdsAttrGuard guard;
-  return launch_lds_kernel(conv3_halo_kernel<T, BM, NBST, false, 8, MODE>, guard, L.grid, L.block, L.lds, 160 * 1024, stream, p);
-}
-template <typename T, int BM, int MODE>
-static int launch_halo_depth(const IgemmParams& p, const IgemmLaunch& L, hipStream_t stream) {
-  if (L.depth == 2) return run_halo<T, BM, 2, MODE>(p, L, stream);
-  if (L.depth == 3) return run_halo<T, BM, 3, MODE>(p, L, stream);
-  if (L.depth == 4) return run_halo<T, BM, 4, MODE>(p, L, stream);
-  return run_halo<T, BM, 6, MODE>(p, L, stream);
-}
-template <typename T, int MODE>
-static int launch_halo_bm(const IgemmParams& p, const IgemmLaunch& L, hipStream_t stream) {
-  return L.bm == 256 ? launch_halo_depth<T, 256, MODE>(p, L, stream) : launch_halo_depth<T, 128, MODE>(p, L, stream);
-}
-
-template <typename T, int BM, int RB>
-static int run_halo3(const IgemmParams& p, const IgemmLaunch& L, hipStream_t stream) {
-  static LdsAttrGuard guard;
-  return launch_lds_kernel(conv3_halo3_kernel<T, BM, RB>, guard, L.grid, L.block, L.lds, 160 * 1024, stream, p);
-}
-template <typename T, int BM>
-static int launch_halo3_depth(const IgemmParams& p, const IgemmLaunch& L, hipStream_t stream) {
-  if (L.depth == 2) return run_halo3<T, BM, 2>(p, L, stream);
-  if (L.depth == 3) return run_halo3<T, BM, 3>(p, L, stream);
-  return run_halo3<T, BM, 4>(p, L, stream);
+// conv3_halo_kernel in form MODE at (L.bm, L.depth)
+template <typename T, int MODE, bool HAS128 = true>
+static int launch_halo_mode(const IgemmParams& p, const IgemmLaunch& L, hipStream_t stream) {
+  auto depth = [&](auto bm) {
+    return halo_with_depth<2, 3, 4, 6>(L.depth, [&](auto d) { return halo_run<conv3_halo_kernel<T, decltype(bm)::value, decltype(d)::value, false, 8, MODE>>(p, L, stream); });
+  };
+  if constexpr (!HAS128) return depth(std::integral_constant<int, 256>{});
+  else return halo_with_bm(L.bm, depth);
 }
 
 // developer tool: conv3_halo_kernel<bf16, 256, NBST> with per-tap s_memtime stamps (wave 0 and wave 5 of block 0):
@@ -546,7 +362,7 @@ int launch_conv3_halo_trace(const IgemmParams& p, int dtype, hipStream_t stream)
   IgemmParams q = p;
   q.splitk = 1; q.xcd_remap = 1;
   const int B = p.M / (p.H * p.W);
-  const int nblocks = B * conv3_halo_tiles_per_image(p, 256) * ((p.N + HALO_BN - 1) / HALO_BN);
+  const int nblocks = B * halo_tiles_per_image(p, 256) * ((p.N + HALO_BN - 1) / HALO_BN);
   if (nbst == 4) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3_halo_kernel<bf16_t, 256, 4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     hipLaunchKernelGGL((conv3_halo_kernel<bf16_t, 256, 4, true>), dim3(nblocks), dim3(512), smem, stream, q);
@@ -566,16 +382,19 @@ int launch_conv3_halo(const IgemmParams& p, int dtype, const IgemmLaunch& L, hip
   return k22_with_dtype(dtype, [&](auto tag) {
     using T = typename decltype(tag)::type;
     if constexpr (!is_x3<T>::value) {
-      if (L.family == IG_FAM_HALO3) return L.bm == 256 ? launch_halo3_depth<T, 256>(p, L, stream) : launch_halo3_depth<T, 128>(p, L, stream);
-      if (L.pipe == 0) return launch_halo_bm<T, 0>(p, L, stream);
-      if (L.pipe == 1) return launch_halo_bm<T, 1>(p, L, stream);
+      if (L.family == IG_FAM_HALO3)
+        return halo_with_bm(L.bm, [&](auto bm) {
+          return halo_with_depth<2, 3, 4>(L.depth, [&](auto d) { return halo_run<conv3_halo3_kernel<T, decltype(bm)::value, decltype(d)::value>>(p, L, stream); });
+        });
+      if (L.pipe == 0) return launch_halo_mode<T, 0>(p, L, stream);
+      if (L.pipe == 1) return launch_halo_mode<T, 1>(p, L, stream);
 #ifdef K22_DEBUG_VARIANTS   // measurement-only variants (wrong results), bf16 at BM = 256: 3 = no LDS-DMA in the loop, 4 = no MFMA
       if constexpr (std::is_same<T, bf16_t>::value) {
-        if (L.pipe == 3) return launch_halo_depth<T, 256, 3>(p, L, stream);
-        if (L.pipe == 4) return launch_halo_depth<T, 256, 4>(p, L, stream);
+        if (L.pipe == 3) return launch_halo_mode<T, 3, false>(p, L, stream);
+        if (L.pipe == 4) return launch_halo_mode<T, 4, false>(p, L, stream);
       }
 #endif
     }
-    return launch_halo_bm<T, 2>(p, L, stream);
+    return launch_halo_mode<T, 2>(p, L, stream);
   });
 }

@@ -40,7 +40,7 @@ __global__ __launch_bounds__(512) void conv3_halo_spec_kernel(const IgemmParams 
   constexpr int B_BYTES = BN * 128;
   constexpr int APT = 2;                       // halo pieces per producer per tap (taps 0 .. 9-NBST)
   constexpr int A_SLOTS = (10 - NBST) * APT;
-  constexpr int GM = 8;
+  constexpr bool GASM = true;
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
   const int tid = threadIdx.x, lane = tid & 63;
@@ -57,36 +57,38 @@ __global__ __launch_bounds__(512) void conv3_halo_spec_kernel(const IgemmParams 
   const int PR_MAX = (p.H + 2) * W2 - 1;
   const int B = p.M / (p.H * p.W);
 
-  const int gx = B * TPI, gy = (p.N + BN - 1) / BN;
-  int L = p.xcd_remap ? xcd_remap_h(blockIdx.x, gridDim.x) : (int)blockIdx.x;
-  const int per_z = gx * gy;
-  const int bz = L / per_z;
-  L -= bz * per_z;
-  const int grp = L / (GM * gy);
-  const int first_m = grp * GM;
-  const int gsz = gx - first_m < GM ? gx - first_m : GM;
-  const int lin = L - grp * GM * gy;
-  const int bx = first_m + lin % gsz, by = lin / gsz;
+  int bz, bx, by;
+  halo_block_map(p, B * TPI, (p.N + BN - 1) / BN, bz, bx, by);
   const int img = bx / TPI, v0 = (bx - img * TPI) * BM;
   const int n0 = by * BN;
-
-  const int nslab = p.Kc / BK;
-  int s0 = 0, s1 = nslab;
-  if (p.splitk > 1) {
-    const int per = (nslab + p.splitk - 1) / p.splitk;
-    s0 = bz * per;
-    s1 = s0 + per < nslab ? s0 + per : nslab;
-  }
+  int s0, s1;
+  halo_slab_range(p, p.Kc / BK, bz, s0, s1);
 
   f32x16_t acc[MI][NI];
-#pragma unroll
-  for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
+  halo_zero_acc(acc);
 
   char* const Bst = smem + 2 * A_BYTES;
+  // The producers' K loop, shared by their two forms: per tap the loaders' half (K22_TAP_FRONT; WAITS / LOADS: the DBG forms leave one
+  // out), whatever the form does to what has landed (AFTER), the rotation of the ring slot
+#define K22_PRODUCER_TAP(TAP, WAITS, LOADS, ISSUE_HALO, AFTER)                                             \
+  {                                                                                                        \
+    K22_TAP_FRONT(TAP, 9, lw, NWL, APT, WAITS, LOADS, ISSUE_HALO, lds0 + (unsigned)anext_off, lds0 + 2 * A_BYTES) \
+    AFTER(TAP)                                                                                             \
+    fill = (fill + 1 == NBST) ? 0 : fill + 1;                                                              \
+  }
+#define K22_PRODUCER_LOOP(WAITS, LOADS, ISSUE_HALO, AFTER)                                                 \
+  int fill = NBST - 1;                                                                                     \
+  for (int s = s0; s < s1; ++s) {                                                                          \
+    const int anext_off = (((s - s0) & 1) ^ 1) * A_BYTES;                                                  \
+    const int sn = s + 1 < s1 ? s + 1 : s1 - 1;   /* past-the-end loads re-read the last slab (uniform counting) */ \
+    const bool more = s + 1 < s1;                 /* a next slab exists */                                 \
+    K22_TAPS_9(K22_PRODUCER_TAP, WAITS, LOADS, ISSUE_HALO, AFTER)                                          \
+  }
+#define K22_PRODUCER_NOTHING(TAP)
+#undef K22_LDS_ADDR
+#undef K22_LDS_PTR
+#define K22_LDS_ADDR(AT) (AT)
+#define K22_LDS_PTR(AT) (smem + ((AT) - lds0))
   if (s0 < s1) {
     if (producer && p.gn_coeff != nullptr) {
       // ------------------------- producers, fused GroupNorm-apply: LDS-DMA of the RAW tensor, then rewrite in place ---------------------
@@ -123,36 +125,24 @@ __global__ __launch_bounds__(512) void conv3_halo_spec_kernel(const IgemmParams 
         bmask |= (border ? 1u : 0u) << q;
       }
       int boff[B_SLOTS];
-#pragma unroll
-      for (int i = 0; i < B_SLOTS; ++i) {
-        const int row = 8 * (lw + NWL * i) + (lane >> 3);
-        int n = n0 + row;
-        if (n > p.Npad - 1) n = p.Npad - 1;
-        boff[i] = n * 9 * p.Kc + ((lane & 7) ^ ((row >> 1) & 7)) * EPC;
-      }
-      const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) char*)smem);
+      K22_ROW_OFFSETS(boff, B_SLOTS, lw, NWL, n0, p.Npad - 1, n * 9 * p.Kc)
+      const unsigned lds0 = halo_lds_base(smem);
       const unsigned lds_scratch = lds0 + 2 * A_BYTES + NBST * B_BYTES;
       u32x4_t cfr[NCF];
 #pragma unroll
       for (int k = 0; k < NCF; ++k) cfr[k] = u32x4_t{0u, 0u, 0u, 0u};
-#define K22_GN_A(Q, SLAB, DSTOFF)                                                                          \
+      // K22_ISSUE_A's signature: the raw pixels of the piece, or the scratch load of a surplus slot
+#define K22_GN_A(LW, NWL_, Q, SLAB, DST)                                                                   \
       {                                                                                                    \
-        const int jn_ = (Q) * NWL + lw;                                                                    \
+        const int jn_ = (Q) * (NWL_) + (LW);                                                               \
         if (jn_ > NP - 1) {                                                                                \
           glds16_asm(reinterpret_cast<const char*>(p.Wp) + lane * 16, __builtin_amdgcn_readfirstlane(lds_scratch)); \
         } else {                                                                                           \
           const int k0_ = (SLAB) * BK;                                                                     \
           const bool second_ = k0_ >= p.gn_C0;                                                             \
           const T* sp_ = (second_ ? X1 + (int64_t)pix[Q] * C1 + (k0_ - p.gn_C0) : X0 + (int64_t)pix[Q] * p.gn_C0 + k0_) + gchunk * EPC; \
-          glds16_asm(sp_, __builtin_amdgcn_readfirstlane(lds0 + (unsigned)(DSTOFF) + jn_ * 1024));         \
+          glds16_asm(sp_, __builtin_amdgcn_readfirstlane((DST) + jn_ * 1024));                             \
         }                                                                                                  \
-      }
-#define K22_GN_B(SLAB, TAP, STAGE)                                                                         \
-      {                                                                                                    \
-        const int kofs_ = (TAP) * p.Kc + (SLAB) * BK;                                                      \
-        const unsigned d_ = lds0 + 2 * A_BYTES + (STAGE) * B_BYTES + lw * 1024;                            \
-        _Pragma("unroll") for (int i = 0; i < B_SLOTS; ++i)                                                \
-            glds16w_asm(Wp + boff[i] + kofs_, __builtin_amdgcn_readfirstlane(d_ + i * NWL * 1024));         \
       }
 #define K22_GN_COEF(SLAB)                                                                                  \
       {                                                                                                    \
@@ -178,121 +168,56 @@ __global__ __launch_bounds__(512) void conv3_halo_spec_kernel(const IgemmParams 
           *a_ = gn_rewrite16(T{}, *a_, cf_, p.gn_act, ((bmask >> (Q)) & 1u) != 0u);                        \
         }                                                                                                  \
       }
+      // behind the barrier of tap 0: the coefficients of the next slab (its halo is rewritten as it lands)
+#undef K22_TAP_HOOK
+#define K22_TAP_HOOK(N, TAP) K22_GN_HOOK_##N(TAP)
+#define K22_GN_HOOK_0(TAP)
+#define K22_GN_HOOK_1(TAP)
+#define K22_GN_HOOK_2(TAP) if constexpr ((TAP) == 0) { if (more) K22_GN_COEF(sn); }
+      // the pieces issued one tap ago (and the coefficients issued at tap 0) have had a whole tap to land: wait for everything
+      // older than THIS tap's DMA, rewrite them, and have the stores complete before the next barrier
+#define K22_GN_AFTER(TAP)                                                                                  \
+      if constexpr ((TAP) >= 1 && (TAP) - 1 <= 9 - NBST) {                                                 \
+        if (more) {                                                                                        \
+          gn_wait<B_SLOTS + ((TAP) <= 9 - NBST ? APT : 0)>(cfr);                                           \
+          _Pragma("unroll") for (int a_i = 0; a_i < APT; ++a_i) {                                          \
+            constexpr int qr_ = ((TAP) >= 1 ? (TAP) - 1 : 0) * APT;                                        \
+            K22_GN_REWRITE(qr_ + a_i, anext_off);                                                          \
+          }                                                                                                \
+          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                               \
+        }                                                                                                  \
+      }
       // prologue: coefficients of the first slab, its whole halo, the weight tiles of taps 0 .. NBST-2; then the halo is rewritten
       K22_GN_COEF(s0);
 #pragma unroll
-      for (int q = 0; q < A_SLOTS; ++q) K22_GN_A(q, s0, 0);
+      for (int q = 0; q < A_SLOTS; ++q) K22_GN_A(lw, NWL, q, s0, lds0);
 #pragma unroll
-      for (int t = 0; t < NBST - 1; ++t) K22_GN_B(s0, t, t);
+      for (int t = 0; t < NBST - 1; ++t) K22_ISSUE_B(lw, NWL, t * p.Kc + s0 * BK, lds0 + 2 * A_BYTES + t * B_BYTES);
       gn_wait<(NBST - 1) * B_SLOTS>(cfr);
 #pragma unroll
       for (int q = 0; q < A_SLOTS; ++q) K22_GN_REWRITE(q, 0);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      int fill = NBST - 1;
-      for (int s = s0; s < s1; ++s) {
-        const int anext_off = (((s - s0) & 1) ^ 1) * A_BYTES;
-        const int sn = s + 1 < s1 ? s + 1 : s1 - 1;   // past-the-end loads re-read the last slab (uniform counting)
-        const bool more = s + 1 < s1;                 // a next slab exists: its halo is rewritten as it lands
-#define K22_GN_PTAP(TAP)                                                                                   \
-        {                                                                                                  \
-          wait_vmcnt<B_SLOTS * (NBST - 2) + APT * halo_count_a<NBST>(TAP)>();                              \
-          raw_barrier();                                                                                   \
-          if constexpr ((TAP) == 0) { if (more) K22_GN_COEF(sn); }                                         \
-          constexpr int ta_ = ((TAP) + NBST - 1) % 9;                                                      \
-          const int sa_ = ((TAP) + NBST - 1 >= 9) ? sn : s;                                                \
-          K22_GN_B(sa_, ta_, fill);                                                                        \
-          if constexpr ((TAP) <= 9 - NBST) {                                                               \
-            _Pragma("unroll") for (int a_i = 0; a_i < APT; ++a_i) {                                        \
-              constexpr int qb_ = ((TAP) <= 9 - NBST ? (TAP) : 0) * APT;                                   \
-              K22_GN_A(qb_ + a_i, sn, anext_off);                                                          \
-            }                                                                                              \
-          }                                                                                                \
-          /* the pieces issued one tap ago (and the coefficients issued at tap 0) have had a whole tap to land: wait for everything   \
-             older than THIS tap's DMA, rewrite them, and have the stores complete before the next barrier */                        \
-          if constexpr ((TAP) >= 1 && (TAP) - 1 <= 9 - NBST) {                                             \
-            if (more) {                                                                                    \
-              gn_wait<B_SLOTS + ((TAP) <= 9 - NBST ? APT : 0)>(cfr);                                       \
-              _Pragma("unroll") for (int a_i = 0; a_i < APT; ++a_i) {                                      \
-                constexpr int qr_ = ((TAP) >= 1 ? (TAP) - 1 : 0) * APT;                                    \
-                K22_GN_REWRITE(qr_ + a_i, anext_off);                                                      \
-              }                                                                                            \
-              asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                           \
-            }                                                                                              \
-          }                                                                                                \
-          fill = (fill + 1 == NBST) ? 0 : fill + 1;                                                        \
-        }
-        K22_GN_PTAP(0) K22_GN_PTAP(1) K22_GN_PTAP(2) K22_GN_PTAP(3) K22_GN_PTAP(4) K22_GN_PTAP(5) K22_GN_PTAP(6) K22_GN_PTAP(7) K22_GN_PTAP(8)
-#undef K22_GN_PTAP
-      }
+      K22_PRODUCER_LOOP(true, true, K22_GN_A, K22_GN_AFTER)
+#undef K22_TAP_HOOK
+#define K22_TAP_HOOK(N, TAP)
 #undef K22_GN_A
-#undef K22_GN_B
 #undef K22_GN_COEF
 #undef K22_GN_REWRITE
+#undef K22_GN_AFTER
     } else if (producer) {
       // ---------------------------------------- producers: LDS-DMA only -----------------------------------------------
       const int lw = wave - 4;
       const T* __restrict__ Aimg = reinterpret_cast<const T*>(p.A0) + (int64_t)img * (p.H + 2) * W2 * p.Kc;
       const T* __restrict__ Wp = reinterpret_cast<const T*>(p.Wp);
-      int aoff[A_SLOTS];
+      int aoff[A_SLOTS], boff[B_SLOTS];
+      K22_PIECE_OFFSETS(aoff, A_SLOTS, lw, NWL, v0, NP, 8)
+      K22_ROW_OFFSETS(boff, B_SLOTS, lw, NWL, n0, p.Npad - 1, n * 9 * p.Kc)
+      const unsigned lds0 = halo_lds_base(smem);
 #pragma unroll
-      for (int q = 0; q < A_SLOTS; ++q) {
-        int j = q * NWL + lw;
-        if (j > NP - 1) j = NP - 1;   // surplus slots re-load the last piece (same bytes, same place): uniform counting
-        const int hr = 8 * j + (lane >> 3);
-        int pr = v0 + hr;
-        if (pr > PR_MAX) pr = PR_MAX;
-        aoff[q] = pr * p.Kc + ((lane & 7) ^ ((hr >> 1) & 7)) * EPC;
-      }
-      int boff[B_SLOTS];
+      for (int q = 0; q < A_SLOTS; ++q) K22_ISSUE_A(lw, NWL, q, s0, lds0);
 #pragma unroll
-      for (int i = 0; i < B_SLOTS; ++i) {
-        const int row = 8 * (lw + NWL * i) + (lane >> 3);
-        int n = n0 + row;
-        if (n > p.Npad - 1) n = p.Npad - 1;
-        boff[i] = n * 9 * p.Kc + ((lane & 7) ^ ((row >> 1) & 7)) * EPC;
-      }
-      const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) char*)smem);
-#define K22_SP_A(Q, SLAB, DSTOFF)                                                                          \
-      {                                                                                                    \
-        int j_ = (Q) * NWL + lw;                                                                           \
-        if (j_ > NP - 1) j_ = NP - 1;                                                                      \
-        glds16_asm(Aimg + aoff[Q] + (SLAB) * BK, __builtin_amdgcn_readfirstlane(lds0 + (unsigned)(DSTOFF) + j_ * 1024)); \
-      }
-#define K22_SP_B(SLAB, TAP, STAGE)                                                                         \
-      {                                                                                                    \
-        const int kofs_ = (TAP) * p.Kc + (SLAB) * BK;                                                      \
-        const unsigned d_ = lds0 + 2 * A_BYTES + (STAGE) * B_BYTES + lw * 1024;                            \
-        _Pragma("unroll") for (int i = 0; i < B_SLOTS; ++i)                                                \
-            glds16w_asm(Wp + boff[i] + kofs_, __builtin_amdgcn_readfirstlane(d_ + i * NWL * 1024));         \
-      }
-#pragma unroll
-      for (int q = 0; q < A_SLOTS; ++q) K22_SP_A(q, s0, 0);
-#pragma unroll
-      for (int t = 0; t < NBST - 1; ++t) K22_SP_B(s0, t, t);
-      int fill = NBST - 1;
-      for (int s = s0; s < s1; ++s) {
-        const int anext_off = (((s - s0) & 1) ^ 1) * A_BYTES;
-        const int sn = s + 1 < s1 ? s + 1 : s1 - 1;   // past-the-end loads re-read the last slab (uniform counting)
-#define K22_SP_PTAP(TAP)                                                                                   \
-        {                                                                                                  \
-          if constexpr (DBG == 0) wait_vmcnt<B_SLOTS * (NBST - 2) + APT * halo_count_a<NBST>(TAP)>();      \
-          raw_barrier();                                                                                   \
-          constexpr int ta_ = ((TAP) + NBST - 1) % 9;                                                      \
-          const int sa_ = ((TAP) + NBST - 1 >= 9) ? sn : s;                                                \
-          if constexpr (DBG != 1) K22_SP_B(sa_, ta_, fill);                                                \
-          if constexpr ((TAP) <= 9 - NBST && DBG != 1) {                                                   \
-            _Pragma("unroll") for (int a_ = 0; a_ < APT; ++a_) {                                           \
-              constexpr int qb_ = ((TAP) <= 9 - NBST ? (TAP) : 0) * APT;                                   \
-              K22_SP_A(qb_ + a_, sn, anext_off);                                                           \
-            }                                                                                              \
-          }                                                                                                \
-          fill = (fill + 1 == NBST) ? 0 : fill + 1;                                                        \
-        }
-        K22_SP_PTAP(0) K22_SP_PTAP(1) K22_SP_PTAP(2) K22_SP_PTAP(3) K22_SP_PTAP(4) K22_SP_PTAP(5) K22_SP_PTAP(6) K22_SP_PTAP(7) K22_SP_PTAP(8)
-#undef K22_SP_PTAP
-      }
-#undef K22_SP_A
-#undef K22_SP_B
+      for (int t = 0; t < NBST - 1; ++t) K22_ISSUE_B(lw, NWL, t * p.Kc + s0 * BK, lds0 + 2 * A_BYTES + t * B_BYTES);
+      K22_PRODUCER_LOOP(DBG == 0, DBG != 1, K22_ISSUE_A, K22_PRODUCER_NOTHING)
     } else {
       // ---------------------------------------- consumers: fragments + MFMA only --------------------------------------
       const int wm = wave >> 1, wn = wave & 1;
@@ -311,93 +236,36 @@ __global__ __launch_bounds__(512) void conv3_halo_spec_kernel(const IgemmParams 
 #pragma unroll
         for (int ni = 0; ni < NI; ++ni) pb[ni] = Frag<T>{};
       }
-      // One block of the pipeline = NRD fragment reads (of the NEXT group) + NMF MFMAs (of the group read one block ago), which
-      // are independent of each other: one read is scheduled behind every MPR MFMAs (0x008 = MFMA, 0x100 = DS read), so that
-      // each ds_read_b128 issues under the 32 cycles the MFMA before it occupies the pipe.
-      constexpr int NRD = is_x2<T>::value ? MI + 2 * NI : (MI + NI) * FragCost<T>::READS;   // x2: the activation fragment is ONE read (hi piece only)
-      constexpr int NMF = MI * NI * FragCost<T>::MFMAS;
-      constexpr int MPR = NMF / NRD;
-#define K22_SP_INTERLEAVE()                                                                                \
+      constexpr int NRD = halo_pipe_reads<T, MI, NI>(), NMF = MI * NI * FragCost<T>::MFMAS, MPR = NMF / NRD;   // K22_INTERLEAVE
+#define K22_SP_CTAP(TAP, ...)                                                                              \
       {                                                                                                    \
-        _Pragma("unroll") for (int i_ = 0; i_ < NRD; ++i_) {                                               \
-          __builtin_amdgcn_sched_group_barrier(0x008, MPR, 0);                                             \
-          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                                               \
-        }                                                                                                  \
-        if constexpr (NMF - MPR * NRD > 0) __builtin_amdgcn_sched_group_barrier(0x008, NMF - MPR * NRD, 0); \
-        __builtin_amdgcn_sched_barrier(0);                                                                 \
+        raw_barrier();                                                                                     \
+        K22_TAP_COMPUTE(TAP, 9,                                                                            \
+          if constexpr (PIPE) K22_TAP_PIPE(FragA<T>, Frag<T>, arow[mi], asw[mi], Bcur + brow[ni], bsw, K22_PIPE_INTERLEAVED) \
+          else { K22_TAP_PLAIN(FragA<T>, Frag<T>, ld_frag_at, arow[mi], asw[mi], Bcur + brow[ni], bsw) })  \
       }
       for (int s = s0; s < s1; ++s) {
         const char* const Acur = smem + ((s - s0) & 1) * A_BYTES;
-#define K22_SP_CTAP(TAP)                                                                                   \
-        {                                                                                                  \
-          raw_barrier();                                                                                   \
-          const char* Bcur = Bst + cur * B_BYTES;                                                          \
-          const int shift = ((TAP) / 3) * W2 + ((TAP) % 3);                                                \
-          const char* arow[MI];                                                                            \
-          int asw[MI];                                                                                     \
-          _Pragma("unroll") for (int mi = 0; mi < MI; ++mi) {                                              \
-            const int ar = abase + mi * 32 + shift;                                                        \
-            arow[mi] = Acur + ar * 128;                                                                    \
-            asw[mi] = (ar >> 1) & 7;                                                                       \
-          }                                                                                                \
-          if constexpr (PIPE) {                                                                            \
-            FragA<T> ca[MI];                                                                               \
-            Frag<T> cb[NI];                                                                                \
-            _Pragma("unroll") for (int ks = 0; ks < KSTEPS; ks += 2) {                                     \
-              _Pragma("unroll") for (int mi = 0; mi < MI; ++mi) ld_frag_at(ca[mi], arow[mi], asw[mi], ks, h); \
-              _Pragma("unroll") for (int ni = 0; ni < NI; ++ni) ld_frag_at(cb[ni], Bcur + brow[ni], bsw, ks, h); \
-              _Pragma("unroll") for (int mi = 0; mi < MI; ++mi)                                            \
-                _Pragma("unroll") for (int ni = 0; ni < NI; ++ni) mma_atom(acc[mi][ni], pb[ni], pa[mi]);   \
-              K22_SP_INTERLEAVE();                                                                         \
-              _Pragma("unroll") for (int mi = 0; mi < MI; ++mi) ld_frag_at(pa[mi], arow[mi], asw[mi], ks + 1, h); \
-              _Pragma("unroll") for (int ni = 0; ni < NI; ++ni) ld_frag_at(pb[ni], Bcur + brow[ni], bsw, ks + 1, h); \
-              _Pragma("unroll") for (int mi = 0; mi < MI; ++mi)                                            \
-                _Pragma("unroll") for (int ni = 0; ni < NI; ++ni) mma_atom(acc[mi][ni], cb[ni], ca[mi]);   \
-              K22_SP_INTERLEAVE();                                                                         \
-            }                                                                                              \
-          } else {                                                                                         \
-          _Pragma("unroll") for (int ks = 0; ks < KSTEPS; ++ks) {                                          \
-            FragA<T> a[MI];                                                                                \
-            Frag<T> b[NI];                                                                                 \
-            _Pragma("unroll") for (int mi = 0; mi < MI; ++mi) ld_frag_at(a[mi], arow[mi], asw[mi], ks, h); \
-            _Pragma("unroll") for (int ni = 0; ni < NI; ++ni) ld_frag_at(b[ni], Bcur + brow[ni], bsw, ks, h); \
-            _Pragma("unroll") for (int mi = 0; mi < MI; ++mi)                                              \
-              _Pragma("unroll") for (int ni = 0; ni < NI; ++ni) mma_atom(acc[mi][ni], b[ni], a[mi]);       \
-          }                                                                                                \
-          }                                                                                                \
-          /* Fragment reads may not stay in flight across the next barrier: right after barrier TAP+1 the producers refill    \
-             slot (TAP + NBST) % NBST = the weight slot THIS tap read, whatever the ring depth (and after tap 8 the halo buffer \
-             of the slab before).  Only the DMA's latency kept the NBST >= 3 forms correct in round 2; now nothing is left to   \
-             timing.  (The MFMAs that use the fragments can still sink below the barrier - registers only - in both forms.) */  \
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                               \
-          cur = (cur + 1 == NBST) ? 0 : cur + 1;                                                           \
-        }
-        K22_SP_CTAP(0) K22_SP_CTAP(1) K22_SP_CTAP(2) K22_SP_CTAP(3) K22_SP_CTAP(4) K22_SP_CTAP(5) K22_SP_CTAP(6) K22_SP_CTAP(7) K22_SP_CTAP(8)
+        K22_TAPS_9(K22_SP_CTAP, )
+      }
 #undef K22_SP_CTAP
-      }
-#undef K22_SP_INTERLEAVE
-      if constexpr (PIPE) {
-#pragma unroll
-        for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-          for (int ni = 0; ni < NI; ++ni) mma_atom(acc[mi][ni], pb[ni], pa[mi]);
-      }
+      if constexpr (PIPE) { K22_MMA_ALL(pb, pa) }
     }
   }
+#undef K22_LDS_ADDR
+#undef K22_LDS_PTR
+#define K22_LDS_ADDR(AT) (lds0 + (unsigned)((AT) - smem))
+#define K22_LDS_PTR(AT) (AT)
+#undef K22_PRODUCER_TAP
+#undef K22_PRODUCER_LOOP
+#undef K22_PRODUCER_NOTHING
   halo_tail<T, BM, false, true>(p, acc, smem, bx, bz, img, v0, n0);
 }
 
-template <typename T, int BM, int NBST, bool PIPE, int DBG = 0>
-static int run_spec(const IgemmParams& p, const IgemmLaunch& L, hipStream_t stream) {
-  static LdsAttrGuard guard;
-  return launch_lds_kernel(conv3_halo_spec_kernel<T, BM, NBST, PIPE, DBG>, guard, L.grid, L.block, L.lds, 160 * 1024, stream, p);
-}
+// conv3_halo_spec_kernel<T, BM, depth, PIPE> at the ring depth L.depth
 template <typename T, int BM, bool PIPE>
 static int launch_spec_depth(const IgemmParams& p, const IgemmLaunch& L, hipStream_t stream) {
-  if (L.depth == 2) return run_spec<T, BM, 2, PIPE>(p, L, stream);
-  if (L.depth == 3) return run_spec<T, BM, 3, PIPE>(p, L, stream);
-  if (L.depth == 4) return run_spec<T, BM, 4, PIPE>(p, L, stream);
-  return run_spec<T, BM, 6, PIPE>(p, L, stream);
+  return halo_with_depth<2, 3, 4, 6>(L.depth, [&](auto d) { return halo_run<conv3_halo_spec_kernel<T, BM, decltype(d)::value, PIPE>>(p, L, stream); });
 }
 
 // L.pipe: 0 = compiler-scheduled consumers, 1 = explicit, interleaved fragment pipeline.  x3 and fp32 at BM = 256 have no pipelined form (two
@@ -408,12 +276,12 @@ int launch_conv3_halo_spec(const IgemmParams& p, int dtype, const IgemmLaunch& L
     using T = typename decltype(tag)::type;
 #ifdef K22_DEBUG_VARIANTS   // measurement-only forms of the pipelined kernel (wrong results), bf16 at BM = 256: DBG 1 = no LDS-DMA inside the tap loop, 2 = LDS-DMA issued but never waited for
     if constexpr (std::is_same<T, bf16_t>::value) {
-      if (L.dbg == 1) return L.depth == 2 ? run_spec<T, 256, 2, true, 1>(p, L, stream) : run_spec<T, 256, 4, true, 1>(p, L, stream);
-      if (L.dbg == 2) return L.depth == 2 ? run_spec<T, 256, 2, true, 2>(p, L, stream) : run_spec<T, 256, 4, true, 2>(p, L, stream);
+      if (L.dbg == 1) return halo_with_depth<2, 4>(L.depth, [&](auto d) { return halo_run<conv3_halo_spec_kernel<T, 256, decltype(d)::value, true, 1>>(p, L, stream); });
+      if (L.dbg == 2) return halo_with_depth<2, 4>(L.depth, [&](auto d) { return halo_run<conv3_halo_spec_kernel<T, 256, decltype(d)::value, true, 2>>(p, L, stream); });
     }
 #endif
-    if (!L.pipe) return L.bm == 256 ? launch_spec_depth<T, 256, false>(p, L, stream) : launch_spec_depth<T, 128, false>(p, L, stream);
-    if constexpr (!std::is_same<T, x3_t>::value && !std::is_same<T, float>::value) { if (L.bm == 256) return launch_spec_depth<T, 256, true>(p, L, stream); }
-    return launch_spec_depth<T, 128, true>(p, L, stream);
+    if (!L.pipe) return halo_with_bm(L.bm, [&](auto bm) { return launch_spec_depth<T, decltype(bm)::value, false>(p, L, stream); });
+    constexpr bool pipe256 = !std::is_same<T, x3_t>::value && !std::is_same<T, float>::value;
+    return halo_with_bm<pipe256>(L.bm, [&](auto bm) { return launch_spec_depth<T, decltype(bm)::value, true>(p, L, stream); });
   });
 }

@@ -23,21 +23,9 @@
 //     hi-res rows finished by the usual fixed-order reduction
 #include "conv3_common.h"
 
-namespace {
-// halo pieces issued in the NBST-1 iterations before tap T (all younger than the weight tile tap T needs): taps 0 .. 4-NBST issue HPT each
-template <int NBST> constexpr int up2_halo_count(int t) {
-  int c = 0;
-  for (int k = 1; k <= NBST - 1; ++k) {
-    const int u = t - k;
-    if (u >= 0 && u <= 4 - NBST) ++c;
-  }
-  return c;
-}
-constexpr int UP2_ASLOTS = 6;   // halo LDS-DMA slots per wave per slab: 48 pieces = 384 rows
-}  // namespace
-
-// PIPE (16-bit types): the explicit fragment pipeline of conv3_halo_kernel's MODE 1 - the fragments of k-step ks+1 are read before the
-// MFMAs of k-step ks are issued, and the last k-step of a tap is multiplied behind the next tap's barrier.
+// PIPE (16-bit types): the explicit fragment pipeline of conv3_halo_kernel's MODE 1.  The kernel is a thin entry to the shared frame
+// and the lock-step K loop of conv3_common.h with TAPS = 4: taps 0 .. 4-NBST issue the next slab's halo, UP2_ASLOTS / (5-NBST) pieces per
+// wave each.
 template <typename T, int BM, int NBST, bool PIPE>
 __global__ __launch_bounds__(512) void conv3_up2_kernel(const IgemmParams p) {
   using TR = TT<T>;
@@ -46,9 +34,8 @@ __global__ __launch_bounds__(512) void conv3_up2_kernel(const IgemmParams p) {
   constexpr int MI = BM / (WM * 32), NI = BN / (WN * 32);
   constexpr int B_SLOTS = BN / 8 / NW;   // weight LDS-DMA instructions per wave per tap
   constexpr int B_BYTES = BN * 128;
-  constexpr int HT = 5 - NBST;           // taps 0 .. HT-1 issue the next slab's halo
-  constexpr int HPT = UP2_ASLOTS / HT;   // pieces per wave in each of them (NBST 2: 2, NBST 4: 6)
-  constexpr int GM = 8;
+  constexpr int HPT = UP2_ASLOTS / (5 - NBST);   // halo pieces per wave in each of taps 0 .. 4-NBST (NBST 2: 2, NBST 4: 6)
+  constexpr bool GASM = true;
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
   const int tid = threadIdx.x, lane = tid & 63;
@@ -65,17 +52,9 @@ __global__ __launch_bounds__(512) void conv3_up2_kernel(const IgemmParams p) {
   const int PR_MAX = (p.H + 2) * W2 - 1;       // last pixel of one padded plane
   const int B = p.M / (4 * p.H * p.W);
 
-  // ---- block -> (m-tile, n-tile x phase, k-split): the phase is the fastest part of the n index ----
-  const int gx = B * TPI, gy = ((p.N + BN - 1) / BN) * 4;
-  int L = p.xcd_remap ? xcd_remap_h(blockIdx.x, gridDim.x) : (int)blockIdx.x;
-  const int per_z = gx * gy;
-  const int bz = L / per_z;
-  L -= bz * per_z;
-  const int grp = L / (GM * gy);
-  const int first_m = grp * GM;
-  const int gsz = gx - first_m < GM ? gx - first_m : GM;
-  const int lin = L - grp * GM * gy;
-  const int bx = first_m + lin % gsz, byp = lin / gsz;
+  // block -> (m-tile, n-tile x phase, k-split): the phase is the fastest part of the n index
+  int bz, bx, byp;
+  halo_block_map(p, B * TPI, ((p.N + BN - 1) / BN) * 4, bz, bx, byp);
   const int ph = byp & 3, by = byp >> 2;
   const int img = bx / TPI, tile = bx - img * TPI, v0 = tile * BM;
   const int n0 = by * BN;
@@ -83,44 +62,14 @@ __global__ __launch_bounds__(512) void conv3_up2_kernel(const IgemmParams p) {
 
   const T* __restrict__ Aimg = reinterpret_cast<const T*>(p.A0) + (int64_t)img * (p.H + 2) * W2 * p.Kc;
   const T* __restrict__ Wp = reinterpret_cast<const T*>(p.Wp);
-
-  // ---- loader geometry: halo piece j (8 rows) is issued by wave j % NW in its slot j / NW; lane -> (row 8j + lane/8, position lane%8) ----
-  int aoff[UP2_ASLOTS];
-#pragma unroll
-  for (int q = 0; q < UP2_ASLOTS; ++q) {
-    int j = q * NW + wave;
-    if (j > NP - 1) j = NP - 1;   // surplus slots re-load the last piece (same bytes, same place): uniform counting
-    const int hr = 8 * j + (lane >> 3);
-    int pr = base + hr;
-    if (pr > PR_MAX) pr = PR_MAX;
-    const int chunk = (lane & 7) ^ ((hr >> 1) & 7);
-    aoff[q] = pr * p.Kc + chunk * EPC;
-  }
-  int boff[B_SLOTS];
-#pragma unroll
-  for (int i = 0; i < B_SLOTS; ++i) {
-    const int row = 8 * (wave + NW * i) + (lane >> 3);
-    int n = n0 + row;
-    if (n > p.Npad - 1) n = p.Npad - 1;
-    const int chunk = (lane & 7) ^ ((row >> 1) & 7);
-    boff[i] = (ph * p.Npad + n) * 4 * p.Kc + chunk * EPC;
-  }
-  const int nslab = p.Kc / BK;
-  int s0 = 0, s1 = nslab;
-  if (p.splitk > 1) {
-    const int per = (nslab + p.splitk - 1) / p.splitk;
-    s0 = bz * per;
-    s1 = s0 + per < nslab ? s0 + per : nslab;
-  }
+  int aoff[UP2_ASLOTS], boff[B_SLOTS];
+  K22_PIECE_OFFSETS(aoff, UP2_ASLOTS, wave, NW, base, NP, 8)
+  K22_ROW_OFFSETS(boff, B_SLOTS, wave, NW, n0, p.Npad - 1, (ph * p.Npad + n) * 4 * p.Kc)
+  int s0, s1;
+  halo_slab_range(p, p.Kc / BK, bz, s0, s1);
 
   f32x16_t acc[MI][NI];
-#pragma unroll
-  for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
-
+  halo_zero_acc(acc);
   FragA<T> pa[MI];          // PIPE: fragments read but not yet multiplied (zero = a no-op group before the first tap)
   Frag<T> pb[NI];
   if constexpr (PIPE) {
@@ -135,129 +84,21 @@ __global__ __launch_bounds__(512) void conv3_up2_kernel(const IgemmParams p) {
 #pragma unroll
   for (int ni = 0; ni < NI; ++ni) brow[ni] = (wn * (BN / WN) + ni * 32 + l31) * 128;
   const int bsw = (l31 >> 1) & 7;
+  const unsigned lds0 = halo_lds_base(smem);
 
-  const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) char*)smem);
-#define K22_ISSUE_A(Q, SLAB, DST)                                                                          \
-  {                                                                                                        \
-    int j_ = (Q) * NW + wave;                                                                              \
-    if (j_ > NP - 1) j_ = NP - 1;                                                                          \
-    glds16_asm(Aimg + aoff[Q] + (SLAB) * BK, __builtin_amdgcn_readfirstlane(lds0 + (unsigned)((DST) - smem) + j_ * 1024)); \
-  }
-#define K22_ISSUE_B(SLAB, TAP, STAGE)                                                                      \
-  {                                                                                                        \
-    const int kofs_ = (TAP) * p.Kc + (SLAB) * BK;                                                          \
-    char* dst_ = Bst + (STAGE) * B_BYTES + wave * 1024;                                                    \
-    _Pragma("unroll") for (int i = 0; i < B_SLOTS; ++i)                                                    \
-        glds16w_asm(Wp + boff[i] + kofs_, __builtin_amdgcn_readfirstlane(lds0 + (unsigned)(dst_ - smem) + i * NW * 1024)); \
-  }
-
-  if (s0 < s1) {
-    // prologue: the whole halo of the first slab, then the weight tiles of taps 0 .. NBST-2 (NBST <= 4: all of the first slab)
-#pragma unroll
-    for (int q = 0; q < UP2_ASLOTS; ++q) K22_ISSUE_A(q, s0, smem);
-#pragma unroll
-    for (int t = 0; t < NBST - 1; ++t) K22_ISSUE_B(s0, t, t);
-    int cur = 0;               // ring slot of the current tap's weights
-    int fill = NBST - 1;       // ring slot the tile NBST-1 taps ahead goes into
-    for (int s = s0; s < s1; ++s) {
-      char* const Acur = smem + ((s - s0) & 1) * A_BYTES;
-      char* const Anext = smem + (((s - s0) & 1) ^ 1) * A_BYTES;
-      const int sn = s + 1 < s1 ? s + 1 : s1 - 1;  // past-the-end loads re-read the last slab (uniform counting)
-      // VMEM queue of a wave per tap: [weight tile NBST-1 taps ahead (B_SLOTS)] then [HPT halo pieces, taps < HT].  At the top of tap T the
-      // weight tile of T has landed when at most the B_SLOTS*(NBST-2) younger weight loads and the halo pieces issued since are in flight;
-      // the last halo piece of a slab (tap HT-1) is followed by the weight loads of NBST-1 taps, so at tap 0 of the next slab it is older
-      // than everything the wait leaves in flight.
-#define K22_TAP(TAP)                                                                                       \
-      {                                                                                                    \
-        wait_vmcnt<B_SLOTS * (NBST - 2) + HPT * up2_halo_count<NBST>(TAP)>();                              \
-        raw_barrier();                                                                                     \
-        {                                                                                                  \
-          constexpr int ta_ = ((TAP) + NBST - 1) % 4;                                                      \
-          const int sa_ = ((TAP) + NBST - 1 >= 4) ? sn : s;                                                \
-          K22_ISSUE_B(sa_, ta_, fill);                                                                     \
-          if constexpr ((TAP) < HT) {                                                                      \
-            _Pragma("unroll") for (int a_ = 0; a_ < HPT; ++a_) {                                           \
-              constexpr int qb_ = ((TAP) < HT ? (TAP) : 0) * HPT;                                          \
-              K22_ISSUE_A(qb_ + a_, sn, Anext);                                                            \
-            }                                                                                              \
-          }                                                                                                \
-        }                                                                                                  \
-        const char* Bcur = Bst + cur * B_BYTES;                                                            \
-        const int shift = ((TAP) >> 1) * W2 + ((TAP) & 1);                                                 \
-        const char* arow[MI];                                                                              \
-        int asw[MI];                                                                                       \
-        _Pragma("unroll") for (int mi = 0; mi < MI; ++mi) {                                                \
-          const int ar = abase + mi * 32 + shift;                                                          \
-          arow[mi] = Acur + ar * 128;                                                                      \
-          asw[mi] = (ar >> 1) & 7;                                                                         \
-        }                                                                                                  \
-        if constexpr (PIPE) {                                                                              \
-          FragA<T> ca[MI];                                                                                 \
-          Frag<T> cb[NI];                                                                                  \
-          _Pragma("unroll") for (int ks = 0; ks < KSTEPS; ks += 2) {                                       \
-            _Pragma("unroll") for (int mi = 0; mi < MI; ++mi) ld_frag_at(ca[mi], arow[mi], asw[mi], ks, h); \
-            _Pragma("unroll") for (int ni = 0; ni < NI; ++ni) ld_frag_at(cb[ni], Bcur + brow[ni], bsw, ks, h); \
-            __builtin_amdgcn_sched_barrier(0);                                                             \
-            _Pragma("unroll") for (int mi = 0; mi < MI; ++mi)                                              \
-              _Pragma("unroll") for (int ni = 0; ni < NI; ++ni) mma_atom(acc[mi][ni], pb[ni], pa[mi]);     \
-            __builtin_amdgcn_sched_barrier(0);                                                             \
-            _Pragma("unroll") for (int mi = 0; mi < MI; ++mi) ld_frag_at(pa[mi], arow[mi], asw[mi], ks + 1, h); \
-            _Pragma("unroll") for (int ni = 0; ni < NI; ++ni) ld_frag_at(pb[ni], Bcur + brow[ni], bsw, ks + 1, h); \
-            __builtin_amdgcn_sched_barrier(0);                                                             \
-            _Pragma("unroll") for (int mi = 0; mi < MI; ++mi)                                              \
-              _Pragma("unroll") for (int ni = 0; ni < NI; ++ni) mma_atom(acc[mi][ni], cb[ni], ca[mi]);     \
-            __builtin_amdgcn_sched_barrier(0);                                                             \
-          }                                                                                                \
-        } else {                                                                                           \
-        _Pragma("unroll") for (int ks = 0; ks < KSTEPS; ++ks) {                                            \
-          FragA<T> a[MI];                                                                                  \
-          Frag<T> b[NI];                                                                                   \
-          _Pragma("unroll") for (int mi = 0; mi < MI; ++mi) ld_frag_at(a[mi], arow[mi], asw[mi], ks, h);   \
-          _Pragma("unroll") for (int ni = 0; ni < NI; ++ni) ld_frag_at(b[ni], Bcur + brow[ni], bsw, ks, h); \
-          _Pragma("unroll") for (int mi = 0; mi < MI; ++mi)                                                \
-            _Pragma("unroll") for (int ni = 0; ni < NI; ++ni) mma_atom(acc[mi][ni], b[ni], a[mi]);         \
-        }                                                                                                  \
-        }                                                                                                  \
-        /* no fragment read of this tap's weight slot in flight when the slot is refilled after the next barrier */ \
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                 \
-        cur = (cur + 1 == NBST) ? 0 : cur + 1;                                                             \
-        fill = (fill + 1 == NBST) ? 0 : fill + 1;                                                          \
-      }
-      K22_TAP(0) K22_TAP(1) K22_TAP(2) K22_TAP(3)
-#undef K22_TAP
-    }
-  }
-#undef K22_ISSUE_A
-#undef K22_ISSUE_B
-  if constexpr (PIPE) {
-#pragma unroll
-    for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-      for (int ni = 0; ni < NI; ++ni) mma_atom(acc[mi][ni], pb[ni], pa[mi]);
-  }
+#define K22_UP2_BODY                                                                                       \
+  if constexpr (PIPE) K22_TAP_PIPE(FragA<T>, Frag<T>, arow[mi], asw[mi], Bcur + brow[ni], bsw, K22_PIPE_LOCKSTEP) \
+  else { K22_TAP_PLAIN(FragA<T>, Frag<T>, ld_frag_at, arow[mi], asw[mi], Bcur + brow[ni], bsw) }
+  K22_LOCKSTEP_LOOP(4, UP2_ASLOTS, HPT, true, true, K22_UP2_BODY)
+#undef K22_UP2_BODY
+  if constexpr (PIPE) { K22_MMA_ALL(pb, pa) }
   halo_tail<T, BM, false, false, true>(p, acc, smem, (img * 4 + ph) * TPI + tile, bz, img, v0, n0, ph);
 }
 
 // ---- host side ---------------------------------------------------------------------------------
-static int up2_rows(const IgemmParams& p, int bm) { return (bm + (p.W + 2) + 1 + 7) & ~7; }
-
-size_t conv3_up2_lds_bytes(const IgemmParams& p, int bm, int nbst) {
-  const size_t main_loop = (size_t)2 * up2_rows(p, bm) * 128 + (size_t)nbst * HALO_BN * 128;
-  const size_t epi = (size_t)bm * (HALO_BN * 4 + 16);
-  const size_t red = (size_t)32 * HALO_BN * 2 * 4;
-  const size_t m = main_loop > epi ? main_loop : epi;
-  return m > red ? m : red;
-}
-
-// deepest instantiated weight ring (4, 2) that fits the LDS next to the double-buffered halo; 0 = the problem does not fit
-int conv3_up2_ring(const IgemmParams& p, int bm) {
-  if (up2_rows(p, bm) / 8 > UP2_ASLOTS * HALO_NW) return 0;
-  for (int nbst : {4, 2})
-    if (conv3_up2_lds_bytes(p, bm, nbst) <= 160 * 1024) return nbst;
-  return 0;
-}
-
-int conv3_up2_tiles_per_image(const IgemmParams& p, int bm) { return (p.H * (p.W + 2) + bm - 1) / bm; }
+size_t conv3_up2_lds_bytes(const IgemmParams& p, int bm, int nbst) { return halo_smem_bytes(p, bm, nbst, 4); }
+int conv3_up2_ring(const IgemmParams& p, int bm) { return halo_pick_nbst(p, bm, 4); }   // 4 or 2; 0 = the problem does not fit
+int conv3_up2_tiles_per_image(const IgemmParams& p, int bm) { return halo_tiles_per_image(p, bm); }
 
 // p: taps == 4, H x W = the LOW resolution, M = B * 2H * 2W output rows, A0 = [B][H+2][W+2][Kc] zero-bordered, Wp = [4][Npad][4][Kc]
 bool conv3_up2_supported(const IgemmParams& p, int dtype, int bm) {
@@ -272,23 +113,18 @@ bool conv3_up2_supported(const IgemmParams& p, int dtype, int bm) {
   return true;
 }
 
-template <typename T, int BM, int NBST, bool PIPE>
-static int run_up2(const IgemmParams& p, const IgemmLaunch& L, hipStream_t stream) {
-  static LdsAttrGuard guard;
-  return launch_lds_kernel(conv3_up2_kernel<T, BM, NBST, PIPE>, guard, L.grid, L.block, L.lds, 160 * 1024, stream, p);
-}
-template <typename T, int BM>
-static int launch_up2_depth(const IgemmParams& p, const IgemmLaunch& L, hipStream_t stream) {
-  if constexpr (sizeof(T) == 2) {
-    if (L.pipe) return L.depth == 2 ? run_up2<T, BM, 2, true>(p, L, stream) : run_up2<T, BM, 4, true>(p, L, stream);
-  }
-  return L.depth == 2 ? run_up2<T, BM, 2, false>(p, L, stream) : run_up2<T, BM, 4, false>(p, L, stream);
-}
-
 int launch_conv3_up2(const IgemmParams& p, int dtype, const IgemmLaunch& L, hipStream_t stream) {
   return k22_with_dtype(dtype, [&](auto tag) {
     using T = typename decltype(tag)::type;
-    return L.bm == 256 ? launch_up2_depth<T, 256>(p, L, stream) : launch_up2_depth<T, 128>(p, L, stream);
+    return halo_with_bm(L.bm, [&](auto bm) {
+      auto depth = [&](auto pipe) {
+        return halo_with_depth<2, 4>(L.depth, [&](auto d) { return halo_run<conv3_up2_kernel<T, decltype(bm)::value, decltype(d)::value, decltype(pipe)::value>>(p, L, stream); });
+      };
+      if constexpr (sizeof(T) == 2) {
+        if (L.pipe) return depth(std::true_type{});
+      }
+      return depth(std::false_type{});
+    });
   });
 }
 

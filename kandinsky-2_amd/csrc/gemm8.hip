@@ -15,6 +15,15 @@
 // two-stage LDS ring, no LDS-DMA - was built, parity-green, and measured equal: 1.29 ms against 1.26-1.31 ms for the GEMMs of one
 // step.  The K loop of these GEMMs is not bound by the LDS-DMA issue cost; removed.)
 // ================================================================================================================
+// one K slab of both operands into ring stage STAGE, by loader wave LW of NWL: A tile, then W tile behind it
+#define K22_ISSUE_G(LW, NWL, SLAB, STAGE)                                                                  \
+  {                                                                                                        \
+    int sl_ = (SLAB);                                                                                      \
+    if (sl_ > s1 - 1) sl_ = s1 - 1;   /* past-the-end stages re-read the last slab: uniform counting */    \
+    const unsigned d_ = lds0 + (STAGE) * BUF + (LW) * 1024;                                                \
+    K22_ISSUE_ROWS(false, A, aoff, A_SLOTS, NWL, sl_ * BK, d_, smem + (d_ - lds0))                         \
+    K22_ISSUE_ROWS(true, Wp, boff, B_SLOTS, NWL, sl_ * BK, d_ + A_BYTES, smem + (d_ - lds0) + A_BYTES)     \
+  }
 template <typename T, int BM, int NST, bool ARAW = false>
 __global__ __launch_bounds__(512) void gemm8_kernel(const IgemmParams p) {
   using TR = TT<T>;
@@ -23,7 +32,7 @@ __global__ __launch_bounds__(512) void gemm8_kernel(const IgemmParams p) {
   constexpr int MI = BM / (WM * 32), NI = BN / (WN * 32);
   constexpr int A_SLOTS = BM / 8 / NW, B_SLOTS = BN / 8 / NW, CH = A_SLOTS + B_SLOTS;
   constexpr int A_BYTES = BM * 128, B_BYTES = BN * 128, BUF = A_BYTES + B_BYTES;
-  constexpr int GM = 8;
+  constexpr bool GASM = true;
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
   const int tid = threadIdx.x, lane = tid & 63;
@@ -34,63 +43,23 @@ __global__ __launch_bounds__(512) void gemm8_kernel(const IgemmParams p) {
   const int HW = p.H > 0 ? p.H * p.W : p.M;   // rows per image
   const int TPI = (HW + BM - 1) / BM;
   const int B = p.M / HW;
-  const int gx = B * TPI, gy = (p.N + BN - 1) / BN;
-  int L = p.xcd_remap ? xcd_remap_h(blockIdx.x, gridDim.x) : (int)blockIdx.x;
-  const int per_z = gx * gy;
-  const int bz = L / per_z;
-  L -= bz * per_z;
-  const int grp = L / (GM * gy);
-  const int first_m = grp * GM;
-  const int gsz = gx - first_m < GM ? gx - first_m : GM;
-  const int lin = L - grp * GM * gy;
-  const int bx = first_m + lin % gsz, by = lin / gsz;
+  int bz, bx, by;
+  halo_block_map(p, B * TPI, (p.N + BN - 1) / BN, bz, bx, by);
   const int img = bx / TPI, v0 = (bx - img * TPI) * BM;
   const int n0 = by * BN;
 
   const T* __restrict__ A = reinterpret_cast<const T*>(p.A0) + (int64_t)img * HW * p.lda0;
   const T* __restrict__ Wp = reinterpret_cast<const T*>(p.Wp);
   int aoff[A_SLOTS], boff[B_SLOTS];
-#pragma unroll
-  for (int i = 0; i < A_SLOTS; ++i) {
-    const int row = 8 * (wave + NW * i) + (lane >> 3);
-    int v = v0 + row;
-    if (v > HW - 1) v = HW - 1;                 // rows past the image re-read its last pixel; they are never stored
-    aoff[i] = v * (int)p.lda0 + ((lane & 7) ^ ((row >> 1) & 7)) * EPC;
-  }
-#pragma unroll
-  for (int i = 0; i < B_SLOTS; ++i) {
-    const int row = 8 * (wave + NW * i) + (lane >> 3);
-    int n = n0 + row;
-    if (n > p.Npad - 1) n = p.Npad - 1;
-    boff[i] = n * p.Kc + ((lane & 7) ^ ((row >> 1) & 7)) * EPC;
-  }
-  const int nslab = p.Kc / BK;
-  int s0 = 0, s1 = nslab;
-  if (p.splitk > 1) {
-    const int per = (nslab + p.splitk - 1) / p.splitk;
-    s0 = bz * per;
-    s1 = s0 + per < nslab ? s0 + per : nslab;
-  }
+  K22_ROW_OFFSETS(aoff, A_SLOTS, wave, NW, v0, HW - 1, n * (int)p.lda0)   // rows past the image re-read its last pixel; they are never stored
+  K22_ROW_OFFSETS(boff, B_SLOTS, wave, NW, n0, p.Npad - 1, n * p.Kc)
+  int s0, s1;
+  halo_slab_range(p, p.Kc / BK, bz, s0, s1);
 
   f32x16_t acc[MI][NI];
-#pragma unroll
-  for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
+  halo_zero_acc(acc);
 
-  const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) char*)smem);
-#define K22_ISSUE_G(SLAB, STAGE)                                                                           \
-  {                                                                                                        \
-    int sl_ = (SLAB);                                                                                      \
-    if (sl_ > s1 - 1) sl_ = s1 - 1;   /* past-the-end stages re-read the last slab: uniform counting */    \
-    const unsigned d_ = lds0 + (STAGE) * BUF + wave * 1024;                                                \
-    _Pragma("unroll") for (int i = 0; i < A_SLOTS; ++i)                                                    \
-        glds16_asm(A + aoff[i] + sl_ * BK, __builtin_amdgcn_readfirstlane(d_ + i * NW * 1024));            \
-    _Pragma("unroll") for (int i = 0; i < B_SLOTS; ++i)                                                    \
-        glds16w_asm(Wp + boff[i] + sl_ * BK, __builtin_amdgcn_readfirstlane(d_ + A_BYTES + i * NW * 1024)); \
-  }
+  const unsigned lds0 = halo_lds_base(smem);
   int arow[MI], brow[NI];
 #pragma unroll
   for (int mi = 0; mi < MI; ++mi) arow[mi] = (wm * (BM / WM) + mi * 32 + l31) * 128;
@@ -100,31 +69,18 @@ __global__ __launch_bounds__(512) void gemm8_kernel(const IgemmParams p) {
 
   if (s0 < s1) {
 #pragma unroll
-    for (int t = 0; t < NST - 1; ++t) K22_ISSUE_G(s0 + t, t);
+    for (int t = 0; t < NST - 1; ++t) K22_ISSUE_G(wave, NW, s0 + t, t);
     int cur = 0, fill = NST - 1;
     for (int s = s0; s < s1; ++s) {
       wait_vmcnt<(NST - 2) * CH>();
       raw_barrier();
-      K22_ISSUE_G(s + NST - 1, fill);
+      K22_ISSUE_G(wave, NW, s + NST - 1, fill);
       const char* St = smem + cur * BUF;
-#pragma unroll
-      for (int ks = 0; ks < KSTEPS; ++ks) {
-        FragA<T> a[MI];
-        Frag<T> b[NI];
-#pragma unroll
-        for (int mi = 0; mi < MI; ++mi) ld_frag_at_a<ARAW, T>(a[mi], St + arow[mi], sw, ks, h);
-#pragma unroll
-        for (int ni = 0; ni < NI; ++ni) ld_frag_at(b[ni], St + brow[ni], sw, ks, h);
-#pragma unroll
-        for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-          for (int ni = 0; ni < NI; ++ni) mma_atom(acc[mi][ni], b[ni], a[mi]);
-      }
+      K22_TAP_PLAIN(FragA<T>, Frag<T>, (ld_frag_at_a<ARAW, T>), St + arow[mi], sw, St + brow[ni], sw)
       cur = (cur + 1 == NST) ? 0 : cur + 1;
       fill = (fill + 1 == NST) ? 0 : fill + 1;
     }
   }
-#undef K22_ISSUE_G
   halo_tail<T, BM, true>(p, acc, smem, bx, bz, img, v0, n0);
 }
 
@@ -149,7 +105,7 @@ __global__ __launch_bounds__(512) void gemm8_spec_kernel(const IgemmParams p) {
   constexpr int MI = BM / (WM * 32), NI = BN / (WN * 32);
   constexpr int A_SLOTS = BM / 8 / NWL, B_SLOTS = BN / 8 / NWL, CH = A_SLOTS + B_SLOTS;
   constexpr int A_BYTES = BM * 128, B_BYTES = BN * 128, BUF = A_BYTES + B_BYTES;
-  constexpr int GM = 8;
+  constexpr bool GASM = true;
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
   const int tid = threadIdx.x, lane = tid & 63;
@@ -160,34 +116,15 @@ __global__ __launch_bounds__(512) void gemm8_spec_kernel(const IgemmParams p) {
   const int HW = p.H > 0 ? p.H * p.W : p.M;   // rows per image
   const int TPI = (HW + BM - 1) / BM;
   const int B = p.M / HW;
-  const int gx = B * TPI, gy = (p.N + BN - 1) / BN;
-  int L = p.xcd_remap ? xcd_remap_h(blockIdx.x, gridDim.x) : (int)blockIdx.x;
-  const int per_z = gx * gy;
-  const int bz = L / per_z;
-  L -= bz * per_z;
-  const int grp = L / (GM * gy);
-  const int first_m = grp * GM;
-  const int gsz = gx - first_m < GM ? gx - first_m : GM;
-  const int lin = L - grp * GM * gy;
-  const int bx = first_m + lin % gsz, by = lin / gsz;
+  int bz, bx, by;
+  halo_block_map(p, B * TPI, (p.N + BN - 1) / BN, bz, bx, by);
   const int img = bx / TPI, v0 = (bx - img * TPI) * BM;
   const int n0 = by * BN;
-
-  const int nslab = p.Kc / BK;
-  int s0 = 0, s1 = nslab;
-  if (p.splitk > 1) {
-    const int per = (nslab + p.splitk - 1) / p.splitk;
-    s0 = bz * per;
-    s1 = s0 + per < nslab ? s0 + per : nslab;
-  }
+  int s0, s1;
+  halo_slab_range(p, p.Kc / BK, bz, s0, s1);
 
   f32x16_t acc[MI][NI];
-#pragma unroll
-  for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
+  halo_zero_acc(acc);
 
   if (s0 < s1) {
     if (producer) {
@@ -195,41 +132,18 @@ __global__ __launch_bounds__(512) void gemm8_spec_kernel(const IgemmParams p) {
       const T* __restrict__ A = reinterpret_cast<const T*>(p.A0) + (int64_t)img * HW * p.lda0;
       const T* __restrict__ Wp = reinterpret_cast<const T*>(p.Wp);
       int aoff[A_SLOTS], boff[B_SLOTS];
+      K22_ROW_OFFSETS(aoff, A_SLOTS, lw, NWL, v0, HW - 1, n * (int)p.lda0)   // rows past the image re-read its last pixel; they are never stored
+      K22_ROW_OFFSETS(boff, B_SLOTS, lw, NWL, n0, p.Npad - 1, n * p.Kc)
+      const unsigned lds0 = halo_lds_base(smem);
 #pragma unroll
-      for (int i = 0; i < A_SLOTS; ++i) {
-        const int row = 8 * (lw + NWL * i) + (lane >> 3);
-        int v = v0 + row;
-        if (v > HW - 1) v = HW - 1;                 // rows past the image re-read its last pixel; they are never stored
-        aoff[i] = v * (int)p.lda0 + ((lane & 7) ^ ((row >> 1) & 7)) * EPC;
-      }
-#pragma unroll
-      for (int i = 0; i < B_SLOTS; ++i) {
-        const int row = 8 * (lw + NWL * i) + (lane >> 3);
-        int n = n0 + row;
-        if (n > p.Npad - 1) n = p.Npad - 1;
-        boff[i] = n * p.Kc + ((lane & 7) ^ ((row >> 1) & 7)) * EPC;
-      }
-      const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) char*)smem);
-#define K22_ISSUE_GS(SLAB, STAGE)                                                                          \
-      {                                                                                                    \
-        int sl_ = (SLAB);                                                                                  \
-        if (sl_ > s1 - 1) sl_ = s1 - 1;   /* past-the-end stages re-read the last slab: uniform counting */ \
-        const unsigned d_ = lds0 + (STAGE) * BUF + lw * 1024;                                              \
-        _Pragma("unroll") for (int i = 0; i < A_SLOTS; ++i)                                                \
-            glds16_asm(A + aoff[i] + sl_ * BK, __builtin_amdgcn_readfirstlane(d_ + i * NWL * 1024));       \
-        _Pragma("unroll") for (int i = 0; i < B_SLOTS; ++i)                                                \
-            glds16w_asm(Wp + boff[i] + sl_ * BK, __builtin_amdgcn_readfirstlane(d_ + A_BYTES + i * NWL * 1024)); \
-      }
-#pragma unroll
-      for (int t = 0; t < NST - 1; ++t) K22_ISSUE_GS(s0 + t, t);
+      for (int t = 0; t < NST - 1; ++t) K22_ISSUE_G(lw, NWL, s0 + t, t);
       int fill = NST - 1;
       for (int s = s0; s < s1; ++s) {
         wait_vmcnt<(NST - 2) * CH>();
         raw_barrier();
-        K22_ISSUE_GS(s + NST - 1, fill);
+        K22_ISSUE_G(lw, NWL, s + NST - 1, fill);
         fill = (fill + 1 == NST) ? 0 : fill + 1;
       }
-#undef K22_ISSUE_GS
     } else {
       const int wm = wave >> 1, wn = wave & 1;
       int arow[MI], brow[NI];
@@ -243,61 +157,25 @@ __global__ __launch_bounds__(512) void gemm8_spec_kernel(const IgemmParams p) {
       for (int mi = 0; mi < MI; ++mi) pa[mi] = Frag<T>{};
 #pragma unroll
       for (int ni = 0; ni < NI; ++ni) pb[ni] = Frag<T>{};
-      constexpr int NRD = MI + NI, NMF = MI * NI, MPR = NMF / NRD;
-#define K22_GS_INTERLEAVE()                                                                                \
-      {                                                                                                    \
-        _Pragma("unroll") for (int i_ = 0; i_ < NRD; ++i_) {                                               \
-          __builtin_amdgcn_sched_group_barrier(0x008, MPR, 0);                                             \
-          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                                               \
-        }                                                                                                  \
-        if constexpr (NMF - MPR * NRD > 0) __builtin_amdgcn_sched_group_barrier(0x008, NMF - MPR * NRD, 0); \
-        __builtin_amdgcn_sched_barrier(0);                                                                 \
-      }
+      constexpr int NRD = halo_pipe_reads<T, MI, NI>(), NMF = MI * NI * FragCost<T>::MFMAS, MPR = NMF / NRD;
       int cur = 0;
       for (int s = s0; s < s1; ++s) {
         raw_barrier();
         const char* St = smem + cur * BUF;
-        Frag<T> ca[MI], cb[NI];
-#pragma unroll
-        for (int ks = 0; ks < KSTEPS; ks += 2) {
-#pragma unroll
-          for (int mi = 0; mi < MI; ++mi) ld_frag_at(ca[mi], St + arow[mi], sw, ks, h);
-#pragma unroll
-          for (int ni = 0; ni < NI; ++ni) ld_frag_at(cb[ni], St + brow[ni], sw, ks, h);
-#pragma unroll
-          for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-            for (int ni = 0; ni < NI; ++ni) mma_atom(acc[mi][ni], pb[ni], pa[mi]);
-          K22_GS_INTERLEAVE();
-#pragma unroll
-          for (int mi = 0; mi < MI; ++mi) ld_frag_at(pa[mi], St + arow[mi], sw, ks + 1, h);
-#pragma unroll
-          for (int ni = 0; ni < NI; ++ni) ld_frag_at(pb[ni], St + brow[ni], sw, ks + 1, h);
-#pragma unroll
-          for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-            for (int ni = 0; ni < NI; ++ni) mma_atom(acc[mi][ni], cb[ni], ca[mi]);
-          K22_GS_INTERLEAVE();
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // no fragment read of this stage in flight when the producers refill it after the next barrier
+        K22_TAP_PIPE(Frag<T>, Frag<T>, St + arow[mi], sw, St + brow[ni], sw, K22_PIPE_INTERLEAVED)
+        K22_READS_DONE();
         cur = (cur + 1 == NST) ? 0 : cur + 1;
       }
-#undef K22_GS_INTERLEAVE
-#pragma unroll
-      for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < NI; ++ni) mma_atom(acc[mi][ni], pb[ni], pa[mi]);
+      K22_MMA_ALL(pb, pa)
     }
   }
   halo_tail<T, BM, true, true>(p, acc, smem, bx, bz, img, v0, n0);
 }
 
+#undef K22_ISSUE_G
+
 // ---- host side ---------------------------------------------------------------------------------
-size_t gemm8_lds_bytes(int bm, int nst) {
-  const size_t main_loop = (size_t)nst * (bm + HALO_BN) * 128;
-  const size_t epi = (size_t)bm * (HALO_BN * 4 + 16);
-  return main_loop > epi ? main_loop : epi;
-}
+size_t gemm8_lds_bytes(int bm, int nst) { return halo_lds_budget(bm, false, (size_t)nst * (bm + HALO_BN) * 128); }
 int gemm8_tiles_per_image(const IgemmParams& p, int bm) { return ((p.H > 0 ? p.H * p.W : p.M) + bm - 1) / bm; }
 
 bool gemm8_supported(const IgemmParams& p, int dtype, int bm) {
@@ -316,34 +194,22 @@ bool gemm8_supported(const IgemmParams& p, int dtype, int bm) {
 // the specialised, pipelined form: 16-bit types (the split types keep the lock-step kernel)
 bool gemm8_spec_supported(int dtype) { return dtype == K22_BF16 || dtype == K22_F16; }
 
-template <typename T, int BM, int NST, bool ARAW>
-static int run_gemm8(const IgemmParams& p, const IgemmLaunch& L, hipStream_t stream) {
-  static LdsAttrGuard guard;
-  return launch_lds_kernel(gemm8_kernel<T, BM, NST, ARAW>, guard, L.grid, L.block, L.lds, 160 * 1024, stream, p);
-}
-template <typename T, int BM, int NST>
-static int run_gemm8_spec(const IgemmParams& p, const IgemmLaunch& L, hipStream_t stream) {
-  static LdsAttrGuard guard;
-  return launch_lds_kernel(gemm8_spec_kernel<T, BM, NST>, guard, L.grid, L.block, L.lds, 160 * 1024, stream, p);
-}
-
 // Launches the kernel the resolved launch names - rings (BM, NST): (256, 3), (128, 4), (128, 2) - only; a split-K reduction is the caller's (launch_igemm).
 int launch_gemm8(const IgemmParams& p, int dtype, const IgemmLaunch& L, hipStream_t stream) {
   return k22_with_dtype(dtype, [&](auto tag) {
     using T = typename decltype(tag)::type;
-    auto ring = [&](auto run256, auto run128_4, auto run128_2) { return L.bm == 256 ? run256() : (L.depth == 2 ? run128_2() : run128_4()); };
+    auto ring = [&](auto run) {
+      using std::integral_constant;
+      return L.bm == 256 ? run(integral_constant<int, 256>{}, integral_constant<int, 3>{})
+                         : (L.depth != 2 ? run(integral_constant<int, 128>{}, integral_constant<int, 4>{}) : run(integral_constant<int, 128>{}, integral_constant<int, 2>{}));
+    };
     if (L.family == IG_FAM_GEMM8_SPEC) {
-      if constexpr (sizeof(T) == 2)
-        return ring([&] { return run_gemm8_spec<T, 256, 3>(p, L, stream); }, [&] { return run_gemm8_spec<T, 128, 4>(p, L, stream); },
-                    [&] { return run_gemm8_spec<T, 128, 2>(p, L, stream); });
+      if constexpr (sizeof(T) == 2) return ring([&](auto bm, auto nst) { return halo_run<gemm8_spec_kernel<T, decltype(bm)::value, decltype(nst)::value>>(p, L, stream); });
       else return k22_set_error(K22_EINVAL, "gemm8: unsupported problem");
     }
     if constexpr (is_x3<T>::value) {
-      if (L.a_raw)
-        return ring([&] { return run_gemm8<T, 256, 3, true>(p, L, stream); }, [&] { return run_gemm8<T, 128, 4, true>(p, L, stream); },
-                    [&] { return run_gemm8<T, 128, 2, true>(p, L, stream); });
+      if (L.a_raw) return ring([&](auto bm, auto nst) { return halo_run<gemm8_kernel<T, decltype(bm)::value, decltype(nst)::value, true>>(p, L, stream); });
     }
-    return ring([&] { return run_gemm8<T, 256, 3, false>(p, L, stream); }, [&] { return run_gemm8<T, 128, 4, false>(p, L, stream); },
-                [&] { return run_gemm8<T, 128, 2, false>(p, L, stream); });
+    return ring([&](auto bm, auto nst) { return halo_run<gemm8_kernel<T, decltype(bm)::value, decltype(nst)::value, false>>(p, L, stream); });
   });
 }
