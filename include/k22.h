@@ -76,7 +76,7 @@ const char* k22_last_error(void);
  * "att_pipe" = -1 as K22_ATT_PIPE says (default), 0 / 1: the unmasked 16-bit attention through attention_kernel / attention_pipe_kernel. */
 int k22_set_option(const char* name, int value);
 /* Host counters for tests, since the library was loaded: "stream_launches" = launches of the weight-streaming kernel;
- * "loop_captures" = whole-loop graphs captured by any loop entry (k22_unet_sample_loop[_keep], k22_unet_ddim_loop, k22_unet_dpmpp_loop, k22_prior_sample_loop); "loop_launches" = whole-loop
+ * "loop_captures" = whole-loop graphs captured by any loop entry (k22_unet_sample_loop[_keep], k22_unet_ddim_loop, k22_unet_dpmpp_loop[_keep], k22_prior_sample_loop); "loop_launches" = whole-loop
  * replays or eager loop runs.  -1 for an unknown name. */
 long k22_debug_counter(const char* name);
 /* Fragment-major copy of a 16-bit weight matrix [Npad][taps * Kc] for the weight-streaming kernel (1 KB contiguous per MFMA B
@@ -239,6 +239,21 @@ int k22_unet_ddim_loop(K22UNet* u, int kind, float* x, float* x_tmp, float* x0_o
  * they were. */
 int k22_unet_dpmpp_loop(K22UNet* u, float* x, float* x_tmp, float* x0_hist, const float* timesteps, const float* table, const int* orders,
                         const float* inpaint_image, const float* inpaint_mask, int n_steps, float guidance, int use_graph, void* stream);
+/* k22_unet_dpmpp_loop for the Kandinsky 2.2 decoders, whose scheduler configs can carry clip_sample and whose inpainting pipeline re-imposes
+ * the known region after every step:
+ *   per step k:  UNet([x_half | x_half], timesteps[k]) -> k22_dpmpp_step_clip(clamp_lo, clamp_hi) [-> k22_keep_region(sa, sb = keep_coef[k])]
+ * as one chain on the capture stream.  "No clip" is the DDPM route's convention, (-3.0e38, 3.0e38).  The keep operands are all four or none
+ * and mean what they mean in k22_unet_sample_loop_keep: keep_init [4][HW], keep_mask [HW] (image 0's, 1 = keep), keep_noise [B / 2][4][HW]
+ * device buffers, keep_coef [n_steps][2] a HOST array (kandinsky2_amd.sampling.dpmpp_keep_coef: the target point's (sqrt(ac), sqrt(1 - ac)),
+ * the last row (1, 0)).  Everything else is k22_unet_dpmpp_loop's.  The engine's ONE cached loop serves this entry too: its key holds a
+ * kind of its own (another one when keep is on), the clamp bits, the three keep pointers and the bits of every keep_coef value besides
+ * k22_unet_dpmpp_loop's; use_graph = 0 issues the same launches eagerly.
+ * K22_EINVAL (with a k22_last_error text) for keep arguments given only in part, clamp_lo > clamp_hi or a NaN bound, and whatever
+ * k22_unet_dpmpp_loop refuses; a refused call leaves the handle and its captured loop as they were. */
+int k22_unet_dpmpp_loop_keep(K22UNet* u, float* x, float* x_tmp, float* x0_hist, const float* timesteps, const float* table, const int* orders,
+                             const float* inpaint_image, const float* inpaint_mask, int n_steps, float guidance, float clamp_lo, float clamp_hi,
+                             const float* keep_init, const float* keep_noise, const float* keep_mask, const float* keep_coef,
+                             int use_graph, void* stream);
 int k22_unet_num_ops(const K22UNet* u);
 /* Tile configurations of the convolutions / GEMMs are chosen by measurement during the first k22_unet_forward
  * after k22_unet_plan (default on; env K22_AUTOTUNE=0 or k22_unet_set_autotune(u, 0) before planning = heuristics).
@@ -303,6 +318,12 @@ int k22_prepare_mask(const float* mask, float* out, int C, int H, int W, void* s
  * x0_prev are distinct buffers (K22_EINVAL otherwise, and for a null argument or an odd N with use_cfg). */
 int k22_dpmpp_step(const float* x, const float* model_out, const float* x0_prev, const float* table_row, float guidance, int use_cfg,
                    float* x_out, float* x0_out, int N, int HW, void* stream);
+/* k22_dpmpp_step with one more operation after the division: x0 = clamp(x0, clamp_lo, clamp_hi) - diffusers DDPMScheduler's clip_sample on
+ * the data prediction.  The clamped value is what enters x_out and what x0_out stores (the next step's history).  The clamp is exact (two
+ * comparisons, a NaN passes through); with (-3.0e38, 3.0e38) the outputs are k22_dpmpp_step's bit for bit.  K22_EINVAL for what
+ * k22_dpmpp_step refuses, clamp_lo > clamp_hi and a NaN bound. */
+int k22_dpmpp_step_clip(const float* x, const float* model_out, const float* x0_prev, const float* table_row, float guidance, int use_cfg,
+                        float clamp_lo, float clamp_hi, float* x_out, float* x0_out, int N, int HW, void* stream);
 /* PLMS step (PLMSSampler.p_sample_plms, kandinsky2/model/samplers.py:566-637; eta = 0) with model_fn's guidance folded in:
  * e_t = u + g (c - u) of this model call; e' = Adams-Bashforth combination of e_t and the eps history by `order`
  * (0: e_t; 1: (3 e_t - h1)/2; 2: (23 e_t - 16 h1 + 5 h2)/12; 3: (55 e_t - 59 h1 + 37 h2 - 9 h3)/24; 4: (h1 + e_t)/2, the second

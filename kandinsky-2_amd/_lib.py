@@ -110,6 +110,7 @@ SIGNATURES = {
                                        _P]),
     "k22_unet_ddim_loop": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _F, _I, _P]),
     "k22_unet_dpmpp_loop": (_I, [_P, _P, _P, _P, _P, _P, C.POINTER(_I), _P, _P, _I, _F, _I, _P]),
+    "k22_unet_dpmpp_loop_keep": (_I, [_P, _P, _P, _P, _P, _P, C.POINTER(_I), _P, _P, _I, _F, _F, _F, _P, _P, _P, C.POINTER(_F), _I, _P]),
     "k22_unet_num_ops": (_I, [_P]),
     "k22_unet_set_autotune": (_I, [_P, _I]),
     "k22_unet_tuning_report": (_I, [_P, C.c_char_p, _Z]),
@@ -143,6 +144,7 @@ SIGNATURES = {
     "k22_movq_num_ops": (_I, [_P]),
     "k22_ddim_step": (_I, [_P, _P, _P, _P, _F, _I, _P, _P, _I, _I, _P]),
     "k22_dpmpp_step": (_I, [_P, _P, _P, _P, _F, _I, _P, _P, _I, _I, _P]),
+    "k22_dpmpp_step_clip": (_I, [_P, _P, _P, _P, _F, _I, _F, _F, _P, _P, _I, _I, _P]),
     "k22_blend_noised": (_I, [_P, _P, _P, _P, _F, _F, _P, _I, _I, _I, _I, _P]),
     "k22_prepare_mask": (_I, [_P, _P, _I, _I, _I, _P]),
     "k22_plms_step": (_I, [_P, _P, _P, _P, _P, _I, _P, _F, _I, _P, _P, _P, _I, _I, _P]),

@@ -486,6 +486,12 @@ int k22_dpmpp_step(const float* x, const float* model_out, const float* x0_prev,
   return launch_dpmpp_step(x, model_out, x0_prev, table_row, guidance, use_cfg, x_out, x0_out, N, HW, reinterpret_cast<hipStream_t>(stream));
 }
 
+int k22_dpmpp_step_clip(const float* x, const float* model_out, const float* x0_prev, const float* table_row, float guidance, int use_cfg,
+                        float clamp_lo, float clamp_hi, float* x_out, float* x0_out, int N, int HW, void* stream) {
+  return launch_dpmpp_step_clip(x, model_out, x0_prev, table_row, guidance, use_cfg, clamp_lo, clamp_hi, x_out, x0_out, N, HW,
+                                reinterpret_cast<hipStream_t>(stream));
+}
+
 int k22_prepare_mask(const float* mask, float* out, int C, int H, int W, void* stream) {
   if (!mask || !out) return k22_set_error(K22_EINVAL, "prepare_mask: null argument");
   return launch_prepare_mask(mask, out, C, H, W, reinterpret_cast<hipStream_t>(stream));

@@ -139,6 +139,9 @@ int launch_ddim_step(const float* x, const float* model_out, const float* noise,
 // sampler.hip: DPM-Solver++ step on tab = (alpha_s, sigma_s, c_x, c_0, c_1); x0_prev NULL = order 1; x0_out required; out of place
 int launch_dpmpp_step(const float* x, const float* model_out, const float* x0_prev, const float* tab, float guidance, int use_cfg,
                       float* x_out, float* x0_out, int N, int HW, hipStream_t s);
+// the same kernel body with x0 = clamp(x0, clamp_lo, clamp_hi) after the division (clip_sample on the data prediction); clamp_lo <= clamp_hi
+int launch_dpmpp_step_clip(const float* x, const float* model_out, const float* x0_prev, const float* tab, float guidance, int use_cfg,
+                           float clamp_lo, float clamp_hi, float* x_out, float* x0_out, int N, int HW, hipStream_t s);
 
 // ---- MoVQ decoder (movq.hip / movq_kernels.hip) -----------------------------------------------------------
 struct SpatialNormParams {

@@ -38,7 +38,8 @@ long loop_launch_count() { return g_loop_launches.load(); }
 void loop_count_capture() { g_loop_captures.fetch_add(1); }
 void loop_count_launch() { g_loop_launches.fetch_add(1); }
 // first word of a captured loop's key: which entry's nodes the graph holds
-enum : unsigned long long { K22_LOOP_KIND_P = 0, K22_LOOP_KIND_DDIM = 1, K22_LOOP_KIND_PLMS = 2, K22_LOOP_KIND_P_KEEP = 3, K22_LOOP_KIND_DPMPP = 4 };
+enum : unsigned long long { K22_LOOP_KIND_P = 0, K22_LOOP_KIND_DDIM = 1, K22_LOOP_KIND_PLMS = 2, K22_LOOP_KIND_P_KEEP = 3, K22_LOOP_KIND_DPMPP = 4,
+                            K22_LOOP_KIND_DPMPP_CLIP = 5, K22_LOOP_KIND_DPMPP_KEEP = 6 };
 
 namespace {
 
@@ -178,7 +179,7 @@ struct K22UNet : GraphPlan {   // dtype: arithmetic type of the MFMA kernels (K2
     return copy_d2d(ptr(s_mask), inpaint_mask, pb * hw * 4, s);
   }
 
-  // ---- the whole-loop entries (k22_unet_sample_loop[_keep], k22_unet_ddim_loop, k22_unet_dpmpp_loop): pieces of unet_loop below -------
+  // ---- the whole-loop entries (k22_unet_sample_loop[_keep], k22_unet_ddim_loop, k22_unet_dpmpp_loop[_keep]): pieces of unet_loop below -------
   // A loop is n_calls model calls, each  UNet([x_half | x_half], timesteps[call])  followed by the entry's own sampler kernels.
   struct LoopRows {   // hoisted time / FiLM rows of all model calls (null members: per-call launches)
     bool hoist = false;
@@ -972,6 +973,49 @@ static int unet_sample_loop_body(K22UNet* u, float* x, float* x_tmp, const float
   return unet_loop(u, a, own_fault, step, key_tail);
 }
 
+// The DPM-Solver++ loop of k22_unet_dpmpp_loop (clamp == NULL: the step is k22_dpmpp_step, the key and the kind what they have always been)
+// and k22_unet_dpmpp_loop_keep (clamp = host (lo, hi): the step is k22_dpmpp_step_clip; keep_* all four or none, as in unet_sample_loop_body).
+// Step k writes its x0 to slot k % 2 of x0_hist and, when orders[k] == 2, reads slot (k - 1) % 2: the rotation is resolved here, at capture
+// time, like the PLMS ring - so every order is in the key.
+static int unet_dpmpp_loop_body(K22UNet* u, const char* who, float* x, float* x_tmp, float* x0_hist, const float* timesteps, const float* table,
+                                const int* orders, const float* inpaint_image, const float* inpaint_mask, int n_steps, float guidance,
+                                const float* clamp, const float* keep_init, const float* keep_noise, const float* keep_mask,
+                                const float* keep_coef, int use_graph, void* stream) {
+  auto own_fault = [&]() -> const char* {
+    if (!x || !x_tmp || !x0_hist || !timesteps || !table || !orders) return "null argument";
+    if (n_steps < 1) return "n_steps must be >= 1";
+    for (int k = 0; k < n_steps; ++k)
+      if (orders[k] != 1 && orders[k] != 2) return "every order is 1 or 2";
+    if (orders[0] != 1) return "the first step has no history (orders[0] must be 1)";
+    if (clamp && !(clamp[0] <= clamp[1])) return "clamp_lo <= clamp_hi, neither a NaN";
+    return nullptr;
+  };
+  auto step = [&](int k, float* cur, float* nxt, auto&, hipStream_t s) -> int {
+    const int B = u->B, HW = u->H * u->W;
+    const size_t lat = (size_t)B * 4 * HW;
+    float* x0_new = x0_hist + (size_t)(k % 2) * lat;
+    const float* x0_old = orders[k] == 2 ? x0_hist + (size_t)((k + 1) % 2) * lat : nullptr;
+    const float* row = table + (size_t)k * 5;
+    if (!clamp) return launch_dpmpp_step(cur, u->model_out(), x0_old, row, guidance, 1, nxt, x0_new, B, HW, s);
+    if (int rc = launch_dpmpp_step_clip(cur, u->model_out(), x0_old, row, guidance, 1, clamp[0], clamp[1], nxt, x0_new, B, HW, s)) return rc;
+    if (!keep_init) return K22_OK;
+    return launch_keep_region(nxt, keep_init, keep_noise, keep_mask, keep_coef[2 * k], keep_coef[2 * k + 1], nxt, B, HW, s);
+  };
+  auto key_tail = [&](std::vector<unsigned long long>& key) {
+    key.insert(key.end(), {loop_key_ptr(x0_hist), loop_key_ptr(table), loop_key_bits(guidance)});
+    for (int k = 0; k < n_steps; ++k) key.push_back((unsigned long long)orders[k]);
+    if (!clamp) return;
+    key.insert(key.end(), {loop_key_bits(clamp[0]), loop_key_bits(clamp[1])});
+    if (!keep_init) return;
+    // the three device operands and the bits of every coefficient baked into the keep-region nodes
+    key.insert(key.end(), {loop_key_ptr(keep_init), loop_key_ptr(keep_noise), loop_key_ptr(keep_mask)});
+    for (int k = 0; k < 2 * n_steps; ++k) key.push_back(loop_key_bits(keep_coef[k]));
+  };
+  const unsigned long long kind = !clamp ? K22_LOOP_KIND_DPMPP : keep_init ? K22_LOOP_KIND_DPMPP_KEEP : K22_LOOP_KIND_DPMPP_CLIP;
+  const UNetLoop a = {who, kind, x, x_tmp, timesteps, inpaint_image, inpaint_mask, n_steps, n_steps, use_graph, stream};
+  return unet_loop(u, a, own_fault, step, key_tail);
+}
+
 // ---------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------
@@ -1146,27 +1190,23 @@ int k22_unet_ddim_loop(K22UNet* u, int kind, float* x, float* x_tmp, float* x0_o
 // orders[k] == 2, reads slot (k - 1) % 2: the rotation is resolved here, at capture time, like the PLMS ring - so every order is in the key.
 int k22_unet_dpmpp_loop(K22UNet* u, float* x, float* x_tmp, float* x0_hist, const float* timesteps, const float* table, const int* orders,
                         const float* inpaint_image, const float* inpaint_mask, int n_steps, float guidance, int use_graph, void* stream) {
-  auto own_fault = [&]() -> const char* {
-    if (!x || !x_tmp || !x0_hist || !timesteps || !table || !orders) return "null argument";
-    if (n_steps < 1) return "n_steps must be >= 1";
-    for (int k = 0; k < n_steps; ++k)
-      if (orders[k] != 1 && orders[k] != 2) return "every order is 1 or 2";
-    if (orders[0] != 1) return "the first step has no history (orders[0] must be 1)";
-    return nullptr;
-  };
-  auto step = [&](int k, float* cur, float* nxt, auto&, hipStream_t s) -> int {
-    const int B = u->B, HW = u->H * u->W;
-    const size_t lat = (size_t)B * 4 * HW;
-    float* x0_new = x0_hist + (size_t)(k % 2) * lat;
-    const float* x0_old = orders[k] == 2 ? x0_hist + (size_t)((k + 1) % 2) * lat : nullptr;
-    return launch_dpmpp_step(cur, u->model_out(), x0_old, table + (size_t)k * 5, guidance, 1, nxt, x0_new, B, HW, s);
-  };
-  auto key_tail = [&](std::vector<unsigned long long>& key) {
-    key.insert(key.end(), {loop_key_ptr(x0_hist), loop_key_ptr(table), loop_key_bits(guidance)});
-    for (int k = 0; k < n_steps; ++k) key.push_back((unsigned long long)orders[k]);
-  };
-  const UNetLoop a = {"unet_dpmpp_loop", K22_LOOP_KIND_DPMPP, x, x_tmp, timesteps, inpaint_image, inpaint_mask, n_steps, n_steps, use_graph, stream};
-  return unet_loop(u, a, own_fault, step, key_tail);
+  return unet_dpmpp_loop_body(u, "unet_dpmpp_loop", x, x_tmp, x0_hist, timesteps, table, orders, inpaint_image, inpaint_mask, n_steps, guidance,
+                              nullptr, nullptr, nullptr, nullptr, nullptr, use_graph, stream);
+}
+
+// k22_unet_dpmpp_loop for the Kandinsky 2.2 decoders: the step is k22_dpmpp_step_clip (the scheduler's clip_sample on the data prediction) and,
+// with the four keep arguments, the known region of the inpainting pipeline is re-imposed on the freshly written latent as in
+// k22_unet_sample_loop_keep: per step  UNet -> k22_dpmpp_step_clip -> k22_keep_region, one chain on the capture stream.
+int k22_unet_dpmpp_loop_keep(K22UNet* u, float* x, float* x_tmp, float* x0_hist, const float* timesteps, const float* table, const int* orders,
+                             const float* inpaint_image, const float* inpaint_mask, int n_steps, float guidance, float clamp_lo, float clamp_hi,
+                             const float* keep_init, const float* keep_noise, const float* keep_mask, const float* keep_coef,
+                             int use_graph, void* stream) {
+  const int n_keep = (keep_init != nullptr) + (keep_noise != nullptr) + (keep_mask != nullptr) + (keep_coef != nullptr);
+  if (n_keep != 0 && n_keep != 4)
+    return k22_set_error(K22_EINVAL, "unet_dpmpp_loop_keep: keep_init, keep_noise, keep_mask and keep_coef go together (all four or none)");
+  const float clamp[2] = {clamp_lo, clamp_hi};
+  return unet_dpmpp_loop_body(u, "unet_dpmpp_loop_keep", x, x_tmp, x0_hist, timesteps, table, orders, inpaint_image, inpaint_mask, n_steps,
+                              guidance, clamp, keep_init, keep_noise, keep_mask, keep_coef, use_graph, stream);
 }
 
 int k22_unet_num_ops(const K22UNet* u) {

@@ -15,6 +15,8 @@
 //   0 sqrt_recip_alphas_cumprod   1 sqrt_recipm1_alphas_cumprod   2 posterior_mean_coef1
 //   3 posterior_mean_coef2        4 posterior_log_variance_clipped 5 log(beta)
 //   6 (t != 0)                    7 model timestep (after respacing map and 1000/T rescale)
+#include <string>
+
 #include "kernels.h"
 #include "elementwise.h"
 
@@ -346,8 +348,12 @@ int launch_plms_step(const float* x, const float* model_out, const float* h1, co
 // last sum - nine on the longest path (tests/dpmpp_ref.py counts them).  Contraction is switched off for the body and the operations are
 // plain operators: the __f*_rn intrinsics are inline functions compiled under the headers' contraction mode and were fused after inlining
 // (see keep_region_kernel, prestep.hip).
+// CLIP (k22_dpmpp_step_clip): x0 = clamp(x0, clamp_lo, clamp_hi) right after the division - DDPMScheduler's clip_sample on the data prediction;
+// the clamped value enters x_out and is what x0_out stores.  Two comparisons, no rounding; a NaN fails both and passes through.
+template <bool CLIP>
 __global__ __launch_bounds__(256) void dpmpp_step_kernel(const float* x, const float* model_out, const float* x0_prev, const float* tab,
-                                                         float guidance, int use_cfg, float* x_out, float* x0_out, int N, int HW) {
+                                                         float guidance, int use_cfg, float clamp_lo, float clamp_hi, float* x_out, float* x0_out,
+                                                         int N, int HW) {
 #pragma clang fp contract(off)
   const float a_s = tab[0], s_s = tab[1], c_x = tab[2], c_0 = tab[3];
   const float c_1 = x0_prev != nullptr ? tab[4] : 0.0f;
@@ -368,7 +374,11 @@ __global__ __launch_bounds__(256) void dpmpp_step_kernel(const float* x, const f
     const float xi = x[i];
     const float se = s_s * e;
     const float num = xi - se;
-    const float x0 = num / a_s;
+    float x0 = num / a_s;
+    if (CLIP) {
+      if (x0 < clamp_lo) x0 = clamp_lo;
+      if (x0 > clamp_hi) x0 = clamp_hi;
+    }
     const float t_x = c_x * xi, t_0 = c_0 * x0;
     float out = t_x + t_0;
     if (x0_prev != nullptr) {
@@ -380,18 +390,37 @@ __global__ __launch_bounds__(256) void dpmpp_step_kernel(const float* x, const f
   }
 }
 
-int launch_dpmpp_step(const float* x, const float* model_out, const float* x0_prev, const float* tab, float guidance, int use_cfg,
-                      float* x_out, float* x0_out, int N, int HW, hipStream_t s) {
-  if (!x || !model_out || !tab || !x_out || !x0_out) return k22_set_error(K22_EINVAL, "dpmpp_step: null argument");
-  if (N <= 0 || HW <= 0 || (use_cfg && (N & 1))) return k22_set_error(K22_EINVAL, "dpmpp_step: bad batch");
+// clamp == nullptr: k22_dpmpp_step; else k22_dpmpp_step_clip with (clamp[0], clamp[1]) - host values
+static int dpmpp_step_launch(const char* who, const float* x, const float* model_out, const float* x0_prev, const float* tab, float guidance,
+                             int use_cfg, const float* clamp, float* x_out, float* x0_out, int N, int HW, hipStream_t s) {
+  auto refuse = [who](const char* what) { return k22_set_error(K22_EINVAL, (std::string(who) + ": " + what).c_str()); };
+  if (!x || !model_out || !tab || !x_out || !x0_out) return refuse("null argument");
+  if (N <= 0 || HW <= 0 || (use_cfg && (N & 1))) return refuse("bad batch");
   if (x_out == x || x0_out == x || x0_out == x_out || (x0_prev && (x0_prev == x0_out || x0_prev == x_out)))
-    return k22_set_error(K22_EINVAL, "dpmpp_step: out of place only (x, x_out, x0_out and x0_prev are four buffers)");
+    return refuse("out of place only (x, x_out, x0_out and x0_prev are four buffers)");
+  if (clamp && !(clamp[0] <= clamp[1])) return refuse("clamp_lo <= clamp_hi, neither a NaN");
   const int64_t total = (int64_t)N * 4 * HW;
   int nb = (int)((total + 255) / 256);
   if (nb > 2048) nb = 2048;
-  hipLaunchKernelGGL(dpmpp_step_kernel, dim3(nb), dim3(256), 0, s, x, model_out, x0_prev, tab, guidance, use_cfg, x_out, x0_out, N, HW);
+  if (clamp)
+    hipLaunchKernelGGL(dpmpp_step_kernel<true>, dim3(nb), dim3(256), 0, s, x, model_out, x0_prev, tab, guidance, use_cfg, clamp[0], clamp[1], x_out,
+                       x0_out, N, HW);
+  else
+    hipLaunchKernelGGL(dpmpp_step_kernel<false>, dim3(nb), dim3(256), 0, s, x, model_out, x0_prev, tab, guidance, use_cfg, 0.0f, 0.0f, x_out, x0_out,
+                       N, HW);
   K22_CHECK_LAUNCH();
   return K22_OK;
+}
+
+int launch_dpmpp_step(const float* x, const float* model_out, const float* x0_prev, const float* tab, float guidance, int use_cfg,
+                      float* x_out, float* x0_out, int N, int HW, hipStream_t s) {
+  return dpmpp_step_launch("dpmpp_step", x, model_out, x0_prev, tab, guidance, use_cfg, nullptr, x_out, x0_out, N, HW, s);
+}
+
+int launch_dpmpp_step_clip(const float* x, const float* model_out, const float* x0_prev, const float* tab, float guidance, int use_cfg,
+                           float clamp_lo, float clamp_hi, float* x_out, float* x0_out, int N, int HW, hipStream_t s) {
+  const float clamp[2] = {clamp_lo, clamp_hi};
+  return dpmpp_step_launch("dpmpp_step_clip", x, model_out, x0_prev, tab, guidance, use_cfg, clamp, x_out, x0_out, N, HW, s);
 }
 
 // ---- inpainting mask pre-step (prepare_mask, kandinsky2/utils.py:11-31) ----------------------------------------------------

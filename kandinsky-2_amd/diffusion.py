@@ -367,10 +367,8 @@ class DPMSolverSamplerHIP(DDIMSamplerHIP):
 
     def make_dpm_schedule(self, S, solver_order=2, lower_order_final=True, discretize="logsnr", init_step=None):
         """self.timesteps (execution order), self.dpm_table (float64 [n,5]) and self.orders of a generation"""
-        ac = self.old_diffusion.alphas_cumprod
-        self.timesteps = sampling.dpmpp_grid(ac, S, discretize, init_step)
-        ac_t = np.asarray(ac[self.timesteps[1:]].tolist() + [ac[0]])[: len(self.timesteps)]
-        self.dpm_table, self.orders = sampling.dpmpp_table(ac[self.timesteps], ac_t, solver_order, lower_order_final)
+        self.timesteps, self.dpm_table, self.orders = sampling.dpmpp_schedule(self.old_diffusion.alphas_cumprod, S, solver_order,
+                                                                              lower_order_final, discretize, init_step)
 
     @torch.no_grad()
     def sample(self, S, batch_size, shape, conditioning=None, eta=0.0, x_T=None, init_step=None, device="cuda",

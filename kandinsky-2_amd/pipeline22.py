@@ -15,6 +15,7 @@ import hashlib
 import os
 from typing import Optional
 
+import numpy as np
 import torch
 
 from . import _lib, prestep, sampling
@@ -51,6 +52,7 @@ def _downscale(height, width, f=8):
     return (height // f ** 2 + (1 if height % f ** 2 else 0)) * f, (width // f ** 2 + (1 if width % f ** 2 else 0)) * f
 
 
+SAMPLERS = ("ddpm_sampler", "dpm_sampler")
 MAX_LOOP_GRAPH_STEPS = 100     # the largest default step count of either pipeline; a captured loop of a few hundred steps crashed the runtime
 
 
@@ -84,13 +86,34 @@ class KandinskyV22DecoderHIP:
     Python.  Same kernels on the same operands: text2img, ControlNet-depth and img2img give the stepwise route's bits, also with
     generator-drawn noise (sampling.ddpm_step_noise makes the stepwise loop's draws).  Inpainting re-imposes the known region with
     k22_keep_region in place of the per-sample k22_blend_noised launches: equal to rounding, not bit for bit.  Longer loops and loops with
-    an arbitrary after_step callback stay stepwise."""
+    an arbitrary after_step callback stay stepwise.
+    sampler ("ddpm_sampler", the default, or "dpm_sampler"; per call: sampler=): "dpm_sampler" is the project's DPM-Solver++ (2M, data
+    prediction, log-SNR grid; sampling.dpmpp_schedule on the scheduler's alphas_cumprod) - NOT a diffusers scheduler class.  One step = UNet
+    on the CFG batch + k22_dpmpp_step_clip with the scheduler's clip range on the data prediction.  num_inference_steps is S: the run may
+    take fewer steps (last_timesteps holds the executed ones, last_x0 the last data prediction), it is deterministic (a noise_seq is
+    refused; a generator still draws x_T), and its result ends at alphas_cumprod[0].  Stepwise (sampling.dpmpp_loop_keep) and as one graph
+    (UNet2DConditionHIP.dpmpp_loop -> k22_unet_dpmpp_loop_keep) it runs the same launches on the same operands: the same bits, inpainting
+    included.  It has never run on trained 2.2 weights; what is known about its accuracy is the toy-model experiment of DESIGN.md section 9."""
 
     def __init__(self, unet: UNet2DConditionHIP, movq: MoVQDecoderHIP, scheduler: Optional[DDPMSchedulerHIP] = None, movq_scale_factor: int = 8,
-                 whole_loop_graph: Optional[bool] = None):
+                 whole_loop_graph: Optional[bool] = None, sampler: str = "ddpm_sampler", solver_order: int = 2):
         self.unet, self.movq, self.scheduler = unet, movq, scheduler or DDPMSchedulerHIP.from_config(SCHEDULER_CONFIG_2_2)
         self.movq_scale_factor = movq_scale_factor
         self.whole_loop_graph = whole_loop_graph
+        self.sampler = None                                  # so that a None here is refused like any other unknown value
+        self.sampler, self.solver_order = self._sampler(sampler), solver_order
+        if solver_order not in (1, 2):
+            raise ValueError("solver_order must be 1 or 2")
+        self.last_timesteps, self.last_x0 = None, None
+
+    def _sampler(self, sampler, noise_seq=None):
+        """the sampler of this call (None = the constructor's); dpm_sampler takes no noise_seq"""
+        sampler = self.sampler if sampler is None else sampler
+        if sampler not in SAMPLERS:
+            raise ValueError(f"sampler must be one of {SAMPLERS}; got {sampler!r}")
+        if sampler == "dpm_sampler" and noise_seq is not None:
+            raise ValueError("dpm_sampler is deterministic (no ancestral noise): noise_seq must be None")
+        return sampler
 
     def _check(self, image_embeds):
         if image_embeds.device.type != "cuda":
@@ -142,6 +165,40 @@ class KandinskyV22DecoderHIP:
         self.last_latent = x[:bs]
         return self.last_latent
 
+    def _dpm_schedule(self, S, init_step=None):
+        """(timesteps, table float64 [n,5], orders) of a dpm_sampler generation of S steps on this scheduler's alphas_cumprod"""
+        return sampling.dpmpp_schedule(self.scheduler.alphas_cumprod, S, self.solver_order, init_step=init_step)
+
+    def _denoise_dpm(self, x, emb, schedule, guidance_scale, hint2=None, extra=None, keep=None):
+        """The dpm_sampler loop over `schedule` (_dpm_schedule's triple).  x, emb, extra: as _denoise; keep = (lat0 [1,4,h,w], noise0
+        [bs,4,h,w], mask [1,1,h,w]): the inpainting known region, re-imposed after every step with sampling.dpmpp_keep_coef's pairs."""
+        timesteps, table64, orders = schedule
+        n, bs, dev = len(timesteps), x.shape[0], x.device
+        x = torch.cat([x, x], 0).float().contiguous()
+        ts_rows = torch.tensor(np.asarray(timesteps, dtype=np.float32), device=dev).reshape(n, 1).expand(n, 2 * bs).contiguous()
+        table = torch.from_numpy(table64.astype(np.float32)).to(dev)            # the one rounding of the coefficients
+        clip = min(self.scheduler.clip, 3.0e38)
+        coef = None if keep is None else sampling.dpmpp_keep_coef(self.scheduler.alphas_cumprod, timesteps)
+        img, msk = (None, None) if extra is None else (extra[:, :4], extra[:, 4:5])
+        with self.unet.fixed_conditioning():
+            if self._one_graph(n, None):
+                x, x0 = self.unet.dpmpp_loop(x, ts_rows, table, orders, guidance_scale, (-clip, clip), image_embeds=emb, hint=hint2, inpaint_image=img,
+                                             inpaint_mask=msk, keep=None if keep is None else keep + (coef,))
+            else:
+                ack = {"image_embeds": emb} if hint2 is None else {"image_embeds": emb, "hint": hint2}
+                h, w = x.shape[-2:]
+                kept = None if keep is None else (keep[0].float().reshape(4, h, w).contiguous(), keep[1].float().contiguous(),
+                                                  keep[2].float().reshape(h, w).contiguous(), coef)
+
+                def call(xc, c):
+                    inp = sampling.cfg_input(xc)
+                    return self.unet(inp if extra is None else torch.cat([inp, extra], 1), ts_rows[c], encoder_hidden_states=None,
+                                     added_cond_kwargs=ack, return_dict=False)[0]
+
+                x, x0 = sampling.dpmpp_loop_keep(call, x, table, orders, guidance=float(guidance_scale), clamp=(-clip, clip), keep=kept)
+        self.last_timesteps, self.last_x0, self.last_latent = [int(t) for t in timesteps], x0[:bs], x[:bs]
+        return self.last_latent
+
     def _images(self, latents, height, width, output_type):
         if output_type == "latent":
             return latents
@@ -150,13 +207,17 @@ class KandinskyV22DecoderHIP:
 
     @torch.no_grad()
     def __call__(self, image_embeds, negative_image_embeds, height=512, width=512, num_inference_steps=100, guidance_scale=4.0,
-                 hint=None, latents=None, noise_seq=None, generator=None, output_type="pil"):
+                 hint=None, latents=None, noise_seq=None, generator=None, output_type="pil", sampler=None):
         self._check(image_embeds)
+        sampler = self._sampler(sampler, noise_seq)
         dev, bs = image_embeds.device, image_embeds.shape[0]
         h, w = _downscale(height, width, self.movq_scale_factor)
         emb = torch.cat([image_embeds, negative_image_embeds], 0).float().contiguous()
         hint2 = None if hint is None else torch.cat([hint, hint], 0).float().contiguous()
         x = latents.float() if latents is not None else torch.randn(bs, 4, h, w, generator=generator, device=dev)
+        if sampler == "dpm_sampler":
+            x = self._denoise_dpm(x, emb, self._dpm_schedule(num_inference_steps), guidance_scale, hint2=hint2)
+            return self._images(x, height, width, output_type)
         self.scheduler.set_timesteps(num_inference_steps, device=dev)
         x = self._denoise(x, emb, self.scheduler.timesteps.tolist(), guidance_scale, noise_seq, generator, hint2=hint2)
         return self._images(x, height, width, output_type)
@@ -169,8 +230,8 @@ class KandinskyV22Img2ImgDecoderHIP(KandinskyV22DecoderHIP):
     (get_timesteps: t_start = steps - min(int(steps * strength), steps)).  PARITY UNPINNED (diffusers, recalled)."""
 
     def __init__(self, unet, movq, movq_encoder: MoVQEncoderHIP, scheduler=None, movq_scale_factor: int = 8,
-                 whole_loop_graph: Optional[bool] = None):
-        super().__init__(unet, movq, scheduler, movq_scale_factor, whole_loop_graph)
+                 whole_loop_graph: Optional[bool] = None, sampler: str = "ddpm_sampler", solver_order: int = 2):
+        super().__init__(unet, movq, scheduler, movq_scale_factor, whole_loop_graph, sampler, solver_order)
         self.movq_encoder = movq_encoder
 
     def get_timesteps(self, num_inference_steps, strength, device="cuda"):
@@ -194,14 +255,24 @@ class KandinskyV22Img2ImgDecoderHIP(KandinskyV22DecoderHIP):
 
     @torch.no_grad()
     def __call__(self, image_embeds, negative_image_embeds, image, height=512, width=512, num_inference_steps=100, guidance_scale=4.0,
-                 strength=0.3, noise=None, noise_seq=None, generator=None, output_type="pil"):
+                 strength=0.3, noise=None, noise_seq=None, generator=None, output_type="pil", sampler=None):
         self._check(image_embeds)
+        sampler = self._sampler(sampler, noise_seq)
         dev, bs = image_embeds.device, image_embeds.shape[0]
         emb = torch.cat([image_embeds, negative_image_embeds], 0).float().contiguous()
         lat0 = self._latents_of(image, height, width, bs)
         ts = self.get_timesteps(num_inference_steps, strength, dev)
+        if sampler == "dpm_sampler":
+            # the DDPM route's first retained timestep is init_step: the grid keeps its points at or below it
+            schedule = self._dpm_schedule(num_inference_steps, init_step=ts[0])
+            if len(schedule[0]) == 0:
+                raise ValueError("strength too small: no denoising step left")
+            ts = [int(schedule[0][0])]
         nz0 = noise.to(dev).float() if noise is not None else torch.randn(lat0.shape, generator=generator, device=dev)
         x = self.scheduler.add_noise(lat0, nz0, ts[0])
+        if sampler == "dpm_sampler":
+            x = self._denoise_dpm(x, emb, schedule, guidance_scale)
+            return self._images(x, height, width, output_type)
         x = self._denoise(x, emb, ts, guidance_scale, noise_seq, generator)
         return self._images(x, height, width, output_type)
 
@@ -215,13 +286,16 @@ class KandinskyV22InpaintDecoderHIP(KandinskyV22Img2ImgDecoderHIP):
     diffusers commit the reference's notebooks install (before diffusers 0.19 inverted it); pass repaint_white=True for the later
     convention.  The latent-resolution mask goes through the same 1-pixel erosion as 2.1 (prepare_mask).  PARITY UNPINNED.
     The one-graph route (whole_loop_graph) re-imposes with k22_keep_region, every operation rounded once, the stepwise route with
-    k22_blend_noised, whose multiply-adds the compiler may contract: the two routes agree to rounding, not bit for bit."""
+    k22_blend_noised, whose multiply-adds the compiler may contract: the two routes agree to rounding, not bit for bit.
+    dpm_sampler re-imposes with k22_keep_region on BOTH routes (coefficients: sampling.dpmpp_keep_coef), so there they agree bit for bit; the
+    known region comes back clean, the unknown region ends at alphas_cumprod[0]."""
 
     @torch.no_grad()
     def __call__(self, image_embeds, negative_image_embeds, image, mask_image, height=512, width=512, num_inference_steps=100,
-                 guidance_scale=4.0, latents=None, noise_seq=None, generator=None, repaint_white=False, output_type="pil"):
+                 guidance_scale=4.0, latents=None, noise_seq=None, generator=None, repaint_white=False, output_type="pil", sampler=None):
         import torch.nn.functional as F
         self._check(image_embeds)
+        sampler = self._sampler(sampler, noise_seq)
         if self.unet.config.in_channels != 9:
             raise ValueError("the inpainting decoder needs the 9-channel UNet (make_arch22(inpainting=True))")
         dev, bs = image_embeds.device, image_embeds.shape[0]
@@ -238,6 +312,9 @@ class KandinskyV22InpaintDecoderHIP(KandinskyV22Img2ImgDecoderHIP):
         extra = torch.cat([masked, m], 1).repeat(2 * bs, 1, 1, 1).contiguous()
         x = latents.float() if latents is not None else torch.randn(bs, 4, h, w, generator=generator, device=dev)
         noise0 = x.clone()
+        if sampler == "dpm_sampler":
+            x = self._denoise_dpm(x, emb, self._dpm_schedule(num_inference_steps), guidance_scale, extra=extra, keep=(lat0, noise0, m))
+            return self._images(x, height, width, output_type)
         self.scheduler.set_timesteps(num_inference_steps, device=dev)
         ts = self.scheduler.timesteps.tolist()
         reimpose = KnownRegion(lat0, noise0, m, self.scheduler, ts)
@@ -285,7 +362,7 @@ class Kandinsky2_2HIP:
     def __init__(self, device="cuda", task_type="text2img", *, unet_state_dict=None, movq_state_dict=None, conditioner=None,
                  cache_dir=None, backend_dtype: torch.dtype = torch.bfloat16, use_graph: bool = True, unet_config=None, controlnet=None,
                  scheduler_config=None, movq_dtype: Optional[torch.dtype] = None, whole_loop_graph: Optional[bool] = None,
-                 prior_cache_dir=None):
+                 prior_cache_dir=None, sampler: str = "ddpm_sampler"):
         if task_type not in ("text2img", "img2img", "inpainting"):
             raise ValueError("Only text2img, img2img, inpainting is available")
         if (unet_state_dict is None or movq_state_dict is None) and cache_dir is not None:
@@ -335,12 +412,12 @@ class Kandinsky2_2HIP:
         movq.load_state_dict(movq_state_dict, strict=True)          # decoder keys; a full MOVQ checkpoint's other keys are skipped
         movq = movq.to(device)
         if task_type == "text2img":
-            self.decoder = KandinskyV22DecoderHIP(self.unet, movq, scheduler(), whole_loop_graph=whole_loop_graph)
+            self.decoder = KandinskyV22DecoderHIP(self.unet, movq, scheduler(), whole_loop_graph=whole_loop_graph, sampler=sampler)
         else:
             enc = MoVQEncoderHIP(backend_dtype=mdt)
             enc.load_state_dict(movq_state_dict, strict=True)
             cls = KandinskyV22Img2ImgDecoderHIP if task_type == "img2img" else KandinskyV22InpaintDecoderHIP
-            self.decoder = cls(self.unet, movq, enc.to(device), scheduler(), whole_loop_graph=whole_loop_graph)
+            self.decoder = cls(self.unet, movq, enc.to(device), scheduler(), whole_loop_graph=whole_loop_graph, sampler=sampler)
 
     def get_new_h_w(self, h, w):
         return (h // 64 + (1 if h % 64 else 0)) * 64, (w // 64 + (1 if w % 64 else 0)) * 64
@@ -354,19 +431,20 @@ class Kandinsky2_2HIP:
     @torch.no_grad()
     def generate_text2img(self, prompt, batch_size=1, decoder_steps=50, prior_steps=25, decoder_guidance_scale=4, prior_guidance_scale=4,
                           h=512, w=512, negative_prior_prompt="", negative_decoder_prompt="", *, hint=None, latents=None, noise_seq=None,
-                          output_type="pil"):
+                          output_type="pil", sampler=None):
         if self.task_type != "text2img":
             raise ValueError(f"this model was built for {self.task_type}")
         h, w = self.get_new_h_w(h, w)
         img_emb, _ = self.conditioner.prior22(prompt, negative_prior_prompt, batch_size, prior_steps, prior_guidance_scale, self.device)
         negative_emb = self._negative(negative_decoder_prompt, negative_decoder_prompt, batch_size, prior_steps, prior_guidance_scale)
         return self.decoder(image_embeds=img_emb, negative_image_embeds=negative_emb, num_inference_steps=decoder_steps, height=h, width=w,
-                            guidance_scale=decoder_guidance_scale, hint=hint, latents=latents, noise_seq=noise_seq, output_type=output_type)
+                            guidance_scale=decoder_guidance_scale, hint=hint, latents=latents, noise_seq=noise_seq, output_type=output_type,
+                            sampler=sampler)
 
     @torch.no_grad()
     def generate_img2img(self, prompt, image, strength=0.4, batch_size=1, decoder_steps=100, prior_steps=25, decoder_guidance_scale=4,
                          prior_guidance_scale=4, h=512, w=512, negative_prior_prompt="", negative_decoder_prompt="", *, noise=None,
-                         noise_seq=None, output_type="pil"):
+                         noise_seq=None, output_type="pil", sampler=None):
         if self.task_type != "img2img":
             raise ValueError(f"this model was built for {self.task_type}")
         h, w = self.get_new_h_w(h, w)
@@ -374,12 +452,12 @@ class Kandinsky2_2HIP:
         negative_emb = self._negative(negative_prior_prompt, negative_decoder_prompt, batch_size, prior_steps, prior_guidance_scale)
         return self.decoder(image_embeds=img_emb, negative_image_embeds=negative_emb, num_inference_steps=decoder_steps, height=h, width=w,
                             guidance_scale=decoder_guidance_scale, strength=strength, image=image, noise=noise, noise_seq=noise_seq,
-                            output_type=output_type)
+                            output_type=output_type, sampler=sampler)
 
     @torch.no_grad()
     def mix_images(self, images_texts, weights, batch_size=1, decoder_steps=50, prior_steps=25, decoder_guidance_scale=4,
                    prior_guidance_scale=4, h=512, w=512, negative_prior_prompt="", negative_decoder_prompt="", *, latents=None,
-                   noise_seq=None, output_type="pil"):
+                   noise_seq=None, output_type="pil", sampler=None):
         """prior.interpolate (kandinsky2_2_model.py:127-130): weighted sum of the prior embedding of every text and the CLIP image
         embedding of every image."""
         assert len(images_texts) == len(weights) and len(images_texts) > 0
@@ -394,16 +472,17 @@ class Kandinsky2_2HIP:
         img_emb = img_emb.repeat(batch_size, 1)
         negative_emb = self._negative(negative_prior_prompt, negative_decoder_prompt, batch_size, prior_steps, prior_guidance_scale)
         return self.decoder(image_embeds=img_emb, negative_image_embeds=negative_emb, num_inference_steps=decoder_steps, height=h, width=w,
-                            guidance_scale=decoder_guidance_scale, latents=latents, noise_seq=noise_seq, output_type=output_type)
+                            guidance_scale=decoder_guidance_scale, latents=latents, noise_seq=noise_seq, output_type=output_type,
+                            sampler=sampler)
 
     @torch.no_grad()
     def generate_inpainting(self, prompt, pil_img, img_mask, batch_size=1, decoder_steps=50, prior_steps=25, decoder_guidance_scale=4,
                             prior_guidance_scale=4, h=512, w=512, negative_prior_prompt="", negative_decoder_prompt="", *, latents=None,
-                            noise_seq=None, repaint_white=False, output_type="pil"):
+                            noise_seq=None, repaint_white=False, output_type="pil", sampler=None):
         if self.task_type != "inpainting":
             raise ValueError(f"this model was built for {self.task_type}")
         img_emb, _ = self.conditioner.prior22(prompt, negative_prior_prompt, batch_size, prior_steps, prior_guidance_scale, self.device)
         negative_emb = self._negative(negative_prior_prompt, negative_decoder_prompt, batch_size, prior_steps, prior_guidance_scale)
         return self.decoder(image_embeds=img_emb, negative_image_embeds=negative_emb, num_inference_steps=decoder_steps, height=h, width=w,
                             guidance_scale=decoder_guidance_scale, image=pil_img, mask_image=img_mask, latents=latents, noise_seq=noise_seq,
-                            repaint_white=repaint_white, output_type=output_type)
+                            repaint_white=repaint_white, output_type=output_type, sampler=sampler)

@@ -1,5 +1,5 @@
 """The host-driven step loops of the three decoder samplers, each written once, and the only ctypes callers of their step kernels
-(k22_sampler_step, k22_ddim_step, k22_plms_step, k22_dpmpp_step).  SpacedDiffusionHIP.p_sample_loop, DDIMSamplerHIP / PLMSSamplerHIP.sample (diffusion.py)
+(k22_sampler_step, k22_ddim_step, k22_plms_step, k22_dpmpp_step[_clip]).  SpacedDiffusionHIP.p_sample_loop, DDIMSamplerHIP / PLMSSamplerHIP.sample (diffusion.py)
 and the two-chain branches of Text2ImUNetHIP.sample_loop / ddim_loop (unet.py) run them; the captured single-chain loops are the same
 sequences in C++ (csrc/engine.hip).  A loop takes `model_call(latent, call_index) -> [N,8,H,W]`, the schedule rows in execution order
 and a step launcher, to which it hands its keywords (guidance, clamp, ...) through: the host tests pass recording launchers.
@@ -145,6 +145,33 @@ def dpmpp_table(ac_s, ac_t, solver_order: int = 2, lower_order_final: bool = Tru
     return table, orders
 
 
+def dpmpp_schedule(ac, S: int, solver_order: int = 2, lower_order_final: bool = True, discretize: str = "logsnr", init_step=None):
+    """(timesteps in execution order, table float64 [n,5], orders) of one DPM-Solver++ generation on the float64 alphas_cumprod `ac`:
+    dpmpp_grid's timesteps and dpmpp_table's coefficients between consecutive ones; the last step targets ac[0].  n may be smaller than S
+    (dpmpp_grid) and is 0 when init_step leaves nothing.  The 2.1 sampler (DPMSolverSamplerHIP.make_dpm_schedule) and the 2.2 decoders
+    (pipeline22) share it: the 2.2 DDPM scheduler's alphas_cumprod is the 2.1 array."""
+    ac = np.asarray(ac, dtype=np.float64)
+    timesteps = dpmpp_grid(ac, S, discretize, init_step)
+    ac_t = np.asarray(ac[timesteps[1:]].tolist() + [ac[0]])[: len(timesteps)]
+    table, orders = dpmpp_table(ac[timesteps], ac_t, solver_order, lower_order_final)
+    return timesteps, table, orders
+
+
+def dpmpp_keep_coef(ac, timesteps) -> np.ndarray:
+    """[n, 2] fp32, the k22_keep_region coefficients of an inpainting DPM-Solver++ loop over `timesteps` (execution order): row k =
+    (sqrt(ac_target_k), sqrt(1 - ac_target_k)) with ac_target_k = ac[timesteps[k + 1]] - the noise level step k arrives at - computed in
+    float64 and rounded once; the last row is (1, 0): the known region comes back CLEAN, as the DDPM route un-noises it after the last step.
+    The unknown region ends where every dpm_sampler result ends, at ac[0] (a residual noise level of sqrt(1 - ac[0]) = 0.029 on the 2.x
+    schedule), not at ac = 1: the solver's last step targets ac[0]."""
+    ac = np.asarray(ac, dtype=np.float64)
+    ts = [int(t) for t in timesteps]
+    coef = np.zeros((len(ts), 2), dtype=np.float32)
+    for k in range(len(ts)):
+        a = float(ac[ts[k + 1]]) if k + 1 < len(ts) else 1.0
+        coef[k] = (np.sqrt(a), np.sqrt(1.0 - a))
+    return coef
+
+
 def sampler_scratch(x: torch.Tensor) -> torch.Tensor:
     return torch.empty(_lib.lib().k22_sampler_scratch_bytes(x.shape[0], x.shape[2] * x.shape[3]), dtype=torch.uint8, device=x.device)
 
@@ -172,9 +199,15 @@ def plms_step(x, model_out, hist, order, row, x_out, eps_out, x0_out, *, guidanc
                                         _lib.current_stream()))
 
 
-def dpmpp_step(x, model_out, x0_prev, row, x_out, x0_out, *, guidance):
+def dpmpp_step(x, model_out, x0_prev, row, x_out, x0_out, *, guidance, clamp=None):
     """One k22_dpmpp_step launch: `row` = the step's [5] table row (dpmpp_table); x0_prev = the previous step's x0_out for an order-2 row,
-    None for an order-1 row; x0_out always receives this step's data prediction."""
+    None for an order-1 row; x0_out always receives this step's data prediction.  clamp=(lo, hi): k22_dpmpp_step_clip, the data prediction
+    clamped before it is used and stored."""
+    if clamp is not None:
+        _lib.check(_lib.lib().k22_dpmpp_step_clip(x.data_ptr(), model_out.data_ptr(), _lib.ptr(x0_prev), row.data_ptr(), float(guidance), 1,
+                                                  float(clamp[0]), float(clamp[1]), x_out.data_ptr(), x0_out.data_ptr(), x.shape[0],
+                                                  x.shape[2] * x.shape[3], _lib.current_stream()))
+        return
     _lib.check(_lib.lib().k22_dpmpp_step(x.data_ptr(), model_out.data_ptr(), _lib.ptr(x0_prev), row.data_ptr(), float(guidance), 1,
                                          x_out.data_ptr(), x0_out.data_ptr(), x.shape[0], x.shape[2] * x.shape[3], _lib.current_stream()))
 
@@ -226,6 +259,21 @@ def dpmpp_loop(model_call, x, rows, orders, step, **operands):
         step(x, model_call(x, k), hist[(k - 1) % 2] if order == 2 else None, row, x_next, x0, **operands)
         x, x_next = x_next, x
     return x, x0
+
+
+def dpmpp_loop_keep(model_call, x, rows, orders, *, guidance, clamp, keep=None):
+    """dpmpp_loop with the step of k22_unet_dpmpp_loop_keep, driven from the host: dpmpp_step(clamp=) and then, with keep = (init [4,h,w],
+    noise0 [B/2,4,h,w], mask [h,w] - contiguous fp32 device tensors - and coef [n,2], a host array), keep_region on the freshly written
+    latent with coef[k].  The same launches on the same values as the captured loop: the same bits."""
+    done = []        # the steps launched so far: the row of coef the next keep_region takes
+
+    def step(xc, model_out, x0_prev, row, x_out, x0_out, **kw):
+        dpmpp_step(xc, model_out, x0_prev, row, x_out, x0_out, **kw)
+        if keep is not None:
+            keep_region(x_out, keep[0], keep[1], keep[2], keep[3][len(done), 0], keep[3][len(done), 1], x_out)
+        done.append(1)
+
+    return dpmpp_loop(model_call, x, rows, orders, step, guidance=guidance, clamp=clamp)
 
 
 class OwnedBuffers:

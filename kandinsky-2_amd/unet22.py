@@ -305,7 +305,8 @@ class UNet2DConditionHIP(Text2ImUNetHIP):
 
     def _release(self):
         super()._release()
-        self._loop22_bufs = sampling.OwnedBuffers()      # operand buffers of sample_loop: the engine's captured loop holds their addresses
+        # operand buffers of sample_loop and dpmpp_loop, one set each: the engine's captured loop holds their addresses
+        self._loop22_bufs, self._dpmpp22_bufs = sampling.OwnedBuffers(), sampling.OwnedBuffers()
 
     @contextlib.contextmanager
     def fixed_conditioning(self):
@@ -426,6 +427,62 @@ class UNet2DConditionHIP(Text2ImUNetHIP):
             bufs["scratch"].data_ptr(), _lib.ptr(bufs["kinit"]), _lib.ptr(bufs["knoise"]), _lib.ptr(bufs["kmask"]), ccoef,
             1 if self.use_graph else 0, _lib.current_stream()))
         return bufs["x"].clone()
+
+    @torch.no_grad()
+    def dpmpp_loop(self, x, ts_rows, table, orders, guidance_scale, clamp, *, image_embeds=None, hint=None, inpaint_image=None,
+                   inpaint_mask=None, keep=None):
+        """The whole guided DPM-Solver++ loop of the 2.2 decoders as ONE hipGraph replay (k22_unet_dpmpp_loop_keep); returns (final latent,
+        x0 of the last step), both [B,4,h,w].  x = the CFG batch [x_T | x_T]; ts_rows [n, B]: the timestep of every model call; table [n, 5]
+        and orders (host ints): sampling.dpmpp_schedule's, the table rounded to fp32; clamp = (lo, hi) on the data prediction
+        (k22_dpmpp_step_clip); the conditioning and inpaint operands as sample_loop's.  keep=(init [1,4,h,w], noise0 [B/2,4,h,w], mask
+        [1,1,h,w], coef [n,2] host array: sampling.dpmpp_keep_coef): the known region re-imposed after every step by k22_keep_region.  The
+        operands are copied into buffers this module OWNS, so a second generation of the same shape and step count replays the capture.
+        Two chains: the host-driven sampling.dpmpp_loop_keep, whose step launches dpmpp_step(clamp=) and then keep_region - the captured
+        loop's pair, so the same bits."""
+        B, Cx, H, W = x.shape
+        if Cx != 4 or x.device.type != "cuda" or B % 2:
+            raise ValueError("dpmpp_loop: x must be the CFG batch [2 bs,4,h,w] on the GPU")
+        n_steps, a, bs = table.shape[0], self.arch, B // 2
+        orders = [int(o) for o in orders]
+        if n_steps < 1 or tuple(table.shape) != (n_steps, 5) or tuple(ts_rows.shape) != (n_steps, B) or len(orders) != n_steps:
+            raise ValueError("dpmpp_loop: table must be [n_steps, 5], ts_rows [n_steps, B] and orders n_steps ints, n_steps >= 1")
+        if a.inpainting != (inpaint_image is not None) or a.inpainting != (inpaint_mask is not None):
+            raise ValueError("dpmpp_loop: inpaint_image / inpaint_mask go with the 9-channel UNet, and only with it")
+        self._ensure_plan(B, H, W)
+        self._ensure_condition22(image_embeds, hint)
+        img = None if inpaint_image is None else inpaint_image.detach().float().expand(B, 4, H, W)
+        msk = None if inpaint_mask is None else inpaint_mask.detach().float().expand(B, 1, H, W)
+        k_init = k_noise = k_mask = coef = None
+        if keep is not None:
+            k_init, k_noise, k_mask, coef = keep
+            coef = np.ascontiguousarray(coef, dtype=np.float32)
+            if k_init.numel() != 4 * H * W or tuple(k_noise.shape) != (bs, 4, H, W) or k_mask.numel() != H * W or coef.shape != (n_steps, 2):
+                raise ValueError("dpmpp_loop: keep = (init [1,4,h,w], noise0 [bs,4,h,w], mask [1,1,h,w], coef [n_steps,2])")
+            k_init, k_mask = k_init.reshape(4, H, W), k_mask.reshape(H, W)
+        dev, g, clip = x.device, float(guidance_scale), (float(clamp[0]), float(clamp[1]))
+        if self._chained(B):
+            ack = {"image_embeds": image_embeds} if hint is None else {"image_embeds": image_embeds, "hint": hint}
+            extra = None if img is None else torch.cat([img, msk], 1)
+            kept = None if keep is None else (k_init.float().contiguous(), k_noise.float().contiguous(), k_mask.float().contiguous(), coef)
+
+            def call(xc, c):
+                inp = sampling.cfg_input(xc)
+                return self.forward(inp if extra is None else torch.cat([inp, extra], 1), ts_rows[c], added_cond_kwargs=ack, return_dict=False)[0]
+
+            return sampling.dpmpp_loop_keep(call, x.detach().float().clone(), table.float().contiguous(), orders, guidance=g, clamp=clip, keep=kept)
+        box, lat = (B, 4, H, W), (4, H, W)
+        bufs = self._dpmpp22_bufs.stage(
+            (B, H, W, n_steps, keep is not None, str(dev)), dev,
+            lambda: dict(x=box, tmp=box, hist=(2,) + box, ts=(n_steps, B), table=(n_steps, 5), img=box if a.inpainting else None,
+                         msk=(B, 1, H, W) if a.inpainting else None, kinit=lat if keep is not None else None,
+                         knoise=(bs,) + lat if keep is not None else None, kmask=(H, W) if keep is not None else None),
+            dict(x=x, ts=ts_rows, table=table, img=img, msk=msk, kinit=k_init, knoise=k_noise, kmask=k_mask))
+        ccoef = None if coef is None else coef.ctypes.data_as(C.POINTER(C.c_float))
+        _lib.check(_lib.lib().k22_unet_dpmpp_loop_keep(
+            self._handle, bufs["x"].data_ptr(), bufs["tmp"].data_ptr(), bufs["hist"].data_ptr(), bufs["ts"].data_ptr(), bufs["table"].data_ptr(),
+            (C.c_int * n_steps)(*orders), _lib.ptr(bufs["img"]), _lib.ptr(bufs["msk"]), n_steps, g, clip[0], clip[1], _lib.ptr(bufs["kinit"]),
+            _lib.ptr(bufs["knoise"]), _lib.ptr(bufs["kmask"]), ccoef, 1 if self.use_graph else 0, _lib.current_stream()))
+        return bufs["x"].clone(), bufs["hist"][(n_steps - 1) % 2].clone()
 
     @torch.no_grad()
     def forward(self, sample, timestep, encoder_hidden_states=None, added_cond_kwargs=None, return_dict: bool = True, **_unused):
