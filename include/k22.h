@@ -414,8 +414,20 @@ typedef struct K22IgemmOperands {
 } K22IgemmOperands;
 /* Host only (no GPU call): does THIS build accept the configuration for the problem?  Builds the launch descriptor the engines build,
  * lists its candidates (tuned_make_candidates) and answers tuned_is_candidate: 1 = a table line with this key and configuration is
- * used as it stands, 0 = it is dropped silently and the problem is measured again on every start.  Negative: K22_EINVAL. */
+ * used as it stands, 0 = it is dropped silently and the problem is measured again on every start.  Negative: K22_EINVAL.
+ * The ALL-ZERO configuration (algo = bm = bn = splitk = stages = 0) stands, here and in k22_igemm_cfg, for the fixed choice: what
+ * tuned_default_cfg resolves for the problem - the table's line where one exists, else the heuristic an engine runs under K22_AUTOTUNE=0 and,
+ * whatever the setting, for M < 64, which the tuner never times.  Accepted unless the problem owes GroupNorm partial sums that choice cannot write, or no
+ * kernel takes the problem at all. */
 int k22_igemm_cfg_accepted(const K22IgemmProblem* pr);
+/* Host only: the configurations tuned_make_candidates generates for the problem - everything tune_igemm_ops may time and keep - from the
+ * same descriptor as above.  Writes the first `capacity` of them to `out` and returns their number (which may exceed capacity; 0 = the
+ * problem has no candidates and always runs its fixed choice).  resolved (optional, [capacity]) receives the launch igemm_resolve makes of each:
+ * kernel, tile, split-K factor and, in `stages`, the ring depth instantiated (halo kernels: conv3_halo_ring's, unless a shallower one was
+ * asked for).  fixed (optional) receives the same for the all-zero configuration: its split-K factor says how large a partial buffer
+ * (splitk * M * N fp32) that launch needs; all zero where k22_igemm_cfg_accepted answers 0 for it. */
+typedef struct K22IgemmCfg { int algo, bm, bn, splitk, stages; } K22IgemmCfg;
+int k22_igemm_candidates(const K22IgemmProblem* pr, K22IgemmCfg* out, int capacity, K22IgemmCfg* resolved, K22IgemmCfg* fixed);
 /* Runs the problem ONCE with exactly that configuration, the way an engine's launch closure does (IgemmParams from the problem,
  * tuned_apply_cfg, launch_igemm); it needs and sets no process-wide option (k22_set_option).  A configuration k22_igemm_cfg_accepted rejects
  * is an error (K22_EINVAL), never a quiet run of another kernel.  With want_stats the GroupNorm partial sums land in ops->stats as in

@@ -64,6 +64,11 @@ class K22IgemmOperands(C.Structure):
         "stats")] + [("stats_capacity_rows", C.c_int)]
 
 
+class K22IgemmCfg(C.Structure):
+    """one tile configuration (include/k22.h: k22_igemm_candidates)"""
+    _fields_ = [(n, C.c_int) for n in ("algo", "bm", "bn", "splitk", "stages")]
+
+
 class K22MoVQConfig(C.Structure):
     _fields_ = [("dtype", C.c_int), ("ch", C.c_int), ("n_levels", C.c_int), ("ch_mult", C.c_int * 8),
                 ("num_res_blocks", C.c_int), ("attn_levels", C.c_int), ("z_channels", C.c_int), ("out_ch", C.c_int)]
@@ -160,6 +165,7 @@ SIGNATURES = {
     "k22_up2_fold": (_I, [_P, _P, _I, _I, _I, _P]),
     "k22_igemm_cfg_accepted": (_I, [C.POINTER(K22IgemmProblem)]),
     "k22_igemm_cfg": (_I, [C.POINTER(K22IgemmProblem), C.POINTER(K22IgemmOperands), C.POINTER(_I), _P]),
+    "k22_igemm_candidates": (_I, [C.POINTER(K22IgemmProblem), C.POINTER(K22IgemmCfg), _I, C.POINTER(K22IgemmCfg), C.POINTER(K22IgemmCfg)]),
     "k22_conv3x3_gn": (_I, [_P, _P, _I, _I, _P, _P, _P, _L, _F, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "k22_debug_conv_trace": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "k22_groupnorm": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _L, _F, _I, _I, _I, _P, _P, _I, _P]),

@@ -288,11 +288,51 @@ static Cfg igemm_problem_cfg(const K22IgemmProblem& d) {
   return c;
 }
 
+static bool igemm_cfg_is_fixed_choice(const Cfg& c) { return !c.algo && !c.bm && !c.bn && !c.splitk && !c.stages; }
+// The all-zero configuration: what tuned_default_cfg leaves in t.cfg (K22_AUTOTUNE=0, and every M < 64).  False when the problem owes
+// GroupNorm partial sums and the fixed choice cannot deliver them (an engine then runs the stand-alone gn_stats kernel), or when no kernel
+// takes the problem at all (igemm_resolve refuses it: a fused skip on an image no halo kernel supports).  L: the launch it resolves to.
+static bool igemm_fixed_choice(const K22IgemmProblem& d, Tuned& t, IgemmLaunch* L = nullptr) {
+  tuned_default_cfg(t, d.dtype);
+  IgemmParams q = t.p;
+  tuned_apply_cfg(q, t.cfg);
+  IgemmLaunch tmp;
+  if (igemm_resolve(q, d.dtype, L ? L : &tmp) != K22_OK) return false;
+  return !d.want_stats || (t.want_stats && t.rpi > 0);
+}
+
 int k22_igemm_cfg_accepted(const K22IgemmProblem* pr) {
   if (!pr) return k22_set_error(K22_EINVAL, "igemm_cfg_accepted: null problem");
   Tuned t;
   if (int rc = igemm_problem_tuned(*pr, t)) return rc;
+  if (igemm_cfg_is_fixed_choice(igemm_problem_cfg(*pr))) return igemm_fixed_choice(*pr, t) ? 1 : 0;
   return tuned_is_candidate(t, igemm_problem_cfg(*pr)) ? 1 : 0;
+}
+
+int k22_igemm_candidates(const K22IgemmProblem* pr, K22IgemmCfg* out, int capacity, K22IgemmCfg* resolved, K22IgemmCfg* fixed) {
+  if (!pr || capacity < 0 || (capacity > 0 && !out)) return k22_set_error(K22_EINVAL, "igemm_candidates: null problem / array");
+  Tuned t;
+  if (int rc = igemm_problem_tuned(*pr, t)) return rc;
+  auto resolve = [&](const Cfg& c, K22IgemmCfg* r) {
+    IgemmParams q = t.p;
+    tuned_apply_cfg(q, c);
+    IgemmLaunch L;
+    if (int rc = igemm_resolve(q, pr->dtype, &L)) return rc;
+    r->algo = L.algo; r->bm = L.bm; r->bn = L.bn; r->splitk = L.splitk; r->stages = L.depth;
+    return (int)K22_OK;
+  };
+  const int n = (int)t.cands.size();
+  for (int i = 0; i < n && i < capacity; ++i) {
+    const Cfg& c = t.cands[i];
+    out[i].algo = c.algo; out[i].bm = c.bm; out[i].bn = c.bn; out[i].splitk = c.splitk; out[i].stages = c.stages;
+    if (resolved) if (int rc = resolve(c, &resolved[i])) return rc;
+  }
+  if (fixed) {
+    IgemmLaunch L = {};
+    if (!igemm_fixed_choice(*pr, t, &L)) L = IgemmLaunch{};   // all zero: k22_igemm_cfg_accepted says 0 for it
+    fixed->algo = L.algo; fixed->bm = L.bm; fixed->bn = L.bn; fixed->splitk = L.splitk; fixed->stages = L.depth;
+  }
+  return n;
 }
 
 int k22_igemm_cfg(const K22IgemmProblem* pr, const K22IgemmOperands* ops, int* rows_per_image, void* stream) {
@@ -302,8 +342,12 @@ int k22_igemm_cfg(const K22IgemmProblem* pr, const K22IgemmOperands* ops, int* r
   const K22IgemmOperands& o = *ops;
   Tuned t;
   if (int rc = igemm_problem_tuned(d, t)) return rc;
-  const Cfg c = igemm_problem_cfg(d);
-  if (!tuned_is_candidate(t, c)) return k22_set_error(K22_EINVAL, "igemm_cfg: this build does not generate the configuration for the problem");
+  Cfg c = igemm_problem_cfg(d);
+  if (igemm_cfg_is_fixed_choice(c)) {
+    if (!igemm_fixed_choice(d, t)) return k22_set_error(K22_EINVAL, "igemm_cfg: the fixed choice cannot run this problem (no kernel takes it, or none writes the GroupNorm partial sums it owes)");
+    c = t.cfg;
+    if (!o.partial) return k22_set_error(K22_EINVAL, "igemm_cfg: the fixed choice needs the fp32 partial buffer (k22_igemm_candidates reports its split)");
+  } else if (!tuned_is_candidate(t, c)) return k22_set_error(K22_EINVAL, "igemm_cfg: this build does not generate the configuration for the problem");
   if (!o.A0 || !o.Wp || !o.out) return k22_set_error(K22_EINVAL, "igemm_cfg: A0, Wp and out are required");
   if (d.K0 < d.Kc && !o.A1) return k22_set_error(K22_EINVAL, "igemm_cfg: A1 missing for the concat operand");
   if (d.SK0 > 0 && (!o.S0 || !o.Ws || (d.SK1 > 0 && !o.S1))) return k22_set_error(K22_EINVAL, "igemm_cfg: fused-skip operands missing");

@@ -511,7 +511,9 @@ def run_tile_line(t, dtype, inp):
     oT = torch.float32 if t.out_mode in (_lib.OUT_ROWMAJOR_F32, _lib.OUT_NCHW_F32) else T
     nan = float("nan")
     outs = {k: torch.full(v.shape, nan, dtype=oT, device=dev) for k, v in igemm_layout(t, torch.zeros(t.M, t.N, device=dev)).items()}
-    partial = torch.empty(max(1, t.splitk) * t.M * t.N + 64, dtype=torch.float32, device=dev)
+    # (the all-zero configuration is the fixed choice: the library reports the split factor that launch resolves to)
+    splitk = t.splitk if any(cfg_of(t)) else igemm_candidates(t, dtype)[2][3]
+    partial = torch.empty(max(1, splitk) * t.M * t.N + 64, dtype=torch.float32, device=dev)
     wfrag = wsfrag = None
     if t.algo == 20:
         L = _lib.lib()
@@ -534,3 +536,91 @@ def run_tile_line(t, dtype, inp):
     _lib.check(_lib.lib().k22_igemm_cfg(C.byref(pr), C.byref(ops), C.byref(rpi), stream()))
     torch.cuda.synchronize()
     return outs, sbuf, rpi.value
+
+
+# ---- off-table problems: what the tuner may pick where the shipped table has no line (tests/test_igemm_candidates_*.py) ------------------------
+# The table holds the C1-C5 shapes only; any other batch or image size is timed on the device over tuned_make_candidates' list (or, with
+# K22_AUTOTUNE=0 and for every M < 64, runs tuned_default_cfg's fixed choice).  OFFTABLE lists the smallest problems at which each edge of
+# those kernels' index arithmetic exists, as TileLines whose configuration fields are zero (= the fixed choice): igemm_candidates reads the
+# build's own candidate list for one, and t._replace(algo=..., ...) runs a candidate through run_tile_line like any table line.  The dtype
+# field is a placeholder: every problem runs in every arithmetic that accepts it (offtable_accepts).
+
+def _ot_conv(B, H, W, Cin, Cout, stats=0, sk=0, out_mode=0):
+    return TileLine(0, 9, B * H * W, Cout, Cin, Cin, H, W, out_mode, 0, 0, 0, stats, sk, 0, 0, 0, 0, 0)
+
+
+def _ot_gemm(M, N, Kc, K0=None, H=0, W=0, out_mode=0, res_f32=0, act=0, a_raw=0, stats=0):
+    return TileLine(0, 1, M, N, Kc, Kc if K0 is None else K0, H, W, out_mode, res_f32, act, a_raw, stats, 0, 0, 0, 0, 0, 0)
+
+
+OFFTABLE = {
+    # 3x3 convolutions  B, H, W, Cin -> Cout (the residual is always there: igemm_inputs)
+    "conv-3x5x5-128-128": _ot_conv(3, 5, 5, 128, 128),                    # image smaller than one tile, odd sizes, odd batch
+    "conv-1x5x5-128-128": _ot_conv(1, 5, 5, 128, 128),                    # M = 25 < 64: the fixed choice only (the tuner skips it)
+    "conv-3x5x7-128-256-st": _ot_conv(3, 5, 7, 128, 256, stats=1),        # prime H: stream bands of 1 or H rows; partial-sum rows of ragged tiles
+    # (35 rows per image admit no row-tiled finish, so with the sums owed the build lists no streaming candidate: the same shape without them)
+    "conv-3x5x7-128-256": _ot_conv(3, 5, 7, 128, 256),
+    "conv-2x10x10-192-192": _ot_conv(2, 10, 10, 192, 192),               # lowest level of a 640-px image; 1.5 halo n-tiles; 3 / 6 k-steps: uneven splits
+    "conv-2x10x10-192-192-st": _ot_conv(2, 10, 10, 192, 192, stats=1),
+    "conv-1x20x20-128-136": _ot_conv(1, 20, 20, 128, 136),                # N % 8 == 0, N % 64 != 0: Npad 192
+    "conv-2x9x13-64-128": _ot_conv(2, 9, 13, 64, 128),                    # 16-bit types: one k-step per tap, ring deeper than the loop
+    "conv-2x9x13-32-128": _ot_conv(2, 9, 13, 32, 128),                    # the same for the 32-wide-BK arithmetics
+    "conv-1x40x40-128-128-st": _ot_conv(1, 40, 40, 128, 128, stats=1),    # next 640-px level, tiles ending mid-row
+    "conv-2x1x37-64-128": _ot_conv(2, 1, 37, 64, 128),                    # H = 1: top and bottom border in one row
+    "conv-2x37x1-64-128": _ot_conv(2, 37, 1, 64, 128),                    # W = 1: every position touches the border, W + 2 = 3
+    "conv-1x2x160-64-128": _ot_conv(1, 2, 160, 64, 128),                  # W + 2 > 128: a tile shorter than a row; bm 128 at ring depth 2
+    "conv-1x2x130-64-128": _ot_conv(1, 2, 130, 64, 128),                  # bm 128 at ring depth 3 (126 <= W <= 157)
+    "conv-1x1x230-64-128": _ot_conv(1, 1, 230, 64, 128),                  # halo3 alone takes W > 189: its ring at depth 3 (bm 128) and 2 (bm 256)
+    "conv-1x1x300-64-128": _ot_conv(1, 1, 300, 64, 128),                  # halo3 bm 128 at ring depth 2, its widest frame (W <= 317)
+    "conv-1x3x100-64-128": _ot_conv(1, 3, 100, 64, 128),                  # bm 256 at ring depth 2
+    "conv-1x3x64-64-128": _ot_conv(1, 3, 64, 64, 128),                    # bm 256 at ring depth 3, bm 128 at depth 4
+    "conv-2x10x10-128-128-skip64": _ot_conv(2, 10, 10, 128, 128, sk=64),  # skip narrower than an n-tile
+    "conv-2x10x10-128-128-skip192": _ot_conv(2, 10, 10, 128, 128, sk=192),   # skip_split: 128 | 64, concat skip source
+    "conv-2x10x10-128-8-nchw": _ot_conv(2, 10, 10, 128, 8, out_mode=_lib.OUT_NCHW_F32),   # head conv: generic kernel only
+    # GEMMs
+    "gemm-300x192x192-st": _ot_gemm(300, 192, 192, H=10, W=10, stats=1),  # 100 rows per image under a 128 / 256-row tile
+    "gemm-333x200x576": _ot_gemm(333, 200, 576),                          # ragged M, Npad 256, nine k-steps
+    "gemm-65x128x64": _ot_gemm(65, 128, 64),                              # second m-tile holds one row; one k-step
+    "gemm-200x128x96-raw": _ot_gemm(200, 128, 96, a_raw=1),               # split types only: three 32-wide steps
+    "gemm-150x256x320cat128-f32": _ot_gemm(150, 256, 320, K0=128, out_mode=_lib.OUT_ROWMAJOR_F32),   # virtual concat
+    "gemm-162x256x256-gelu-resf32": _ot_gemm(162, 256, 256, res_f32=1, act=_lib.ACT_GELU),            # prior-like
+    "qkv-2x10x10-128-h2": _ot_gemm(200, 384, 128, H=10, W=10, out_mode=_lib.OUT_QKV),     # Tkp 192: keys scattered behind S = 77 into padded K_all / V^T_all
+    "qkv-2x10x10-128-h6": _ot_gemm(200, 1152, 128, H=10, W=10, out_mode=_lib.OUT_QKV),
+    "gemm-2x1536x384": _ot_gemm(2, 1536, 384),                            # M < 64: the fixed choice only
+}
+ALL_DTYPES = (_lib.K22_BF16, _lib.K22_F16, _lib.K22_F32, _lib.K22_F16X3, _lib.K22_F16X2)
+CFG_FIELDS = ("algo", "bm", "bn", "splitk", "stages")
+
+
+def offtable_accepts(t, dtype):
+    """does the arithmetic take the problem at all: K per tap, both concat halves and the skip widths in whole k-steps (64 elements for the
+    16-bit types, 32 for fp32 and the split ones); raw fp32 activation rows are an option of the split arithmetics only"""
+    bk = 64 if dtype in (_lib.K22_BF16, _lib.K22_F16) else 32
+    sk0, sk1 = skip_split(t.sk_total)
+    return not (t.Kc % bk or t.K0 % bk or sk0 % bk or sk1 % bk) and (not t.a_raw or dtype in X_DTYPES)
+
+
+def offtable_cases():
+    """[(id, TileLine, dtype)] of every (problem, arithmetic) pair that is run"""
+    return [(f"{name}-{DT_NAME[dt]}", t, dt) for name, t in OFFTABLE.items() for dt in ALL_DTYPES if offtable_accepts(t, dt)]
+
+
+def cfg_of(t):
+    return tuple(getattr(t, f) for f in CFG_FIELDS)
+
+
+def igemm_candidates(t, dtype, has_frag=0):
+    """the build's own list for the problem (k22_igemm_candidates: tuned_make_candidates over the engines' descriptor; no device needed)
+    -> (candidates, resolved, fixed): lists of (algo, bm, bn, splitk, stages) as generated / as igemm_resolve makes them (stages = the ring
+    depth instantiated), and the resolved launch of the all-zero configuration, tuned_default_cfg's choice"""
+    import ctypes as C
+    pr = tile_problem(t._replace(algo=0, bm=0, bn=0, splitk=0, stages=0), dtype)
+    pr.has_frag = has_frag
+    cap = 512
+    out, res, fixed = (_lib.K22IgemmCfg * cap)(), (_lib.K22IgemmCfg * cap)(), _lib.K22IgemmCfg()
+    n = _lib.lib().k22_igemm_candidates(C.byref(pr), out, cap, res, C.byref(fixed))
+    if n < 0:
+        _lib.check(n)
+    assert n <= cap
+    tup = lambda c: tuple(getattr(c, f) for f in CFG_FIELDS)
+    return [tup(out[i]) for i in range(n)], [tup(res[i]) for i in range(n)], tup(fixed)
