@@ -721,7 +721,8 @@ int k22_enc_vision_assemble(const float* patch_out, const float* cls, const floa
 int k22_enc_mlp_act(const float* x, void* y, long n, int exact, int dtype, void* stream);
 int k22_enc_attention_generic(const void* qkv, void* out, int B, int heads, int n, int hd, int dtype, void* stream);
 /* Prior (k22_prior_sampler_step above belongs to the same surface).
- *   prior_layernorm    `rows` fp32 rows x + r * ldx of D values -> rows y + r * D, fp32 (to_f32 != 0) or T; eps 1e-5
+ *   prior_layernorm    `rows` fp32 rows x + r * ldx of D <= 2048 values (K22_EINVAL above) -> rows y + r * D, fp32 (to_f32 != 0) or T;
+ *                      eps 1e-5: enc_layernorm's kernel with one of its outputs
  *   prior_finish_input inp [B][n_ctx][D] += pos [n_ctx][D], the last row of every sequence = prd [D] + pos[n_ctx - 1] */
 int k22_prior_layernorm(const float* x, long ldx, const float* gain, const float* beta, void* y, int rows, int D, int to_f32, int dtype,
                         void* stream);

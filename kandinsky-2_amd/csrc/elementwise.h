@@ -122,6 +122,10 @@ int launch_conv_in(const ConvInParams& p, int dtype, hipStream_t s);
 int launch_timestep_embedding(const float* t, const float* freqs, float* out, int B, int half, hipStream_t s);
 int launch_linear_smallm(const LinearSmallParams& p, int wdtype, hipStream_t s);
 int launch_layernorm_f32(const float* x, const float* g, const float* b, float* y, int rows, int D, float eps, hipStream_t s);
+// LayerNorm of `rows` fp32 rows of x (stride ldx, D <= 2048): fp32 copy into yf (stride ldyf; may be x itself) and / or a copy in `dtype` into
+// yt (stride D); either may be null
+int launch_layernorm_rows(const float* x, int64_t ldx, const float* g, const float* b, float* yf, int64_t ldyf, void* yt, int rows, int D,
+                          float eps, int dtype, hipStream_t s);
 int launch_cast_rows(const float* x, void* y, int rows, int cols, int64_t ldx, int64_t ldy, int dtype, hipStream_t s);
 int launch_kv_pack(const KvPackParams& p, int dtype, hipStream_t s);
 int launch_attention(const AttentionParams& p, int dtype, hipStream_t s);

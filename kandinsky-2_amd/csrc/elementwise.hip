@@ -455,6 +455,41 @@ __global__ __launch_bounds__(256) void layernorm_f32_kernel(const float* x, cons
   for (int i = tid; i < D; i += 256) y[(int64_t)row * D + i] = (xr[i] - mean) * rstd * g[i] + bta[i];
 }
 
+// ---- LayerNorm over the last dim of fp32 rows (stride ldx), the transformer engines' (prior.hip, encoder.hip): optional fp32 output
+// (may alias the input row: post-LN blocks normalise the residual stream in place) and optional TO output (the next GEMM's operand).
+// The row stays in eight registers per thread: D <= 2048. ------------------------------------------------------------------------
+template <typename TO>
+__global__ __launch_bounds__(256) void layernorm_rows_kernel(const float* x, int64_t ldx, const float* g, const float* bta, float* yf,
+                                                             int64_t ldyf, TO* yt, int64_t ldyt, int D, float eps) {
+  __shared__ float red[8];
+  const int row = blockIdx.x, tid = threadIdx.x;
+  const float* xr = x + (int64_t)row * ldx;
+  float v[8];
+  float s = 0.f;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) { const int i = tid + k * 256; v[k] = i < D ? xr[i] : 0.f; s += v[k]; }
+  s = wave_sum(s);
+  if ((tid & 63) == 0) red[tid >> 6] = s;
+  __syncthreads();
+  const float mean = ((red[0] + red[1]) + (red[2] + red[3])) / D;
+  float q = 0.f;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) { const int i = tid + k * 256; if (i < D) { const float d = v[k] - mean; q += d * d; } }
+  q = wave_sum(q);
+  if ((tid & 63) == 0) red[4 + (tid >> 6)] = q;
+  __syncthreads();
+  const float rstd = rsqrtf(((red[4] + red[5]) + (red[6] + red[7])) / D + eps);
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const int i = tid + k * 256;
+    if (i < D) {
+      const float y = (v[k] - mean) * rstd * g[i] + bta[i];
+      if (yf != nullptr) yf[(int64_t)row * ldyf + i] = y;
+      if (yt != nullptr) yt[(int64_t)row * ldyt + i] = from_f32<TO>(y);
+    }
+  }
+}
+
 // ---- fp32 -> T cast with row re-striding (ctx assembly) -----------------------------------
 template <typename T>
 __global__ void cast_rows_kernel(const float* x, void* yout, int rows, int cols, int64_t ldx, int64_t ldy) {
@@ -645,6 +680,18 @@ int launch_linear_smallm(const LinearSmallParams& p0, int wdtype, hipStream_t s)
 }
 int launch_layernorm_f32(const float* x, const float* g, const float* b, float* y, int rows, int D, float eps, hipStream_t s) {
   hipLaunchKernelGGL(layernorm_f32_kernel, dim3(rows), dim3(256), 0, s, x, g, b, y, D, eps);
+  K22_CHECK_LAUNCH();
+  return K22_OK;
+}
+int launch_layernorm_rows(const float* x, int64_t ldx, const float* g, const float* b, float* yf, int64_t ldyf, void* yt, int rows, int D,
+                          float eps, int dtype, hipStream_t s) {
+  if (D > 2048) return k22_set_error(K22_EINVAL, "layernorm_rows: D <= 2048 (8 x 256 values per row)");
+  if (yt != nullptr && dtype == K22_BF16)
+    hipLaunchKernelGGL(layernorm_rows_kernel<bf16_t>, dim3(rows), dim3(256), 0, s, x, ldx, g, b, yf, ldyf, reinterpret_cast<bf16_t*>(yt), (int64_t)D, D, eps);
+  else if (yt != nullptr && dtype == K22_F16)
+    hipLaunchKernelGGL(layernorm_rows_kernel<f16_t>, dim3(rows), dim3(256), 0, s, x, ldx, g, b, yf, ldyf, reinterpret_cast<f16_t*>(yt), (int64_t)D, D, eps);
+  else
+    hipLaunchKernelGGL(layernorm_rows_kernel<float>, dim3(rows), dim3(256), 0, s, x, ldx, g, b, yf, ldyf, reinterpret_cast<float*>(yt), (int64_t)D, D, eps);
   K22_CHECK_LAUNCH();
   return K22_OK;
 }

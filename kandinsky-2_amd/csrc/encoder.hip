@@ -14,9 +14,9 @@
 //                        LinearTransformation(masked mean over tokens) -> [B,768]
 //
 // They run once per prompt, not per denoising step (a "next" row, outside the per-step roofline accounting).
-// MI355X mapping: the same frame as the prior engine (prior.hip) - every Linear is one launch_igemm over the [N][K] weight, the
-// fp32 residual stream is updated in place by the GEMM epilogue, LayerNorm writes the next GEMM's operand, attention is the UNet's
-// flash kernel with a causal / key-validity mask.  QuickGELU is applied by a separate pass on the fp32 accumulator output of c_fc
+// MI355X mapping: the transformer engines' shared launch list and ops (xf_plan.h) - every Linear is one launch_igemm over the [N][K]
+// weight, the fp32 residual stream is updated in place by the GEMM epilogue, LayerNorm writes the next GEMM's operand, attention is the
+// UNet's flash kernel with a causal / key-validity mask.  QuickGELU is applied by a separate pass on the fp32 accumulator output of c_fc
 // (one rounding, like a fused epilogue) so that the hot GEMM kernels' epilogue is left exactly as validated.
 // Tile configurations of the transformer Linears come from the process-wide tile table like the other engines' (tuning.h): the
 // production shapes (2/4/8 sequences, 1/2 images) are in the shipped table, so nothing is timed for them and the bits are the same
@@ -25,7 +25,7 @@
 #include "elementwise.h"
 #include "../../include/k22.h"
 #include "tuning.h"
-#include "plan.h"
+#include "xf_plan.h"
 
 #include <deque>
 #include <functional>
@@ -34,40 +34,6 @@
 #include <vector>
 
 namespace {
-
-// ---- LayerNorm over the last dim of fp32 rows; optional fp32 output (may alias the input row: post-LN blocks normalise the
-// residual stream in place) and optional T output (the next GEMM's operand).  D <= 2048. -------------------------------------
-template <typename TO>
-__global__ __launch_bounds__(256) void enc_layernorm_kernel(const float* x, int64_t ldx, const float* g, const float* bta, float* yf,
-                                                            int64_t ldyf, TO* yt, int64_t ldyt, int D, float eps) {
-  __shared__ float red[8];
-  const int row = blockIdx.x, tid = threadIdx.x;
-  const float* xr = x + (int64_t)row * ldx;
-  float v[8];
-  float s = 0.f;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) { const int i = tid + k * 256; v[k] = i < D ? xr[i] : 0.f; s += v[k]; }
-  s = wave_sum(s);
-  if ((tid & 63) == 0) red[tid >> 6] = s;
-  __syncthreads();
-  const float mean = ((red[0] + red[1]) + (red[2] + red[3])) / D;
-  float q = 0.f;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) { const int i = tid + k * 256; if (i < D) { const float d = v[k] - mean; q += d * d; } }
-  q = wave_sum(q);
-  if ((tid & 63) == 0) red[4 + (tid >> 6)] = q;
-  __syncthreads();
-  const float rstd = rsqrtf(((red[4] + red[5]) + (red[6] + red[7])) / D + eps);
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const int i = tid + k * 256;
-    if (i < D) {
-      const float y = (v[k] - mean) * rstd * g[i] + bta[i];
-      if (yf != nullptr) yf[(int64_t)row * ldyf + i] = y;
-      if (yt != nullptr) yt[(int64_t)row * ldyt + i] = from_f32<TO>(y);
-    }
-  }
-}
 
 // ---- token (+ position (+ token-type)) embedding -> fp32 sequence.  xlmr: position ids as transformers'
 // create_position_ids_from_input_ids: (running count of non-padding tokens) * (token != pad) + pad_id -------------------------------
@@ -232,17 +198,6 @@ __global__ __launch_bounds__(256) void enc_attention_generic_kernel(const T* __r
 }
 
 // ---- launchers: the plan's ops and the single-kernel entry points (include/k22.h) go through the same code ------------------------------
-int launch_enc_layernorm(const float* x, int64_t ldx, const float* g, const float* b, float* yf, int64_t ldyf, void* yt, int rows, int D,
-                         float eps, int dt, hipStream_t st) {
-  if (yt != nullptr && dt == K22_BF16)
-    hipLaunchKernelGGL(enc_layernorm_kernel<bf16_t>, dim3(rows), dim3(256), 0, st, x, ldx, g, b, yf, ldyf, reinterpret_cast<bf16_t*>(yt), (int64_t)D, D, eps);
-  else if (yt != nullptr && dt == K22_F16)
-    hipLaunchKernelGGL(enc_layernorm_kernel<f16_t>, dim3(rows), dim3(256), 0, st, x, ldx, g, b, yf, ldyf, reinterpret_cast<f16_t*>(yt), (int64_t)D, D, eps);
-  else
-    hipLaunchKernelGGL(enc_layernorm_kernel<float>, dim3(rows), dim3(256), 0, st, x, ldx, g, b, yf, ldyf, reinterpret_cast<float*>(yt), (int64_t)D, D, eps);
-  K22_CHECK_LAUNCH();
-  return K22_OK;
-}
 int launch_enc_embed(const int* tok, const float* te, const float* pe, const float* ty, float* x, int B, int n, int D, int vocab, int xlmr,
                      int pad, int maxp, hipStream_t st) {
   hipLaunchKernelGGL(enc_embed_kernel, dim3(n, B), dim3(256), 0, st, tok, te, pe, ty, x, n, D, vocab, xlmr ? 1 : 0, pad, maxp);
@@ -301,36 +256,12 @@ int launch_enc_attention_generic(const void* qkv, void* out, int B, int heads, i
   return K22_OK;
 }
 
-typedef std::function<int(hipStream_t)> EOp;
 }  // namespace
 
-struct K22Encoder : GraphPlan {   // tuned: every transformer Linear; graph: the 150-300 launches of one tower pass
+struct K22Encoder : XfPlan {   // tuned: every transformer Linear; graph: the 150-300 launches of one tower pass
   K22EncoderConfig cfg;
   int B = 0;
-  std::vector<EOp> ops;
-  Slot *s_tok, *s_valid, *s_img, *s_patch, *s_pout, *s_inp, *s_ln, *s_qkv, *s_att, *s_fc, *s_fc32, *s_seq, *s_pool_in, *s_pooled, *s_splitk,
-      *s_kall, *s_vtall, *s_flush;
-
-  int run_ops(hipStream_t st) const {
-    for (auto& op : ops) { int rc = op(st); if (rc) return rc; }
-    return K22_OK;
-  }
-
-  // out = A[M][K] . W[N][K]^T + bias:  mode 0 -> T rows; 1 -> fp32 rows; 2 -> fp32 rows += (in-place residual stream)
-  void op_linear(Slot* a, int M, int N, int K, const std::string& pfx, int act, Slot* dst, int ldo, int mode) {
-    Tuned* t = tuned_linear(a, 0, M, N, K, pfx, act, dst, 0, ldo, mode, s_splitk);
-    ops.push_back([=](hipStream_t st) { return t->run(st); });
-  }
-  // LayerNorm of `rows` fp32 rows of x (stride ldx): fp32 copy into yf (may be x itself) and / or T copy into yt
-  void op_ln(Slot* x, size_t x_off, int64_t ldx, int rows, const std::string& pfx, Slot* yf, int64_t ldyf, Slot* yt) {
-    const float* g = Wf(pfx + ".weight"); const float* b = Wf(pfx + ".bias");
-    const int D = cfg.width, dt = dtype;
-    const float eps = cfg.ln_eps;
-    ops.push_back([=](hipStream_t st) {
-      const float* xp = reinterpret_cast<const float*>(ptr(x) + x_off);
-      return launch_enc_layernorm(xp, ldx, g, b, yf ? ptr<float>(yf) : nullptr, ldyf, yt ? ptr(yt) : nullptr, rows, D, eps, dt, st);
-    });
-  }
+  Slot *s_tok, *s_valid, *s_img, *s_patch, *s_pout, *s_inp, *s_ln, *s_qkv, *s_att, *s_fc, *s_fc32, *s_seq, *s_pool_in, *s_pooled;
 
   int plan(int nB) {
     const int D = cfg.width, n = cfg.n_ctx, M = nB * n, heads = cfg.heads, od = cfg.out_dim, kind = cfg.kind;
@@ -367,6 +298,7 @@ struct K22Encoder : GraphPlan {   // tuned: every transformer Linear; graph: the
     s_splitk = new_slot(256); s_kall = new_slot(); s_vtall = new_slot();
     s_flush = new_slot(autotune ? ((size_t)320 << 20) : 0);
     const int Bn = B, dt = dtype;
+    const float eps = cfg.ln_eps;
 
     // ---- input sequence ------------------------------------------------------------------------------------------------------
     if (vision) {
@@ -385,7 +317,7 @@ struct K22Encoder : GraphPlan {   // tuned: every transformer Linear; graph: the
         });
       }
       ops.push_back([=](hipStream_t st) { return launch_enc_vision_assemble(ptr<float>(s_pout), cls, pos, ptr<float>(s_inp), Bn, P, D, st); });
-      op_ln(s_inp, 0, D, M, "ln_pre", s_inp, D, nullptr);
+      op_ln(s_inp, 0, D, M, D, eps, "ln_pre", s_inp, D, nullptr);
     } else {
       const float* te = Wf("token_embedding"); const float* pe = Wf("positional_embedding");
       const float* ty = xlmr ? Wf("token_type_embedding") : nullptr;
@@ -393,61 +325,40 @@ struct K22Encoder : GraphPlan {   // tuned: every transformer Linear; graph: the
       ops.push_back([=](hipStream_t st) {
         return launch_enc_embed(ptr<int>(s_tok), te, pe, ty, ptr<float>(s_inp), Bn, n, D, vocab, xlmr ? 1 : 0, pad, maxp, st);
       });
-      if (xlmr) op_ln(s_inp, 0, D, M, "embeddings_ln", s_inp, D, s_ln);
+      if (xlmr) op_ln(s_inp, 0, D, M, D, eps, "embeddings_ln", s_inp, D, s_ln);
     }
     // ---- transformer -----------------------------------------------------------------------------------------------------------
-    const int Tkp = (n + 63) / 64 * 64;
-    if (flash) {
-      need(s_kall, (size_t)B * heads * Tkp * 64 * esz);
-      need(s_vtall, (size_t)B * heads * Tkp * 64 * esz);
-    }
     for (int l = 0; l < cfg.layers; ++l) {
       const std::string pfx = "layers." + std::to_string(l);
-      if (!xlmr) op_ln(s_inp, 0, D, M, pfx + ".ln_1", nullptr, 0, s_ln);
-      op_linear(s_ln, M, 3 * D, D, pfx + ".qkv", K22_ACT_NONE, s_qkv, 3 * D, 0);
+      if (!xlmr) op_ln(s_inp, 0, D, M, D, eps, pfx + ".ln_1", nullptr, 0, s_ln);
+      op_linear(s_ln, 0, M, 3 * D, D, pfx + ".qkv", K22_ACT_NONE, s_qkv, 0, 3 * D, 0);
       const int causal = kind == K22_ENC_CLIP_TEXT ? 1 : 0;
       const bool masked = xlmr || cfg.key_mask != 0;   // the attention_mask: XLM-R always, CLIP text (under the causal triangle) by config
-      if (!flash) {
-        ops.push_back([=](hipStream_t st) { return launch_enc_attention_generic(ptr(s_qkv), ptr(s_att), Bn, heads, n, hd, dt, st); });
-      } else
-      ops.push_back([=](hipStream_t st) {
-        KvPackParams kp;
-        kp.qkv = ptr(s_qkv); kp.ctxkv = nullptr; kp.kall = ptr(s_kall); kp.vtall = ptr(s_vtall);
-        kp.B = Bn; kp.H = heads; kp.T = n; kp.S = 0; kp.Tkp = Tkp;
-        int rc = launch_kv_pack(kp, dt, st);
-        if (rc) return rc;
-        AttentionParams ap = {};
-        ap.q = ptr(s_qkv); ap.ldq = 3 * D; ap.kall = ptr(s_kall); ap.vtall = ptr(s_vtall); ap.out = ptr(s_att); ap.ldo = D;
-        ap.B = Bn; ap.H = heads; ap.T = n; ap.Tk = n; ap.Tkp = Tkp; ap.scale = 0.125f;
-        ap.causal = causal;
-        if (masked) { ap.key_valid = ptr<float>(s_valid); ap.kv_ld = n; ap.kv_n = n; }
-        return launch_attention(ap, dt, st);
-      });
-      op_linear(s_att, M, D, D, pfx + ".proj", K22_ACT_NONE, s_inp, D, 2);
+      if (!flash) ops.push_back([=](hipStream_t st) { return launch_enc_attention_generic(ptr(s_qkv), ptr(s_att), Bn, heads, n, hd, dt, st); });
+      else op_flash_self_attention(s_qkv, s_att, B, heads, n, D, causal, masked ? s_valid : nullptr, n, n);
+      op_linear(s_att, 0, M, D, D, pfx + ".proj", K22_ACT_NONE, s_inp, 0, D, 2);
       if (xlmr) {
         // BertSelfOutput: LayerNorm(dense(attn) + x);  BertIntermediate: GELU(dense);  BertOutput: LayerNorm(dense(h) + x)
-        op_ln(s_inp, 0, D, M, pfx + ".ln_1", s_inp, D, s_ln);
-        op_linear(s_ln, M, F, D, pfx + ".fc", K22_ACT_GELU, s_fc, F, 0);
-        op_linear(s_fc, M, D, F, pfx + ".out", K22_ACT_NONE, s_inp, D, 2);
-        op_ln(s_inp, 0, D, M, pfx + ".ln_2", s_inp, D, l + 1 < cfg.layers ? s_ln : nullptr);
+        op_ln(s_inp, 0, D, M, D, eps, pfx + ".ln_1", s_inp, D, s_ln);
+        op_linear(s_ln, 0, M, F, D, pfx + ".fc", K22_ACT_GELU, s_fc, 0, F, 0);
+        op_linear(s_fc, 0, M, D, F, pfx + ".out", K22_ACT_NONE, s_inp, 0, D, 2);
+        op_ln(s_inp, 0, D, M, D, eps, pfx + ".ln_2", s_inp, D, l + 1 < cfg.layers ? s_ln : nullptr);
       } else {
-        op_ln(s_inp, 0, D, M, pfx + ".ln_2", nullptr, 0, s_ln);
-        op_linear(s_ln, M, F, D, pfx + ".fc", K22_ACT_NONE, s_fc32, F, 1);
+        op_ln(s_inp, 0, D, M, D, eps, pfx + ".ln_2", nullptr, 0, s_ln);
+        op_linear(s_ln, 0, M, F, D, pfx + ".fc", K22_ACT_NONE, s_fc32, 0, F, 1);
         const int64_t nel = (int64_t)M * F;
         const int exact = cfg.hidden_act == 1 ? 1 : 0;
         ops.push_back([=](hipStream_t st) { return launch_enc_mlp_act(ptr<float>(s_fc32), ptr(s_fc), nel, exact, dt, st); });
-        op_linear(s_fc, M, D, F, pfx + ".out", K22_ACT_NONE, s_inp, D, 2);
+        op_linear(s_fc, 0, M, D, F, pfx + ".out", K22_ACT_NONE, s_inp, 0, D, 2);
       }
     }
     // ---- heads ---------------------------------------------------------------------------------------------------------------
-    const void* hw = W_("head.weight");
-    const float* hb = xlmr ? Wf("head.bias") : nullptr;
     if (kind == K22_ENC_CLIP_TEXT) {
-      op_ln(s_inp, 0, D, M, "ln_final", s_seq, D, nullptr);
+      op_ln(s_inp, 0, D, M, D, eps, "ln_final", s_seq, D, nullptr);
       const int eos = cfg.eos_id;
       ops.push_back([=](hipStream_t st) { return launch_enc_gather_eot(ptr<int>(s_tok), ptr<float>(s_seq), ptr<float>(s_pool_in), Bn, n, D, eos, st); });
     } else if (vision) {
-      op_ln(s_inp, 0, (int64_t)n * D, B, "ln_post", s_pool_in, D, nullptr);      // class-token rows only
+      op_ln(s_inp, 0, (int64_t)n * D, B, D, eps, "ln_post", s_pool_in, D, nullptr);      // class-token rows only
     } else {
       ops.push_back([=](hipStream_t st) {
         hipError_t e = hipMemcpyAsync(ptr(s_seq), ptr(s_inp), (size_t)M * D * 4, hipMemcpyDeviceToDevice, st);
@@ -455,12 +366,7 @@ struct K22Encoder : GraphPlan {   // tuned: every transformer Linear; graph: the
         return launch_enc_masked_mean(ptr<float>(s_inp), ptr<float>(s_valid), ptr<float>(s_pool_in), Bn, n, D, st);
       });
     }
-    ops.push_back([=](hipStream_t st) {
-      LinearSmallParams lp = {};
-      lp.x = ptr<float>(s_pool_in); lp.ldx = D; lp.W = hw; lp.bias = hb; lp.out = ptr<float>(s_pooled); lp.ldo = od;
-      lp.M = Bn; lp.N = od; lp.K = D; lp.act_in = K22_ACT_NONE; lp.act_out = K22_ACT_NONE;
-      return launch_linear_smallm(lp, K22_F32, st);
-    });
+    op_linear_small(s_pool_in, D, B, od, D, "head", xlmr, K22_ACT_NONE, s_pooled, 0, od);
     return finish_plan();
   }
 };
@@ -504,8 +410,7 @@ int k22_encoder_forward(K22Encoder* m, const int* tokens, const float* key_valid
   if (vision) { if (int rc = copy_d2d(m->ptr(m->s_img), image, (size_t)m->B * 3 * c.image_size * c.image_size * 4, st)) return rc; }
   else { if (int rc = copy_d2d(m->ptr(m->s_tok), tokens, M * 4, st)) return rc; }
   if (masked) { if (int rc = copy_d2d(m->ptr(m->s_valid), key_valid, M * 4, st)) return rc; }
-  if (int rc = m->tune_once(m->s_flush, st)) return rc;
-  if (int rc = m->replay(m->graph, st, [m](hipStream_t s) { return m->run_ops(s); })) return rc;
+  if (int rc = m->forward_list(st)) return rc;
   if (seq_out) { if (int rc = copy_d2d(seq_out, m->ptr(m->s_seq), M * c.width * 4, st)) return rc; }
   return copy_d2d(pooled_out, m->ptr(m->s_pooled), (size_t)m->B * c.out_dim * 4, st);
 }
@@ -518,7 +423,7 @@ int k22_enc_layernorm(const float* x, long ldx, const float* gain, const float* 
   if (!x || !gain || !beta || (!out_f32 && !out_t) || rows < 1 || D < 1 || ldx < D || (out_f32 && ld_out < D) || !aux_dtype_ok(dtype))
     return k22_set_error(K22_EINVAL, "enc_layernorm: bad argument");
   if (D > 2048) return k22_set_error(K22_EINVAL, "enc_layernorm: D <= 2048 (8 x 256 values per row)");
-  return launch_enc_layernorm(x, ldx, gain, beta, out_f32, ld_out, out_t, rows, D, eps, dtype, reinterpret_cast<hipStream_t>(stream));
+  return launch_layernorm_rows(x, ldx, gain, beta, out_f32, ld_out, out_t, rows, D, eps, dtype, reinterpret_cast<hipStream_t>(stream));
 }
 int k22_enc_embed(const int* tokens, const float* tok_emb, const float* pos_emb, const float* type_emb, float* x, int B, int n_ctx, int D,
                   int vocab, int xlmr, int pad_id, int max_pos, void* stream) {

@@ -248,11 +248,8 @@ struct K22UNet : GraphPlan {   // dtype: arithmetic type of the MFMA kernels (K2
   // i.e. a parallel branch of the captured graph joined by the first FiLM consumer, was measured on one box, alternating
   // runs: 116.9 / 117.2 steps/s with the branch against 119.4 / 119.1 without - the 231 MB weight stream slows the
   // convolutions it runs beside by more than the 80 us it hides.  Removed.)
-  int run_ops_range(hipStream_t st, size_t lo, size_t hi) {
-    for (size_t i = lo; i < hi && i < ops.size(); ++i) { int rc = ops[i](st); if (rc) return rc; }
-    return K22_OK;
-  }
-  int run_ops(hipStream_t st) { return run_ops_range(st, 0, ops.size()); }
+  int run_ops_range(hipStream_t st, size_t lo, size_t hi) { return run_list(ops, st, lo, hi); }
+  int run_ops(hipStream_t st) { return run_list(ops, st); }
 
   // ------------------------------------------------------------------------------------------
   void op_gn(OpList& L, const Act& in, const std::string& pfx, int64_t film_off,

@@ -321,7 +321,7 @@ int k22_movq_decode(K22MoVQ* m, const float* z, float* out, unsigned char* out_u
   if (!z || (!out && !out_u8)) return k22_set_error(K22_EINVAL, "movq_decode: null argument");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (int rc = copy_d2d(m->ptr(m->s_z), z, (size_t)m->B * 4 * m->h0 * m->w0 * 4, st)) return rc;
-  for (auto& op : m->ops) { int rc = op(st); if (rc) return rc; }
+  if (int rc = run_list(m->ops, st)) return rc;
   const int H8 = m->h0 << (m->cfg.n_levels - 1), W8 = m->w0 << (m->cfg.n_levels - 1);
   if (out) { if (int rc = copy_d2d(out, m->ptr(m->s_out), (size_t)m->B * m->cfg.out_ch * H8 * W8 * 4, st)) return rc; }
   if (out_u8) return launch_to_uint8_nhwc(m->ptr<float>(m->s_out), out_u8, m->B, m->cfg.out_ch, H8, W8, st);
@@ -339,7 +339,7 @@ int k22_movq_encode(K22MoVQ* m, const float* image, float* latent, void* stream)
   if (!image || !latent) return k22_set_error(K22_EINVAL, "movq_encode: null argument");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (int rc = copy_d2d(m->ptr(m->s_img), image, (size_t)m->B * 3 * m->encH * m->encW * 4, st)) return rc;
-  for (auto& op : m->ops) { int rc = op(st); if (rc) return rc; }
+  if (int rc = run_list(m->ops, st)) return rc;
   return copy_d2d(latent, m->ptr(m->s_lat), (size_t)m->B * 4 * m->h0 * m->w0 * 4, st);
 }
 int k22_movq_num_ops(const K22MoVQ* m) { return m && m->planned ? (int)m->ops.size() : 0; }

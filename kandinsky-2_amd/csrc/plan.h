@@ -33,6 +33,12 @@ inline int env_flag(const char* name, int dflt) {
   return e ? (atoi(e) != 0) : dflt;
 }
 
+// A launch list (callables taking the stream) in order, entries [lo, hi) of it; the first failing entry ends the run.
+template <typename List> int run_list(const List& ops, hipStream_t st, size_t lo = 0, size_t hi = (size_t)-1) {
+  for (size_t i = lo; i < hi && i < ops.size(); ++i) { if (int rc = ops[i](st)) return rc; }
+  return K22_OK;
+}
+
 struct PlanBase {
   int dtype = 0;     // K22DType of the arithmetic
   size_t esz = 0;    // bytes per stored activation element

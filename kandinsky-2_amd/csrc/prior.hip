@@ -6,15 +6,15 @@
 // START_X mean, FIXED_SMALL variance, denoised_fn clamp, gaussian_diffusion.py:223-322, 352-382).
 //
 // MI355X mapping: the transformer is weight-streaming bound (2.0 GB of bf16 weights per forward for 162 token rows at
-// bs = 1), so every Linear is one launch_igemm over the [N][K] weight exactly as the reference stores it, the fp32
-// residual stream is updated in place by the GEMM epilogue (res_f32), LayerNorm writes the GEMM's T operand, and
-// the 81-token attention runs one workgroup per (batch, head) out of LDS.  c_qkv rows are packed as Q | K | V planes
+// bs = 1).  Its launch list and the ops of the plain path (Linear, LayerNorm, flash self-attention, the small fp32 Linears) are the
+// transformer engines' shared ones (xf_plan.h); 16-bit engines run the blocks through the skinny path below instead, with the
+// 81-token attention as one workgroup per (batch, head) out of LDS.  c_qkv rows are packed as Q | K | V planes
 // (the reference keeps per-head [q|k|v] interleaved, prior.py:93-95).
 #include "kernels.h"
 #include "elementwise.h"
 #include "../../include/k22.h"
 #include "tuning.h"
-#include "plan.h"
+#include "xf_plan.h"
 #include "skinny.h"
 
 #include <algorithm>
@@ -23,28 +23,6 @@
 #include <string>
 #include <unordered_map>
 #include <vector>
-
-// ---- LayerNorm over the last dim: fp32 rows (stride ldx) -> T or fp32 rows -----------------------------------
-template <typename TO>
-__global__ __launch_bounds__(256) void prior_layernorm_kernel(const float* x, int64_t ldx, const float* g, const float* bta,
-                                                              TO* y, int64_t ldy, int D, float eps) {
-  __shared__ float red[8];
-  const int row = blockIdx.x, tid = threadIdx.x;
-  const float* xr = x + (int64_t)row * ldx;
-  float s = 0.f;
-  for (int i = tid; i < D; i += 256) s += xr[i];
-  s = wave_sum(s);
-  if ((tid & 63) == 0) red[tid >> 6] = s;
-  __syncthreads();
-  const float mean = ((red[0] + red[1]) + (red[2] + red[3])) / D;
-  float q = 0.f;
-  for (int i = tid; i < D; i += 256) { const float d = xr[i] - mean; q += d * d; }
-  q = wave_sum(q);
-  if ((tid & 63) == 0) red[4 + (tid >> 6)] = q;
-  __syncthreads();
-  const float rstd = rsqrtf(((red[4] + red[5]) + (red[6] + red[7])) / D + eps);
-  for (int i = tid; i < D; i += 256) y[(int64_t)row * ldy + i] = from_f32<TO>((xr[i] - mean) * rstd * g[i] + bta[i]);
-}
 
 // ---- input sequence: rows 0..n_text-1 / n_text / n_text+1 / n_text+2 were written by the projections; add the
 // positional embedding everywhere and put prd_emb in the last row (prior.py:248-256) -----------------------------
@@ -91,15 +69,6 @@ __global__ void prior_ddim_step_kernel(const float* x, const float* model_out, c
 }
 
 // ---- launchers: the plan's ops and the single-kernel entry points (include/k22.h) go through the same code ------------------
-static int launch_prior_layernorm(const float* x, int64_t ldx, const float* g, const float* b, void* y, int rows, int D, bool to_f32, int dt,
-                                  hipStream_t st) {
-  if (to_f32) hipLaunchKernelGGL(prior_layernorm_kernel<float>, dim3(rows), dim3(256), 0, st, x, ldx, g, b, reinterpret_cast<float*>(y), (int64_t)D, D, 1e-5f);
-  else if (dt == K22_BF16) hipLaunchKernelGGL(prior_layernorm_kernel<bf16_t>, dim3(rows), dim3(256), 0, st, x, ldx, g, b, reinterpret_cast<bf16_t*>(y), (int64_t)D, D, 1e-5f);
-  else if (dt == K22_F16) hipLaunchKernelGGL(prior_layernorm_kernel<f16_t>, dim3(rows), dim3(256), 0, st, x, ldx, g, b, reinterpret_cast<f16_t*>(y), (int64_t)D, D, 1e-5f);
-  else hipLaunchKernelGGL(prior_layernorm_kernel<float>, dim3(rows), dim3(256), 0, st, x, ldx, g, b, reinterpret_cast<float*>(y), (int64_t)D, D, 1e-5f);
-  K22_CHECK_LAUNCH();
-  return K22_OK;
-}
 static int launch_prior_finish_input(float* inp, const float* pos, const float* prd, int B, int n_ctx, int D, hipStream_t st) {
   hipLaunchKernelGGL(prior_finish_input_kernel, dim3(256), dim3(256), 0, st, inp, pos, prd, B, n_ctx, D);
   K22_CHECK_LAUNCH();
@@ -118,16 +87,11 @@ static int launch_prior_ddim_step(const float* x, const float* model_out, const 
   return K22_OK;
 }
 
-namespace {
-typedef std::function<int(hipStream_t)> POp;
-}  // namespace
-
-struct K22Prior : GraphPlan {   // tuned: every transformer Linear; graph: the ~250 launches of one forward
+struct K22Prior : XfPlan {   // tuned: every transformer Linear; graph: the ~250 launches of one forward
   K22PriorConfig cfg;
   int B = 0;
-  std::vector<POp> ops;
   Slot *s_x, *s_t, *s_temb, *s_te1, *s_txtemb, *s_txtenc, *s_txtencT, *s_valid, *s_mask, *s_inp, *s_ln, *s_qkv, *s_att, *s_fc,
-      *s_lnlast, *s_out, *s_splitk, *s_flush, *s_kall, *s_vtall;
+      *s_lnlast, *s_out;
   // skinny path (round 6; skinny.hip): 16-bit engines run the transformer through the fragment-major weight-streaming GEMM, the fused
   // split-K finish + LayerNorm and the small-T attention: 7 launches per layer instead of 12.  K22_PRIOR_SKINNY=0 keeps the old path.
   bool skinny = false;
@@ -146,26 +110,6 @@ struct K22Prior : GraphPlan {   // tuned: every transformer Linear; graph: the ~
     }
     wfrag_done = true;
     return K22_OK;
-  }
-
-  int run_ops(hipStream_t st) const {
-    for (auto& op : ops) { int rc = op(st); if (rc) return rc; }
-    return K22_OK;
-  }
-
-  // out (+)= A[M][K] . W[N][K]^T + bias; A is T; out T, or fp32 with an fp32 residual (in-place residual stream)
-  void op_linear(Slot* a, size_t a_off, int M, int N, int K, const std::string& pfx, int act, Slot* dst, size_t dst_off, int ldo,
-                 bool f32_out_residual) {
-    Tuned* t = tuned_linear(a, a_off, M, N, K, pfx, act, dst, dst_off, ldo, f32_out_residual ? 2 : 0, s_splitk);
-    ops.push_back([=](hipStream_t st) { return t->run(st); });
-  }
-  void op_ln(Slot* x, size_t x_off, int64_t ldx, int rows, const std::string& pfx, Slot* y, bool to_f32) {
-    const float* g = Wf(pfx + ".weight"); const float* b = Wf(pfx + ".bias");
-    const int D = cfg.xf_width, dt = dtype;
-    ops.push_back([=](hipStream_t st) {
-      const float* xp = reinterpret_cast<const float*>(ptr(x) + x_off);
-      return launch_prior_layernorm(xp, ldx, g, b, ptr(y), rows, D, to_f32, dt, st);
-    });
   }
 
   // fragment-major copy of a transformer weight [Npad][K] (slot in the workspace, repacked at the first forward after a bind)
@@ -207,6 +151,7 @@ struct K22Prior : GraphPlan {   // tuned: every transformer Linear; graph: the ~
     const int D = cfg.xf_width, nt = cfg.text_ctx, nc = nt + 4, cd = cfg.clip_dim, cw = cfg.clip_xf_width, M = nB * nc;
     if (nB < 1 || nB > 8) return k22_set_error(K22_EINVAL, "prior: batch (2*bs) must be in 1..8 per engine call");
     if (D % 64 || D / cfg.xf_heads != 64) return k22_set_error(K22_EINVAL, "prior: 64 channels per head");
+    if (D > 2048) return k22_set_error(K22_EINVAL, "prior: xf_width <= 2048 (LayerNorm keeps a row in 8 x 256 registers)");
     begin_plan();
     B = nB;
     ops.clear(); wfrags.clear(); wfrag_done = false; loop.drop();
@@ -227,30 +172,13 @@ struct K22Prior : GraphPlan {   // tuned: every transformer Linear; graph: the ~
     // ---- input sequence (prior.py:238-256) ----------------------------------------------------------------
     {
       const float* freqs = Wf("time_freqs");
-      const float* w0 = Wf("time_embed.0.weight"); const float* b0 = Wf("time_embed.0.bias");
-      const float* w2 = Wf("time_embed.2.weight"); const float* b2 = Wf("time_embed.2.bias");
-      const float* wte = Wf("text_emb_proj.weight"); const float* bte = Wf("text_emb_proj.bias");
-      const float* wci = Wf("clip_img_proj.weight"); const float* bci = Wf("clip_img_proj.bias");
-      ops.push_back([=](hipStream_t st) {
-        int rc = launch_timestep_embedding(ptr<float>(s_t), freqs, ptr<float>(s_temb), Bn, D / 2, st);
-        if (rc) return rc;
-        LinearSmallParams lp = {};
-        lp.x = ptr<float>(s_temb); lp.ldx = D; lp.W = w0; lp.bias = b0; lp.out = ptr<float>(s_te1); lp.ldo = D;
-        lp.M = Bn; lp.N = D; lp.K = D; lp.act_in = K22_ACT_NONE; lp.act_out = K22_ACT_SILU;
-        rc = launch_linear_smallm(lp, K22_F32, st);
-        if (rc) return rc;
-        float* inp = ptr<float>(s_inp);
-        lp.x = ptr<float>(s_te1); lp.W = w2; lp.bias = b2; lp.out = inp + (size_t)(nt + 1) * D; lp.ldo = (int64_t)nc * D; lp.act_out = K22_ACT_NONE;
-        rc = launch_linear_smallm(lp, K22_F32, st);                                   // t_emb -> row n_text+1
-        if (rc) return rc;
-        lp.x = ptr<float>(s_txtemb); lp.ldx = cd; lp.K = cd; lp.W = wte; lp.bias = bte; lp.out = inp + (size_t)nt * D;
-        rc = launch_linear_smallm(lp, K22_F32, st);                                   // text_emb -> row n_text
-        if (rc) return rc;
-        lp.x = ptr<float>(s_x); lp.W = wci; lp.bias = bci; lp.out = inp + (size_t)(nt + 2) * D;
-        rc = launch_linear_smallm(lp, K22_F32, st);                                   // clip_img_proj(x) -> row n_text+2
-        if (rc) return rc;
-        return launch_cast_rows(ptr<float>(s_txtenc), ptr(s_txtencT), Bn * nt, cw, cw, cw, dt, st);
-      });
+      ops.push_back([=](hipStream_t st) { return launch_timestep_embedding(ptr<float>(s_t), freqs, ptr<float>(s_temb), Bn, D / 2, st); });
+      const int64_t ldseq = (int64_t)nc * D;   // row n_text + k of every sequence of s_inp: one row per batch element
+      op_linear_small(s_temb, D, B, D, D, "time_embed.0", true, K22_ACT_SILU, s_te1, 0, D);
+      op_linear_small(s_te1, D, B, D, D, "time_embed.2", true, K22_ACT_NONE, s_inp, (size_t)(nt + 1) * D * 4, ldseq);   // t_emb -> row n_text+1
+      op_linear_small(s_txtemb, cd, B, D, cd, "text_emb_proj", true, K22_ACT_NONE, s_inp, (size_t)nt * D * 4, ldseq);    // text_emb -> row n_text
+      op_linear_small(s_x, cd, B, D, cd, "clip_img_proj", true, K22_ACT_NONE, s_inp, (size_t)(nt + 2) * D * 4, ldseq);   // clip_img_proj(x) -> row n_text+2
+      ops.push_back([=](hipStream_t st) { return launch_cast_rows(ptr<float>(s_txtenc), ptr(s_txtencT), Bn * nt, cw, cw, cw, dt, st); });
       // text_enc_proj: one GEMM per batch element straight into rows 0..n_text-1 of the sequence (fp32 out)
       for (int b = 0; b < B; ++b) {
         IgemmParams p = igemm_gemm_problem(nt, D, cw, 0, IG_OUT_ROWMAJOR_F32);
@@ -297,33 +225,19 @@ struct K22Prior : GraphPlan {   // tuned: every transformer Linear; graph: the ~
     } else
     for (int l = 0; l < cfg.xf_layers; ++l) {
       const std::string pfx = "transformer.resblocks." + std::to_string(l);
-      op_ln(s_inp, 0, D, M, pfx + ".ln_1", s_ln, false);
-      op_linear(s_ln, 0, M, 3 * D, D, pfx + ".attn.c_qkv", K22_ACT_NONE, s_qkv, 0, 3 * D, false);
+      op_ln(s_inp, 0, D, M, D, 1e-5f, pfx + ".ln_1", nullptr, 0, s_ln);
+      op_linear(s_ln, 0, M, 3 * D, D, pfx + ".attn.c_qkv", K22_ACT_NONE, s_qkv, 0, 3 * D, 0);
       // attention: the UNet's flash kernel (attention.hip) with the prior's mask (prior.py:262-263) — the additive
       // mask is -inf exactly for padding keys and for keys after the query, the 4 extra positions are always valid
-      const int heads = cfg.xf_heads, Tkp = (nc + 63) / 64 * 64;
-      need(s_kall, (size_t)B * heads * Tkp * 64 * esz);
-      need(s_vtall, (size_t)B * heads * Tkp * 64 * esz);
-      ops.push_back([=](hipStream_t st) {
-        KvPackParams kp;
-        kp.qkv = ptr(s_qkv); kp.ctxkv = nullptr; kp.kall = ptr(s_kall); kp.vtall = ptr(s_vtall);
-        kp.B = Bn; kp.H = heads; kp.T = nc; kp.S = 0; kp.Tkp = Tkp;
-        int rc = launch_kv_pack(kp, dt, st);
-        if (rc) return rc;
-        AttentionParams ap = {};
-        ap.q = ptr(s_qkv); ap.ldq = 3 * D; ap.kall = ptr(s_kall); ap.vtall = ptr(s_vtall); ap.out = ptr(s_att); ap.ldo = D;
-        ap.B = Bn; ap.H = heads; ap.T = nc; ap.Tk = nc; ap.Tkp = Tkp; ap.scale = 0.125f;
-        ap.causal = 1; ap.key_valid = ptr<float>(s_valid); ap.kv_ld = nt; ap.kv_n = nt;
-        return launch_attention(ap, dt, st);
-      });
-      op_linear(s_att, 0, M, D, D, pfx + ".attn.c_proj", K22_ACT_NONE, s_inp, 0, D, true);
-      op_ln(s_inp, 0, D, M, pfx + ".ln_2", s_ln, false);
-      op_linear(s_ln, 0, M, 4 * D, D, pfx + ".mlp.c_fc", K22_ACT_GELU, s_fc, 0, 4 * D, false);
-      op_linear(s_fc, 0, M, D, 4 * D, pfx + ".mlp.c_proj", K22_ACT_NONE, s_inp, 0, D, true);
+      op_flash_self_attention(s_qkv, s_att, B, cfg.xf_heads, nc, D, 1, s_valid, nt, nt);
+      op_linear(s_att, 0, M, D, D, pfx + ".attn.c_proj", K22_ACT_NONE, s_inp, 0, D, 2);
+      op_ln(s_inp, 0, D, M, D, 1e-5f, pfx + ".ln_2", nullptr, 0, s_ln);
+      op_linear(s_ln, 0, M, 4 * D, D, pfx + ".mlp.c_fc", K22_ACT_GELU, s_fc, 0, 4 * D, 0);
+      op_linear(s_fc, 0, M, D, 4 * D, pfx + ".mlp.c_proj", K22_ACT_NONE, s_inp, 0, D, 2);
     }
     // ---- final_ln on the last token + out_proj (prior.py:266-269) -------------------------------------------
     if (cfg.xf_final_ln) {
-      op_ln(s_inp, (size_t)(nc - 1) * D * 4, (int64_t)nc * D, B, "final_ln", s_lnlast, true);
+      op_ln(s_inp, (size_t)(nc - 1) * D * 4, (int64_t)nc * D, B, D, 1e-5f, "final_ln", s_lnlast, D, nullptr);
     } else {
       ops.push_back([=](hipStream_t st) {
         hipError_t e = hipMemcpy2DAsync(ptr(s_lnlast), (size_t)D * 4, ptr(s_inp) + (size_t)(nc - 1) * D * 4, (size_t)nc * D * 4, (size_t)D * 4, Bn,
@@ -331,15 +245,7 @@ struct K22Prior : GraphPlan {   // tuned: every transformer Linear; graph: the ~
         return e == hipSuccess ? K22_OK : k22_set_error_hip(e, __FILE__, __LINE__);
       });
     }
-    {
-      const float* wo = Wf("out_proj.weight"); const float* bo = Wf("out_proj.bias");
-      ops.push_back([=](hipStream_t st) {
-        LinearSmallParams lp = {};
-        lp.x = ptr<float>(s_lnlast); lp.ldx = D; lp.W = wo; lp.bias = bo; lp.out = ptr<float>(s_out); lp.ldo = cd;
-        lp.M = Bn; lp.N = cd; lp.K = D; lp.act_in = K22_ACT_NONE; lp.act_out = K22_ACT_NONE;
-        return launch_linear_smallm(lp, K22_F32, st);
-      });
-    }
+    op_linear_small(s_lnlast, D, B, cd, D, "out_proj", true, K22_ACT_NONE, s_out, 0, cd);
     return finish_plan();
   }
 };
@@ -388,8 +294,7 @@ int k22_prior_forward(K22Prior* m, const float* x, const float* timesteps, const
   if (int rc = copy_d2d(m->ptr(m->s_txtenc), text_enc, (size_t)m->B * c.text_ctx * c.clip_xf_width * 4, st)) return rc;
   if (int rc = copy_d2d(m->ptr(m->s_valid), key_valid, (size_t)m->B * c.text_ctx * 4, st)) return rc;
   if (int rc = m->repack_once(st)) return rc;
-  if (int rc = m->tune_once(m->s_flush, st)) return rc;
-  if (int rc = m->replay(m->graph, st, [m](hipStream_t s) { return m->run_ops(s); })) return rc;
+  if (int rc = m->forward_list(st)) return rc;
   return copy_d2d(out, m->ptr(m->s_out), (size_t)m->B * c.clip_dim * 4, st);
 }
 
@@ -434,12 +339,7 @@ int k22_prior_sample_loop(K22Prior* m, int kind, float* x, float* x_tmp, float* 
     return copy_d2d(m->ptr(m->s_t), timesteps + (size_t)k * B, (size_t)B * 4, s);
   };
   if (int rc = m->repack_once(st)) return rc;
-  if ((m->autotune && !m->tuned_done) || !m->warmed) {   // first use of this plan: measure, then one eager pass of the launch list (as k22_prior_forward)
-    if (int rc = conditioning(st)) return rc;
-    if (int rc = model_input(x, 0, st)) return rc;
-    if (int rc = m->tune_once(m->s_flush, st)) return rc;
-    if (!m->warmed) { if (int rc = m->run_eager(st, [m](hipStream_t s) { return m->run_ops(s); })) return rc; }
-  }
+  if (int rc = m->first_use(st, [&](hipStream_t s) -> int { if (int rc = conditioning(s)) return rc; return model_input(x, 0, s); })) return rc;
   auto body = [&](hipStream_t s) -> int {
     if (int rc = conditioning(s)) return rc;
     float* cur = x; float* nxt = x_tmp;
@@ -467,7 +367,9 @@ int k22_prior_layernorm(const float* x, long ldx, const float* gain, const float
                         void* stream) {
   if (!x || !gain || !beta || !y || rows < 1 || D < 1 || ldx < D || (dtype != K22_BF16 && dtype != K22_F16 && dtype != K22_F32))
     return k22_set_error(K22_EINVAL, "prior_layernorm: bad argument");
-  return launch_prior_layernorm(x, ldx, gain, beta, y, rows, D, to_f32 != 0, dtype, reinterpret_cast<hipStream_t>(stream));
+  if (D > 2048) return k22_set_error(K22_EINVAL, "prior_layernorm: D <= 2048 (8 x 256 values per row)");
+  return launch_layernorm_rows(x, ldx, gain, beta, to_f32 ? reinterpret_cast<float*>(y) : nullptr, D, to_f32 ? nullptr : y, rows, D, 1e-5f, dtype,
+                               reinterpret_cast<hipStream_t>(stream));
 }
 int k22_prior_finish_input(float* inp, const float* pos, const float* prd, int B, int n_ctx, int D, void* stream) {
   if (!inp || !pos || !prd || B < 1 || n_ctx < 1 || D < 1) return k22_set_error(K22_EINVAL, "prior_finish_input: bad argument");

@@ -284,6 +284,53 @@ def test_prior_layernorm(dtype):
               f"c = {ar.AUX_C['layernorm']}), largest |out - ref| / bound = {max(w for _, w in ys):.3f}")
 
 
+@pytest.mark.parametrize("dtype", DTYPES, ids=DT_IDS)
+def test_layernorm_entries_are_one_kernel(dtype):
+    """k22_prior_layernorm is an argument mapping onto the kernel k22_enc_layernorm launches (strides, eps = 1e-5, which output): equal bits"""
+    T, R = hp.tdt(dtype), ar.LN_ROWS
+    for D in ar.PRIOR_LN_D:
+        for ld_mult in (1, 3):
+            d = ar.to_dev(ar.layernorm_inputs(D, ld_mult), DEV)
+            ldx = ld_mult * D
+            x, g, b = d["x"].clone(), d["g"], d["b"]
+            for to_f32 in (0, 1):
+                TO = torch.float32 if to_f32 else T
+                pbuf, pout = guarded((R, D), TO)
+                ebuf, eout = guarded((R, D), TO)
+                assert L().k22_prior_layernorm(x[1].data_ptr(), ldx, g.data_ptr(), b.data_ptr(), pout.data_ptr(), R, D, to_f32, dtype, hp.stream()) == 0
+                f_ptr, t_ptr = (eout.data_ptr(), None) if to_f32 else (None, eout.data_ptr())
+                assert L().k22_enc_layernorm(x[1].data_ptr(), ldx, g.data_ptr(), b.data_ptr(), f_ptr, D, t_ptr, R, D, 1e-5, dtype, hp.stream()) == 0
+                sync()
+                assert torch.equal(x, d["x"]), (D, ld_mult, to_f32)
+                assert bool(torch.isfinite(pout.float()).all()), (D, ld_mult, to_f32)
+                assert check_exact(pbuf, eout) == 0, (D, ld_mult, to_f32)       # the prior entry's bits and its guards
+                assert check_exact(ebuf, pout) == 0, (D, ld_mult, to_f32)       # the encoder entry's guards
+
+
+def test_prior_layernorm_width_is_bounded():
+    """the shared kernel holds 8 x 256 values of a row: the prior's entry and its plan refuse anything wider, as the towers' do"""
+    import ctypes as C
+    from kandinsky2_amd import prior as kp
+    x = torch.zeros(2, 2112, device=DEV)
+    for dtype in DTYPES:
+        assert L().k22_prior_layernorm(x.data_ptr(), 2112, x.data_ptr(), x.data_ptr(), x.data_ptr(), 1, 2112, 1, dtype, hp.stream()) == _EINVAL
+        assert b"2048" in L().k22_last_error()
+    wide = _lib.K22PriorConfig(dtype=_lib.K22_BF16, text_ctx=77, xf_width=2112, xf_layers=4, xf_heads=33, xf_final_ln=1, clip_dim=768, clip_xf_width=768)
+    h, n = C.c_void_p(), C.c_size_t()
+    assert L().k22_prior_create(C.byref(wide), None, 0, C.byref(h)) == 0
+    try:
+        assert L().k22_prior_plan(h, 2, C.byref(n)) == _EINVAL
+        assert b"2048" in L().k22_last_error()
+    finally:
+        L().k22_prior_destroy(h)
+    # the configuration is fixed at create: the tiny one is its own handle, refused for its batch first (a refusal leaves a handle usable)
+    m = kp.PriorDiffusionModelHIP(kp.tiny_prior_hparams(), backend_dtype=torch.bfloat16).to(DEV).prepare()
+    e = m._engines["prior"]
+    assert L().k22_prior_plan(e.handle, 9, C.byref(n)) == _EINVAL
+    e.plan(2)
+    assert e.plan_key == (2,) and e.ws is not None
+
+
 # ---- encoder helpers ----------------------------------------------------------------------------------------------------------------
 def test_enc_embed_exact():
     for (name, D, xlmr, max_pos, tok) in ar.embed_cases():
