@@ -758,6 +758,37 @@ int k22_gn_coeff(const float* st0, int rpi0, int C0, const float* st1, int rpi1,
                  const float* film, long film_ld, float eps, float* coeff, void* stream);
 int k22_gn_apply(const void* x0, const void* x1, int C0, int C1, int B, int H, int W, const float* coeff, int act, int mode, int pad, void* out,
                  int dtype, void* stream);
+/* The kernels that open and close a UNet step, one per entry (csrc/elementwise.hip, csrc/sampler.hip; tests/test_seam_kernels_gpu.py,
+ * tests/seam_ref.py), each through the launcher named with it.  k22_ddim_step / k22_plms_step above belong to the same surface.  K22_EINVAL
+ * with nothing launched: a null required argument, a non-positive size, and what each line names.
+ *   conv_in            launch_conv_in (K22UNet::plan, the stem op): out T NHWC [B][H][W][Cout] = conv3x3(pad 1) of the fp32 NCHW input
+ *                      [x (4) | img (4) | mask (1)] + bias; w_packed fp32 [Cin * 9][Cout] (pack.py: pack_stem), Cin 4 | 8 | 9; channels 4-7
+ *                      are img (img_premul != 0) or img * mask, channel 8 the mask [B][1][H][W].  Refused: another Cin, Cin = 9 without img
+ *                      and mask, Cin = 8 without img, img_premul = 0 without mask
+ *   timestep_embedding launch_timestep_embedding (K22UNet::time_rows; the prior's plan): out [rows][2 half] = [cos(t f) | sin(t f)], the
+ *                      argument t[r] * freqs[k] formed in fp32
+ *   linear_smallm_ld   launch_linear_smallm with every field of LinearSmallParams (K22UNet::time_rows: rows = steps x B, add_mod = B,
+ *                      ldo = film_total; build_cond_ops / build_cond_ops_22): out[m * ldo + n] = act_out(sum_k act_in(x[m * ldx + k]) W[n][k] + bias[n])
+ *                      + add[(add_mod > 0 ? m % add_mod : m) * ld_add + n]; bias / add optional; W [N][K] of wdtype.  Refused: M outside
+ *                      1..8, K % (16 bytes of wdtype), M_template * K * 4 > 64 KB, ldx < K, ldo < N, ld_add < N, an act outside 0 | K22_ACT_SILU
+ *   layernorm_f32      launch_layernorm_f32 (K22UNet::build_cond_ops / build_cond_ops_22: ln_model_n, ctx_norm, emb_norm): y = LN(x)
+ *                      over rows of D contiguous fp32 values, biased variance
+ *   resample           launch_resample (K22UNet::resblock, the skip branch of an up / down block): T NHWC [B][H][W][C] -> mode 1: 2x2 average
+ *                      [B][H / 2][W / 2][C] (floor; a trailing odd row / column is not read), mode 2: nearest [B][2H][2W][C].  Refused: another
+ *                      mode, C % 8 (16-bit types) / % 4 (fp32), mode 1 with H < 2 or W < 2
+ *   cast_rows          launch_cast_rows (K22UNet::build_cond_ops / build_cond_ops_22: ctx assembly; the prior's plan): y T [r * ldy + c] = T(x fp32 [r * ldx + c]), c < cols
+ *   kv_pack            launch_kv_pack (K22UNet::attnblock; xf_plan.h): K_all T [B][H][Tkp][64], V^T_all T [B][H][64][Tkp] with keys
+ *                      [ctx 0..S-1 | self S..S+T-1 | zero pad], Tkp = roundup(S + T, 64) as k22_attention derives it; qkv [B * T][3 * 64 H]
+ *                      columns Q | K | V, ctxkv [B * S][2 * 64 H] columns K | V (null allowed when S == 0) */
+int k22_conv_in(const float* x, const float* img, const float* mask, const float* w_packed, const float* bias, void* out, int B, int H, int W,
+                int Cin, int Cout, int img_premul, int dtype, void* stream);
+int k22_timestep_embedding(const float* t, const float* freqs, float* out, int rows, int half, void* stream);
+int k22_linear_smallm_ld(const float* x, long ldx, const void* W, const float* bias, const float* add, long ld_add, int add_mod, float* out,
+                         long ldo, int M, int N, int K, int act_in, int act_out, int wdtype, void* stream);
+int k22_layernorm_f32(const float* x, const float* gain, const float* beta, float* y, int rows, int D, float eps, void* stream);
+int k22_resample(const void* x, void* y, int B, int H, int W, int C, int mode, int dtype, void* stream);
+int k22_cast_rows(const float* x, void* y, int rows, int cols, long ldx, long ldy, int dtype, void* stream);
+int k22_kv_pack(const void* qkv, const void* ctxkv, void* kall, void* vtall, int B, int H, int T, int S, int dtype, void* stream);
 
 #ifdef __cplusplus
 }

@@ -206,6 +206,14 @@ SIGNATURES = {
     "k22_gn_stats": (_I, [_P, _P, _I, _I, _I, _I, _P, C.POINTER(_I), _I, _P]),
     "k22_gn_coeff": (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _P, _P, _P, _L, _F, _P, _P]),
     "k22_gn_apply": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _P, _I, _P]),
+    # the kernels that open and close a UNet step, one per entry (tests/test_seam_kernels_gpu.py)
+    "k22_conv_in": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "k22_timestep_embedding": (_I, [_P, _P, _P, _I, _I, _P]),
+    "k22_linear_smallm_ld": (_I, [_P, _L, _P, _P, _P, _L, _I, _P, _L, _I, _I, _I, _I, _I, _I, _P]),
+    "k22_layernorm_f32": (_I, [_P, _P, _P, _P, _I, _I, _F, _P]),
+    "k22_resample": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "k22_cast_rows": (_I, [_P, _P, _I, _I, _L, _L, _I, _P]),
+    "k22_kv_pack": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
 }
 
 _lib = None

@@ -655,6 +655,53 @@ int k22_gn_apply(const void* x0, const void* x1, int C0, int C1, int B, int H, i
   return launch_gn_apply(ap, k22_storage_dtype(dtype), reinterpret_cast<hipStream_t>(stream));
 }
 
+// ---- the kernels that open and close a UNet step, one per entry (tests/test_seam_kernels_gpu.py): the launchers K22UNet's plan, its
+// conditioning heads and the sampler loops call, with the fields they fill.  What protects a kernel is refused in its launcher ----------
+int k22_conv_in(const float* x, const float* img, const float* mask, const float* w_packed, const float* bias, void* out, int B, int H, int W,
+                int Cin, int Cout, int img_premul, int dtype, void* stream) {
+  if (!x || !w_packed || !bias || !out || B < 1 || B > 65535 || H < 1 || H > 65535 || W < 1 || Cout < 1 || !aux_dtype_ok(dtype))
+    return k22_set_error(K22_EINVAL, "conv_in: bad argument");
+  ConvInParams p = {};
+  p.x = x; p.img = img; p.mask = mask; p.w = w_packed; p.bias = bias; p.out = out;
+  p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.img_premul = img_premul ? 1 : 0;
+  return launch_conv_in(p, dtype, reinterpret_cast<hipStream_t>(stream));
+}
+int k22_timestep_embedding(const float* t, const float* freqs, float* out, int rows, int half, void* stream) {
+  if (!t || !freqs || !out || rows < 1 || half < 1) return k22_set_error(K22_EINVAL, "timestep_embedding: bad argument");
+  return launch_timestep_embedding(t, freqs, out, rows, half, reinterpret_cast<hipStream_t>(stream));
+}
+int k22_linear_smallm_ld(const float* x, long ldx, const void* W, const float* bias, const float* add, long ld_add, int add_mod, float* out,
+                         long ldo, int M, int N, int K, int act_in, int act_out, int wdtype, void* stream) {
+  if (!x || !W || !out || N < 1 || K < 1 || ldx < K || ldo < N || (add && ld_add < N) || add_mod < 0 || !aux_dtype_ok(wdtype) ||
+      (act_in != K22_ACT_NONE && act_in != K22_ACT_SILU) || (act_out != K22_ACT_NONE && act_out != K22_ACT_SILU))
+    return k22_set_error(K22_EINVAL, "linear_smallm_ld: bad argument");
+  LinearSmallParams lp = {};
+  lp.x = x; lp.ldx = ldx; lp.W = W; lp.bias = bias; lp.add = add; lp.ld_add = ld_add; lp.add_mod = add_mod; lp.out = out; lp.ldo = ldo;
+  lp.M = M; lp.N = N; lp.K = K; lp.act_in = act_in; lp.act_out = act_out;
+  return launch_linear_smallm(lp, wdtype, reinterpret_cast<hipStream_t>(stream));   // M in 1..8, K alignment, the LDS stage: the launcher's
+}
+int k22_layernorm_f32(const float* x, const float* gain, const float* beta, float* y, int rows, int D, float eps, void* stream) {
+  if (!x || !gain || !beta || !y || rows < 1 || D < 1) return k22_set_error(K22_EINVAL, "layernorm_f32: bad argument");
+  return launch_layernorm_f32(x, gain, beta, y, rows, D, eps, reinterpret_cast<hipStream_t>(stream));
+}
+int k22_resample(const void* x, void* y, int B, int H, int W, int C, int mode, int dtype, void* stream) {
+  if (!x || !y || B < 1 || H < 1 || W < 1 || C < 1 || (mode == 1 && (H < 2 || W < 2)) || !aux_dtype_ok(dtype))
+    return k22_set_error(K22_EINVAL, "resample: bad argument");
+  return launch_resample(x, y, B, H, W, C, mode, dtype, reinterpret_cast<hipStream_t>(stream));   // mode 1 | 2, C % vector: the launcher's
+}
+int k22_cast_rows(const float* x, void* y, int rows, int cols, long ldx, long ldy, int dtype, void* stream) {
+  if (!x || !y || rows < 1 || cols < 1 || ldx < cols || ldy < cols || !aux_dtype_ok(dtype)) return k22_set_error(K22_EINVAL, "cast_rows: bad argument");
+  return launch_cast_rows(x, y, rows, cols, ldx, ldy, dtype, reinterpret_cast<hipStream_t>(stream));
+}
+int k22_kv_pack(const void* qkv, const void* ctxkv, void* kall, void* vtall, int B, int H, int T, int S, int dtype, void* stream) {
+  if (!qkv || !kall || !vtall || B < 1 || B > 65535 || H < 1 || H > 65535 || T < 1 || S < 0 || (S > 0 && !ctxkv) || !aux_dtype_ok(dtype))
+    return k22_set_error(K22_EINVAL, "kv_pack: bad argument");
+  KvPackParams kp;
+  kp.qkv = qkv; kp.ctxkv = ctxkv; kp.kall = kall; kp.vtall = vtall; kp.B = B; kp.H = H; kp.T = T; kp.S = S;
+  kp.Tkp = (S + T + 63) / 64 * 64;   // as attention_seq
+  return launch_kv_pack(kp, dtype, reinterpret_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"
 
 // ---- debug: LDS sentinel (tools/lds_victim_probe.py) -------------------------------------------------------------

@@ -608,6 +608,8 @@ int launch_gn_apply(const GnApplyParams& p, int dtype, hipStream_t s) {
 }
 int launch_resample(const void* x, void* y, int B, int H, int W, int C, int mode, int dtype, hipStream_t s) {
   const int epv = dtype == K22_F32 ? 4 : 8;
+  if (mode != 1 && mode != 2) return k22_set_error(K22_EINVAL, "resample: mode must be 1 (2x2 average) or 2 (nearest x2)");
+  if (C < epv || C % epv) return k22_set_error(K22_EINVAL, "resample: C must be a multiple of the 16-byte channel vector");
   const int Ho = mode == 1 ? H / 2 : H * 2, Wo = mode == 1 ? W / 2 : W * 2;
   const int nb = grid_for((int64_t)B * Ho * Wo * (C / epv), 256, 8192);
   if (dtype == K22_BF16) hipLaunchKernelGGL(resample_kernel<bf16_t>, dim3(nb), dim3(256), 0, s, x, y, B, H, W, C, mode);
@@ -617,6 +619,10 @@ int launch_resample(const void* x, void* y, int B, int H, int W, int C, int mode
   return K22_OK;
 }
 int launch_conv_in(const ConvInParams& p, int dtype, hipStream_t s) {
+  // the kernel reads img for channels 4-7, mask for channel 8 and - unless img_premul - mask again as the factor of channels 4-7
+  if (p.Cin == 9 && (!p.img || !p.mask)) return k22_set_error(K22_EINVAL, "conv_in: 9 input channels need img and mask");
+  if (p.Cin == 8 && !p.img) return k22_set_error(K22_EINVAL, "conv_in: 8 input channels need img");
+  if (p.Cin > 4 && !p.img_premul && !p.mask) return k22_set_error(K22_EINVAL, "conv_in: img_premul = 0 needs the mask");
   dim3 grid((p.W + CONV_IN_PT - 1) / CONV_IN_PT, p.H, p.B);
   if (p.Cin == 4) {
     if (dtype == K22_BF16) hipLaunchKernelGGL((conv_in_kernel<bf16_t, 4>), grid, dim3(128), 0, s, p);

@@ -67,6 +67,16 @@ def fold_up2(w: torch.Tensor) -> torch.Tensor:
     return torch.stack(phases, 0)
 
 
+def pack_stem(w: torch.Tensor) -> torch.Tensor:
+    """stem conv [O, I, 3, 3] -> fp32 [I*9][O] (row c * 9 + ky * 3 + kx): conv_in_kernel reads one weight per thread, coalesced over O"""
+    return w.reshape(w.shape[0], -1).t().contiguous()
+
+
+def time_freqs(half: int) -> torch.Tensor:
+    """exp(-ln(10000) * arange(half) / half) in fp32, exactly as nn.py:113-117 builds it"""
+    return torch.exp(-math.log(10000) * torch.arange(0, half, dtype=torch.float32) / half)
+
+
 def packed_entries(arch: UNetArch, sd: Dict[str, torch.Tensor], tdtype, device) -> "OrderedDict[str, torch.Tensor]":
     f32 = torch.float32
     out: "OrderedDict[str, torch.Tensor]" = OrderedDict()
@@ -98,7 +108,7 @@ def packed_entries(arch: UNetArch, sd: Dict[str, torch.Tensor], tdtype, device) 
         return cast(_pad_rows(w.reshape(w.shape[0], -1)))
 
     half = arch.model_channels // 2
-    out["time_freqs"] = torch.exp(-math.log(10000) * torch.arange(0, half, dtype=f32) / half).to(device)
+    out["time_freqs"] = time_freqs(half).to(device)
     head = (["head22.ctx_proj", "head22.ctx_norm", "head22.emb_proj", "head22.emb_norm"] + [f"hint.{k}" for k in range(8 if arch.hint_channels else 0)]
             if head22 else ["clip_to_seq", "proj_n", "img_layer"])
     for n in ["time_embed.0", "time_embed.2"] + head:
@@ -114,8 +124,7 @@ def packed_entries(arch: UNetArch, sd: Dict[str, torch.Tensor], tdtype, device) 
     for b in arch.blocks:
         if b[0] == "stem":
             pfx = b[1]
-            w = get(pfx + ".weight")               # [O, I, 3, 3] -> [I*9][O]: the stem kernel reads one weight per thread, coalesced over O
-            out[pfx + ".weight"] = w.reshape(w.shape[0], -1).t().contiguous()
+            out[pfx + ".weight"] = pack_stem(get(pfx + ".weight"))
             out[pfx + ".bias"] = get(pfx + ".bias")
         elif b[0] == "res":
             _, pfx, cin, cout, _ud = b
