@@ -596,6 +596,16 @@ int k22_movq_decode(K22MoVQ* m, const float* z, float* out, unsigned char* out_u
 int k22_movq_plan_encoder(K22MoVQ* m, int B, int H, int W, size_t* workspace_bytes);
 int k22_movq_encode(K22MoVQ* m, const float* image, float* latent, void* stream);
 int k22_movq_num_ops(const K22MoVQ* m);
+/* Which form of the AttnBlock the NEXT plan of this handle (decoder or encoder) is built with; the current plan is not touched.
+ *   K22_MOVQ_ATTN_AUTO (default)  fused exactly when T = h * w > 16384 and the block's width C is one the fused kernel admits
+ *                                 (k22_movq_attention below), the scores form otherwise.  The rule reads T and C alone, never B.
+ *   K22_MOVQ_ATTN_SCORES          q.k^T as a GEMM per image into a [B][T][T] workspace slot, row softmax, P.V^T as a GEMM per image.
+ *   K22_MOVQ_ATTN_FUSED           ONE k22_movq_attention launch for all images; the plan has no [T][T] slot.  A plan whose AttnBlocks
+ *                                 the kernel does not admit fails with K22_EINVAL and leaves the previous plan as it was.
+ * The GEMMs before (norm, q, k, V^T) and after (proj_out) are the same in both forms.  K22_EINVAL for a null handle or another mode.
+ * k22_debug_counter("movq_fused_attn_launches") counts the fused launches. */
+enum { K22_MOVQ_ATTN_AUTO = 0, K22_MOVQ_ATTN_SCORES = 1, K22_MOVQ_ATTN_FUSED = 2 };
+int k22_movq_set_attention(K22MoVQ* m, int mode);
 
 /* ---- conditioning encoders ---------------------------------------------------------------------
  * The transformer towers that run once per prompt / image, one engine type for the three of them:
@@ -686,6 +696,18 @@ int k22_upsample2_pad(const void* x, void* y, int B, int H, int W, int C, int dt
 int k22_pad_copy(const void* x, void* y, int B, int H, int W, int C, int dtype, void* stream);
 int k22_subsample_odd(const void* x, void* y, int B, int H, int W, int C, int dtype, void* stream);
 int k22_softmax_rows(void* x, long rows, int L, float scale, int dtype, void* stream);
+/* Fused single-head attention of the MoVQ AttnBlock (csrc/movq_attention.hip).  Per image b and query t
+ *     out[b][t][:] = sum_j softmax_j(C^-1/2 * q_t . k_j) * v_j + bias_v,   j = 0 .. T-1, one head, no mask.
+ * Layouts: q, k [B][T][C] row-major and vt = V^T [B][C][T], in the storage type `dtype` (K22_BF16 | K22_F16 | K22_F32), 16-byte aligned;
+ * bias_v fp32 [C] or NULL; out [B][T][C] in the storage type.  The [T][T] scores are never written to memory.
+ * Rounding: fp32 scores and online softmax (running maximum and sum); the row sum is taken over the unrounded probabilities; P is rounded
+ * ONCE to the storage type in front of the P.V product (K22_F32: not at all); bias_v is added after the normalisation (the weights sum
+ * to 1, so this is exact); the output is rounded once on store.  No atomics and a fixed reduction order: two launches give equal bits, and
+ * image b of a batch has the bits of the same image launched alone.
+ * K22_EINVAL (with a k22_last_error text that names the rule) for a null q, k, vt or out; C outside {128, 256, 384, 512}; T < 64,
+ * T % 64 != 0 or T > 4194304; B < 1; a dtype outside the three; a misaligned pointer.  A refused call launches nothing and leaves the library usable. */
+int k22_movq_attention(const void* q, const void* k, const void* vt, const float* bias_v, void* out,
+                       int B, int T, int C, int dtype, void* stream);
 int k22_movq_prepare(const float* z, const float* wpq, const float* bpq, float* zq, void* xin, int B, int h, int w, int Cpad, int dtype, void* stream);
 int k22_movq_enc_prepare(const float* image, void* xin, int B, int H, int W, int Cpad, int dtype, void* stream);
 int k22_movq_quant_conv(const float* h, const float* wq, const float* bq, float* out, int B, int HW, void* stream);

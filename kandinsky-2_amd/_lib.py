@@ -147,6 +147,7 @@ SIGNATURES = {
     "k22_movq_plan_encoder": (_I, [_P, _I, _I, _I, C.POINTER(_Z)]),
     "k22_movq_encode": (_I, [_P, _P, _P, _P]),
     "k22_movq_num_ops": (_I, [_P]),
+    "k22_movq_set_attention": (_I, [_P, _I]),
     "k22_ddim_step": (_I, [_P, _P, _P, _P, _F, _I, _P, _P, _I, _I, _P]),
     "k22_dpmpp_step": (_I, [_P, _P, _P, _P, _F, _I, _P, _P, _I, _I, _P]),
     "k22_dpmpp_step_clip": (_I, [_P, _P, _P, _P, _F, _I, _F, _F, _P, _P, _I, _I, _P]),
@@ -186,6 +187,7 @@ SIGNATURES = {
     "k22_pad_copy": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
     "k22_subsample_odd": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
     "k22_softmax_rows": (_I, [_P, _L, _I, _F, _I, _P]),
+    "k22_movq_attention": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "k22_movq_prepare": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "k22_movq_enc_prepare": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
     "k22_movq_quant_conv": (_I, [_P, _P, _P, _P, _I, _I, _P]),

@@ -85,6 +85,7 @@ int k22_stream_repack(const void* W, void* out, int Npad, int taps, int Kc, int 
 
 long k22_debug_counter(const char* name) {
   if (name && !strcmp(name, "stream_launches")) return stream_launch_count();
+  if (name && !strcmp(name, "movq_fused_attn_launches")) return movq_fused_attn_launch_count();
   if (name && !strcmp(name, "loop_captures")) return loop_capture_count();
   if (name && !strcmp(name, "loop_launches")) return loop_launch_count();
   return -1;
@@ -590,6 +591,9 @@ K22_AUX_NHWC(subsample_odd)
 int k22_softmax_rows(void* x, long rows, int L, float scale, int dtype, void* stream) {
   if (!x || L < 1 || !aux_dtype_ok(dtype)) return k22_set_error(K22_EINVAL, "softmax_rows: bad argument");
   return launch_softmax_rows(x, rows, L, scale, dtype, reinterpret_cast<hipStream_t>(stream));
+}
+int k22_movq_attention(const void* q, const void* k, const void* vt, const float* bias_v, void* out, int B, int T, int C, int dtype, void* stream) {
+  return launch_movq_attention(q, k, vt, bias_v, out, B, T, C, dtype, reinterpret_cast<hipStream_t>(stream));
 }
 int k22_movq_prepare(const float* z, const float* wpq, const float* bpq, float* zq, void* xin, int B, int h, int w, int Cpad, int dtype, void* stream) {
   if (!z || !wpq || !bpq || !zq || !xin || B < 1 || h < 1 || w < 1 || Cpad < 4 || !aux_dtype_ok(dtype)) return k22_set_error(K22_EINVAL, "movq_prepare: bad argument");

@@ -223,6 +223,14 @@ int stream_mtiles(const IgemmParams& p, int mb);
 size_t stream_lds_bytes(const IgemmParams& p, int mb);
 int launch_stream(const IgemmParams& p, int dtype, const IgemmLaunch& L, hipStream_t stream);
 long stream_launch_count();
+// movq_attention.hip: fused single-head attention of the MoVQ AttnBlock, out[b][t][:] = softmax_j(C^-1/2 q_t . k_j) v_j + bias_v with
+// q, k [B][T][C], vt [B][C][T], out [B][T][C] in the storage type (K22_BF16 / K22_F16 / K22_F32; 16-byte aligned), bias_v fp32 [C] or null.
+// Admitted: C in {128, 256, 384, 512}, T a positive multiple of 64 (at most 2^22: the kernel's lane offsets are 32-bit), B >= 1; anything else
+// is K22_EINVAL.  One launch for all images.
+inline bool movq_attention_admits_c(int C) { return C == 128 || C == 256 || C == 384 || C == 512; }
+inline bool movq_attention_admits_t(int T) { return T >= 64 && T % 64 == 0 && T <= (1 << 22); }
+int launch_movq_attention(const void* q, const void* k, const void* vt, const float* bias_v, void* out, int B, int T, int C, int dtype, hipStream_t s);
+long movq_fused_attn_launch_count();   // successful launches since the library was loaded
 // engine.hip: whole-loop graphs captured / whole-loop replays or eager loop runs since the library was loaded
 long loop_capture_count();
 long loop_launch_count();

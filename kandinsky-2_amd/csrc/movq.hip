@@ -13,6 +13,8 @@
 //     the GEMM operands (V^T = Wv . h^T, so it is directly the [N][K] operand of the P.V GEMM), scores = Q K^T as a
 //     GEMM per image into a [T][T] buffer (the reference materialises it too, movq_modules.py:214-218), row softmax,
 //     O = P V^T^T + bv (softmax rows sum to 1, so the v bias moves behind the product), proj_out + residual.
+//     Second form ("fused", k22_movq_set_attention): scores, softmax and P V as ONE launch of movq_attention.hip for all images;
+//     the [T][T] buffer is not part of such a plan.
 #include "kernels.h"
 #include "elementwise.h"
 #include "../../include/k22.h"
@@ -39,6 +41,31 @@ struct K22MoVQ : PlanBase {
   int encH = 0, encW = 0;
   Slot* s_h[3];
   int hrot = 0;
+  int attn_mode = K22_MOVQ_ATTN_AUTO;         // k22_movq_set_attention: read when a plan is built
+  static constexpr int ATTN_AUTO_T = 16384;   // auto: fused above this many keys (the largest T the scores form is tested and measured at)
+
+  // the form of an AttnBlock of width C over T keys under attn_mode; never a function of B (images are independent chains)
+  bool attn_fused(int T, int C) const {
+    if (attn_mode == K22_MOVQ_ATTN_SCORES) return false;
+    if (attn_mode == K22_MOVQ_ATTN_FUSED) return true;
+    return T > ATTN_AUTO_T && movq_attention_admits_c(C) && movq_attention_admits_t(T);
+  }
+  // the widths of the plan's AttnBlocks: mid (the deepest level's width) and every level with attention
+  bool attn_widths_admitted() const {
+    const int nres = cfg.n_levels;
+    if (!movq_attention_admits_c(cfg.ch * cfg.ch_mult[nres - 1])) return false;
+    for (int lvl = 0; lvl < nres; ++lvl)
+      if (((cfg.attn_levels >> lvl) & 1) && !movq_attention_admits_c(cfg.ch * cfg.ch_mult[lvl])) return false;
+    return true;
+  }
+  // "fused" asked for a plan the kernel does not admit: refused before the current plan is touched.  T0: keys at the deepest level
+  // (every AttnBlock of a plan runs there or, in the encoder, at a level whose key count is 4^k T0).
+  int check_fused(int64_t T0) {
+    if (attn_mode != K22_MOVQ_ATTN_FUSED) return K22_OK;
+    if (!attn_widths_admitted()) return k22_set_error(K22_EINVAL, "movq: fused attention needs AttnBlock widths of 128, 256, 384 or 512 channels");
+    if (T0 < 64 || T0 % 64) return k22_set_error(K22_EINVAL, "movq: fused attention needs h * w to be a positive multiple of 64");
+    return K22_OK;
+  }
 
   Slot* next_h() { Slot* s = s_h[hrot]; hrot = (hrot + 1) % 3; return s; }
   static int ilog2(int v) { int s = 0; while ((1 << s) < v) ++s; return s; }
@@ -142,15 +169,25 @@ struct K22MoVQ : PlanBase {
     op_gemm(s_N, B * T, C, C, pfx + ".q", nullptr, s_Q);
     op_gemm(s_N, B * T, C, C, pfx + ".k", nullptr, s_K);
     need(s_VT, (size_t)B * C * T * esz);
-    need(s_SC, (size_t)B * T * T * esz);
     need(s_O, (size_t)B * T * C * esz);
     const void* wv = W_(pfx + ".v.weight"); const float* bv = Wf(pfx + ".v.bias");
+    Slot* d = next_h();
+    if (d == in.s) d = next_h();
+    MAct out; out.s = d; out.C = C; out.H = in.H; out.W = in.W;
+    // V^T_b [C][T] = Wv [C][C] . N_b [T][C]^T
+    auto push_vt = [&](int b) {
+      IgemmParams p = igemm_gemm_problem(C, T, C, 0);   // (T % 64 == 0: Npad = T)
+      push_igemm(p, [=](IgemmParams& q) { q.A0 = wv; q.Wp = ptr(s_N) + (size_t)b * T * C * es; q.bias = nullptr; q.out = ptr(s_VT) + (size_t)b * C * T * es; });
+    };
+    if (attn_fused(T, C)) {
+      for (int b = 0; b < Bn; ++b) push_vt(b);
+      ops.push_back([=](hipStream_t st) { return launch_movq_attention(ptr(s_Q), ptr(s_K), ptr(s_VT), bv, ptr(s_O), Bn, T, C, dt, st); });
+      op_gemm(s_O, B * T, C, C, pfx + ".proj_out", in.s, d);
+      return out;
+    }
+    need(s_SC, (size_t)B * T * T * esz);
     for (int b = 0; b < Bn; ++b) {
-      // V^T_b [C][T] = Wv [C][C] . N_b [T][C]^T
-      {
-        IgemmParams p = igemm_gemm_problem(C, T, C, 0);   // (T % 64 == 0: Npad = T)
-        push_igemm(p, [=](IgemmParams& q) { q.A0 = wv; q.Wp = ptr(s_N) + (size_t)b * T * C * es; q.bias = nullptr; q.out = ptr(s_VT) + (size_t)b * C * T * es; });
-      }
+      push_vt(b);
       // scores_b [T][T] = Q_b . K_b^T
       {
         IgemmParams p = igemm_gemm_problem(T, T, C, 0);
@@ -165,16 +202,14 @@ struct K22MoVQ : PlanBase {
       push_igemm(p, [=](IgemmParams& q) { q.A0 = ptr(s_SC) + (size_t)b * T * T * es; q.Wp = ptr(s_VT) + (size_t)b * C * T * es; q.bias = bv;
                                           q.out = ptr(s_O) + (size_t)b * T * C * es; });
     }
-    Slot* d = next_h();
-    if (d == in.s) d = next_h();
     op_gemm(s_O, B * T, C, C, pfx + ".proj_out", in.s, d);
-    MAct out; out.s = d; out.C = C; out.H = in.H; out.W = in.W;
     return out;
   }
 
   int plan(int nB, int nh, int nw) {
     // validate before touching the current plan: rejected arguments leave the engine usable as it was
     if (nB < 1 || nh < 1 || nw < 1) return k22_set_error(K22_EINVAL, "movq: empty input");
+    if (int rc = check_fused((int64_t)nh * nw)) return rc;
     begin_plan();
     B = nB; h0 = nh; w0 = nw; enc = false;
     ops.clear(); hrot = 0;
@@ -235,6 +270,7 @@ struct K22MoVQ : PlanBase {
   int plan_enc(int nB, int H, int W) {
     const int nres = cfg.n_levels;
     if (nB < 1 || H < 1 || W < 1 || H % (1 << (nres - 1)) || W % (1 << (nres - 1))) return k22_set_error(K22_EINVAL, "movq encoder: H, W must be positive multiples of 2^(levels-1)");
+    if (int rc = check_fused((int64_t)(H >> (nres - 1)) * (W >> (nres - 1)))) return rc;
     begin_plan();
     B = nB; enc = true; encH = H; encW = W;
     ops.clear(); hrot = 0;
@@ -343,5 +379,12 @@ int k22_movq_encode(K22MoVQ* m, const float* image, float* latent, void* stream)
   return copy_d2d(latent, m->ptr(m->s_lat), (size_t)m->B * 4 * m->h0 * m->w0 * 4, st);
 }
 int k22_movq_num_ops(const K22MoVQ* m) { return m && m->planned ? (int)m->ops.size() : 0; }
+int k22_movq_set_attention(K22MoVQ* m, int mode) {
+  if (!m) return k22_set_error(K22_EINVAL, "movq_set_attention: null argument");
+  if (mode != K22_MOVQ_ATTN_AUTO && mode != K22_MOVQ_ATTN_SCORES && mode != K22_MOVQ_ATTN_FUSED)
+    return k22_set_error(K22_EINVAL, "movq_set_attention: mode must be 0 (auto), 1 (scores) or 2 (fused)");
+  m->attn_mode = mode;
+  return K22_OK;
+}
 
 }  // extern "C"

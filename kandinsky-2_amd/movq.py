@@ -18,7 +18,7 @@ from typing import Dict, Optional, Tuple
 import torch
 
 from . import _lib
-from .native import NativeEngine, NativeModule, _pad_rows, layout_arena
+from .native import FAMILIES, NativeEngine, NativeModule, _pad_rows, layout_arena
 
 MOVQ_CONFIG_2_1 = {  # CONFIG_2_1["image_enc_params"]["params"] (kandinsky2/configs.py:68-90)
     "embed_dim": 4, "n_embed": 16384,
@@ -41,6 +41,10 @@ class MoVQArch:
         self.attn_levels = [i for i in range(n) if (res // 2 ** i) in ddconfig["attn_resolutions"]]
         if self.z_channels != 4 or embed_dim != 4:
             raise NotImplementedError("the engine supports z_channels == embed_dim == 4")
+
+    def __repr__(self):     # by value: two architectures print alike exactly when they are alike (caches key on it)
+        return (f"MoVQArch(ch={self.ch}, ch_mult={self.ch_mult}, num_res_blocks={self.num_res_blocks}, z_channels={self.z_channels}, "
+                f"out_ch={self.out_ch}, zq_ch={self.zq_ch}, attn_levels={self.attn_levels})")
 
     def blocks(self):
         """(kind, prefix, cin, cout) in forward order: 'res' | 'attn' | 'up' (Upsample conv)."""
@@ -154,13 +158,51 @@ def _movq_config(a: MoVQArch, backend_dtype) -> _lib.K22MoVQConfig:
     return cfg
 
 
-class MoVQDecoderHIP(NativeModule):
-    """MI355X-native `MOVQ.decode` (kandinsky2/vqgan/autoencoder.py:182-185)."""
+# attention= of the two modules -> k22_movq_set_attention's mode: "auto" = the fused kernel above 16384 keys (no [T][T] workspace), the
+# scores route at every size up to it; "scores" / "fused" force one form at every size
+ATTENTION_MODES = {"auto": 0, "scores": 1, "fused": 2}
+
+
+def movq_family(kind: str, entries=None):
+    """The (create, destroy, plan, bind) callables NativeEngine drives for the "movq" / "movq_encoder" family, with the AttnBlock form in
+    the plan's key: plan(handle, B, h, w, mode, nbytes) sets the mode on the handle (k22_movq_set_attention holds from the next plan) and
+    plans.  entries: (create, destroy, plan, bind, set_attention) in place of the C entries (the host tests pass recording fakes)."""
+    create, destroy, plan, bind, set_attention = entries or [getattr(_lib.lib(), n) for n in FAMILIES[kind] + ("k22_movq_set_attention",)]
+
+    def plan_with_mode(handle, B, h, w, mode, nbytes):
+        rc = set_attention(handle, mode)
+        return rc if rc else plan(handle, B, h, w, nbytes)
+
+    return create, destroy, plan_with_mode, bind
+
+
+class _MoVQAttention:
+    """attention= of MoVQDecoderHIP / MoVQEncoderHIP: validated on assignment, part of the plan key (assigning it re-plans at the next call)"""
+
+    @property
+    def attention(self) -> str:
+        return self._attention
+
+    @attention.setter
+    def attention(self, mode: str):
+        if mode not in ATTENTION_MODES:
+            raise ValueError(f"attention must be one of {sorted(ATTENTION_MODES)}, not {mode!r}")
+        self._attention = mode
+
+    def _ensure_plan(self, B, h, w):
+        if not self._engines:
+            self.prepare()
+        self._engines["movq"].ensure_plan(B, h, w, ATTENTION_MODES[self._attention])
+
+
+class MoVQDecoderHIP(_MoVQAttention, NativeModule):
+    """MI355X-native `MOVQ.decode` (kandinsky2/vqgan/autoencoder.py:182-185).  attention: "auto" | "scores" | "fused" (ATTENTION_MODES)."""
 
     def __init__(self, ddconfig: Optional[dict] = None, n_embed: int = 16384, embed_dim: int = 4,
-                 backend_dtype: torch.dtype = torch.bfloat16):
+                 backend_dtype: torch.dtype = torch.bfloat16, attention: str = "auto"):
         self.arch = MoVQArch(ddconfig or MOVQ_CONFIG_2_1["ddconfig"], embed_dim)
         super().__init__(movq_param_shapes(self.arch), backend_dtype)
+        self.attention = attention
 
     def load_state_dict(self, state_dict, strict: bool = False, **kw):
         own = set(movq_param_shapes(self.arch).keys())
@@ -173,13 +215,8 @@ class MoVQDecoderHIP(NativeModule):
         dev = self._device()
         self._release()
         arena, table = pack_movq_arena(self.arch, self.state_dict(), self.backend_dtype, dev)
-        self._engines["movq"] = NativeEngine("movq", _movq_config(self.arch, self.backend_dtype), arena, table)
+        self._engines["movq"] = NativeEngine(movq_family("movq"), _movq_config(self.arch, self.backend_dtype), arena, table)
         return self
-
-    def _ensure_plan(self, B, h, w):
-        if not self._engines:
-            self.prepare()
-        self._engines["movq"].ensure_plan(B, h, w)
 
     @torch.no_grad()
     def decode(self, quant: torch.Tensor, return_uint8: bool = False):
@@ -293,19 +330,20 @@ def pack_movq_encoder_arena(a: MoVQArch, sd: Dict[str, torch.Tensor], tdtype: to
     return layout_arena(ent, device)
 
 
-class MoVQEncoderHIP(NativeModule):
+class MoVQEncoderHIP(_MoVQAttention, NativeModule):
     """MI355X-native `MOVQ.encode` (kandinsky2/vqgan/autoencoder.py:176-180): image [B,3,H,W] in [-1,1] -> latent [B,4,H/8,W/8]
     (before the pipeline multiplies by its latent scale, kandinsky2_1_model.py:467).  State-dict keys are the reference's
-    `encoder.*` and `quant_conv.*`; the other keys of a full MOVQ checkpoint are ignored."""
+    `encoder.*` and `quant_conv.*`; the other keys of a full MOVQ checkpoint are ignored.  attention: as MoVQDecoderHIP's."""
 
     def __init__(self, ddconfig: Optional[dict] = None, n_embed: int = 16384, embed_dim: int = 4,
-                 backend_dtype: torch.dtype = torch.bfloat16):
+                 backend_dtype: torch.dtype = torch.bfloat16, attention: str = "auto"):
         dd = ddconfig or MOVQ_CONFIG_2_1["ddconfig"]
         self.arch = MoVQArch(dd, embed_dim)
         self.in_channels = dd.get("in_channels", 3)
         if self.in_channels != 3:
             raise NotImplementedError("the encoder engine takes 3-channel images")
         super().__init__(movq_encoder_param_shapes(self.arch), backend_dtype)
+        self.attention = attention
 
     def load_state_dict(self, state_dict, strict: bool = False, **kw):
         own = set(movq_encoder_param_shapes(self.arch).keys())
@@ -318,7 +356,7 @@ class MoVQEncoderHIP(NativeModule):
         dev = self._device()
         self._release()
         arena, table = pack_movq_encoder_arena(self.arch, self.state_dict(), self.backend_dtype, dev)
-        self._engines["movq"] = NativeEngine("movq_encoder", _movq_config(self.arch, self.backend_dtype), arena, table)
+        self._engines["movq"] = NativeEngine(movq_family("movq_encoder"), _movq_config(self.arch, self.backend_dtype), arena, table)
         return self
 
     @torch.no_grad()
@@ -328,9 +366,7 @@ class MoVQEncoderHIP(NativeModule):
         B, Ci, H, W = image.shape
         if Ci != 3:
             raise ValueError("expected a 3-channel image")
-        if not self._engines:
-            self.prepare()
-        self._engines["movq"].ensure_plan(B, H, W)
+        self._ensure_plan(B, H, W)
         x = image.detach().float().contiguous()
         down = 1 << (len(self.arch.ch_mult) - 1)
         out = torch.empty(B, 4, H // down, W // down, dtype=torch.float32, device=image.device)

@@ -172,7 +172,7 @@ class Kandinsky2_1HIP:
 
     def __init__(self, config, model_path, prior_path, device="cuda", task_type="text2img", *, conditioner=None,
                  backend_dtype: torch.dtype = torch.bfloat16, use_graph: bool = True, whole_loop_graph: Optional[bool] = None,
-                 movq_dtype: Optional[torch.dtype] = None, chains: Optional[int] = None):
+                 movq_dtype: Optional[torch.dtype] = None, chains: Optional[int] = None, movq_attention: str = "auto"):
         if task_type not in ("text2img", "inpainting"):
             raise ValueError("Only text2img and inpainting is available")
         if torch.device(device).type != "cuda":
@@ -224,7 +224,8 @@ class Kandinsky2_1HIP:
         # in fp16 - within 3 grey levels, 88 % of the bytes identical, at 12 ms instead of 53 (bf16 would move pixels by up to 24 levels, which
         # is why a bf16 UNet still gets an fp16 MoVQ; tests/test_movq_gpu.py, profiles/r03_movq_precision.txt).
         self.movq_dtype = movq_auto
-        self.image_encoder = _MoVQ(ie["params"], movq_sd, self.movq_dtype, device)
+        # movq_attention: "auto" | "scores" | "fused" - the AttnBlock form of the MoVQ engines (movq.ATTENTION_MODES)
+        self.image_encoder = _MoVQ(ie["params"], movq_sd, self.movq_dtype, device, movq_attention=movq_attention)
 
         # chains: Text2ImUNetHIP(chains=...) - 2 = the CFG pair as two half-batch engines side by side (None: env K22_CHAINS, else 1)
         self.model = Text2ImUNetHIP(make_arch(mcfg, inpainting=mcfg["inpainting"]), backend_dtype=backend_dtype, use_graph=use_graph,
@@ -484,9 +485,10 @@ class _MoVQ:
     """self.image_encoder of the reference (`MOVQ`, kandinsky2/vqgan/autoencoder.py:163-185): .decode / .encode on the HIP engines;
     the encoder engine is built on first use (text2img never needs it)."""
 
-    def __init__(self, params, state_dict, backend_dtype, device):
-        self._params, self._sd, self._dt, self._dev = params, state_dict, backend_dtype, device
-        self.decoder = MoVQDecoderHIP(params["ddconfig"], params.get("n_embed", 16384), params.get("embed_dim", 4), backend_dtype=backend_dtype)
+    def __init__(self, params, state_dict, backend_dtype, device, movq_attention: str = "auto"):
+        self._params, self._sd, self._dt, self._dev, self._attention = params, state_dict, backend_dtype, device, movq_attention
+        self.decoder = MoVQDecoderHIP(params["ddconfig"], params.get("n_embed", 16384), params.get("embed_dim", 4), backend_dtype=backend_dtype,
+                                      attention=movq_attention)
         self.decoder.load_state_dict(state_dict, strict=True)
         self.decoder = self.decoder.to(device)
         self._encoder = None
@@ -494,7 +496,8 @@ class _MoVQ:
     @property
     def encoder(self):
         if self._encoder is None:
-            e = MoVQEncoderHIP(self._params["ddconfig"], self._params.get("n_embed", 16384), self._params.get("embed_dim", 4), backend_dtype=self._dt)
+            e = MoVQEncoderHIP(self._params["ddconfig"], self._params.get("n_embed", 16384), self._params.get("embed_dim", 4), backend_dtype=self._dt,
+                               attention=self._attention)
             e.load_state_dict(self._sd, strict=True)
             self._encoder = e.to(self._dev)
         return self._encoder
@@ -564,11 +567,12 @@ def _conditioner_from_cache_dir(cache_dir, device, backend_dtype, tokenizer2=Non
 
 def get_kandinsky2(device, task_type="text2img", cache_dir="/tmp/kandinsky2", use_auth_token=None, model_version="2.1",
                    use_flash_attention=False, *, conditioner=None, backend_dtype: torch.dtype = torch.bfloat16, use_graph: bool = True,
-                   movq_dtype: Optional[torch.dtype] = None, tokenizer2=None, prior_cache_dir=None):
+                   movq_dtype: Optional[torch.dtype] = None, tokenizer2=None, prior_cache_dir=None, movq_attention: str = "auto"):
     """`get_kandinsky2` (kandinsky2/__init__.py:164-192) for the HIP engines.  The reference downloads the checkpoints into
     cache_dir (kandinsky2/__init__.py:100-160); this box-local variant reads the same file names from cache_dir and raises if
     they are not there (there is no download path).  use_flash_attention is accepted and ignored: attention always runs in the
-    engine's own fused kernel.  2.2: conditioner="native" with prior_cache_dir= builds the native prior (prior22.py)."""
+    engine's own fused kernel.  2.2: conditioner="native" with prior_cache_dir= builds the native prior (prior22.py).
+    movq_attention: "auto" | "scores" | "fused", the AttnBlock form of the MoVQ engines (movq.ATTENTION_MODES)."""
     if model_version == "2.1":
         config = copy.deepcopy(CONFIG_2_1)
         model_name = {"text2img": "decoder_fp16.ckpt", "inpainting": "inpainting_fp16.ckpt"}.get(task_type)
@@ -583,9 +587,9 @@ def get_kandinsky2(device, task_type="text2img", cache_dir="/tmp/kandinsky2", us
         if conditioner is None:
             conditioner = _conditioner_from_cache_dir(cache_dir, device, backend_dtype, tokenizer2)
         return Kandinsky2_1HIP(config, need[model_name], need["prior_fp16.ckpt"], device, task_type=task_type, conditioner=conditioner,
-                               backend_dtype=backend_dtype, use_graph=use_graph, movq_dtype=movq_dtype)
+                               backend_dtype=backend_dtype, use_graph=use_graph, movq_dtype=movq_dtype, movq_attention=movq_attention)
     if model_version == "2.2":
         from .pipeline22 import Kandinsky2_2HIP
         return Kandinsky2_2HIP(device=device, task_type=task_type, cache_dir=cache_dir, conditioner=conditioner, backend_dtype=backend_dtype,
-                               use_graph=use_graph, movq_dtype=movq_dtype, prior_cache_dir=prior_cache_dir)
+                               use_graph=use_graph, movq_dtype=movq_dtype, prior_cache_dir=prior_cache_dir, movq_attention=movq_attention)
     raise ValueError("Only 2.1 and 2.2 are available on the HIP engines")

@@ -337,12 +337,14 @@ def _load_weights(folder):
     return sd, (json.load(open(cfg)) if os.path.exists(cfg) else None)
 
 
-def load_decoder22_from_cache_dir(cache_dir, task_type="text2img", controlnet=False, whole_loop_graph: Optional[bool] = None):
+def load_decoder22_from_cache_dir(cache_dir, task_type="text2img", controlnet=False, whole_loop_graph: Optional[bool] = None,
+                                  movq_attention: str = "auto"):
     """What `from_pretrained('kandinsky-community/kandinsky-2-2-<repo>', subfolder='unet' | 'movq' | 'scheduler')` reads
     (kandinsky2_2_model.py:26-41), from a local copy `cache_dir/<repo>/{unet,movq,scheduler}/`: the UNet and MoVQ state dicts plus
     unet/config.json and scheduler/scheduler_config.json, which DRIVE the architecture and the scheduler (make_arch22,
     DDPMSchedulerHIP.from_config) - nothing about the checkpoint is assumed.  Raises when a folder is missing (no download path).
-    whole_loop_graph is handed through under its own key: the decoders' route switch (KandinskyV22DecoderHIP), not read from any file."""
+    whole_loop_graph is handed through under its own key: the decoders' route switch (KandinskyV22DecoderHIP), not read from any file;
+    so is movq_attention, the AttnBlock form of the MoVQ engines (movq.ATTENTION_MODES)."""
     import json
     repo = "kandinsky-2-2-controlnet-depth" if controlnet else ("kandinsky-2-2-decoder-inpaint" if task_type == "inpainting" else "kandinsky-2-2-decoder")
     root = os.path.join(cache_dir, repo)
@@ -352,7 +354,7 @@ def load_decoder22_from_cache_dir(cache_dir, task_type="text2img", controlnet=Fa
     movq_sd, _ = _load_weights(os.path.join(root, "movq"))
     sc = os.path.join(root, "scheduler", "scheduler_config.json")
     return {"unet": unet_sd, "unet_config": unet_cfg, "movq": movq_sd, "scheduler_config": json.load(open(sc)) if os.path.exists(sc) else None,
-            "whole_loop_graph": whole_loop_graph}
+            "whole_loop_graph": whole_loop_graph, "movq_attention": movq_attention}
 
 
 class Kandinsky2_2HIP:
@@ -362,13 +364,13 @@ class Kandinsky2_2HIP:
     def __init__(self, device="cuda", task_type="text2img", *, unet_state_dict=None, movq_state_dict=None, conditioner=None,
                  cache_dir=None, backend_dtype: torch.dtype = torch.bfloat16, use_graph: bool = True, unet_config=None, controlnet=None,
                  scheduler_config=None, movq_dtype: Optional[torch.dtype] = None, whole_loop_graph: Optional[bool] = None,
-                 prior_cache_dir=None, sampler: str = "ddpm_sampler"):
+                 prior_cache_dir=None, sampler: str = "ddpm_sampler", movq_attention: str = "auto"):
         if task_type not in ("text2img", "img2img", "inpainting"):
             raise ValueError("Only text2img, img2img, inpainting is available")
         if (unet_state_dict is None or movq_state_dict is None) and cache_dir is not None:
             # the files from_pretrained('kandinsky-community/kandinsky-2-2-decoder[-inpaint]', subfolder=...) caches (kandinsky2_2_model.py:26-41)
-            loaded = load_decoder22_from_cache_dir(cache_dir, task_type, bool(controlnet), whole_loop_graph)
-            whole_loop_graph = loaded["whole_loop_graph"]
+            loaded = load_decoder22_from_cache_dir(cache_dir, task_type, bool(controlnet), whole_loop_graph, movq_attention)
+            whole_loop_graph, movq_attention = loaded["whole_loop_graph"], loaded["movq_attention"]
             unet_state_dict = unet_state_dict if unet_state_dict is not None else loaded["unet"]
             movq_state_dict = movq_state_dict if movq_state_dict is not None else loaded["movq"]
             unet_config = unet_config if unet_config is not None else loaded["unet_config"]
@@ -408,13 +410,13 @@ class Kandinsky2_2HIP:
         # None: fp32 engines decode in fp32, 16-bit engines in fp16 (pipeline.py: within one / three grey levels of the fp32 decode)
         from .pipeline import aux_engine_dtypes
         mdt = aux_engine_dtypes(backend_dtype, movq_dtype)[1]     # one rule with the 2.1 driver: fp32 beside fp32 / split-precision engines
-        movq = MoVQDecoderHIP(backend_dtype=mdt)
+        movq = MoVQDecoderHIP(backend_dtype=mdt, attention=movq_attention)
         movq.load_state_dict(movq_state_dict, strict=True)          # decoder keys; a full MOVQ checkpoint's other keys are skipped
         movq = movq.to(device)
         if task_type == "text2img":
             self.decoder = KandinskyV22DecoderHIP(self.unet, movq, scheduler(), whole_loop_graph=whole_loop_graph, sampler=sampler)
         else:
-            enc = MoVQEncoderHIP(backend_dtype=mdt)
+            enc = MoVQEncoderHIP(backend_dtype=mdt, attention=movq_attention)
             enc.load_state_dict(movq_state_dict, strict=True)
             cls = KandinskyV22Img2ImgDecoderHIP if task_type == "img2img" else KandinskyV22InpaintDecoderHIP
             self.decoder = cls(self.unet, movq, enc.to(device), scheduler(), whole_loop_graph=whole_loop_graph, sampler=sampler)
