@@ -696,7 +696,7 @@ int k22_upsample2_pad(const void* x, void* y, int B, int H, int W, int C, int dt
 int k22_pad_copy(const void* x, void* y, int B, int H, int W, int C, int dtype, void* stream);
 int k22_subsample_odd(const void* x, void* y, int B, int H, int W, int C, int dtype, void* stream);
 int k22_softmax_rows(void* x, long rows, int L, float scale, int dtype, void* stream);
-/* Fused single-head attention of the MoVQ AttnBlock (csrc/movq_attention.hip).  Per image b and query t
+/* Fused single-head attention of the MoVQ AttnBlock (csrc/movq_attention.hip; arithmetic contract: csrc/attention_common.h).  Per image b and query t
  *     out[b][t][:] = sum_j softmax_j(C^-1/2 * q_t . k_j) * v_j + bias_v,   j = 0 .. T-1, one head, no mask.
  * Layouts: q, k [B][T][C] row-major and vt = V^T [B][C][T], in the storage type `dtype` (K22_BF16 | K22_F16 | K22_F32), 16-byte aligned;
  * bias_v fp32 [C] or NULL; out [B][T][C] in the storage type.  The [T][T] scores are never written to memory.
@@ -749,8 +749,8 @@ int k22_enc_attention_generic(const void* qkv, void* out, int B, int heads, int 
 int k22_prior_layernorm(const float* x, long ldx, const float* gain, const float* beta, void* y, int rows, int D, int to_f32, int dtype,
                         void* stream);
 int k22_prior_finish_input(float* inp, const float* pos, const float* prd, int B, int n_ctx, int D, void* stream);
-/* Flash attention with the mask and output-format fields the engines set (csrc/attention.hip; tests/test_attention_parity_gpu.py,
- * tests/attention_ref.py).  k22_attention's sequence - kv_pack, then launch_attention - and its tensors (ctxkv may be null when S == 0;
+/* Flash attention with the mask and output-format fields the engines set (csrc/attention.hip, arithmetic contract: csrc/attention_common.h;
+ * tests/test_attention_parity_gpu.py, tests/attention_ref.py).  k22_attention's sequence - kv_pack, then launch_attention - and its tensors (ctxkv may be null when S == 0;
  * dtype: all five arithmetics, fp32 tensors for the split ones), plus
  *   causal     key j is dead for query t when j > t (the CLIP text tower, the prior); compares key index with query index: S must be 0
  *   key_valid  optional fp32 [B][kv_n]: 0 = key dead for every query of the image; keys >= kv_n are alive (the prior's appended tokens)

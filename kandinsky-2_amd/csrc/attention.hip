@@ -2,116 +2,16 @@
 //
 // Restates QKVAttention.forward's einsum path (kandinsky2/model/unet.py:286-340): per (batch, head)
 // softmax((q*s)(k*s)^T) v with s = ch^-0.25, keys = [encoder K | self K], fp32 softmax.  The
-// [B*H, T, S] score tensor of the reference is never materialised.
+// [B*H, T, S] score tensor of the reference is never materialised.  Scheme, fragments, V^T tile layout and
+// the arithmetic contract: attention_common.h.
 //
-// Work split: workgroup = 4 waves = 128 queries of one (b, head); wave = 32 queries.
-//   S^T[key][q] = K[key][:] . Q[q][:]   (A = K tile rows from LDS, B = Q fragments in registers)
-//     -> C layout puts ONE query per lane column (lane&31) and 32 keys of the 64-key tile in the
-//        lane's 32 accumulator registers: row max / row sum are lane-local plus one xor-32 shuffle.
-//   O^T[d][q] += V^T[d][key] . P^T[key][q]   (A = V^T tile rows from LDS, B = P straight from the
-//        S^T accumulator registers: no LDS round trip, the rescale factor is lane-local).
+// Work split: workgroup = 4 waves = 128 queries of one (b, head); wave = 32 queries, 64 channels per head,
+// 64-key tiles: a lane holds 32 keys of the tile for its query in its 32 score registers.
 // K_all / V^T_all are produced by kv_pack_kernel (elementwise.hip), zero padded to 64 keys.
-#include "kernels.h"
+#include "attention_common.h"
 #include "elementwise.h"
 #include <atomic>
-#include <type_traits>
 #include <stdlib.h>
-
-// V^T fragment whose K (= key) order matches the S^T accumulator registers:
-// element j<4 -> key 16a + 4h + j ; j>=4 -> key 16a + 8 + 4h + (j-4).
-// 16-bit tiles (round 6): the V^T tile is stored KEY-PERMUTED within every block of 16 keys - piece 2a + h' of a row holds
-// [keys 16a + 4h' .. + 3 | keys 16a + 8 + 4h' .. + 3] (vt_store16 below) - so that the fragment is ONE conflict-free ds_read_b128.  With the
-// natural key order it was two 8-byte reads gathered by six register moves per PV atom: 24 v_mov per 64-key tile, and the LDS array - not the
-// matrix pipe and not VALU issue - was what the tile loop waited for (ds_read2st64_b64: 8+ LDS cycles per wave-instruction against 4;
-// SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE = 1.64 on this kernel, profiles/r05_pmc_mfma_bf16.txt).
-__device__ __forceinline__ void ld_frag_split(Frag<bf16_t>& f, const char* tile, int r, int a, int h) {
-  f.v = *reinterpret_cast<const u32x4_t*>(tile + lds_chunk_off(r, 2 * a + h));
-}
-__device__ __forceinline__ void ld_frag_split(Frag<f16_t>& f, const char* tile, int r, int a, int h) {
-  f.v = *reinterpret_cast<const u32x4_t*>(tile + lds_chunk_off(r, 2 * a + h));
-}
-// stores keys 8 cc .. 8 cc + 7 (one 16-byte register, natural order) of V^T row `row` into the key-permuted 16-bit tile: keys +0..3 go to
-// piece 2 (cc >> 1), keys +4..7 to piece 2 (cc >> 1) + 1, both at byte 8 (cc & 1)
-__device__ __forceinline__ void vt_store16(char* tile, int row, int cc, const u32x4_t v) {
-  typedef __attribute__((ext_vector_type(2))) unsigned int u32x2_t;
-  *reinterpret_cast<u32x2_t*>(tile + lds_chunk_off(row, cc & ~1) + 8 * (cc & 1)) = u32x2_t{v.x, v.y};
-  *reinterpret_cast<u32x2_t*>(tile + lds_chunk_off(row, cc | 1) + 8 * (cc & 1)) = u32x2_t{v.z, v.w};
-}
-__device__ __forceinline__ void ld_frag_split(Frag<float>& f, const char* tile, int r, int a, int h) {
-  const char* sub = tile + (a >> 1) * 8192;
-  const int al = a & 1;
-  const float4 lo = *reinterpret_cast<const float4*>(sub + lds_chunk_off(r, 4 * al + h));
-  const float4 hi = *reinterpret_cast<const float4*>(sub + lds_chunk_off(r, 4 * al + 2 + h));
-  f.v[0] = lo.x; f.v[1] = lo.y; f.v[2] = lo.z; f.v[3] = lo.w;
-  f.v[4] = hi.x; f.v[5] = hi.y; f.v[6] = hi.z; f.v[7] = hi.w;
-}
-// split precision: the LDS tiles hold x3 chunks (converted once per workgroup while staging: K22_ATT_LSTORE), P and Q are split in registers
-__device__ __forceinline__ void ld_frag_split(Frag<x3_t>& f, const char* tile, int r, int a, int h) {
-  const char* sub = tile + (a >> 1) * 8192;
-  const int al = a & 1;
-  // keys 16 a + 4 h + {0..3} = elements 4 h .. of group 2 al, keys 16 a + 8 + 4 h + {0..3} = the same elements of group 2 al + 1: 8-byte
-  // halves of the groups' hi pieces (chunks 4 al, 4 al + 2) and lo pieces (4 al + 1, 4 al + 3)
-  const u32x2_t h0 = *reinterpret_cast<const u32x2_t*>(sub + lds_chunk_off(r, 4 * al) + 8 * h);
-  const u32x2_t l0 = *reinterpret_cast<const u32x2_t*>(sub + lds_chunk_off(r, 4 * al + 1) + 8 * h);
-  const u32x2_t h1 = *reinterpret_cast<const u32x2_t*>(sub + lds_chunk_off(r, 4 * al + 2) + 8 * h);
-  const u32x2_t l1 = *reinterpret_cast<const u32x2_t*>(sub + lds_chunk_off(r, 4 * al + 3) + 8 * h);
-  f.hi = u32x4_t{h0.x, h0.y, h1.x, h1.y};
-  f.lo = u32x4_t{l0.x, l0.y, l1.x, l1.y};
-}
-// P (<= 1) is split as 2^10 P: the lo half of an unscaled probability under 2^-3 is a fp16 subnormal, i.e. P carried to 2^-25 ABSOLUTE
-// (common.h, "x3 chunk") where the arithmetic promises 2^-22 relative - on a row whose heavy keys have a small V element the many light
-// keys then decide the error (tests/test_attention_parity_gpu.py: 1.03 of the float64 bound at T = 81, causal, before).  The exact power
-// of two comes out of the accumulators with 1 / l (K22_ATT_X3_PSCALE_INV below); 2^10 P <= 1024 is far inside fp16's range.
-constexpr float K22_ATT_X3_PSCALE = 1024.f, K22_ATT_X3_PSCALE_INV = 1.f / 1024.f;
-__device__ __forceinline__ void make_pfrag(Frag<x3_t>& f, const float* p) {
-  constexpr float c = K22_ATT_X3_PSCALE;
-  x3_frag_from_f32(f, make_float4(c * p[0], c * p[1], c * p[2], c * p[3]), make_float4(c * p[4], c * p[5], c * p[6], c * p[7]));
-}
-__device__ __forceinline__ void ld_qfrag(Frag<x3_t>& f, const x3_t* p) {
-  x3_frag_from_f32(f, *reinterpret_cast<const float4*>(p), *reinterpret_cast<const float4*>(p + 4));
-}
-__device__ __forceinline__ void make_pfrag(Frag<bf16_t>& f, const float* p) {
-  f.v = u32x4_t{pack2_bf16(p[0], p[1]),
-                pack2_bf16(p[2], p[3]),
-                pack2_bf16(p[4], p[5]),
-                pack2_bf16(p[6], p[7])};
-}
-__device__ __forceinline__ void make_pfrag(Frag<f16_t>& f, const float* p) {
-  f.v = u32x4_t{pack2_f16(p[0], p[1]), pack2_f16(p[2], p[3]), pack2_f16(p[4], p[5]), pack2_f16(p[6], p[7])};
-}
-__device__ __forceinline__ void make_pfrag(Frag<float>& f, const float* p) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) f.v[j] = p[j];
-}
-__device__ __forceinline__ void ld_qfrag(Frag<bf16_t>& f, const bf16_t* p) { f.v = *reinterpret_cast<const u32x4_t*>(p); }
-__device__ __forceinline__ void ld_qfrag(Frag<f16_t>& f, const f16_t* p) { f.v = *reinterpret_cast<const u32x4_t*>(p); }
-__device__ __forceinline__ void ld_qfrag(Frag<float>& f, const float* p) {
-  const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
-  f.v[0] = a.x; f.v[1] = a.y; f.v[2] = a.z; f.v[3] = a.w;
-  f.v[4] = b.x; f.v[5] = b.y; f.v[6] = b.z; f.v[7] = b.w;
-}
-// xh_t (round 5): the attention of the ASYMMETRIC split engine (K22_F16X2).  q / K_all / V^T_all are the fp32 tensors the split engines'
-// qkv GEMM writes; they are rounded to fp16 while the tiles are staged (Q: at fragment load) and the kernel runs the fp16 engine's body:
-// ONE MFMA per product, fp32 online softmax, native exp2.  The operand rounding of the attention is 1.5 % of the error budget of that
-// engine (tests/golden/drift_ablation_x2.json, kind `a`); the output is written as x3 chunks for the proj_out GEMM, which keeps all
-// three MFMAs.
-struct xh_t { float f; };
-template <typename T> struct AttC { using type = T; static constexpr bool MIX = false; };
-template <> struct AttC<xh_t> { using type = f16_t; static constexpr bool MIX = true; };
-__device__ __forceinline__ u32x4_t f16x8_from_f32(const u32x4_t a, const u32x4_t b) {
-  const float4 x = __builtin_bit_cast(float4, a), y = __builtin_bit_cast(float4, b);
-  return u32x4_t{pack2_f16(x.x, x.y), pack2_f16(x.z, x.w), pack2_f16(y.x, y.y), pack2_f16(y.z, y.w)};
-}
-__device__ __forceinline__ void ld_qfrag(Frag<f16_t>& f, const float* p) {
-  f.v = f16x8_from_f32(*reinterpret_cast<const u32x4_t*>(p), *reinterpret_cast<const u32x4_t*>(p + 4));
-}
-// 2^x: the bf16 path uses the raw v_exp_f32 (inputs here are <= 0; results below 2^-126 flush, which is
-// far below bf16 resolution of the probabilities), the fp32 parity path the accurate exp2f.
-template <typename T> __device__ __forceinline__ float exp2_t(float x);
-template <> __device__ __forceinline__ float exp2_t<bf16_t>(float x) { return __builtin_amdgcn_exp2f(x); }
-template <> __device__ __forceinline__ float exp2_t<f16_t>(float x) { return __builtin_amdgcn_exp2f(x); }
-template <> __device__ __forceinline__ float exp2_t<float>(float x) { return exp2f(x); }
-template <> __device__ __forceinline__ float exp2_t<x3_t>(float x) { return exp2f(x); }
 
 // The online softmax is the issue-bound part of this kernel (measured at T = 2304: waves ISSUING 49 % of their cycles,
 // matrix pipe 18 % busy), so its instruction count is what matters:
@@ -132,13 +32,51 @@ __device__ __forceinline__ float max2f(float a, float b) {
   return r;
 }
 
+// ---- shared by attention_kernel and attention_pipe_kernel ---------------------------------------------------------------------------
+// One text wherever the pipelined kernel's pinned issue order can see it, so macros that use names of the kernel around them (as functions -
+// out-parameters or a returned struct for the prologue, whole-tile loops for the loads - attention_pipe_kernel's schedule moves).
+// K22_ATT_PROLOGUE(QB), 128-query block QB of (image b, head hd): reads T, TG, p, wave, l31, h, b, hd; DECLARES this lane's query t (may be
+// >= T: tq, the row its loads read, is then the last query), qrow, its Q fragments qf, the head's planes Kg / Vg, the number of tiles nkt.
+#define K22_ATT_PROLOGUE(QB)                                                                             \
+  const int t = (QB) * 128 + wave * 32 + l31;                                                            \
+  const int tq = t < p.T ? t : p.T - 1;                                                                  \
+  const TG* qrow = reinterpret_cast<const TG*>(p.q) + (int64_t)(b * p.T + tq) * p.ldq + hd * 64;         \
+  Frag<T> qf[4];                                                                                         \
+  _Pragma("unroll") for (int a = 0; a < 4; ++a) ld_qfrag(qf[a], qrow + 16 * a + 8 * h);                  \
+  const TG* Kg = reinterpret_cast<const TG*>(p.kall) + (int64_t)(b * p.H + hd) * p.Tkp * 64;             \
+  const TG* Vg = reinterpret_cast<const TG*>(p.vtall) + (int64_t)(b * p.H + hd) * 64 * p.Tkp;            \
+  const int nkt = (p.Tk + 63) / 64
+// Global -> register staging of the 64 x 64 tiles of K_all (rows = keys) / V^T_all (rows = channels): unconditional native-vector loads
+// (conditional staging ends up in scratch memory).  Chunk i of a thread is 16 bytes OF THE TILE; MIX: two consecutive fp32 chunks in memory.
+template <bool MIX, typename TG> __device__ __forceinline__ void att_gload(u32x4_t* reg, int i, const TG* g) {
+  if constexpr (MIX) { reg[2 * i] = *reinterpret_cast<const u32x4_t*>(g); reg[2 * i + 1] = *reinterpret_cast<const u32x4_t*>(g + 4); }
+  else reg[i] = *reinterpret_cast<const u32x4_t*>(g);
+}
+// where chunk (row, cc) of tile KT starts in memory: reads Kg, Vg, p, EPC and, of the loop it stands in, row = q / CPR, cc = q - row * CPR
+#define K22_ATT_K_AT(KT) (Kg + (int64_t)((KT) * 64 + row) * 64 + cc * EPC)
+#define K22_ATT_V_AT(KT) (Vg + (int64_t)row * p.Tkp + (KT) * 64 + cc * EPC)
+// O^T accumulators of a lane (two 32-channel blocks of its query t) * inv -> out, one rounding
+template <typename TS>
+__device__ __forceinline__ void att_store_out(const AttentionParams& p, const f32x16_t (&o)[2], float inv, int t, int b, int hd, int h) {
+  using T = typename AttC<TS>::type;
+  using TG = typename AttC<TS>::mem;
+  if (t >= p.T) return;
+  TG* orow = reinterpret_cast<TG*>(p.out) + (int64_t)(b * p.T + t) * p.ldo + hd * 64;
+  const bool x3 = (AttC<TS>::MIX || is_x3<T>::value) && p.out_x3;   // the proj_out GEMM of the split engines reads this tensor as its A operand
+#pragma unroll
+  for (int db = 0; db < 2; ++db)
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+      att_store4(orow, db * 32 + 8 * g + 4 * h, x3, [&](int j) { return o[db][4 * g + j] * inv; });
+}
+
 // DBG (K22_ATT_PROBE builds only, wrong results; 32 = attention_pipe_kernel without its sched_group_barrier pins): 1 = the K / V^T tiles are staged once (no barriers, stores or global loads inside the loop),
 // 2 = no v_exp (p = the fma result), 4 = no S MFMAs, 8 = no PV MFMAs, 16 = no max / rescale.  tools/micro/attn_probe.hip
 template <typename TS, int DBG = 0>
 __global__ __launch_bounds__(256, 2) void attention_kernel(AttentionParams p) {
   using T = typename AttC<TS>::type;          // arithmetic / LDS type
   constexpr bool MIX = AttC<TS>::MIX;         // fp32 tensors in memory, fp16 tiles and MFMAs (xh_t)
-  using TG = typename std::conditional<MIX, float, T>::type;   // element type of q / K_all / V^T_all / out in memory
+  using TG = typename AttC<TS>::mem;          // element type of q / K_all / V^T_all / out in memory
   using TR = TT<T>;
   constexpr int EPC = TR::EPC, BK = TR::BK, KSTEPS = TR::KSTEPS;
   constexpr int NSUB = 64 / BK;   // 128-byte sub-tiles per 64-element row (1 bf16, 2 fp32)
@@ -152,33 +90,19 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(AttentionParams p) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int h = lane >> 5, l31 = lane & 31;
   const int hd = blockIdx.y, b = blockIdx.z;
-  const int t = blockIdx.x * 128 + wave * 32 + l31;
-  const int tq = t < p.T ? t : p.T - 1;
+  K22_ATT_PROLOGUE(blockIdx.x);
 
-  const TG* qrow = reinterpret_cast<const TG*>(p.q) + (int64_t)(b * p.T + tq) * p.ldq + hd * 64;
-  Frag<T> qf[4];
-#pragma unroll
-  for (int a = 0; a < 4; ++a) ld_qfrag(qf[a], qrow + 16 * a + 8 * h);
-
-  const TG* Kg = reinterpret_cast<const TG*>(p.kall) + (int64_t)(b * p.H + hd) * p.Tkp * 64;
-  const TG* Vg = reinterpret_cast<const TG*>(p.vtall) + (int64_t)(b * p.H + hd) * 64 * p.Tkp;
-  const int nkt = (p.Tk + 63) / 64;
-
-  // unconditional, native-vector staging (conditional staging ends up in scratch memory)
   u32x4_t kreg[GCH], vreg[GCH];
 #define K22_ATT_GLOAD(KT)                                                                                \
   {                                                                                                      \
     const int kt_ = (KT);                                                                                \
     _Pragma("unroll") for (int i = 0; i < LCH; ++i) {                                                    \
       const int q = tid + i * 256, row = q / CPR, cc = q - row * CPR;                                    \
-      if constexpr (MIX) {   /* one fp16 chunk of the tile = two consecutive fp32 chunks in memory */    \
-        const float* kp_ = Kg + (int64_t)(kt_ * 64 + row) * 64 + cc * EPC;                               \
-        const float* vp_ = Vg + (int64_t)row * p.Tkp + kt_ * 64 + cc * EPC;                              \
-        kreg[2 * i] = *reinterpret_cast<const u32x4_t*>(kp_); kreg[2 * i + 1] = *reinterpret_cast<const u32x4_t*>(kp_ + 4); \
-        vreg[2 * i] = *reinterpret_cast<const u32x4_t*>(vp_); vreg[2 * i + 1] = *reinterpret_cast<const u32x4_t*>(vp_ + 4); \
+      if constexpr (MIX) {   /* both addresses first, then the four loads */                            \
+        const TG* kp_ = K22_ATT_K_AT(kt_); const TG* vp_ = K22_ATT_V_AT(kt_);                            \
+        att_gload<MIX>(kreg, i, kp_); att_gload<MIX>(vreg, i, vp_);                                      \
       } else {                                                                                           \
-      kreg[i] = *reinterpret_cast<const u32x4_t*>(Kg + (int64_t)(kt_ * 64 + row) * 64 + cc * EPC);       \
-      vreg[i] = *reinterpret_cast<const u32x4_t*>(Vg + (int64_t)row * p.Tkp + kt_ * 64 + cc * EPC);      \
+        att_gload<MIX>(kreg, i, K22_ATT_K_AT(kt_)); att_gload<MIX>(vreg, i, K22_ATT_V_AT(kt_));          \
       }                                                                                                  \
     }                                                                                                    \
   }
@@ -297,28 +221,20 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(AttentionParams p) {
 
   const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
   const float inv = (std::is_same<T, x3_t>::value ? K22_ATT_X3_PSCALE_INV : 1.f) / l_tot;   // x3: the accumulators hold 2^10 P V (make_pfrag)
-  if (t < p.T) {
-    TG* orow = reinterpret_cast<TG*>(p.out) + (int64_t)(b * p.T + t) * p.ldo + hd * 64;
+  if constexpr (MIX || is_x3<T>::value) {   // the split types keep their own store loop: through att_store_out their instruction order moves
+    if (t < p.T) {
+      TG* orow = reinterpret_cast<TG*>(p.out) + (int64_t)(b * p.T + t) * p.ldo + hd * 64;
 #pragma unroll
-    for (int db = 0; db < 2; ++db)
+      for (int db = 0; db < 2; ++db)
 #pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int d = db * 32 + 8 * g + 4 * h;
-        if constexpr (MIX) {
+        for (int g = 0; g < 4; ++g) {
+          const int d = db * 32 + 8 * g + 4 * h;
           if (p.out_x3) x3_store4(orow + d, x3_split4(o[db][4 * g] * inv, o[db][4 * g + 1] * inv, o[db][4 * g + 2] * inv, o[db][4 * g + 3] * inv));
           else *reinterpret_cast<float4*>(orow + d) = make_float4(o[db][4 * g] * inv, o[db][4 * g + 1] * inv, o[db][4 * g + 2] * inv, o[db][4 * g + 3] * inv);
-        } else if constexpr (sizeof(T) == 2) {
-          uint2 w;
-          w.x = pack2<T>(o[db][4 * g] * inv, o[db][4 * g + 1] * inv);
-          w.y = pack2<T>(o[db][4 * g + 2] * inv, o[db][4 * g + 3] * inv);
-          *reinterpret_cast<uint2*>(orow + d) = w;
-        } else if (is_x3<T>::value && p.out_x3) {   // the proj_out GEMM reads this tensor as its A operand: x3 chunks
-          x3_store4(orow + d, x3_split4(o[db][4 * g] * inv, o[db][4 * g + 1] * inv, o[db][4 * g + 2] * inv, o[db][4 * g + 3] * inv));
-        } else {
-          *reinterpret_cast<float4*>(orow + d) =
-              make_float4(o[db][4 * g] * inv, o[db][4 * g + 1] * inv, o[db][4 * g + 2] * inv, o[db][4 * g + 3] * inv);
         }
-      }
+    }
+  } else {
+    att_store_out<TS>(p, o, inv, t, b, hd, h);
   }
 }
 
@@ -353,7 +269,7 @@ template <typename TS, int DBG = 0>
 __global__ __launch_bounds__(256, 2) void attention_pipe_kernel(AttentionParams p) {
   using T = typename AttC<TS>::type;
   constexpr bool MIX = AttC<TS>::MIX;
-  using TG = typename std::conditional<MIX, float, T>::type;
+  using TG = typename AttC<TS>::mem;
   static_assert(sizeof(T) == 2, "attention_pipe_kernel: 16-bit tiles");
   constexpr int EPC = 8, CPR = 8, LCH = 2;
   constexpr int GCH = MIX ? 2 * LCH : LCH;
@@ -372,43 +288,20 @@ __global__ __launch_bounds__(256, 2) void attention_pipe_kernel(AttentionParams 
   if (!(DBG & 64)) { const int q8 = nblk >> 3, r8 = nblk & 7, x8 = L & 7; L = (x8 < r8 ? x8 * (q8 + 1) : r8 * (q8 + 1) + (x8 - r8) * q8) + (L >> 3); }
   const int pair = L / nqb, qb = L - pair * nqb;
   const int b = pair / p.H, hd = pair - b * p.H;
-  const int t = qb * 128 + wave * 32 + l31;
-  const int tq = t < p.T ? t : p.T - 1;
-  const TG* qrow = reinterpret_cast<const TG*>(p.q) + (int64_t)(b * p.T + tq) * p.ldq + hd * 64;
-  Frag<T> qf[4];
-#pragma unroll
-  for (int a = 0; a < 4; ++a) ld_qfrag(qf[a], qrow + 16 * a + 8 * h);
-  const TG* Kg = reinterpret_cast<const TG*>(p.kall) + (int64_t)(b * p.H + hd) * p.Tkp * 64;
-  const TG* Vg = reinterpret_cast<const TG*>(p.vtall) + (int64_t)(b * p.H + hd) * 64 * p.Tkp;
-  const int nkt = (p.Tk + 63) / 64;
+  K22_ATT_PROLOGUE(qb);
 
   u32x4_t kreg[GCH], vreg[GCH];
-#define K22_AP_KLOAD(KT)                                                                                 \
+  // tiles past the last one are loaded as the last one (never stored)
+#define K22_AP_LOAD(KT, REG, AT)                                                                         \
   {                                                                                                      \
     const int kt_ = (KT) < nkt ? (KT) : nkt - 1;                                                         \
     _Pragma("unroll") for (int i = 0; i < LCH; ++i) {                                                    \
       const int q = tid + i * 256, row = q / CPR, cc = q - row * CPR;                                    \
-      if constexpr (MIX) {                                                                               \
-        const float* kp_ = reinterpret_cast<const float*>(Kg) + (int64_t)(kt_ * 64 + row) * 64 + cc * EPC; \
-        kreg[2 * i] = *reinterpret_cast<const u32x4_t*>(kp_); kreg[2 * i + 1] = *reinterpret_cast<const u32x4_t*>(kp_ + 4); \
-      } else {                                                                                           \
-        kreg[i] = *reinterpret_cast<const u32x4_t*>(Kg + (int64_t)(kt_ * 64 + row) * 64 + cc * EPC);     \
-      }                                                                                                  \
+      att_gload<MIX>(REG, i, AT);                                                                        \
     }                                                                                                    \
   }
-#define K22_AP_VLOAD(KT)                                                                                 \
-  {                                                                                                      \
-    const int kt_ = (KT) < nkt ? (KT) : nkt - 1;                                                         \
-    _Pragma("unroll") for (int i = 0; i < LCH; ++i) {                                                    \
-      const int q = tid + i * 256, row = q / CPR, cc = q - row * CPR;                                    \
-      if constexpr (MIX) {                                                                               \
-        const float* vp_ = reinterpret_cast<const float*>(Vg) + (int64_t)row * p.Tkp + kt_ * 64 + cc * EPC; \
-        vreg[2 * i] = *reinterpret_cast<const u32x4_t*>(vp_); vreg[2 * i + 1] = *reinterpret_cast<const u32x4_t*>(vp_ + 4); \
-      } else {                                                                                           \
-        vreg[i] = *reinterpret_cast<const u32x4_t*>(Vg + (int64_t)row * p.Tkp + kt_ * 64 + cc * EPC);    \
-      }                                                                                                  \
-    }                                                                                                    \
-  }
+#define K22_AP_KLOAD(KT) K22_AP_LOAD(KT, kreg, K22_ATT_K_AT(kt_))
+#define K22_AP_VLOAD(KT) K22_AP_LOAD(KT, vreg, K22_ATT_V_AT(kt_))
 #define K22_AP_KSTORE(DST)                                                                               \
   {                                                                                                      \
     _Pragma("unroll") for (int i = 0; i < LCH; ++i) {                                                    \
@@ -561,33 +454,16 @@ __global__ __launch_bounds__(256, 2) void attention_pipe_kernel(AttentionParams 
 
   const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
   const float inv = 1.f / l_tot;
-  if (t < p.T) {
-    TG* orow = reinterpret_cast<TG*>(p.out) + (int64_t)(b * p.T + t) * p.ldo + hd * 64;
-#pragma unroll
-    for (int db = 0; db < 2; ++db)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int d = db * 32 + 8 * g + 4 * h;
-        if constexpr (MIX) {
-          if (p.out_x3) x3_store4(orow + d, x3_split4(o[db][4 * g] * inv, o[db][4 * g + 1] * inv, o[db][4 * g + 2] * inv, o[db][4 * g + 3] * inv));
-          else *reinterpret_cast<float4*>(orow + d) = make_float4(o[db][4 * g] * inv, o[db][4 * g + 1] * inv, o[db][4 * g + 2] * inv, o[db][4 * g + 3] * inv);
-        } else {
-          uint2 w;
-          w.x = pack2<T>(o[db][4 * g] * inv, o[db][4 * g + 1] * inv);
-          w.y = pack2<T>(o[db][4 * g + 2] * inv, o[db][4 * g + 3] * inv);
-          *reinterpret_cast<uint2*>(orow + d) = w;
-        }
-      }
-  }
+  att_store_out<TS>(p, o, inv, t, b, hd, h);
 }
 
 // ---- small-T attention of the prior transformer (QKVMultiheadAttention, kandinsky2/model/prior.py:86-102) ---------------------------
 // T <= 128 tokens (the prior: 81), one workgroup per (head, image), every key in ONE tile: no online rescale, no kv_pack pass and no
 // per-score global mask loads.  q / k / v are read straight from the c_qkv output  qkv[B * T][ldq] = [Q | K | V] x [head][64]  (row-major,
 // written by the skinny GEMM); K goes to the LDS as rows, V transposed, the additive mask of prior.py:262-263 (-inf for padding keys and
-// for keys after the query) as one float per key.  Wave w owns queries 32 w .. 32 w + 31; the arithmetic is attention_kernel's (S^T = K Q^T
-// so a lane owns one query, lane-local fp32 softmax, P from the accumulator registers).  The output is written row-major or in the
-// A-fragment order of the skinny GEMM that reads it (c_proj), selected by out_frag.  16-bit storage types.
+// for keys after the query) as one float per key.  Wave w owns queries 32 w .. 32 w + 31; scheme and arithmetic contract:
+// attention_common.h.  The output is written row-major or in the A-fragment order of the skinny GEMM that reads it (c_proj), selected by
+// out_frag.  16-bit storage types.  LDS: K 16 KB + V^T 16 KB + the key mask.
 template <typename T>
 __global__ __launch_bounds__(256) void small_attention_kernel(SmallAttnParams p) {
   __shared__ __attribute__((aligned(16))) char smem[2 * 16384 + 512];
@@ -645,8 +521,7 @@ __global__ __launch_bounds__(256) void small_attention_kernel(SmallAttnParams p)
     char* vsub = Vs + (key >> 6) * 8192;
     const int kk = key & 63;
 #pragma unroll
-    for (int e = 0; e < 8; ++e)   // key-permuted V^T tile (vt_store16's layout): key kk -> piece 2 (kk >> 4) + ((kk >> 2) & 1), byte 8 ((kk >> 3) & 1) + 2 (kk & 3)
-      *reinterpret_cast<unsigned short*>(vsub + lds_chunk_off(c * 8 + e, 2 * (kk >> 4) + ((kk >> 2) & 1)) + 8 * ((kk >> 3) & 1) + 2 * (kk & 3)) = ve[e];
+    for (int e = 0; e < 8; ++e) K22_VT_STORE1(vsub, c * 8 + e, kk, ve[e]);   // transpose: channel c * 8 + e is the V^T row
   }
   if (tid < 128) kdead[tid] = (p.key_valid != nullptr && tid < p.kv_n && p.key_valid[(int64_t)b * p.kv_ld + tid] == 0.f) ? 1.f : 0.f;
   __syncthreads();
@@ -715,15 +590,13 @@ __global__ __launch_bounds__(256) void small_attention_kernel(SmallAttnParams p)
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
       const int d = db * 32 + 8 * g + 4 * h;
-      uint2 w2;
-      w2.x = pack2<T>(o[db][4 * g] * inv, o[db][4 * g + 1] * inv);
-      w2.y = pack2<T>(o[db][4 * g + 2] * inv, o[db][4 * g + 3] * inv);
+      const auto y = [&](int j) { return o[db][4 * g + j] * inv; };
       if (p.out_frag) {
         const int k = hd * 64 + d;   // K index of the consumer GEMM: [K / 64][MA][4][64][8]
         const int64_t off = ((((int64_t)(k >> 6) * p.MA + (m >> 5)) * 4 + ((k >> 4) & 3)) * 64 + (m & 31) + 32 * ((k >> 3) & 1)) * 8 + (k & 7);
-        *reinterpret_cast<uint2*>(out + off) = w2;
+        att_store4(out, off, false, y);
       } else {
-        *reinterpret_cast<uint2*>(out + (int64_t)m * p.ldo + hd * 64 + d) = w2;
+        att_store4(out, (int64_t)m * p.ldo + hd * 64 + d, false, y);
       }
     }
 }

@@ -300,7 +300,7 @@ template <typename T> __device__ __forceinline__ float acc_unscale(float v) {
   if constexpr (is_x3<T>::value) return v * K22_X3_WSCALE_INV; else return v;
 }
 
-__device__ __forceinline__ int c_row(int reg, int lane) { return (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5); }
+constexpr __host__ __device__ __forceinline__ int c_row(int reg, int lane) { return (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5); }
 
 // Raw workgroup barrier (no implied vmcnt/lgkmcnt drain: LDS-DMA stays in flight across it) that the COMPILER may not
 // move LDS accesses across: the builtin alone is not a memory barrier for the optimiser.

@@ -9,13 +9,14 @@
 //   per 32-key tile   S_w^T[key][q] = K[key][slice w] . Q[q][slice w]   (A = K tile rows from LDS, B = the wave's Q slice in registers)
 //                     S^T = ((S_0 + S_1) + S_2) + S_3                   (partials exchanged through LDS, summed in wave order by every wave:
 //                                                                        the four waves hold the same bits)
-//                     lane-local fp32 online softmax as attention.hip's (ONE query per lane column, 16 keys of the tile per lane half)
+//                     lane-local fp32 online softmax (ONE query per lane column, 16 keys of the tile per lane half)
 //                     O_w^T[d][q] += V^T[d][key] . P^T[key][q]          (A = the wave's C/4 rows of the V^T tile, B = P from the S^T registers)
-// Arithmetic contract (attention.hip's): fp32 scores, maximum and sum; the sum is taken over the unrounded probabilities; P is rounded once to
-// the storage type in front of the P V product (fp32: not at all); one rounding on store.  No atomics, a fixed reduction order, and nothing in
-// a tile's arithmetic depends on B or on the grid: image b of a batch has the bits of the same image launched alone.
+// Scheme, fragments, V^T tile layout and the arithmetic contract: attention_common.h.  bias_v is added after the normalisation, before the
+// one rounding on store.
 // LDS at C = 512: K tile 32 KB + V^T tile 32 KB + exchange 32 KB (16-bit); fp32: 64 + 64 KB, the exchange reuses the K tile's bytes.
-#include "kernels.h"
+// 16-bit V^T tile: a row of 32 keys is 64 bytes, so one 128-byte LDS row holds channel d (pieces 0-3) and channel d + C/2 (pieces 4-7),
+// each half key-permuted (vt_store16 / ld_frag_split with base piece 4 * half).  fp32 tiles: row = channel, 32 keys in natural order.
+#include "attention_common.h"
 #include <atomic>
 #include <math.h>
 
@@ -33,51 +34,6 @@ constexpr int MQ_KT = 32;            // keys per tile
 template <typename T> constexpr int MQ_NQB = sizeof(T) == 2 ? 2 : 1;
 // partial-score exchange, bytes per wave: [q block][register group 4][lane 64] float4 (fp32: 4 x 4 KB, never more than the smallest K tile)
 template <typename T> constexpr int MQ_XWAVE = MQ_NQB<T> * 4096;
-
-template <typename T> __device__ __forceinline__ float mq_exp2(float x);
-template <> __device__ __forceinline__ float mq_exp2<bf16_t>(float x) { return __builtin_amdgcn_exp2f(x); }
-template <> __device__ __forceinline__ float mq_exp2<f16_t>(float x) { return __builtin_amdgcn_exp2f(x); }
-template <> __device__ __forceinline__ float mq_exp2<float>(float x) { return exp2f(x); }
-
-__device__ __forceinline__ void mq_qfrag(Frag<bf16_t>& f, const bf16_t* p) { f.v = *reinterpret_cast<const u32x4_t*>(p); }
-__device__ __forceinline__ void mq_qfrag(Frag<f16_t>& f, const f16_t* p) { f.v = *reinterpret_cast<const u32x4_t*>(p); }
-__device__ __forceinline__ void mq_qfrag(Frag<float>& f, const float* p) {
-  const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
-  f.v[0] = a.x; f.v[1] = a.y; f.v[2] = a.z; f.v[3] = a.w;
-  f.v[4] = b.x; f.v[5] = b.y; f.v[6] = b.z; f.v[7] = b.w;
-}
-__device__ __forceinline__ void mq_pfrag(Frag<bf16_t>& f, const float* p) {
-  f.v = u32x4_t{pack2_bf16(p[0], p[1]), pack2_bf16(p[2], p[3]), pack2_bf16(p[4], p[5]), pack2_bf16(p[6], p[7])};
-}
-__device__ __forceinline__ void mq_pfrag(Frag<f16_t>& f, const float* p) {
-  f.v = u32x4_t{pack2_f16(p[0], p[1]), pack2_f16(p[2], p[3]), pack2_f16(p[4], p[5]), pack2_f16(p[6], p[7])};
-}
-__device__ __forceinline__ void mq_pfrag(Frag<float>& f, const float* p) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) f.v[j] = p[j];
-}
-
-// V^T fragment of 16-key atom a whose K (= key) order is that of the S^T accumulator registers:
-// element j < 4 -> key 16 a + 4 h + j ; j >= 4 -> key 16 a + 8 + 4 h + (j - 4).
-// 16-bit tiles: a V^T row of 32 keys is 64 bytes, so one 128-byte LDS row holds channel d (pieces 0-3) and channel d + C/2 (pieces 4-7);
-// within a row the keys are permuted as in attention.hip (mq_vt_store16) so that the fragment is ONE ds_read_b128 of piece 2 a + h.
-template <typename T> __device__ __forceinline__ void mq_vfrag(Frag<T>& f, const char* tile, int row, int half, int a, int h) {
-  f.v = *reinterpret_cast<const u32x4_t*>(tile + lds_chunk_off(row, 4 * half + 2 * a + h));
-}
-// fp32 tiles: row = channel, 32 keys in natural order
-template <> __device__ __forceinline__ void mq_vfrag<float>(Frag<float>& f, const char* tile, int row, int half, int a, int h) {
-  (void)half;
-  const float4 lo = *reinterpret_cast<const float4*>(tile + lds_chunk_off(row, 4 * a + h));
-  const float4 hi = *reinterpret_cast<const float4*>(tile + lds_chunk_off(row, 4 * a + 2 + h));
-  f.v[0] = lo.x; f.v[1] = lo.y; f.v[2] = lo.z; f.v[3] = lo.w;
-  f.v[4] = hi.x; f.v[5] = hi.y; f.v[6] = hi.z; f.v[7] = hi.w;
-}
-// keys 8 cc .. 8 cc + 7 (one 16-byte register, natural order) of a 16-bit V^T row: keys +0..3 go to piece (cc & ~1), keys +4..7 to
-// piece (cc | 1) of the row's half, both at byte 8 (cc & 1)
-__device__ __forceinline__ void mq_vt_store16(char* tile, int row, int half, int cc, const u32x4_t v) {
-  *reinterpret_cast<u32x2_t*>(tile + lds_chunk_off(row, 4 * half + (cc & ~1)) + 8 * (cc & 1)) = u32x2_t{v.x, v.y};
-  *reinterpret_cast<u32x2_t*>(tile + lds_chunk_off(row, 4 * half + (cc | 1)) + 8 * (cc & 1)) = u32x2_t{v.z, v.w};
-}
 
 template <typename T, int C>
 __global__ __launch_bounds__(256) void movq_attention_kernel(MovqAttnParams p) {
@@ -115,7 +71,7 @@ __global__ __launch_bounds__(256) void movq_attention_kernel(MovqAttnParams p) {
 #pragma unroll
   for (int qb = 0; qb < NQB; ++qb)
 #pragma unroll
-    for (int a = 0; a < NA; ++a) mq_qfrag(qf[qb][a], Qg + (int64_t)(q0 + qb * 32 + l31) * C + wave * CW + 16 * a + 8 * h);
+    for (int a = 0; a < NA; ++a) ld_qfrag(qf[qb][a], Qg + (int64_t)(q0 + qb * 32 + l31) * C + wave * CW + 16 * a + 8 * h);
 
   // Staging: thread -> (row, 16-byte piece) maps under which every LDS swizzle and every lane offset is the same for all of a thread's
   // chunks (one address register per tensor, the rest immediates).  K: row = tid >> 3, chunk (tid & 7) of sub-tile i.  V^T: channel
@@ -151,7 +107,7 @@ __global__ __launch_bounds__(256) void movq_attention_kernel(MovqAttnParams p) {
         *reinterpret_cast<u32x4_t*>(Vs + i * DR * 128 + lds_chunk_off(vd, vc)) = VR[i];                   \
       } else {                                                                                            \
         const int half = i * DR >= C / 2 ? 1 : 0;   /* channel vd + i DR: LDS row vd + i DR - half C/2 */ \
-        mq_vt_store16(Vs + (i * DR - half * (C / 2)) * 128, vd, half, vc, VR[i]);                         \
+        vt_store16(Vs + (i * DR - half * (C / 2)) * 128, vd, vc, VR[i], 4 * half);                        \
       }                                                                                                   \
     }                                                                                                     \
   }
@@ -242,7 +198,7 @@ __global__ __launch_bounds__(256) void movq_attention_kernel(MovqAttnParams p) {
 #pragma unroll
       for (int qb = 0; qb < NQB; ++qb) {
         const float m_new = fmaxf(m_run[qb], mloc[qb]);
-        const float alpha = mq_exp2<T>((m_run[qb] - m_new) * cexp);
+        const float alpha = exp2_t<T>((m_run[qb] - m_new) * cexp);
         l_run[qb] *= alpha;
         m_run[qb] = m_new;
 #pragma unroll
@@ -257,7 +213,7 @@ __global__ __launch_bounds__(256) void movq_attention_kernel(MovqAttnParams p) {
       float lsum = 0.f;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const float e = mq_exp2<T>(fmaf(pv[qb][r], cexp, -mc));
+        const float e = exp2_t<T>(fmaf(pv[qb][r], cexp, -mc));
         pv[qb][r] = e;
         lsum += e;
       }
@@ -269,12 +225,12 @@ __global__ __launch_bounds__(256) void movq_attention_kernel(MovqAttnParams p) {
     for (int a = 0; a < 2; ++a) {
       Frag<T> pf[NQB];
 #pragma unroll
-      for (int qb = 0; qb < NQB; ++qb) mq_pfrag(pf[qb], &pv[qb][8 * a]);
+      for (int qb = 0; qb < NQB; ++qb) make_pfrag(pf[qb], &pv[qb][8 * a]);
 #pragma unroll
       for (int db = 0; db < NDB; ++db) {
         Frag<T> vf;
-        if constexpr (WIDE) mq_vfrag<T>(vf, Vs, wave * CW + db * 32 + l31, 0, a, h);
-        else mq_vfrag<T>(vf, Vs, (wave & 1) * CW + db * 32 + l31, wave >> 1, a, h);
+        if constexpr (WIDE) ld_frag_split(vf, Vs, wave * CW + db * 32 + l31, a, h);
+        else ld_frag_split(vf, Vs, (wave & 1) * CW + db * 32 + l31, a, h, 4 * (wave >> 1));
 #pragma unroll
         for (int qb = 0; qb < NQB; ++qb) mma_atom(o[db][qb], vf, pf[qb]);
       }
@@ -300,16 +256,10 @@ __global__ __launch_bounds__(256) void movq_attention_kernel(MovqAttnParams p) {
 #pragma unroll
           for (int j = 0; j < 4; ++j) bv[j] = p.bias_v[wave * CW + d + j];
         }
-        const float y0 = o[db][qb][4 * g] * inv + bv[0], y1 = o[db][qb][4 * g + 1] * inv + bv[1];
-        const float y2 = o[db][qb][4 * g + 2] * inv + bv[2], y3 = o[db][qb][4 * g + 3] * inv + bv[3];
-        if constexpr (ES == 2) {
-          uint2 w2;
-          w2.x = pack2<T>(y0, y1);
-          w2.y = pack2<T>(y2, y3);
-          *reinterpret_cast<uint2*>(orow + d) = w2;
-        } else {
-          *reinterpret_cast<float4*>(orow + d) = make_float4(y0, y1, y2, y3);
-        }
+        float y[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) y[j] = o[db][qb][4 * g + j] * inv + bv[j];
+        att_store4(orow, d, false, [&](int j) { return y[j]; });
       }
   }
 }
