@@ -14,6 +14,10 @@ LIB_PATH = os.environ.get("K22_LIB_PATH") or os.path.join(_HERE, "libk22hip.so")
 # loaded when the library is opened so that those shapes run the same configurations - the same bits - on every box.
 # K22_TILE_TABLE=<file> substitutes another table, K22_TILE_TABLE=0 starts with an empty one.
 TILE_TABLE_PATH = os.path.join(_HERE, "tiles_gfx950.txt")
+# Lines re-measured since, for a candidate that joined the list later: loaded behind the shipped table (a later line wins), so the lines
+# they replace stay in tiles_gfx950.txt - still configurations this build generates, still swept by tests/test_tile_table_gpu.py, and
+# what K22_TILE_TABLE=<that file> selects for an A/B.  Only loaded with the shipped table itself (K22_TILE_TABLE unset).
+TILE_TABLE_LATER_PATHS = (os.path.join(_HERE, "tiles_gfx950_bm224.txt"),)   # the 224-row tile at the 96x96 level
 
 K22_BF16, K22_F32, K22_F16, K22_F16X3, K22_F16X2 = 0, 1, 2, 3, 4
 K22_LOOP_DDIM, K22_LOOP_PLMS = 0, 1   # include/k22.h: kind of k22_unet_ddim_loop
@@ -238,6 +242,10 @@ def lib() -> C.CDLL:
         if tbl != "0" and os.path.exists(tbl):
             if l.k22_tile_table_load(tbl.encode()) < 0:
                 raise RuntimeError(f"k22: cannot read the tile table {tbl}")
+            if "K22_TILE_TABLE" not in os.environ:
+                for later in TILE_TABLE_LATER_PATHS:     # part of the package: a missing file is an error, not a slower run
+                    if l.k22_tile_table_load(later.encode()) < 0:
+                        raise RuntimeError(f"k22: cannot read the tile table {later}")
     return _lib
 
 

@@ -351,6 +351,18 @@ template <bool GASM, bool WEIGHT> __device__ __forceinline__ void halo_dma16(con
     __builtin_amdgcn_sched_barrier(0);                                                                     \
   }
 #define K22_PIPE_INTERLEAVED (void)0, K22_INTERLEAVE()
+// The same for a block with one read MORE than it has MFMAs (NRD = NMF + 1: the 224-row tile's 7 + 1 reads for 7 MFMAs per k-step, where
+// MPR is 0): the surplus read in front, then one read behind every MFMA.
+#define K22_INTERLEAVE_LEAD()                                                                              \
+  {                                                                                                        \
+    static_assert(NRD == NMF + 1, "one read in front, one behind every MFMA");                             \
+    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                                                     \
+    _Pragma("unroll") for (int i_ = 0; i_ < NMF; ++i_) {                                                   \
+      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                                   \
+      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                                                   \
+    }                                                                                                      \
+    __builtin_amdgcn_sched_barrier(0);                                                                     \
+  }
 
 // M(tap, ...) for every tap of the filter, with literal tap numbers: the vmcnt immediates and the (slab, tap) of the prefetched weight
 // tile are compile-time functions of the tap
@@ -430,29 +442,39 @@ template <bool GASM, bool WEIGHT> __device__ __forceinline__ void halo_dma16(con
 namespace {
 // fragment reads of one block of the interleaved pipeline (x2: the activation fragment is ONE read, hi piece only)
 template <typename T, int MI, int NI> constexpr int halo_pipe_reads() { return is_x2<T>::value ? MI + 2 * NI : (MI + NI) * FragCost<T>::READS; }
+// How the waves that hold accumulators share the BM x 128 tile: WM x WN waves of (BM / WM) x (128 / WN) each.  Lock-step kernels: all eight,
+// 4 x 2.  conv3_halo_spec_kernel: its four consumers, 2 x 2 - except the 224-row tile (7 m-blocks of 32 rows do not halve): 1 x 4, one
+// 32-column strip of all seven m-blocks per wave.
+constexpr int HALO_BM_STRIP = 224;
+template <int BM, bool SPEC> constexpr int halo_wm() { return !SPEC ? 4 : (BM == HALO_BM_STRIP ? 1 : 2); }
+template <int BM, bool SPEC> constexpr int halo_wn() { return (SPEC && BM == HALO_BM_STRIP) ? 4 : 2; }
+template <int BM, bool SPEC> constexpr int halo_mi() { return BM / (halo_wm<BM, SPEC>() * 32); }
+template <int BM, bool SPEC> constexpr int halo_ni() { return HALO_BN / (halo_wn<BM, SPEC>() * 32); }
+// stages of the fused skip's LDS-DMA ring (kernel and LDS budget): 3 x 48 KB (44 KB at 224 rows) / 4 x 32 KB of the 160 KB
+constexpr int halo_skip_stages(int bm) { return bm > 128 ? 3 : 4; }
 }  // namespace
 
 // Everything after the 3x3 K loop, shared by the halo kernels: optional fused 1x1 skip connection (a plain-GEMM K loop
 // on 128-byte rows), then the epilogue through LDS (bias, residual, one rounding, 16-byte stores, GroupNorm partials).
 // PLAIN = false: rows are positions v of the padded plane (3x3 convolution); PLAIN = true: rows are the pixels
 // v < H*W of image `img` themselves (gemm8_kernel), and the qkv-projection output mode is available.
-// SPEC = true (conv3_halo_spec_kernel): only waves 0-3 hold accumulators, 2 x 2 over the tile with (BM/2) x 64 each; waves 4-7
-// were the producers of the main loop.  All eight waves issue the skip loop's LDS-DMA and run the store / statistics epilogue.
+// SPEC = true (conv3_halo_spec_kernel): only waves 0-3 hold accumulators, 2 x 2 over the tile with (BM/2) x 64 each (BM = 224: 1 x 4,
+// 224 x 32 each - halo_wm / halo_wn); waves 4-7 were the producers of the main loop.  All eight waves issue the skip loop's LDS-DMA and run the store / statistics epilogue.
 // UP2 = true (conv3_up2_kernel, conv3_up2.hip): rows are positions v of the LOW-resolution padded plane and row (y, x) of phase ph = 2*py + px
 // is stored at (2y + py, 2x + px) of the unpadded 2H x 2W output; p.M counts the output's rows; bx = the statistics row of this tile.
 template <typename T, int BM, bool PLAIN = false, bool SPEC = false, bool UP2 = false>
-__device__ __forceinline__ void halo_tail(const IgemmParams& p, f32x16_t (&acc)[SPEC ? BM / 64 : BM / 128][2], char* smem, int bx, int bz, int img, int v0, int n0,
+__device__ __forceinline__ void halo_tail(const IgemmParams& p, f32x16_t (&acc)[halo_mi<BM, SPEC>()][halo_ni<BM, SPEC>()], char* smem, int bx, int bz, int img, int v0, int n0,
                                           int ph = 0) {
   using TR = TT<T>;
   constexpr int BK = TR::BK, EPC = TR::EPC, KSTEPS = TR::KSTEPS;
-  constexpr int BN = HALO_BN, NW = HALO_NW, WM = SPEC ? 2 : 4, WN = 2;
+  constexpr int BN = HALO_BN, NW = HALO_NW, WM = halo_wm<BM, SPEC>(), WN = halo_wn<BM, SPEC>();
   constexpr int MI = BM / (WM * 32), NI = BN / (WN * 32);
   constexpr int B_SLOTS = BN / 8 / NW;
   constexpr int B_BYTES = BN * 128;
   constexpr int TS = BN * 4 + 16;       // epilogue tile row stride (bytes): conflict-free float4 writes
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 1, wn = wave & 1;
+  const int wm = WN == 4 ? 0 : wave >> 1, wn = WN == 4 ? wave & 3 : wave & 1;
   const bool cw = !SPEC || wave < 4;      // this wave holds accumulators (wave-uniform)
   const int h = lane >> 5, l31 = lane & 31;
   const int W2 = PLAIN ? 1 : p.W + 2;
@@ -470,14 +492,17 @@ __device__ __forceinline__ void halo_tail(const IgemmParams& p, f32x16_t (&acc)[
     const int sp = p.splitk > 1 ? p.splitk : 1;
     const int q0 = nss * bz / sp, q1 = nss * (bz + 1) / sp;
     if (q0 < q1) {
-      constexpr int SA_SLOTS = BM / 8 / NW;             // input-tile LDS-DMA instructions per wave per slab
+      constexpr int SA_SLOTS = (BM / 8 + NW - 1) / NW;  // input-tile LDS-DMA instructions per wave per slab
+      constexpr bool SA_RAGGED = BM / 8 % NW != 0;      // 224 rows: 28 pieces in 4 x 8 slots - the surplus slots re-load the last piece (same bytes, same place: uniform counting)
       constexpr int SBUF = BM * 128 + B_BYTES;
       wait_vmcnt<0>();
       __syncthreads();                                   // main-loop buffers are free
       int spix[SA_SLOTS], schunk[SA_SLOTS];
 #pragma unroll
       for (int i = 0; i < SA_SLOTS; ++i) {
-        const int row = 8 * (wave + NW * i) + (lane >> 3);
+        int piece = wave + NW * i;
+        if constexpr (SA_RAGGED) { if (piece > BM / 8 - 1) piece = BM / 8 - 1; }
+        const int row = 8 * piece + (lane >> 3);
         int v = v0 + row;
         if (v > VR - 1) v = VR - 1;
         const int y = v / W2;
@@ -497,7 +522,7 @@ __device__ __forceinline__ void halo_tail(const IgemmParams& p, f32x16_t (&acc)[
       // barrier per slab; the DMA is issued from inline asm (glds16_asm) so that hipcc neither drains it nor waits lgkmcnt(0) for it.
       // Slot reuse: iteration q refills the stage iteration q - 1 read, after the barrier every wave reaches only behind its
       // lgkmcnt(0); past-the-end issues re-load the last slab (uniform counting), drained by the vmcnt(0) below the loop.
-      constexpr int NSK = BM == 256 ? 3 : 4;               // 3 x 48 KB / 4 x 32 KB of the 160 KB
+      constexpr int NSK = halo_skip_stages(BM);
       constexpr int SCH = SA_SLOTS + B_SLOTS;              // LDS-DMA instructions per wave per slab
       constexpr bool GASM = true;
       const unsigned lds0 = halo_lds_base(smem);
@@ -511,8 +536,13 @@ __device__ __forceinline__ void halo_tail(const IgemmParams& p, f32x16_t (&acc)[
         const int ldx_ = second_ ? p.SK1 : p.SK0;                                                          \
         const int kk_ = second_ ? k0_ - p.SK0 : k0_;                                                       \
         const unsigned dA_ = lds0 + (BUFI) * SBUF + wave * 1024;                                           \
-        _Pragma("unroll") for (int i = 0; i < SA_SLOTS; ++i)                                               \
+        _Pragma("unroll") for (int i = 0; i < SA_SLOTS; ++i) {                                             \
+          if constexpr (SA_RAGGED) {   /* the destination is clamped with the source: behind the input tile stands the weight stage */ \
+            const int pc_ = wave + NW * i < BM / 8 - 1 ? wave + NW * i : BM / 8 - 1;                       \
+            glds16_asm(xs_ + (int64_t)spix[i] * ldx_ + kk_ + schunk[i], __builtin_amdgcn_readfirstlane(lds0 + (BUFI) * SBUF + pc_ * 1024)); \
+          } else                                                                                           \
             glds16_asm(xs_ + (int64_t)spix[i] * ldx_ + kk_ + schunk[i], __builtin_amdgcn_readfirstlane(dA_ + i * NW * 1024)); \
+        }                                                                                                  \
         K22_ISSUE_ROWS(true, Ws, wsoff, B_SLOTS, NW, k0_, dA_ + BM * 128, smem + (dA_ - lds0) + BM * 128)  \
       }
 #pragma unroll
@@ -705,7 +735,7 @@ inline int halo_tiles_per_image(const IgemmParams& p, int bm) { return (p.H * (p
 inline size_t halo_lds_budget(int bm, bool skip, size_t main_loop) {
   const size_t epi = (size_t)bm * (HALO_BN * 4 + 16);
   const size_t red = (size_t)32 * HALO_BN * 2 * 4;
-  const size_t sk = skip ? (size_t)(bm == 256 ? 3 : 4) * (bm * 128 + HALO_BN * 128) : 0;
+  const size_t sk = skip ? (size_t)halo_skip_stages(bm) * (bm * 128 + HALO_BN * 128) : 0;
   size_t m = main_loop > epi ? main_loop : epi;
   m = m > sk ? m : sk;
   return m > red ? m : red;
@@ -738,10 +768,13 @@ template <auto K> int halo_run(const IgemmParams& p, const IgemmLaunch& L, hipSt
   static LdsAttrGuard guard;
   return launch_lds_kernel(K, guard, L.grid, L.block, L.lds, 160 * 1024, stream, p);
 }
-// f(std::integral_constant<int, BM>): BM = 256 if bm says so and the form has it (HAS256), else 128
-template <bool HAS256 = true, typename F> int halo_with_bm(int bm, F&& f) {
+// f(std::integral_constant<int, BM>): BM = 256 / 224 if bm says so and the form has it (HAS256 / HAS224), else 128
+template <bool HAS256 = true, bool HAS224 = false, typename F> int halo_with_bm(int bm, F&& f) {
   if constexpr (HAS256) {
     if (bm == 256) return f(std::integral_constant<int, 256>{});
+  }
+  if constexpr (HAS224) {
+    if (bm == HALO_BM_STRIP) return f(std::integral_constant<int, HALO_BM_STRIP>{});
   }
   return f(std::integral_constant<int, 128>{});
 }

@@ -320,7 +320,9 @@ int conv3_halo_ring(const IgemmParams& p, int bm) { return p.algo == IG_ALGO_HAL
 
 bool conv3_halo_supported(const IgemmParams& p, int dtype, int bm) {
   const int BK = k22_bk(dtype);
-  if (p.taps != 9 || (bm != 256 && bm != 128)) return false;
+  if (p.taps != 9 || (bm != 256 && bm != 128 && bm != HALO_BM_STRIP)) return false;
+  // the 224-row tile: conv3_halo_spec_kernel's pipelined form in the 16-bit types, without the fused GroupNorm-apply
+  if (bm == HALO_BM_STRIP && (p.algo != IG_ALGO_SPEC_PIPE || k22_esz(dtype) != 2 || p.gn_coeff != nullptr)) return false;
   // split precision: the input is read in x3 chunks; instantiated forms = the lock-step kernel with asm LDS-DMA (algo 2 / 6 / 7 all
   // run it) and the specialised kernel (11 / 12)
   if (k22_is_split(dtype) && (p.a_raw || p.algo == IG_ALGO_HALO3)) return false;

@@ -12,6 +12,10 @@
 //              each) right after its barrier and sit in the counted vmcnt wait for the next tap's tile.
 // Producers and consumers execute the same barriers (one per tap): the ring-slot / halo-buffer reuse argument of
 // conv3_halo_kernel holds unchanged.
+// BM = 224 (16-bit types, PIPE only; no fused GroupNorm-apply): the tile that divides a 96 x 98 plane exactly - 42 tiles per image, 252
+//              workgroups of a 2 x 384-channel problem on 256 CUs where BM = 256 makes 222 - and whose halo image (424 rows) leaves room for a
+//              THIRD weight slot there.  7 m-blocks do not halve, so the consumers take one 32-column strip each (1 x 4: 7 accumulators,
+//              7 + 1 fragment reads per 7 MFMAs; K22_INTERLEAVE_LEAD).  Same MFMA, same order of slabs, taps and k-steps per element.
 // PIPE (algo 12): explicit fragment pipeline in the consumers.  The fragments of k-step ks+1 are read while the MFMAs of
 // k-step ks are issued (two register sets), and the last k-step of a tap is multiplied after the next tap's barrier, where
 // its eight MFMAs cover the latency of that tap's first fragment reads.  Within a block the reads and the MFMAs are
@@ -34,8 +38,9 @@ template <typename T, int BM, int NBST, bool PIPE = false, int DBG = 0>
 __global__ __launch_bounds__(512) void conv3_halo_spec_kernel(const IgemmParams p) {
   using TR = TT<T>;
   constexpr int BK = TR::BK, EPC = TR::EPC, KSTEPS = TR::KSTEPS;
-  constexpr int BN = HALO_BN, NWL = 4, WM = 2, WN = 2;
+  constexpr int BN = HALO_BN, NWL = 4, WM = halo_wm<BM, true>(), WN = halo_wn<BM, true>();
   constexpr int MI = BM / (WM * 32), NI = BN / (WN * 32);
+  constexpr bool STRIP = BM == HALO_BM_STRIP;  // 224 rows: one 32-column strip per consumer, no fused GroupNorm-apply form
   constexpr int B_SLOTS = BN / 8 / NWL;        // 4 weight LDS-DMA instructions per producer per tap
   constexpr int B_BYTES = BN * 128;
   constexpr int APT = 2;                       // halo pieces per producer per tap (taps 0 .. 9-NBST)
@@ -90,7 +95,7 @@ __global__ __launch_bounds__(512) void conv3_halo_spec_kernel(const IgemmParams 
 #define K22_LDS_ADDR(AT) (AT)
 #define K22_LDS_PTR(AT) (smem + ((AT) - lds0))
   if (s0 < s1) {
-    if (producer && p.gn_coeff != nullptr) {
+    if (!STRIP && producer && p.gn_coeff != nullptr) {
       // ------------------------- producers, fused GroupNorm-apply: LDS-DMA of the RAW tensor, then rewrite in place ---------------------
       // The halo piece a producer wave loaded is rewritten by the SAME wave one tap later (its own counted vmcnt orders the ds_read behind
       // the DMA; no other wave touches the buffer until the barrier that opens the next slab): y = act(x * A[c] + Bc[c]), zero at the
@@ -220,7 +225,7 @@ __global__ __launch_bounds__(512) void conv3_halo_spec_kernel(const IgemmParams 
       K22_PRODUCER_LOOP(DBG == 0, DBG != 1, K22_ISSUE_A, K22_PRODUCER_NOTHING)
     } else {
       // ---------------------------------------- consumers: fragments + MFMA only --------------------------------------
-      const int wm = wave >> 1, wn = wave & 1;
+      const int wm = STRIP ? 0 : wave >> 1, wn = STRIP ? wave : wave & 1;
       const int abase = wm * (BM / WM) + l31;
       int brow[NI];
 #pragma unroll
@@ -241,7 +246,8 @@ __global__ __launch_bounds__(512) void conv3_halo_spec_kernel(const IgemmParams 
       {                                                                                                    \
         raw_barrier();                                                                                     \
         K22_TAP_COMPUTE(TAP, 9,                                                                            \
-          if constexpr (PIPE) K22_TAP_PIPE(FragA<T>, Frag<T>, arow[mi], asw[mi], Bcur + brow[ni], bsw, K22_PIPE_INTERLEAVED) \
+          if constexpr (PIPE && STRIP) K22_TAP_PIPE(FragA<T>, Frag<T>, arow[mi], asw[mi], Bcur + brow[ni], bsw, (void)0, K22_INTERLEAVE_LEAD()) \
+          else if constexpr (PIPE) K22_TAP_PIPE(FragA<T>, Frag<T>, arow[mi], asw[mi], Bcur + brow[ni], bsw, K22_PIPE_INTERLEAVED) \
           else { K22_TAP_PLAIN(FragA<T>, Frag<T>, ld_frag_at, arow[mi], asw[mi], Bcur + brow[ni], bsw) })  \
       }
       for (int s = s0; s < s1; ++s) {
@@ -280,8 +286,13 @@ int launch_conv3_halo_spec(const IgemmParams& p, int dtype, const IgemmLaunch& L
       if (L.dbg == 2) return halo_with_depth<2, 4>(L.depth, [&](auto d) { return halo_run<conv3_halo_spec_kernel<T, 256, decltype(d)::value, true, 2>>(p, L, stream); });
     }
 #endif
+    // the 224-row tile: 16-bit types, pipelined form, no fused GroupNorm-apply (112 accumulators beside two sets of 7 + 1 fragments of 4
+    // registers; the wider fragments of the other types do not fit).  conv3_halo_supported says the same; a launch that names it otherwise is refused.
+    constexpr bool pipe224 = std::is_same<T, bf16_t>::value || std::is_same<T, f16_t>::value;
+    if (L.bm == HALO_BM_STRIP && !(pipe224 && L.pipe && p.gn_coeff == nullptr))
+      return k22_set_error(K22_EINVAL, "conv3_halo_spec: the 224-row tile is the pipelined 16-bit form only, without the fused GroupNorm-apply");
     if (!L.pipe) return halo_with_bm(L.bm, [&](auto bm) { return launch_spec_depth<T, decltype(bm)::value, false>(p, L, stream); });
     constexpr bool pipe256 = !std::is_same<T, x3_t>::value && !std::is_same<T, float>::value;
-    return halo_with_bm<pipe256>(L.bm, [&](auto bm) { return launch_spec_depth<T, decltype(bm)::value, true>(p, L, stream); });
+    return halo_with_bm<pipe256, pipe224>(L.bm, [&](auto bm) { return launch_spec_depth<T, decltype(bm)::value, true>(p, L, stream); });
   });
 }

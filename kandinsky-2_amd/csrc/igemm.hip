@@ -522,7 +522,7 @@ int igemm_resolve(const IgemmParams& p, int dtype, IgemmLaunch* out) {
     IgemmParams ph = p;
     ph.algo = igemm_algo_is_halo(conv_algo) ? conv_algo : IG_ALGO_HALO;
     int bm = 0;
-    if (p.force_bm == 256 || p.force_bm == 128) {
+    if (p.force_bm == 256 || p.force_bm == 128 || p.force_bm == 224) {   // (224: the pipelined specialised kernel in the 16-bit types only)
       if (conv3_halo_supported(ph, dtype, p.force_bm) && (conv_algo >= IG_ALGO_HALO || p.force_bn == 0)) bm = p.force_bm;
     } else if (p.force_bm == 0) {
       if (conv3_halo_supported(ph, dtype, 256)) bm = 256;

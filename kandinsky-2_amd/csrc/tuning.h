@@ -17,7 +17,7 @@
 #include <stdlib.h>
 
 // One tile configuration of launch_igemm, as a table line spells it: algo = IgemmAlgo (kernels.h) - the generic implicit GEMM (bm x bn tile,
-// LDS-DMA depth `stages`), the LDS-resident halo kernels for 3x3 convolutions and their specialised forms (bm = 256 / 128), gemm8 (bm = 256 /
+// LDS-DMA depth `stages`), the LDS-resident halo kernels for 3x3 convolutions and their specialised forms (bm = 256 / 128; 224 in the pipelined specialised kernel), gemm8 (bm = 256 /
 // 128; stages 2 = two workgroups per CU, 3 / 4 = the specialised kernel) or the weight-streaming kernel (bm = 160 / 288); splitk >= 1.
 // igemm_resolve (igemm.hip) turns a problem with a Cfg applied into the launch that runs.
 struct Cfg { int algo = 0, bm = 0, bn = 0, splitk = 0, stages = 0; };
@@ -121,7 +121,11 @@ inline void tuned_make_candidates(Tuned& t, int dtype) {
       IgemmParams ph = p;
       ph.algo = algo;
       const int nsplit_max = (p.Kc / BK) * (algo == IG_ALGO_HALO3 ? 2 : 1);
-      for (int bm : {256, 128}) {
+      for (int bm : {256, 128, 224}) {
+        // 224 rows (the pipelined specialised kernel, 16-bit types: conv3_halo_supported): only where the tile divides the H x (W + 2) plane -
+        // that is what it exists for: no ragged last tile, 252 workgroups for 256 CUs at 96 x 96 - and spans at least two image rows (a
+        // shorter tile has no halo economy)
+        if (bm == 224 && ((p.H * (p.W + 2)) % 224 != 0 || 2 * (p.W + 2) > 224)) continue;
         if (!conv3_halo_supported(ph, dtype, bm) || p.N < 128) continue;
         const int nb = B * conv3_halo_tiles_per_image(p, bm) * ((p.N + 127) / 128);
         for (int sk : {1, 2, 3, 4, 5, 6, 8, 10, 12}) {

@@ -20,6 +20,9 @@ FUSED_SKIP = "--fused-skip" in sys.argv     # keep the shipped table except the 
                                             # (round 5: their second K loop became an NSK-deep LDS-DMA ring - the specialised kernels may win them now)
 X2_ONLY = "--x2-only" in sys.argv           # keep the shipped table and add the asymmetric split's (K22_F16X2) own lines: measured with every
                                             # convolution of the plan at two MFMAs (K22_X2_PLAN=3) and without the fall-back to the x3 lines
+LEVEL96 = "--level96" in sys.argv           # keep the shipped table except the bf16 3x3 convolutions at H = W = 96 with N >= 128: re-measured
+                                            # (the 224-row tile of conv3_halo_spec_kernel joined their candidate list); the re-measured lines that
+                                            # hold up against repeated timing go to kandinsky-2_amd/tiles_gfx950_bm224.txt, loaded behind the table
 if X2_ONLY:
     os.environ["K22_X2_OWN_LINES"] = "1"
     os.environ["K22_X2_PLAN"] = "3"
@@ -38,6 +41,20 @@ if FUSED_SKIP:
             else:
                 dropped += 1
     print(f"--fused-skip: {kept} table lines kept, {dropped} dropped for re-measurement")
+    os.environ["K22_TILE_TABLE"] = _tmp
+elif LEVEL96:
+    _here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    _src = os.path.join(_here, "kandinsky-2_amd", "tiles_gfx950.txt")
+    _tmp = "/tmp/k22_tiles_without_level96.txt"
+    with open(_src) as f, open(_tmp, "w") as g:
+        kept = dropped = 0
+        for line in f:
+            v = line.split()
+            if line.startswith("#") or len(v) < 8 or not (v[0] == "0" and v[1] == "9" and v[6] == "96" and v[7] == "96" and int(v[3]) >= 128):
+                g.write(line); kept += 1
+            else:
+                dropped += 1
+    print(f"--level96: {kept} table lines kept, {dropped} dropped for re-measurement")
     os.environ["K22_TILE_TABLE"] = _tmp
 elif SMALL_CONV:
     _here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -222,6 +239,12 @@ def main():
         unet(k22.MODEL_CONFIG_2_1, True, [(8, 96, 96)], dtypes=x3)
         n = _lib.lib().k22_tile_table_save(out.encode())
         print(f"{n0} shipped + {n - n0} new = {n} entries -> {out}")
+        return
+    if LEVEL96:
+        n0 = _lib.lib().k22_tile_table_size()
+        unet(k22.MODEL_CONFIG_2_1, False, [(1, 96, 96), (2, 96, 96), (4, 96, 96), (8, 96, 96)], dtypes=(torch.bfloat16,))
+        n = _lib.lib().k22_tile_table_save(out.encode())
+        print(f"{n0} kept + {n - n0} re-measured = {n} entries -> {out}")
         return
     if SMALL_CONV:
         b16 = (torch.bfloat16,)
