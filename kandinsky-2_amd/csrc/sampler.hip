@@ -231,13 +231,22 @@ __global__ __launch_bounds__(1024) void sampler_threshold_kernel(SamplerParams p
   if ((threadIdx.x & 63) == 0) { atomicAdd(&succ_cnt[0], cnt); atomicMin(&succ_cnt[1], mn); }
   __syncthreads();
   if (threadIdx.x == 0) {
+    // numpy rounds the product and the sum of its lerp separately.  Contraction is switched off for this block and the operations are plain
+    // operators: the __f*_rn intrinsics were fused into one v_fma after inlining (see keep_region_kernel, prestep.hip), one rounding fewer
+    // and another last bit of s where b - a is large against a (tests/test_sampler_select_gpu.py: tie_above).
+#pragma clang fp contract(off)
     const uint32_t kb = ((int)succ_cnt[0] > k_hi || k_hi == p.n_lo) ? ka : succ_cnt[1];
     const float a = __uint_as_float(ka), b = __uint_as_float(kb);
     // numpy _lerp in float32: a + (b-a)*t, or b - (b-a)*(1-t) when t >= 0.5
     const float t = (float)p.gamma;
-    const float d = __fsub_rn(b, a);
-    float r = __fadd_rn(a, __fmul_rn(d, t));
-    if (t >= 0.5f) r = __fsub_rn(b, __fmul_rn(d, __fsub_rn(1.f, t)));
+    const float d = b - a;
+    const float dt = d * t;
+    float r = a + dt;
+    if (t >= 0.5f) {
+      const float u = 1.f - t;
+      const float du = d * u;
+      r = b - du;
+    }
     p.s_buf[0] = r > 1.f ? r : 1.f;
   }
 }

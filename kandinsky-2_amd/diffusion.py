@@ -61,9 +61,11 @@ def space_timesteps(num_timesteps: int, section_counts) -> List[int]:
 
 def percentile_index(n: int, p: float = 99.5):
     """(floor index, float32 weight) of np.percentile(float32 array of n values, p), method 'linear',
-    using numpy's own float32 arithmetic for the virtual index (numpy/lib/_function_base_impl.py)."""
+    using numpy's own float32 arithmetic for the virtual index (numpy/lib/_function_base_impl.py: 'linear' takes (n - 1) * q in
+    one product; the general n * q + (alpha + q * (1 - alpha - beta)) - 1 of the other methods is the same number but rounds three
+    times, and gave another weight at about a third of all n - 4 * 24 * 24 and 4 * 72 * 72 among them)."""
     q = np.asanyarray(np.true_divide(p, np.float32(100)))
-    vi = n * q + (1 + q * (1 - 1 - 1)) - 1
+    vi = (n - 1) * q
     lo = int(np.floor(vi))
     gamma = np.float32(vi - lo)
     if lo >= n - 1:

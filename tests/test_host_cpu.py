@@ -104,7 +104,8 @@ def test_space_timesteps_ddim_and_sections():
         k22.space_timesteps(10, "20")
 
 
-@pytest.mark.parametrize("n", [4 * 8 * 8, 4 * 16 * 16, 4 * 32 * 32, 4 * 96 * 96, 4 * 128 * 128, 7, 1])
+@pytest.mark.parametrize("n", [4 * 8 * 8, 4 * 16 * 16, 4 * 32 * 32, 4 * 96 * 96, 4 * 128 * 128, 7, 1,
+                               4 * 8 * 12, 4 * 24 * 24, 4 * 72 * 72, 4 * 1025, 3])   # n at which (n - 1) * q and the three-rounding form differ in fp32
 def test_percentile_index_reproduces_numpy(n):
     rng = np.random.default_rng(n)
     a = np.abs(rng.standard_normal(n).astype(np.float32))
