@@ -21,7 +21,7 @@ import torch
 from . import _lib, prestep, sampling
 from .movq import MoVQDecoderHIP, MoVQEncoderHIP
 from .pipeline import prepare_image, process_images
-from .unet22 import SCHEDULER_CONFIG_2_2, DDPMSchedulerHIP, UNet2DConditionHIP, make_arch22
+from .unet22 import SCHEDULER_CONFIG_2_2, DDPMSchedulerHIP, UNet2DConditionHIP, make_arch22, model_call22
 
 
 class SeededPrior22:
@@ -147,14 +147,10 @@ class KandinskyV22DecoderHIP:
                                           keep=keep)
             self.last_latent = x[:bs]
             return self.last_latent
-        ack = {"image_embeds": emb} if hint2 is None else {"image_embeds": emb, "hint": hint2}
+        call = model_call22(self.unet, timesteps, emb, hint2, extra)
         with self.unet.fixed_conditioning():          # emb / hint2 are this call's own and do not change during the loop
             for k, t in enumerate(timesteps):
-                half = x[:bs]
-                inp = torch.cat([half, half], 0)
-                if extra is not None:
-                    inp = torch.cat([inp, extra], 1)
-                out = self.unet(inp, t, encoder_hidden_states=None, added_cond_kwargs=ack, return_dict=False)[0]
+                out = call(x, k)
                 nz = None
                 if noise_seq is not None:
                     nz = torch.cat([noise_seq[k], noise_seq[k]], 0).to(x.device)
@@ -185,17 +181,9 @@ class KandinskyV22DecoderHIP:
                 x, x0 = self.unet.dpmpp_loop(x, ts_rows, table, orders, guidance_scale, (-clip, clip), image_embeds=emb, hint=hint2, inpaint_image=img,
                                              inpaint_mask=msk, keep=None if keep is None else keep + (coef,))
             else:
-                ack = {"image_embeds": emb} if hint2 is None else {"image_embeds": emb, "hint": hint2}
-                h, w = x.shape[-2:]
-                kept = None if keep is None else (keep[0].float().reshape(4, h, w).contiguous(), keep[1].float().contiguous(),
-                                                  keep[2].float().reshape(h, w).contiguous(), coef)
-
-                def call(xc, c):
-                    inp = sampling.cfg_input(xc)
-                    return self.unet(inp if extra is None else torch.cat([inp, extra], 1), ts_rows[c], encoder_hidden_states=None,
-                                     added_cond_kwargs=ack, return_dict=False)[0]
-
-                x, x0 = sampling.dpmpp_loop_keep(call, x, table, orders, guidance=float(guidance_scale), clamp=(-clip, clip), keep=kept)
+                kept = sampling.keep_operands("dpm_sampler", None if keep is None else keep + (coef,), bs, *x.shape[-2:], n, host=True)
+                x, x0 = sampling.dpmpp_loop_keep(model_call22(self.unet, ts_rows, emb, hint2, extra), x, table, orders, guidance=float(guidance_scale),
+                                                 clamp=(-clip, clip), keep=kept)
         self.last_timesteps, self.last_x0, self.last_latent = [int(t) for t in timesteps], x0[:bs], x[:bs]
         return self.last_latent
 

@@ -1,6 +1,6 @@
 """The host-driven step loops of the three decoder samplers, each written once, and the only ctypes callers of their step kernels
 (k22_sampler_step, k22_ddim_step, k22_plms_step, k22_dpmpp_step[_clip]).  SpacedDiffusionHIP.p_sample_loop, DDIMSamplerHIP / PLMSSamplerHIP.sample (diffusion.py)
-and the two-chain branches of Text2ImUNetHIP.sample_loop / ddim_loop (unet.py) run them; the captured single-chain loops are the same
+and the two-chain route of the UNet modules' whole-loop entries (Text2ImUNetHIP._run_loop, unet.py) run them; the captured single-chain loops are the same
 sequences in C++ (csrc/engine.hip).  A loop takes `model_call(latent, call_index) -> [N,8,H,W]`, the schedule rows in execution order
 and a step launcher, to which it hands its keywords (guidance, clamp, ...) through: the host tests pass recording launchers.
 """
@@ -71,6 +71,20 @@ def keep_region(x, init, noise0, mask, sa, sb, out):
     """One k22_keep_region launch over the CFG batch x [B,4,h,w] (out may be x)."""
     _lib.check(_lib.lib().k22_keep_region(x.data_ptr(), init.data_ptr(), noise0.data_ptr(), mask.data_ptr(), float(sa), float(sb), out.data_ptr(),
                                           x.shape[0], x.shape[2] * x.shape[3], _lib.current_stream()))
+
+
+def keep_operands(name: str, keep, bs: int, H: int, W: int, n_steps: int, host: bool = False):
+    """The known region of a 2.2 loop entry `name`, keep = (init [1,4,h,w], noise0 [bs,4,h,w], mask [1,1,h,w], coef [n_steps,2]) or None,
+    checked -> (init [4,h,w], noise0, mask [h,w], coef as a contiguous fp32 host array): what the entry stages and hands to C.  host: the
+    three tensors as the contiguous fp32 the keep_region launches of a host-driven loop read.  None stays None; a checked tuple passes again."""
+    if keep is None:
+        return None
+    k_init, k_noise, k_mask, coef = keep
+    coef = np.ascontiguousarray(coef, dtype=np.float32)
+    if k_init.numel() != 4 * H * W or tuple(k_noise.shape) != (bs, 4, H, W) or k_mask.numel() != H * W or coef.shape != (n_steps, 2):
+        raise ValueError(f"{name}: keep = (init [1,4,h,w], noise0 [bs,4,h,w], mask [1,1,h,w], coef [n_steps,2])")
+    kept = (k_init.reshape(4, H, W), k_noise, k_mask.reshape(H, W))
+    return (tuple(t.float().contiguous() for t in kept) if host else kept) + (coef,)
 
 
 def plms_calls(steps: list) -> list:

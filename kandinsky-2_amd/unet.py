@@ -272,46 +272,114 @@ class Text2ImUNetHIP(NativeModule):
         self._join(B)
         return out
 
+    # ---- the whole-loop entries: one driver (_run_loop), three hooks the 2.2 module overrides, the two sampler bodies both modules share ----
+    def _loop_x(self, name, x, cfg_batch=False):
+        """(B, H, W) of a loop entry's x: [N,4,h,w] on the GPU (cfg_batch: the CFG pair, N even), before the entry checks its own operands"""
+        B, Cx, H, W = x.shape
+        if Cx != 4 or x.device.type != "cuda" or (cfg_batch and B % 2):
+            raise ValueError(f"{name}: x must be {'the CFG batch [2 bs,4,h,w]' if cfg_batch else '[N,4,h,w]'} on the GPU")
+        return B, H, W
+
+    def _loop_condition(self, full_emb=None, pooled_emb=None, image_emb=None):
+        self._ensure_condition(full_emb, pooled_emb, image_emb)
+
+    def _loop_inpaint(self, name, x, inpaint_image, inpaint_mask):
+        return self._inpaint_operands(x, inpaint_image, inpaint_mask)
+
+    def _loop_model_call(self, ts_rows, cond, img, msk):
+        return sampling.fused_call(self.forward, ts_rows, inpaint_image=img, inpaint_mask=msk)
+
+    def _run_loop(self, name, owned, x, ts_rows, cond, inpaint, *, key, shapes, operands, host, native, results, keep=None):
+        """What every whole-loop entry does once x (_loop_x) and its own operands are checked.  cond: _loop_condition's keywords; inpaint =
+        (inpaint_image, inpaint_mask), which _loop_inpaint refuses or brings to [B,4,h,w] / [B,1,h,w]; keep: sampling.keep_operands' tuple.
+        One chain: the operands are copied into the entry's OwnedBuffers (attribute `owned`; the common ones here, the entry's own by shapes(box) /
+        operands), because the captured loop holds their addresses - a second generation under the same key replays it instead of capturing
+        20 000 nodes again; native(bufs, the four keep pointers, use_graph, stream) is the entry's one C call, results(bufs) clones its returns.
+        Two chains: host(model_call, a copy of x, keep as contiguous fp32) drives the same launches from sampling.py - per model call the two
+        half-batch graphs side by side, a join, the step kernels (one captured graph with two branches runs them back to back: round 4)."""
+        B, _, H, W = x.shape
+        img, msk = self._loop_inpaint(name, x, *inpaint)
+        self._ensure_plan(B, H, W)
+        self._loop_condition(**cond)
+        if self._chained(B):
+            hk = None if keep is None else sampling.keep_operands(name, keep, B // 2, H, W, len(keep[3]), host=True)
+            return host(self._loop_model_call(ts_rows, cond, img, msk), x.detach().float().clone(), hk)
+        dev, box, one = x.device, (B, 4, H, W), (B, 1, H, W)
+        on9, onk = (lambda s: s if self.arch.inpainting else None), (lambda s: s if keep is not None else None)
+        k_init, k_noise, k_mask, coef = keep or (None, None, None, None)
+        bufs = getattr(self, owned).stage(                       # read behind _ensure_plan: a first prepare() renews the buffer sets
+            key + (B, H, W, tuple(ts_rows.shape), keep is not None, str(dev)), dev,
+            lambda: dict(x=box, tmp=box, ts=tuple(ts_rows.shape), img=on9(box), msk=on9(one), kinit=onk((4, H, W)), knoise=onk((B // 2, 4, H, W)),
+                         kmask=onk((H, W)), **shapes(box)),
+            dict(x=x, ts=ts_rows, img=img, msk=msk, kinit=k_init, knoise=k_noise, kmask=k_mask, **operands))
+        kp = (_lib.ptr(bufs["kinit"]), _lib.ptr(bufs["knoise"]), _lib.ptr(bufs["kmask"]),
+              None if keep is None else coef.ctypes.data_as(C.POINTER(C.c_float)))
+        _lib.check(native(bufs, kp, 1 if self.use_graph else 0, _lib.current_stream()))
+        return results(bufs)
+
+    def _ddpm_loop(self, owned, x, ts_rows, noise_seq, table, table_rows, guidance_scale, clamp, pct, cond, inpaint, init_img=None, img_mask=None,
+                   keep=None):
+        """sample_loop of both UNets behind their checks: k22_unet_sample_loop_keep, which with no keep IS k22_unet_sample_loop (one body, one
+        loop key), or step_loop with sampler_step and, with a keep, keep_region on the freshly written latent."""
+        B, _, H, W = x.shape
+        n, rows, tshape, g = len(table_rows), [int(r) for r in table_rows], tuple(table.shape), float(guidance_scale)
+        clip, pct = (float(clamp[0]), float(clamp[1])), (int(pct[0]), float(pct[1]))
+        ii = None if init_img is None else init_img.float().expand(B, 4, H, W)
+        mm = None if init_img is None else img_mask.float().expand(B, 1, H, W)
+
+        def host(call, xc, hk):
+            def step(xs, model_out, nz, krow, x_out, x0, **kw):
+                sampling.sampler_step(xs, model_out, nz, krow[1], x_out, x0, **kw)
+                if hk is not None:
+                    sampling.keep_region(x_out, hk[0], hk[1], hk[2], hk[3][krow[0], 0], hk[3][krow[0], 1], x_out)
+
+            return sampling.step_loop(call, xc, list(enumerate(rows)), noise_seq.float().contiguous(), None, step, table=table.float().contiguous(),
+                                      guidance=g, use_cfg=1, clamp=clip, pct=pct, init=None if ii is None else ii.contiguous(),
+                                      mask=None if mm is None else mm.contiguous(), scratch=sampling.sampler_scratch(xc))[0]
+
+        def native(b, kp, *tail):
+            return _lib.lib().k22_unet_sample_loop_keep(
+                self._handle, b["x"].data_ptr(), b["tmp"].data_ptr(), b["ts"].data_ptr(), b["noise"].data_ptr(), _lib.ptr(b["init"]), _lib.ptr(b["mask"]),
+                _lib.ptr(b["img"]), _lib.ptr(b["msk"]), b["table"].data_ptr(), (C.c_int * n)(*rows), n, g, clip[0], clip[1], pct[0], pct[1],
+                b["scratch"].data_ptr(), *kp, *tail)
+
+        return self._run_loop(
+            "sample_loop", owned, x, ts_rows, cond, inpaint, key=(n, tshape, ii is not None),
+            shapes=lambda box: dict(noise=(n,) + box, table=tshape, scratch=_lib.lib().k22_sampler_scratch_bytes(B, H * W),
+                                    init=box if ii is not None else None, mask=(B, 1, H, W) if ii is not None else None),
+            operands=dict(noise=noise_seq, table=table, init=ii, mask=mm), host=host, native=native, results=lambda b: b["x"].clone(), keep=keep)
+
+    def _dpm_loop(self, owned, x, ts_rows, table, orders, guidance_scale, clamp, cond, inpaint, keep=None):
+        """dpmpp_loop of both UNets behind their checks.  clamp None: k22_unet_dpmpp_loop / dpmpp_step; (lo, hi): k22_unet_dpmpp_loop_keep /
+        dpmpp_step(clamp=) and, with a keep, keep_region - sampling.dpmpp_loop_keep either way."""
+        n, orders, g = table.shape[0], [int(o) for o in orders], float(guidance_scale)
+        clip = None if clamp is None else (float(clamp[0]), float(clamp[1]))
+
+        def host(call, xc, hk):
+            return sampling.dpmpp_loop_keep(call, xc, table.float().contiguous(), orders, guidance=g, clamp=clip, keep=hk)
+
+        def native(b, kp, *tail):
+            head = (self._handle, b["x"].data_ptr(), b["tmp"].data_ptr(), b["hist"].data_ptr(), b["ts"].data_ptr(), b["table"].data_ptr(),
+                    (C.c_int * n)(*orders), _lib.ptr(b["img"]), _lib.ptr(b["msk"]), n, g)
+            L = _lib.lib()
+            return L.k22_unet_dpmpp_loop(*head, *tail) if clip is None else L.k22_unet_dpmpp_loop_keep(*head, *clip, *kp, *tail)
+
+        return self._run_loop("dpmpp_loop", owned, x, ts_rows, cond, inpaint, key=(n,), shapes=lambda box: dict(hist=(2,) + box, table=(n, 5)),
+                              operands=dict(table=table), host=host, native=native,
+                              results=lambda b: (b["x"].clone(), b["hist"][(n - 1) % 2].clone()), keep=keep)
+
     @torch.no_grad()
     def sample_loop(self, x, ts_rows, noise_seq, table, table_rows, guidance_scale, clamp, pct, *, full_emb=None, pooled_emb=None,
                     image_emb=None, inpaint_image=None, inpaint_mask=None, init_img=None, img_mask=None):
         """The whole guided p_sampler loop as ONE hipGraph replay (k22_unet_sample_loop); returns the final latent [N,4,h,w].
         x [N,4,h,w] = x_T; ts_rows [n_steps, N] and noise_seq [n_steps, N,4,h,w] in execution order; table [T,8] + table_rows (host ints):
-        the schedule row of every step.  The operands are copied into buffers this module OWNS, so that a second generation of the
-        same shape and step count replays the captured graph (its nodes hold those addresses) instead of capturing 20 000 nodes again."""
-        B, Cx, H, W = x.shape
-        if Cx != 4 or x.device.type != "cuda":
-            raise ValueError("sample_loop: x must be [N,4,h,w] on the GPU")
+        the schedule row of every step.  Owned operand buffers, replay and the two-chain route: _run_loop."""
+        B, H, W = self._loop_x("sample_loop", x)
         n_steps = len(table_rows)
         if tuple(ts_rows.shape) != (n_steps, B) or tuple(noise_seq.shape) != (n_steps, B, 4, H, W):
             raise ValueError("sample_loop: ts_rows must be [n_steps, N] and noise_seq [n_steps, N, 4, h, w]")
-        self._ensure_plan(B, H, W)
-        self._ensure_condition(full_emb, pooled_emb, image_emb)
-        img, msk = self._inpaint_operands(x, inpaint_image, inpaint_mask)
-        ii = None if init_img is None else init_img.float().expand(B, 4, H, W)
-        mm = None if init_img is None else img_mask.float().expand(B, 1, H, W)
-        dev, g, rows = x.device, float(guidance_scale), [int(r) for r in table_rows]
-        if self._chained(B):
-            # two chains: the loop is driven from the host - per step the two half-batch graphs side by side, a join, the sampler kernels (one
-            # captured graph with two branches runs them back to back: measured in round 4).  Same step arithmetic as k22_unet_sample_loop.
-            x = x.detach().float().clone()
-            return sampling.step_loop(sampling.fused_call(self.forward, ts_rows, inpaint_image=img, inpaint_mask=msk), x, rows, noise_seq.contiguous(),
-                                      None, sampling.sampler_step, table=table.float().contiguous(), guidance=g, use_cfg=1, clamp=clamp, pct=pct,
-                                      init=None if ii is None else ii.contiguous(), mask=None if mm is None else mm.contiguous(),
-                                      scratch=sampling.sampler_scratch(x))[0]
-        box, img9 = (B, 4, H, W), self.arch.inpainting
-        bufs = self._loop_bufs.stage(
-            (B, H, W, n_steps, tuple(table.shape), init_img is not None, str(dev)), dev,
-            lambda: dict(x=box, tmp=box, ts=(n_steps, B), noise=(n_steps,) + box, table=tuple(table.shape),
-                         scratch=_lib.lib().k22_sampler_scratch_bytes(B, H * W), init=box if ii is not None else None,
-                         mask=(B, 1, H, W) if ii is not None else None, img=box if img9 else None, msk=(B, 1, H, W) if img9 else None),
-            dict(x=x, ts=ts_rows, noise=noise_seq, table=table, init=ii, mask=mm, img=img, msk=msk))
-        _lib.check(_lib.lib().k22_unet_sample_loop(
-            self._handle, bufs["x"].data_ptr(), bufs["tmp"].data_ptr(), bufs["ts"].data_ptr(), bufs["noise"].data_ptr(), _lib.ptr(bufs["init"]),
-            _lib.ptr(bufs["mask"]), _lib.ptr(bufs["img"]), _lib.ptr(bufs["msk"]), bufs["table"].data_ptr(), (C.c_int * n_steps)(*rows), n_steps, g,
-            float(clamp[0]), float(clamp[1]), int(pct[0]), float(pct[1]), bufs["scratch"].data_ptr(), 1 if self.use_graph else 0,
-            _lib.current_stream()))
-        return bufs["x"].clone()
+        return self._ddpm_loop("_loop_bufs", x, ts_rows, noise_seq, table, table_rows, guidance_scale, clamp, pct,
+                               dict(full_emb=full_emb, pooled_emb=pooled_emb, image_emb=image_emb), (inpaint_image, inpaint_mask), init_img, img_mask)
 
     @torch.no_grad()
     def ddim_loop(self, kind, x, ts_rows, table, guidance_scale, noise_seq=None, *, full_emb=None, pooled_emb=None, image_emb=None,
@@ -319,13 +387,11 @@ class Text2ImUNetHIP(NativeModule):
         """The whole guided DDIM (kind "ddim") or PLMS ("plms") loop as ONE hipGraph replay (k22_unet_ddim_loop); returns (final latent,
         predicted x0 of the last step), both [N,4,h,w].  x = x_T; table [n_steps, 4]: the k22_ddim_step rows in execution order; ts_rows
         [n_calls, N]: the timestep of every model call in execution order - n_calls = n_steps for DDIM, n_steps + 1 for PLMS (its first step
-        calls the model a second time, at the next step's timestep); noise_seq [n_steps, N,4,h,w]: DDIM with eta > 0 only.  As in sample_loop
-        the operands are copied into buffers this module OWNS: a second generation of the same shape, step count and kind replays the capture."""
+        calls the model a second time, at the next step's timestep); noise_seq [n_steps, N,4,h,w]: DDIM with eta > 0 only.  A second
+        generation of the same shape, step count and kind replays the capture (_run_loop)."""
         if kind not in ("ddim", "plms"):
             raise ValueError('ddim_loop: kind must be "ddim" or "plms"')
-        B, Cx, H, W = x.shape
-        if Cx != 4 or x.device.type != "cuda":
-            raise ValueError("ddim_loop: x must be [N,4,h,w] on the GPU")
+        B, H, W = self._loop_x("ddim_loop", x)
         plms = kind == "plms"
         n_steps = table.shape[0]
         n_calls = n_steps + 1 if plms else n_steps
@@ -333,63 +399,41 @@ class Text2ImUNetHIP(NativeModule):
             raise ValueError("ddim_loop: table must be [n_steps, 4] and ts_rows [n_calls, N] (n_calls = n_steps, + 1 for PLMS)")
         if noise_seq is not None and (plms or tuple(noise_seq.shape) != (n_steps, B, 4, H, W)):
             raise ValueError("ddim_loop: noise_seq is [n_steps, N, 4, h, w], for DDIM only (PLMS is eta = 0)")
-        self._ensure_plan(B, H, W)
-        self._ensure_condition(full_emb, pooled_emb, image_emb)
-        img, msk = self._inpaint_operands(x, inpaint_image, inpaint_mask)
-        dev, g = x.device, float(guidance_scale)
-        if self._chained(B):
-            # two chains: host-driven, per model call the two half-batch graphs side by side (see sample_loop).  The steps of k22_unet_ddim_loop.
-            call = sampling.fused_call(self.forward, ts_rows, inpaint_image=img, inpaint_mask=msk)
-            x, tbl = x.detach().float().clone(), table.float().contiguous()
+        g = float(guidance_scale)
+
+        def host(call, xc, _keep):                     # the steps of k22_unet_ddim_loop
+            tbl = table.float().contiguous()
             if plms:
-                return sampling.plms_loop(call, x, tbl, sampling.plms_step, guidance=g)
+                return sampling.plms_loop(call, xc, tbl, sampling.plms_step, guidance=g)
             nzs = None if noise_seq is None else noise_seq.float().contiguous()
-            return sampling.step_loop(call, x, tbl, nzs, torch.empty_like(x), sampling.ddim_step, guidance=g)
-        box, img9 = (B, 4, H, W), self.arch.inpainting
-        bufs = self._ddim_bufs.stage(
-            (kind, B, H, W, n_steps, noise_seq is not None, str(dev)), dev,
-            lambda: dict(x=box, tmp=box, x0=box, ts=(n_calls, B), table=(n_steps, 4), noise=(n_steps,) + box if noise_seq is not None else None,
-                         hist=(4,) + box if plms else None, img=box if img9 else None, msk=(B, 1, H, W) if img9 else None),
-            dict(x=x, ts=ts_rows, table=table, noise=noise_seq, img=img, msk=msk))
-        _lib.check(_lib.lib().k22_unet_ddim_loop(
-            self._handle, _lib.K22_LOOP_PLMS if plms else _lib.K22_LOOP_DDIM, bufs["x"].data_ptr(), bufs["tmp"].data_ptr(), bufs["x0"].data_ptr(),
-            bufs["ts"].data_ptr(), bufs["table"].data_ptr(), _lib.ptr(bufs["noise"]), _lib.ptr(bufs["img"]), _lib.ptr(bufs["msk"]),
-            _lib.ptr(bufs["hist"]), n_steps, g, 1 if self.use_graph else 0, _lib.current_stream()))
-        return bufs["x"].clone(), bufs["x0"].clone()
+            return sampling.step_loop(call, xc, tbl, nzs, torch.empty_like(xc), sampling.ddim_step, guidance=g)
+
+        def native(b, _kp, *tail):
+            return _lib.lib().k22_unet_ddim_loop(
+                self._handle, _lib.K22_LOOP_PLMS if plms else _lib.K22_LOOP_DDIM, b["x"].data_ptr(), b["tmp"].data_ptr(), b["x0"].data_ptr(),
+                b["ts"].data_ptr(), b["table"].data_ptr(), _lib.ptr(b["noise"]), _lib.ptr(b["img"]), _lib.ptr(b["msk"]), _lib.ptr(b["hist"]),
+                n_steps, g, *tail)
+
+        return self._run_loop(
+            "ddim_loop", "_ddim_bufs", x, ts_rows, dict(full_emb=full_emb, pooled_emb=pooled_emb, image_emb=image_emb),
+            (inpaint_image, inpaint_mask), key=(kind, n_steps, noise_seq is not None),
+            shapes=lambda box: dict(x0=box, table=(n_steps, 4), noise=(n_steps,) + box if noise_seq is not None else None,
+                                    hist=(4,) + box if plms else None),
+            operands=dict(table=table, noise=noise_seq), host=host, native=native, results=lambda b: (b["x"].clone(), b["x0"].clone()))
 
     @torch.no_grad()
     def dpmpp_loop(self, x, ts_rows, table, orders, guidance_scale, *, full_emb=None, pooled_emb=None, image_emb=None, inpaint_image=None,
                    inpaint_mask=None):
         """The whole guided DPM-Solver++ loop as ONE hipGraph replay (k22_unet_dpmpp_loop); returns (final latent, predicted x0 of the last
         step), both [N,4,h,w].  x = x_T; table [n_steps, 5]: the k22_dpmpp_step rows and orders (host ints, 1 or 2): sampling.dpmpp_table's
-        pair, in execution order; ts_rows [n_steps, N]: the timestep of every model call.  As in ddim_loop the operands are copied into
-        buffers this module OWNS: a second generation of the same shape, step count and orders replays the capture."""
-        B, Cx, H, W = x.shape
-        if Cx != 4 or x.device.type != "cuda":
-            raise ValueError("dpmpp_loop: x must be [N,4,h,w] on the GPU")
-        n_steps = table.shape[0]
-        orders = [int(o) for o in orders]
+        pair, in execution order; ts_rows [n_steps, N]: the timestep of every model call.  A second generation of the same shape,
+        step count and orders replays the capture (_run_loop)."""
+        B, H, W = self._loop_x("dpmpp_loop", x)
+        n_steps, orders = table.shape[0], [int(o) for o in orders]
         if n_steps < 1 or tuple(table.shape) != (n_steps, 5) or tuple(ts_rows.shape) != (n_steps, B) or len(orders) != n_steps:
             raise ValueError("dpmpp_loop: table must be [n_steps, 5], ts_rows [n_steps, N] and orders n_steps ints")
-        self._ensure_plan(B, H, W)
-        self._ensure_condition(full_emb, pooled_emb, image_emb)
-        img, msk = self._inpaint_operands(x, inpaint_image, inpaint_mask)
-        dev, g = x.device, float(guidance_scale)
-        if self._chained(B):
-            # two chains: host-driven, per model call the two half-batch graphs side by side (see sample_loop).  The steps of k22_unet_dpmpp_loop.
-            call = sampling.fused_call(self.forward, ts_rows, inpaint_image=img, inpaint_mask=msk)
-            return sampling.dpmpp_loop(call, x.detach().float().clone(), table.float().contiguous(), orders, sampling.dpmpp_step, guidance=g)
-        box, img9 = (B, 4, H, W), self.arch.inpainting
-        bufs = self._dpmpp_bufs.stage(
-            (B, H, W, n_steps, str(dev)), dev,
-            lambda: dict(x=box, tmp=box, hist=(2,) + box, ts=(n_steps, B), table=(n_steps, 5), img=box if img9 else None,
-                         msk=(B, 1, H, W) if img9 else None),
-            dict(x=x, ts=ts_rows, table=table, img=img, msk=msk))
-        _lib.check(_lib.lib().k22_unet_dpmpp_loop(
-            self._handle, bufs["x"].data_ptr(), bufs["tmp"].data_ptr(), bufs["hist"].data_ptr(), bufs["ts"].data_ptr(), bufs["table"].data_ptr(),
-            (C.c_int * n_steps)(*orders), _lib.ptr(bufs["img"]), _lib.ptr(bufs["msk"]), n_steps, g, 1 if self.use_graph else 0,
-            _lib.current_stream()))
-        return bufs["x"].clone(), bufs["hist"][(n_steps - 1) % 2].clone()
+        return self._dpm_loop("_dpmpp_bufs", x, ts_rows, table, orders, guidance_scale, None,
+                              dict(full_emb=full_emb, pooled_emb=pooled_emb, image_emb=image_emb), (inpaint_image, inpaint_mask))
 
 
 def create_model(backend_dtype: torch.dtype = torch.bfloat16, use_graph: bool = True, inpainting: bool = False,

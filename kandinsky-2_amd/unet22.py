@@ -24,7 +24,6 @@ So the engine runs the same kernels; this file maps the diffusers state_dict key
 from __future__ import annotations
 
 import contextlib
-import ctypes as C
 import math
 from collections import OrderedDict
 from types import SimpleNamespace
@@ -275,6 +274,20 @@ def init_unet22_state_dict(a: UNetArch, seed: int = 0) -> "OrderedDict[str, torc
     return sd
 
 
+def model_call22(unet, ts_rows, image_embeds, hint=None, extra=None):
+    """model_call of the host-driven 2.2 loops (sampling.py), the call the diffusers pipelines make: `unet` on cfg_input(latent), the five
+    inpainting channels `extra` [B,5,h,w] appended, at entry c of ts_rows (rows [n_calls, B] or one timestep per call), with image_embeds
+    (and hint: the ControlNet-depth UNet only) as added_cond_kwargs"""
+    ack = {"image_embeds": image_embeds} if hint is None else {"image_embeds": image_embeds, "hint": hint}
+
+    def call(x, c):
+        inp = sampling.cfg_input(x)
+        return unet(inp if extra is None else torch.cat([inp, extra], 1), ts_rows[c], encoder_hidden_states=None, added_cond_kwargs=ack,
+                    return_dict=False)[0]
+
+    return call
+
+
 class UNet2DConditionHIP(Text2ImUNetHIP):
     """Drop-in for the `unet=` the reference passes to the diffusers Kandinsky 2.2 pipelines: diffusers state_dict keys, and the
     call the pipelines make:
@@ -284,11 +297,15 @@ class UNet2DConditionHIP(Text2ImUNetHIP):
     image_embeds / hint passed differ in CONTENT from the ones it was computed from (device copies of those are kept and compared,
     one device-side equality test per call), so the module never computes from conditioning other than what it is given - as
     diffusers' UNet2DConditionModel, which has no cache.  Callers that own the conditioning tensors and keep them fixed over a
-    loop (the pipelines' denoising loops) skip the comparison inside `with unet.fixed_conditioning():`."""
+    loop (the pipelines' denoising loops) skip the comparison inside `with unet.fixed_conditioning():`.
+    One chain, always: K22_CHAINS reaches Text2ImUNetHIP only.  The host-driven loop route stays behind _chained for the day a two-engine
+    2.2 module exists; the inherited ddim_loop (the 2.1 conditioning) is refused."""
 
     def __init__(self, arch: Optional[UNetArch] = None, backend_dtype: torch.dtype = torch.bfloat16, use_graph: bool = True,
                  meta_params: bool = False):
-        super().__init__(arch or make_arch22(), backend_dtype=backend_dtype, use_graph=use_graph, cache_text_emb=True, meta_params=meta_params)
+        # chains=1: forward, set_condition and set_hint below address one engine (self._handle) with the whole batch
+        super().__init__(arch or make_arch22(), backend_dtype=backend_dtype, use_graph=use_graph, cache_text_emb=True, meta_params=meta_params,
+                         chains=1)
         a = self.arch
         self.config = SimpleNamespace(in_channels=a.in_channels, out_channels=a.out_channels, cross_attention_dim=a.model_dim,
                                       encoder_hid_dim=a.image_dim, addition_embed_type="image_hint" if a.hint_channels else "image")
@@ -363,6 +380,19 @@ class UNet2DConditionHIP(Text2ImUNetHIP):
                 self._cond_hint = None if hint is None else hint.detach().float().clone()
             self.cache = {"cached": True}
 
+    # ---- the whole-loop entries: Text2ImUNetHIP._run_loop with this module's conditioning, inpaint policy and model call -----------------
+    def _loop_condition(self, image_embeds=None, hint=None):
+        self._ensure_condition22(image_embeds, hint)
+
+    def _loop_inpaint(self, name, x, inpaint_image, inpaint_mask):
+        """required with the 9-channel UNet and only with it (no zeros for an absent operand); the image latents come already masked"""
+        if self.arch.inpainting != (inpaint_image is not None) or self.arch.inpainting != (inpaint_mask is not None):
+            raise ValueError(f"{name}: inpaint_image / inpaint_mask go with the 9-channel UNet, and only with it")
+        return self._inpaint_operands(x, inpaint_image, inpaint_mask)
+
+    def _loop_model_call(self, ts_rows, cond, img, msk):
+        return model_call22(self, ts_rows, cond["image_embeds"], cond["hint"], None if img is None else torch.cat([img, msk], 1))
+
     @torch.no_grad()
     def sample_loop(self, x, ts_rows, noise_seq, table, table_rows, guidance_scale, clamp, *, image_embeds=None, hint=None,
                     inpaint_image=None, inpaint_mask=None, keep=None):
@@ -373,60 +403,14 @@ class UNet2DConditionHIP(Text2ImUNetHIP):
         latents) / inpaint_mask [.,1,h,w]: channels 4-8 of the 9-channel UNet's input.  keep=(init [1,4,h,w], noise0 [B/2,4,h,w], mask
         [1,1,h,w], coef [n,2] host array): the known region re-imposed after every step by k22_keep_region, which rounds every operation
         once - equal to the stepwise route's k22_blend_noised launches to rounding, not bit for bit; without keep the loop equals the
-        stepwise calls bit for bit.  The operands are copied into buffers this module OWNS, so a second generation of the same shape and
-        step count replays the capture.  Two chains: the host-driven loop, as Text2ImUNetHIP.sample_loop."""
-        B, Cx, H, W = x.shape
-        if Cx != 4 or x.device.type != "cuda" or B % 2:
-            raise ValueError("sample_loop: x must be the CFG batch [2 bs,4,h,w] on the GPU")
-        n_steps, a, bs = len(table_rows), self.arch, B // 2
+        stepwise calls bit for bit.  Owned operand buffers, replay and the host-driven route under _chained: Text2ImUNetHIP._run_loop."""
+        B, H, W = self._loop_x("sample_loop", x, cfg_batch=True)
+        n_steps = len(table_rows)
         if n_steps < 1 or tuple(ts_rows.shape) != (n_steps, B) or tuple(noise_seq.shape) != (n_steps, B, 4, H, W):
             raise ValueError("sample_loop: ts_rows must be [n_steps, B] and noise_seq [n_steps, B, 4, h, w], n_steps >= 1")
-        if a.inpainting != (inpaint_image is not None) or a.inpainting != (inpaint_mask is not None):
-            raise ValueError("sample_loop: inpaint_image / inpaint_mask go with the 9-channel UNet, and only with it")
-        self._ensure_plan(B, H, W)
-        self._ensure_condition22(image_embeds, hint)
-        img = None if inpaint_image is None else inpaint_image.detach().float().expand(B, 4, H, W)
-        msk = None if inpaint_mask is None else inpaint_mask.detach().float().expand(B, 1, H, W)
-        k_init = k_noise = k_mask = coef = None
-        if keep is not None:
-            k_init, k_noise, k_mask, coef = keep
-            coef = np.ascontiguousarray(coef, dtype=np.float32)
-            if k_init.numel() != 4 * H * W or tuple(k_noise.shape) != (bs, 4, H, W) or k_mask.numel() != H * W or coef.shape != (n_steps, 2):
-                raise ValueError("sample_loop: keep = (init [1,4,h,w], noise0 [bs,4,h,w], mask [1,1,h,w], coef [n_steps,2])")
-            k_init, k_mask = k_init.reshape(4, H, W), k_mask.reshape(H, W)
-        dev, g, rows, clip = x.device, float(guidance_scale), [int(r) for r in table_rows], (float(clamp[0]), float(clamp[1]))
-        if self._chained(B):
-            ack = {"image_embeds": image_embeds} if hint is None else {"image_embeds": image_embeds, "hint": hint}
-            extra = None if img is None else torch.cat([img, msk], 1)
-
-            def call(xc, c):
-                inp = sampling.cfg_input(xc)
-                return self.forward(inp if extra is None else torch.cat([inp, extra], 1), ts_rows[c], added_cond_kwargs=ack, return_dict=False)[0]
-
-            def step(xc, mo, nz, krow, x_out, x0, **kw):
-                sampling.sampler_step(xc, mo, nz, krow[1], x_out, x0, **kw)
-                if keep is not None:
-                    sampling.keep_region(x_out, k_init.float().contiguous(), k_noise.float().contiguous(), k_mask.float().contiguous(),
-                                         coef[krow[0], 0], coef[krow[0], 1], x_out)
-
-            xc = x.detach().float().clone()
-            return sampling.step_loop(call, xc, list(enumerate(rows)), noise_seq.float().contiguous(), None, step, table=table.float().contiguous(),
-                                      guidance=g, use_cfg=1, clamp=clip, pct=(-1, 0.0), init=None, mask=None, scratch=sampling.sampler_scratch(xc))[0]
-        box, lat = (B, 4, H, W), (4, H, W)
-        bufs = self._loop22_bufs.stage(
-            (B, H, W, n_steps, tuple(table.shape), keep is not None, str(dev)), dev,
-            lambda: dict(x=box, tmp=box, ts=(n_steps, B), noise=(n_steps,) + box, table=tuple(table.shape),
-                         scratch=_lib.lib().k22_sampler_scratch_bytes(B, H * W), img=box if a.inpainting else None,
-                         msk=(B, 1, H, W) if a.inpainting else None, kinit=lat if keep is not None else None,
-                         knoise=(bs,) + lat if keep is not None else None, kmask=(H, W) if keep is not None else None),
-            dict(x=x, ts=ts_rows, noise=noise_seq, table=table, img=img, msk=msk, kinit=k_init, knoise=k_noise, kmask=k_mask))
-        ccoef = None if coef is None else coef.ctypes.data_as(C.POINTER(C.c_float))
-        _lib.check(_lib.lib().k22_unet_sample_loop_keep(
-            self._handle, bufs["x"].data_ptr(), bufs["tmp"].data_ptr(), bufs["ts"].data_ptr(), bufs["noise"].data_ptr(), None, None,
-            _lib.ptr(bufs["img"]), _lib.ptr(bufs["msk"]), bufs["table"].data_ptr(), (C.c_int * n_steps)(*rows), n_steps, g, clip[0], clip[1], -1, 0.0,
-            bufs["scratch"].data_ptr(), _lib.ptr(bufs["kinit"]), _lib.ptr(bufs["knoise"]), _lib.ptr(bufs["kmask"]), ccoef,
-            1 if self.use_graph else 0, _lib.current_stream()))
-        return bufs["x"].clone()
+        keep = sampling.keep_operands("sample_loop", keep, B // 2, H, W, n_steps)
+        return self._ddpm_loop("_loop22_bufs", x, ts_rows, noise_seq, table, table_rows, guidance_scale, clamp, (-1, 0.0),
+                               dict(image_embeds=image_embeds, hint=hint), (inpaint_image, inpaint_mask), keep=keep)
 
     @torch.no_grad()
     def dpmpp_loop(self, x, ts_rows, table, orders, guidance_scale, clamp, *, image_embeds=None, hint=None, inpaint_image=None,
@@ -435,54 +419,19 @@ class UNet2DConditionHIP(Text2ImUNetHIP):
         x0 of the last step), both [B,4,h,w].  x = the CFG batch [x_T | x_T]; ts_rows [n, B]: the timestep of every model call; table [n, 5]
         and orders (host ints): sampling.dpmpp_schedule's, the table rounded to fp32; clamp = (lo, hi) on the data prediction
         (k22_dpmpp_step_clip); the conditioning and inpaint operands as sample_loop's.  keep=(init [1,4,h,w], noise0 [B/2,4,h,w], mask
-        [1,1,h,w], coef [n,2] host array: sampling.dpmpp_keep_coef): the known region re-imposed after every step by k22_keep_region.  The
-        operands are copied into buffers this module OWNS, so a second generation of the same shape and step count replays the capture.
-        Two chains: the host-driven sampling.dpmpp_loop_keep, whose step launches dpmpp_step(clamp=) and then keep_region - the captured
-        loop's pair, so the same bits."""
-        B, Cx, H, W = x.shape
-        if Cx != 4 or x.device.type != "cuda" or B % 2:
-            raise ValueError("dpmpp_loop: x must be the CFG batch [2 bs,4,h,w] on the GPU")
-        n_steps, a, bs = table.shape[0], self.arch, B // 2
-        orders = [int(o) for o in orders]
+        [1,1,h,w], coef [n,2] host array: sampling.dpmpp_keep_coef): the known region re-imposed after every step by k22_keep_region.
+        Under _chained the host-driven sampling.dpmpp_loop_keep, whose step launches dpmpp_step(clamp=) and then keep_region - the captured
+        loop's pair, so the same bits.  Owned operand buffers and replay: Text2ImUNetHIP._run_loop."""
+        B, H, W = self._loop_x("dpmpp_loop", x, cfg_batch=True)
+        n_steps, orders = table.shape[0], [int(o) for o in orders]
         if n_steps < 1 or tuple(table.shape) != (n_steps, 5) or tuple(ts_rows.shape) != (n_steps, B) or len(orders) != n_steps:
             raise ValueError("dpmpp_loop: table must be [n_steps, 5], ts_rows [n_steps, B] and orders n_steps ints, n_steps >= 1")
-        if a.inpainting != (inpaint_image is not None) or a.inpainting != (inpaint_mask is not None):
-            raise ValueError("dpmpp_loop: inpaint_image / inpaint_mask go with the 9-channel UNet, and only with it")
-        self._ensure_plan(B, H, W)
-        self._ensure_condition22(image_embeds, hint)
-        img = None if inpaint_image is None else inpaint_image.detach().float().expand(B, 4, H, W)
-        msk = None if inpaint_mask is None else inpaint_mask.detach().float().expand(B, 1, H, W)
-        k_init = k_noise = k_mask = coef = None
-        if keep is not None:
-            k_init, k_noise, k_mask, coef = keep
-            coef = np.ascontiguousarray(coef, dtype=np.float32)
-            if k_init.numel() != 4 * H * W or tuple(k_noise.shape) != (bs, 4, H, W) or k_mask.numel() != H * W or coef.shape != (n_steps, 2):
-                raise ValueError("dpmpp_loop: keep = (init [1,4,h,w], noise0 [bs,4,h,w], mask [1,1,h,w], coef [n_steps,2])")
-            k_init, k_mask = k_init.reshape(4, H, W), k_mask.reshape(H, W)
-        dev, g, clip = x.device, float(guidance_scale), (float(clamp[0]), float(clamp[1]))
-        if self._chained(B):
-            ack = {"image_embeds": image_embeds} if hint is None else {"image_embeds": image_embeds, "hint": hint}
-            extra = None if img is None else torch.cat([img, msk], 1)
-            kept = None if keep is None else (k_init.float().contiguous(), k_noise.float().contiguous(), k_mask.float().contiguous(), coef)
+        keep = sampling.keep_operands("dpmpp_loop", keep, B // 2, H, W, n_steps)
+        return self._dpm_loop("_dpmpp22_bufs", x, ts_rows, table, orders, guidance_scale, clamp, dict(image_embeds=image_embeds, hint=hint),
+                              (inpaint_image, inpaint_mask), keep=keep)
 
-            def call(xc, c):
-                inp = sampling.cfg_input(xc)
-                return self.forward(inp if extra is None else torch.cat([inp, extra], 1), ts_rows[c], added_cond_kwargs=ack, return_dict=False)[0]
-
-            return sampling.dpmpp_loop_keep(call, x.detach().float().clone(), table.float().contiguous(), orders, guidance=g, clamp=clip, keep=kept)
-        box, lat = (B, 4, H, W), (4, H, W)
-        bufs = self._dpmpp22_bufs.stage(
-            (B, H, W, n_steps, keep is not None, str(dev)), dev,
-            lambda: dict(x=box, tmp=box, hist=(2,) + box, ts=(n_steps, B), table=(n_steps, 5), img=box if a.inpainting else None,
-                         msk=(B, 1, H, W) if a.inpainting else None, kinit=lat if keep is not None else None,
-                         knoise=(bs,) + lat if keep is not None else None, kmask=(H, W) if keep is not None else None),
-            dict(x=x, ts=ts_rows, table=table, img=img, msk=msk, kinit=k_init, knoise=k_noise, kmask=k_mask))
-        ccoef = None if coef is None else coef.ctypes.data_as(C.POINTER(C.c_float))
-        _lib.check(_lib.lib().k22_unet_dpmpp_loop_keep(
-            self._handle, bufs["x"].data_ptr(), bufs["tmp"].data_ptr(), bufs["hist"].data_ptr(), bufs["ts"].data_ptr(), bufs["table"].data_ptr(),
-            (C.c_int * n_steps)(*orders), _lib.ptr(bufs["img"]), _lib.ptr(bufs["msk"]), n_steps, g, clip[0], clip[1], _lib.ptr(bufs["kinit"]),
-            _lib.ptr(bufs["knoise"]), _lib.ptr(bufs["kmask"]), ccoef, 1 if self.use_graph else 0, _lib.current_stream()))
-        return bufs["x"].clone(), bufs["hist"][(n_steps - 1) % 2].clone()
+    def ddim_loop(self, *args, **kwargs):
+        raise NotImplementedError("UNet2DConditionHIP has no DDIM / PLMS loop: the 2.2 decoders sample with sample_loop (DDPM) or dpmpp_loop")
 
     @torch.no_grad()
     def forward(self, sample, timestep, encoder_hidden_states=None, added_cond_kwargs=None, return_dict: bool = True, **_unused):

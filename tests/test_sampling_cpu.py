@@ -260,3 +260,14 @@ def test_inpaint_operands_helper():
     assert tuple(img.shape) == (4, 4, 2, 3) and tuple(msk.shape) == (4, 1, 2, 3) and img.dtype == msk.dtype == torch.float32
     with pytest.raises(ValueError, match="do not match x"):
         inp._inpaint_operands(x, torch.ones(3, 4, 2, 3), None)
+
+
+def test_k22_chains_reaches_the_2_1_module_only_and_the_2_2_module_has_no_ddim_loop(monkeypatch):
+    monkeypatch.setenv("K22_CHAINS", "2")
+    assert k22.Text2ImUNetHIP(k22.make_arch(k22.tiny_model_config()), meta_params=True).chains == 2
+    m = k22.UNet2DConditionHIP(k22.make_arch22(k22.tiny_unet22_config()), meta_params=True)
+    assert m.chains == 1                                                          # its forward and set_condition address one engine
+    with pytest.raises(NotImplementedError):                                      # the inherited loop conditions through the 2.1 head
+        m.ddim_loop("ddim", _x(), torch.zeros(5, 2), torch.zeros(5, 4), 4.0)
+    assert not m._engines                                                         # refused before anything was prepared
+    assert k22.UNet2DConditionHIP(meta_params=True).chains == 1

@@ -333,3 +333,21 @@ def test_unet22_conditioning_follows_content_not_tensor_identity():
         a = m(x, t, added_cond_kwargs={"image_embeds": e, "hint": hh}, return_dict=False)[0]
         b = m(x, t, added_cond_kwargs={"image_embeds": e, "hint": hh}, return_dict=False)[0]
     assert torch.equal(a, b) and torch.equal(a, want(emb1, hint1)) and m._cond_key is None
+
+
+def test_k22_chains_does_not_reach_the_2_2_module(monkeypatch):
+    """UNet2DConditionHIP's forward, set_condition and set_hint address one engine with the whole batch, so the module runs one chain whatever
+    K22_CHAINS says: one engine after the first forward, and the bits of a module constructed with the variable unset.  (Two engines planned
+    at B // 2 would leave the second half of the output unwritten.)"""
+    B, h, w = 2, 8, 8                                                # the CFG pair, two different embedding rows; 8 = 2^3 levels
+    x, emb, _ = _inputs(B, h, w, seed=21)
+    x, t, ack = x.cuda(), torch.tensor([700.0, 700.0]).cuda(), {"image_embeds": emb.cuda()}
+    assert not torch.equal(emb[0], emb[1])
+    monkeypatch.delenv("K22_CHAINS", raising=False)
+    _, _, plain = _unet(False, torch.float32)
+    monkeypatch.setenv("K22_CHAINS", "2")
+    _, _, m = _unet(False, torch.float32)
+    want = plain(x, t, added_cond_kwargs=ack, return_dict=False)[0]
+    got = m(x, t, added_cond_kwargs=ack, return_dict=False)[0]
+    assert m.chains == 1 and len(m._engines) == 1 and not m._chained(B)
+    assert torch.equal(got, want) and not torch.equal(got[0], got[1])
