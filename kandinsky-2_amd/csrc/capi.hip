@@ -403,27 +403,6 @@ int k22_groupnorm(const void* x0, const void* x1, int C0, int C1, int B, int H, 
   return launch_gn_apply(ap, dtype, st);
 }
 
-// conv3x3(GroupNorm32(cat(x0, x1)) [*(1 + scale) + shift] -> act) with the GroupNorm-apply FUSED into the convolution's halo fill
-// (conv3_halo_spec_kernel, IgemmParams::gn_coeff): statistics pass + coefficient kernel, then ONE convolution launch that reads the raw
-// tensors.  algo = 11 / 12 (the specialised kernels).  scratch: k22_groupnorm_scratch_bytes(B, C0 + C1).
-int k22_conv3x3_gn(const void* x0, const void* x1, int C0, int C1, const float* gamma, const float* beta, const float* film, long film_ld,
-                   float eps, int act, void* scratch, const void* Wp, const float* bias, const void* residual, void* out, void* partial,
-                   int B, int H, int W, int Cout, int Npad, int splitk, int bm, int algo, int dtype, void* stream) {
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int C = C0 + C1, HW = H * W;
-  const int sdt = k22_storage_dtype(dtype);
-  float* part = reinterpret_cast<float*>(scratch);
-  float* coeff = part + (size_t)B * 128 * C * 2;
-  const int rc = launch_gn_stats_coeff(x0, x1, C0, C1, B, HW, eps, gamma, beta, film, film_ld, part, coeff, sdt, st);
-  if (rc) return rc;
-  IgemmParams p = igemm_conv3_problem(B, H, W, C, Cout);   // (no A0: the input is read through gn_x0 / gn_x1)
-  p.Wp = Wp; p.bias = bias; p.residual = residual; p.out = out; p.partial = reinterpret_cast<float*>(partial);
-  p.Npad = Npad; p.splitk = splitk > 0 ? splitk : 1; p.force_bm = bm; p.algo = algo;
-  p.gn_coeff = coeff; p.gn_x0 = x0; p.gn_x1 = x1; p.gn_C0 = C0; p.gn_act = act;
-  return launch_igemm(p, dtype, st);
-}
-
-
 // kv_pack, then attention, with the mask and output-format fields of AttentionParams the engines set
 static int attention_seq(const void* qkv, const void* ctxkv, void* kall, void* vtall, void* out, int B, int H, int T, int S, int causal,
                          const float* key_valid, int kv_n, int out_x3, int dtype, hipStream_t st) {

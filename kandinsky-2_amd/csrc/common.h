@@ -77,7 +77,7 @@ template <> __device__ __forceinline__ float from_f32<float>(float f) { return f
 __device__ __forceinline__ float silu_f(float x) { return x / (1.0f + __expf(-x)); }
 // SiLU from the two native transcendentals, x * rcp(1 + exp2(-x * log2 e)): a few ulp of fp32 in 6 instructions, where the IEEE form
 // above (precise expf + a true division) compiles to ~55.  Used ONLY by the split-precision engine's GroupNorm store (gn_apply's
-// out_x3, gn_rewrite16<x3_t>), whose parity gates were measured with it (C2 final latent 3.6e-6).  The bf16 / fp16 engines keep the
+// out_x3), whose parity gates were measured with it (C2 final latent 3.6e-6).  The bf16 / fp16 engines keep the
 // IEEE form: round 4 tried silu_fast there and measured (a) no speed-up of the bf16 step (GroupNorm class 1.16 -> 1.18 ms: those
 // launches are latency-, not VALU-bound) and (b) a WORSE fp16 / bf16 MoVQ decode against the reference goldens in 9 of 10 fp16
 // cases (768 px fp16: uint8 max diff 3 -> 6, 11.5 % -> 12.6 % of the bytes differ; bf16: 24 -> 36 grey levels), reproduced as an
@@ -155,7 +155,7 @@ template <> struct is_x3<x2_t> { static constexpr bool value = true; };
 // Host-side dispatch on an arithmetic type: f(k22_tag<T>{}) with T the element type of `dtype`; -1 (K22_EINVAL) for a dtype outside K22DType.
 // A kernel that is not instantiated for some T is kept out with `if constexpr` inside f.
 // The order of the cases is the order in which a file's kernels are instantiated, and the compiler's output is not independent of it: with
-// the 16-bit types first, conv3_halo_spec_kernel<x3_t, 256, 2 / 3> (kernels that spill SGPRs) come out with three more spills.  With this
+// the 16-bit types first, conv3_halo_spec_kernel<x3_t, 256, 2 / 3> (kernels that spilled SGPRs when this was measured) came out with three more spills.  With this
 // order every kernel has the bytes it had under the hand-written ladders (tools/compare_device_code.py).
 template <typename T> struct k22_tag { using type = T; };
 template <typename F> inline int k22_with_dtype(int dtype, F&& f) {

@@ -1,5 +1,5 @@
 // k22 - shared by the LDS-resident-halo convolution kernels (conv3_halo.hip: lock-step kernels; conv3_up2.hip; gemm8.hip; conv3_spec.hip:
-// the producer / consumer specialised kernel): fragment loaders, the LDS-DMA helper, the fused GroupNorm-apply rewrite, the one definition
+// the producer / consumer specialised kernel): fragment loaders, the LDS-DMA helper, the one definition
 // of the 8-wave frame (block map, slab range, loader offsets and issues), of the tap body and of the tap step, the common epilogue
 // halo_tail, and the LDS budget and launch dispatch every launcher and kernel agrees on.
 #pragma once
@@ -109,56 +109,6 @@ __device__ __forceinline__ void glds16_asm(const void* g, unsigned lds_dst) {
   unsigned keep;
   asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
                : "=&s"(keep) : "v"(g), "s"(lds_dst) : "memory");
-}
-
-
-// ---- fused GroupNorm-apply (conv3_halo_spec_kernel producers; IgemmParams::gn_coeff) -------------------------------------------
-// 16 bytes of raw T values as the LDS-DMA left them (EPC consecutive channels of one pixel) -> act(x * A[c] + Bc[c]) in the operand
-// format of T, zero at a border position.  cf = this lane's coefficients (A, Bc) x EPC as gn_coeff_kernel wrote them.  Same
-// expression and rounding as gn_apply_kernel (elementwise.hip): the fused and the stand-alone path give the same bits.
-__device__ __forceinline__ u32x4_t gn_rewrite16(bf16_t, u32x4_t raw, const float* cf, int act, bool border) {
-  float v[8];
-  unpack2_bf16(raw.x, v[0], v[1]); unpack2_bf16(raw.y, v[2], v[3]); unpack2_bf16(raw.z, v[4], v[5]); unpack2_bf16(raw.w, v[6], v[7]);
-#pragma unroll
-  for (int k = 0; k < 8; ++k) v[k] = apply_act(v[k] * cf[2 * k] + cf[2 * k + 1], act);
-  const u32x4_t o = {pack2_bf16(v[0], v[1]), pack2_bf16(v[2], v[3]), pack2_bf16(v[4], v[5]), pack2_bf16(v[6], v[7])};
-  return border ? u32x4_t{0u, 0u, 0u, 0u} : o;
-}
-__device__ __forceinline__ u32x4_t gn_rewrite16(f16_t, u32x4_t raw, const float* cf, int act, bool border) {
-  float v[8];
-  unpack2_f16(raw.x, v[0], v[1]); unpack2_f16(raw.y, v[2], v[3]); unpack2_f16(raw.z, v[4], v[5]); unpack2_f16(raw.w, v[6], v[7]);
-#pragma unroll
-  for (int k = 0; k < 8; ++k) v[k] = apply_act(v[k] * cf[2 * k] + cf[2 * k + 1], act);
-  const u32x4_t o = {pack2_f16(v[0], v[1]), pack2_f16(v[2], v[3]), pack2_f16(v[4], v[5]), pack2_f16(v[6], v[7])};
-  return border ? u32x4_t{0u, 0u, 0u, 0u} : o;
-}
-__device__ __forceinline__ u32x4_t gn_rewrite16(float, u32x4_t raw, const float* cf, int act, bool border) {
-  float v[4] = {__uint_as_float(raw.x), __uint_as_float(raw.y), __uint_as_float(raw.z), __uint_as_float(raw.w)};
-#pragma unroll
-  for (int k = 0; k < 4; ++k) v[k] = apply_act_sel<false>(v[k] * cf[2 * k] + cf[2 * k + 1], act);
-  const u32x4_t o = {__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])};
-  return border ? u32x4_t{0u, 0u, 0u, 0u} : o;
-}
-// split precision: fp32 in, x3 chunk out (what gn_apply_kernel's out_x3 store writes)
-__device__ __forceinline__ u32x4_t gn_rewrite16(x3_t, u32x4_t raw, const float* cf, int act, bool border) {
-  float v[4] = {__uint_as_float(raw.x), __uint_as_float(raw.y), __uint_as_float(raw.z), __uint_as_float(raw.w)};
-#pragma unroll
-  for (int k = 0; k < 4; ++k) v[k] = apply_act_sel<true>(v[k] * cf[2 * k] + cf[2 * k + 1], act);
-  const u32x4_t o = x3_split4(v[0], v[1], v[2], v[3]);
-  return border ? u32x4_t{0u, 0u, 0u, 0u} : o;
-}
-__device__ __forceinline__ u32x4_t gn_rewrite16(x2_t, u32x4_t raw, const float* cf, int act, bool border) { return gn_rewrite16(x3_t{}, raw, cf, act, border); }
-// plain 16-byte global load from inline asm: one more entry of the producers' hand-counted VMEM queue (a compiler-issued load would
-// make hipcc wait vmcnt(0) - draining every LDS-DMA in flight - before its first use); the destination is valid only behind a
-// gn_wait_* statement that names it
-__device__ __forceinline__ void gload16_asm(u32x4_t& dst, const void* g) {
-  asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(dst) : "v"(g) : "memory");
-}
-template <int N> __device__ __forceinline__ void gn_wait(u32x4_t (&c)[4]) {
-  asm volatile("s_waitcnt vmcnt(%4)" : "+v"(c[0]), "+v"(c[1]), "+v"(c[2]), "+v"(c[3]) : "n"(N) : "memory");
-}
-template <int N> __device__ __forceinline__ void gn_wait(u32x4_t (&c)[2]) {
-  asm volatile("s_waitcnt vmcnt(%2)" : "+v"(c[0]), "+v"(c[1]) : "n"(N) : "memory");
 }
 
 // the same for a WEIGHT piece.  K22_W_NT (measurement build): non-temporal hint - each weight byte is read by the few workgroups of one
@@ -369,17 +319,17 @@ template <bool GASM, bool WEIGHT> __device__ __forceinline__ void halo_dma16(con
 #define K22_TAPS_9(M, ...) M(0, __VA_ARGS__) M(1, __VA_ARGS__) M(2, __VA_ARGS__) M(3, __VA_ARGS__) M(4, __VA_ARGS__) M(5, __VA_ARGS__) M(6, __VA_ARGS__) M(7, __VA_ARGS__) M(8, __VA_ARGS__)
 #define K22_TAPS_4(M, ...) M(0, __VA_ARGS__) M(1, __VA_ARGS__) M(2, __VA_ARGS__) M(3, __VA_ARGS__)
 // A kernel may stand statements at four points of a tap: K22_TAP_HOOK(0 .. 3, TAP) = before the counted wait, behind it, behind the
-// barrier, behind the tap body (conv3_halo_kernel's TRACE stamps; the fused GroupNorm-apply producers' coefficient load)
+// barrier, behind the tap body (conv3_halo_kernel's TRACE stamps)
 #define K22_TAP_HOOK(N, TAP)
 // The loaders' half of a tap, for loader wave LW of NWL in a TAPS-tap filter (weights [n][tap][Kc]) with an NBST-deep weight ring behind
 // the two halo buffers: the counted vmcnt wait for this tap's weight tile (VMEM queue of a wave per tap: [weight tile NBST-1 taps ahead,
 // B_SLOTS loads] then [PPT halo pieces, taps 0 .. TAPS-NBST]: at most the B_SLOTS * (NBST-2) younger weight loads and the halo pieces issued
 // since stay in flight; the last halo piece of a slab is followed by the weight loads of NBST-1 taps, so at tap 0 of the next slab it is
 // older than everything the wait leaves in flight), the ONE raw barrier of the tap, then the weight tile NBST-1 taps ahead into ring slot
-// `fill` and the next PPT pieces of the next slab's halo (ISSUE_HALO: K22_ISSUE_A or a macro of its signature) into the halo buffer at
-// LDS location ANEXT; RING = the LDS location of the weight ring (pasted as written: its sum with the slot offset is one expression).
+// `fill` and the next PPT pieces of the next slab's halo (K22_ISSUE_A) into the halo buffer at LDS location ANEXT; RING = the LDS
+// location of the weight ring (pasted as written: its sum with the slot offset is one expression).
 // Needs s, sn, fill, B_BYTES, B_SLOTS, NBST, p.
-#define K22_TAP_FRONT(TAP, TAPS, LW, NWL, PPT, WAITS, LOADS, ISSUE_HALO, ANEXT, RING)                      \
+#define K22_TAP_FRONT(TAP, TAPS, LW, NWL, PPT, WAITS, LOADS, ANEXT, RING)                                  \
   K22_TAP_HOOK(0, TAP)                                                                                     \
   if (WAITS) wait_vmcnt<B_SLOTS * (NBST - 2) + (PPT) * halo_count<TAPS, NBST>(TAP)>();                     \
   K22_TAP_HOOK(1, TAP)                                                                                     \
@@ -392,7 +342,7 @@ template <bool GASM, bool WEIGHT> __device__ __forceinline__ void halo_dma16(con
     if constexpr ((TAP) <= (TAPS) - NBST) {                                                                \
       _Pragma("unroll") for (int a_ = 0; a_ < (PPT); ++a_) {                                               \
         constexpr int qb_ = ((TAP) <= (TAPS) - NBST ? (TAP) : 0) * (PPT);                                  \
-        ISSUE_HALO(LW, NWL, qb_ + a_, sn, ANEXT);                                                          \
+        K22_ISSUE_A(LW, NWL, qb_ + a_, sn, ANEXT);                                                       \
       }                                                                                                    \
     }                                                                                                      \
   }
@@ -416,7 +366,7 @@ template <bool GASM, bool WEIGHT> __device__ __forceinline__ void halo_dma16(con
 // One tap of a lock-step kernel: every wave loads, then multiplies
 #define K22_LOCKSTEP_TAP(TAP, TAPS, PPT, INLOOP, ...)                                                      \
   {                                                                                                        \
-    K22_TAP_FRONT(TAP, TAPS, wave, NW, PPT, INLOOP, INLOOP, K22_ISSUE_A, Anext, Bst)                       \
+    K22_TAP_FRONT(TAP, TAPS, wave, NW, PPT, INLOOP, INLOOP, Anext, Bst)                                    \
     K22_TAP_COMPUTE(TAP, TAPS, __VA_ARGS__)                                                                \
     fill = (fill + 1 == NBST) ? 0 : fill + 1;                                                              \
   }
@@ -740,10 +690,9 @@ inline size_t halo_lds_budget(int bm, bool skip, size_t main_loop) {
   m = m > sk ? m : sk;
   return m > red ? m : red;
 }
-// 128-byte-row kernels: two halo buffers + an nbst-deep weight ring (+ 1 KB behind the ring for the fused GroupNorm-apply form: the
-// landing place of its surplus DMA slots).  The four-phase problems have neither that form nor a fused skip.
+// 128-byte-row kernels: two halo buffers + an nbst-deep weight ring.  The four-phase problems have no fused skip.
 inline size_t halo_smem_bytes(const IgemmParams& p, int bm, int nbst, int taps = 9) {
-  const size_t main_loop = (size_t)2 * halo_rows(p, bm, taps) * 128 + (size_t)nbst * HALO_BN * 128 + (taps == 9 && p.gn_coeff ? 1024 : 0);
+  const size_t main_loop = (size_t)2 * halo_rows(p, bm, taps) * 128 + (size_t)nbst * HALO_BN * 128;
   return halo_lds_budget(bm, taps == 9 && p.S0, main_loop);
 }
 

@@ -321,15 +321,11 @@ int conv3_halo_ring(const IgemmParams& p, int bm) { return p.algo == IG_ALGO_HAL
 bool conv3_halo_supported(const IgemmParams& p, int dtype, int bm) {
   const int BK = k22_bk(dtype);
   if (p.taps != 9 || (bm != 256 && bm != 128 && bm != HALO_BM_STRIP)) return false;
-  // the 224-row tile: conv3_halo_spec_kernel's pipelined form in the 16-bit types, without the fused GroupNorm-apply
-  if (bm == HALO_BM_STRIP && (p.algo != IG_ALGO_SPEC_PIPE || k22_esz(dtype) != 2 || p.gn_coeff != nullptr)) return false;
+  // the 224-row tile: conv3_halo_spec_kernel's pipelined form in the 16-bit types
+  if (bm == HALO_BM_STRIP && (p.algo != IG_ALGO_SPEC_PIPE || k22_esz(dtype) != 2)) return false;
   // split precision: the input is read in x3 chunks; instantiated forms = the lock-step kernel with asm LDS-DMA (algo 2 / 6 / 7 all
   // run it) and the specialised kernel (11 / 12)
   if (k22_is_split(dtype) && (p.a_raw || p.algo == IG_ALGO_HALO3)) return false;
-  if (p.gn_coeff != nullptr) {   // fused GroupNorm-apply: the specialised kernels only; slabs never straddle the two raw sources
-    if (!conv3_algo_fuses_gn(p.algo) || !p.gn_x0 || p.gn_C0 <= 0 || p.gn_C0 > p.Kc || p.gn_C0 % BK || (p.gn_C0 < p.Kc && !p.gn_x1)) return false;
-    if ((int64_t)p.H * p.W * p.Kc >= (1ll << 31)) return false;
-  }
   if (p.out_mode != IG_OUT_ROWMAJOR && p.out_mode != IG_OUT_ROWMAJOR_F32) return false;
   if (p.N % 8 || p.ldo % 8 || (p.residual && p.ldr % 8) || p.Kc % BK) return false;
   if (p.H <= 0 || p.W <= 0 || p.M % (p.H * p.W)) return false;

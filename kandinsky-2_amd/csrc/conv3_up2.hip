@@ -104,7 +104,7 @@ int conv3_up2_tiles_per_image(const IgemmParams& p, int bm) { return halo_tiles_
 bool conv3_up2_supported(const IgemmParams& p, int dtype, int bm) {
   const int BK = k22_bk(dtype);
   if (p.taps != 4 || (bm != 256 && bm != 128)) return false;
-  if (p.a_raw || p.gn_coeff != nullptr || p.S0 != nullptr || p.A1 != nullptr || p.res_f32) return false;
+  if (p.a_raw || p.S0 != nullptr || p.A1 != nullptr || p.res_f32) return false;
   if (p.out_mode != IG_OUT_ROWMAJOR && p.out_mode != IG_OUT_ROWMAJOR_F32) return false;
   if (p.N % 8 || p.ldo % 8 || (p.residual && p.ldr % 8) || p.Kc % BK || p.K0 != p.Kc) return false;
   if (p.H <= 0 || p.W <= 0 || p.M % (4 * p.H * p.W)) return false;

@@ -194,8 +194,7 @@ __global__ __launch_bounds__(256) void gn_coeff_kernel(GnCoeffParams p) {
 template <typename T>
 __global__ __launch_bounds__(256) void gn_apply_kernel(GnApplyParams p) {
   constexpr int EPV = Vec16<T>::N;
-  // split-precision store: SiLU through the native exp2 / rcp (common.h: silu_fast; the same choice as the fused form of this pass in
-  // conv3_common.h: gn_rewrite16 - the two give the same bits).  The 16-bit engines keep the IEEE form: see common.h
+  // split-precision store: SiLU through the native exp2 / rcp (common.h: silu_fast).  The 16-bit engines keep the IEEE form: see common.h
   const bool fast = p.out_x3 != 0;
   const int C = p.C0 + p.C1, CV = C / EPV;
   const int Ho = p.mode == 1 ? p.H / 2 : (p.mode == 2 ? p.H * 2 : p.H);

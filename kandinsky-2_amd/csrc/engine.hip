@@ -81,15 +81,10 @@ struct K22UNet : GraphPlan {   // dtype: arithmetic type of the MFMA kernels (K2
   OpList hint_ops;  // 2.2 ControlNet-depth: input_hint_block over the hint image (once per generation)
   bool hint_set = false;
   int fuse_skip = 1;
-  // GroupNorm-apply (+FiLM, +SiLU, zero border) fused into the consuming 3x3 convolution's halo fill (conv3_halo_spec_kernel producers)
-  // wherever the convolution's tile configuration is one of the specialised kernels; the stand-alone gn_apply stays for the rest.
-  // OFF by default (K22_FUSE_GN=1 turns it on): parity-green and bit-identical to the two-kernel path, but measured SLOWER on MI355X -
-  // bf16 C2 step 143.5 -> 112.9 steps/s (conv class 4.30 -> 6.48 ms for 0.26 ms of gn_apply removed), f16x3 66.5 -> 59.4: the matrix
-  // pipe's owner shares its SIMD's issue port with the producer wave, every n-tile of an m-tile re-normalises the same pixels (6-12x
-  // the work of one stand-alone pass), and the rewrite pins each halo piece to land within ONE tap (profiles/r04_gn_fused_negative.txt).
-  int fuse_gn = 0;
-  struct GnLink { const Tuned* consumer = nullptr; };   // GroupNorm op -> the convolution that reads its output (set after both exist)
-  std::deque<GnLink> gn_links;
+  // (GroupNorm-apply fused into the consuming 3x3 convolution's halo fill - conv3_halo_spec_kernel's producers rewriting the raw tensor in
+  // the LDS - was built, bit-identical to the two-kernel path, and measured SLOWER on MI355X: bf16 C2 step 143.5 -> 112.9 steps/s, f16x3
+  // 66.5 -> 59.4 (profiles/r04_gn_fused_negative.txt).  Removed; the code is in the parent of the commit that removed it.  Every GroupNorm
+  // runs the stand-alone gn_apply.)
   // weight-streaming kernel (stream_gemm.hip) for the small-M 3x3 convolutions: fragment-major copies of their weights live in the
   // workspace (one more copy of those weights: ~1.2 GB of the 2.1 UNet in bf16), written once per bind before the first forward
   int stream_frag = 1;
@@ -253,7 +248,7 @@ struct K22UNet : GraphPlan {   // dtype: arithmetic type of the MFMA kernels (K2
 
   // ------------------------------------------------------------------------------------------
   void op_gn(OpList& L, const Act& in, const std::string& pfx, int64_t film_off,
-             int act, int mode, int pad, Slot* dst, const GnLink* link = nullptr) {
+             int act, int mode, int pad, Slot* dst) {
     const int Bn = B, C = in.C(), HW = in.H * in.W;
     const int nsplit = gn_nsplit(Bn, HW);
     // producer-side partial sums for every part of the input?  Otherwise the stand-alone stats pass.
@@ -294,8 +289,6 @@ struct K22UNet : GraphPlan {   // dtype: arithmetic type of the MFMA kernels (K2
       ap.mode = mode; ap.pad = pad; ap.act = act; ap.coeff = ptr<float>(s_coeff); ap.out = ptr(dst); ap.out_x3 = x3;
       int rc = launch_gn_coeff(cp, Bn, st);
       if (rc) return rc;
-      // the consuming convolution applies the coefficients itself while it fills its LDS halo (fused GroupNorm-apply): nothing to write
-      if (link != nullptr && link->consumer != nullptr && conv3_algo_fuses_gn(link->consumer->cfg.algo)) return K22_OK;
       return launch_gn_apply(ap, dt, st);
     }, OP_GN, 0.0, gn_bytes, fused ? 2 : 3));
   }
@@ -335,11 +328,9 @@ struct K22UNet : GraphPlan {   // dtype: arithmetic type of the MFMA kernels (K2
 
   // conv3x3 over a zero-bordered slot `src` [B][Hc+2][Wc+2][Cin].  `stats` (optional) receives the GroupNorm
   // partial sums of the output; returns the launch descriptor (null when the output is not a tunable T tensor).
-  // gn_in (optional): the raw tensor(s) whose GroupNorm (coefficients in s_coeff, written by the op_gn just before) `src` holds: with a
-  // specialised-kernel configuration the convolution reads gn_in and applies the coefficients in its halo fill instead of reading `src`
   Tuned* op_conv(OpList& L, int role, Slot* src, int Hc, int Wc, int Cin, int Cout,
                  const std::string& pfx, const Act* residual, Slot* dst, int out_mode, Slot* stats = nullptr,
-                 const Act* skip_in = nullptr, const std::string& skip_pfx = std::string(), const Act* gn_in = nullptr, int gn_act = K22_ACT_NONE) {
+                 const Act* skip_in = nullptr, const std::string& skip_pfx = std::string()) {
     tuned.emplace_back();
     Tuned* t = &tuned.back();
     t->dt = conv_dt(role, Hc);
@@ -387,16 +378,10 @@ struct K22UNet : GraphPlan {   // dtype: arithmetic type of the MFMA kernels (K2
     need(dst, out_mode == IG_OUT_ROWMAJOR ? (size_t)p.M * Cout * esz : (size_t)p.M * Cout * sizeof(float));
     Slot* rs = residual ? residual->s0 : nullptr;
     const int dt = t->dt;
-    const bool gnf = gn_in != nullptr && fuse_gn;
-    Act ga;
-    if (gnf) ga = *gn_in;
     t->run = [=](hipStream_t st) {
       IgemmParams q = t->p;
       apply_cfg(q, t->cfg);
       q.A0 = ptr(src); q.residual = rs ? ptr(rs) : nullptr; q.out = ptr(dst); q.partial = ptr<float>(s_splitk);
-      if (gnf && conv3_algo_fuses_gn(t->cfg.algo)) {
-        q.gn_coeff = ptr<float>(s_coeff); q.gn_x0 = ptr(ga.s0); q.gn_x1 = ga.s1 ? ptr(ga.s1) : nullptr; q.gn_C0 = ga.C0; q.gn_act = gn_act;
-      }
       q.stats = t->want_stats ? ptr<float>(stats) : nullptr;
       if (q.S0) { q.S0 = ptr(sk.s0); q.S1 = sk.s1 ? ptr(sk.s1) : nullptr; }
       q.Wfrag = wf ? ptr(wf) : nullptr; q.Wsfrag = wsf ? ptr(wsf) : nullptr;
@@ -482,34 +467,34 @@ struct K22UNet : GraphPlan {   // dtype: arithmetic type of the MFMA kernels (K2
     return t;
   }
 
+  // The tensor `t` wrote: [B][Ho][Wo][C] in `s`, with its GroupNorm partial sums in `stats` where t delivers them
+  static Act produced(Slot* s, int C, int Ho, int Wo, const Tuned* t, Slot* stats) {
+    Act a; a.s0 = s; a.C0 = C; a.H = Ho; a.W = Wo;
+    if (t->want_stats) { a.p0 = t; a.st0 = stats; }
+    return a;
+  }
+
   // ResBlock (unet.py:110-220) with use_scale_shift_norm=True; updown: 0 none, 1 down, 2 up.
   Act resblock(const std::string& pfx, const Act& in, int Cout, int updown, int64_t& film_cursor, Slot* dst, Slot* dst_stats) {
     const int Cin = in.C();
     const int Ho = updown == 1 ? in.H / 2 : (updown == 2 ? in.H * 2 : in.H);
     const int Wo = updown == 1 ? in.W / 2 : (updown == 2 ? in.W * 2 : in.W);
     // in_layers: GN + SiLU (+ resample) -> conv3x3
-    GnLink* l1 = nullptr;
-    if (fuse_gn && updown == 0) { gn_links.emplace_back(); l1 = &gn_links.back(); }   // (the resampling GroupNorms keep gn_apply)
     const bool up2 = updown == 2 && !in.s1 && up2_route(pfx + ".in_layers.2.weight_up2", in.H, in.W, Cin, Cout);
     Tuned* t1;
     if (up2) {
       // GroupNorm + SiLU at the LOW resolution (zero border), then the four 2x2 phase convolutions write the high-resolution tensor
-      op_gn(ops, in, pfx + ".in_layers.0", -1, K22_ACT_SILU, 0, 1, s_P1, nullptr);
+      op_gn(ops, in, pfx + ".in_layers.0", -1, K22_ACT_SILU, 0, 1, s_P1);
       t1 = op_conv_up2(ops, s_P1, in.H, in.W, Cin, Cout, pfx + ".in_layers.2", s_U1, s_U1st);
     } else {
-      op_gn(ops, in, pfx + ".in_layers.0", -1, K22_ACT_SILU, updown, 1, s_P1, l1);
-      t1 = op_conv(ops, CONV_IN, s_P1, Ho, Wo, Cin, Cout, pfx + ".in_layers.2", nullptr, s_U1, IG_OUT_ROWMAJOR, s_U1st, nullptr, std::string(),
-                   l1 ? &in : nullptr, K22_ACT_SILU);
+      op_gn(ops, in, pfx + ".in_layers.0", -1, K22_ACT_SILU, updown, 1, s_P1);
+      t1 = op_conv(ops, CONV_IN, s_P1, Ho, Wo, Cin, Cout, pfx + ".in_layers.2", nullptr, s_U1, IG_OUT_ROWMAJOR, s_U1st);
     }
-    if (l1) l1->consumer = t1;
     // out_layers: GN * (1+scale) + shift -> SiLU -> conv3x3 (+ skip)
-    Act u1; u1.s0 = s_U1; u1.C0 = Cout; u1.H = Ho; u1.W = Wo;
-    if (t1->want_stats) { u1.p0 = t1; u1.st0 = s_U1st; }
+    const Act u1 = produced(s_U1, Cout, Ho, Wo, t1, s_U1st);
     const int64_t film_off = film_cursor;
     film_cursor += 2 * Cout;
-    GnLink* l2 = nullptr;
-    if (fuse_gn) { gn_links.emplace_back(); l2 = &gn_links.back(); }
-    op_gn(ops, u1, pfx + ".out_layers.0", film_off, K22_ACT_SILU, 0, 1, s_P2, l2);
+    op_gn(ops, u1, pfx + ".out_layers.0", film_off, K22_ACT_SILU, 0, 1, s_P2);
     Act skip;
     skip.H = Ho; skip.W = Wo; skip.C0 = Cout;
     if (updown) {
@@ -525,11 +510,8 @@ struct K22UNet : GraphPlan {   // dtype: arithmetic type of the MFMA kernels (K2
       probe.SK0 = in.C0; probe.SK1 = in.C1; probe.Ws = reinterpret_cast<const void*>(1);
       if (fuse_skip && Cout >= 128 && (conv3_halo_supported(probe, dtype, 256) || conv3_halo_supported(probe, dtype, 128))) {
         Tuned* t2 = op_conv(ops, CONV_OUT, s_P2, Ho, Wo, Cout, Cout, pfx + ".out_layers.3", nullptr, dst, IG_OUT_ROWMAJOR, dst_stats,
-                            &in, pfx + ".skip_connection", l2 ? &u1 : nullptr, K22_ACT_SILU);
-        if (l2) l2->consumer = t2;
-        Act out; out.s0 = dst; out.C0 = Cout; out.H = Ho; out.W = Wo;
-        if (t2->want_stats) { out.p0 = t2; out.st0 = dst_stats; }
-        return out;
+                            &in, pfx + ".skip_connection");
+        return produced(dst, Cout, Ho, Wo, t2, dst_stats);
       }
       op_gemm(ops, in, B * Ho * Wo, Cout, pfx + ".skip_connection", nullptr, s_S, 0, IG_OUT_ROWMAJOR, nullptr, /*a_raw=*/true);
       skip.s0 = s_S;
@@ -537,12 +519,8 @@ struct K22UNet : GraphPlan {   // dtype: arithmetic type of the MFMA kernels (K2
       if (in.s1) { if (err.empty()) err = "identity skip over a concat input"; }
       skip.s0 = in.s0;
     }
-    Tuned* t2 = op_conv(ops, CONV_OUT, s_P2, Ho, Wo, Cout, Cout, pfx + ".out_layers.3", &skip, dst, IG_OUT_ROWMAJOR, dst_stats, nullptr, std::string(),
-                        l2 ? &u1 : nullptr, K22_ACT_SILU);
-    if (l2) l2->consumer = t2;
-    Act out; out.s0 = dst; out.C0 = Cout; out.H = Ho; out.W = Wo;
-    if (t2->want_stats) { out.p0 = t2; out.st0 = dst_stats; }
-    return out;
+    Tuned* t2 = op_conv(ops, CONV_OUT, s_P2, Ho, Wo, Cout, Cout, pfx + ".out_layers.3", &skip, dst, IG_OUT_ROWMAJOR, dst_stats);
+    return produced(dst, Cout, Ho, Wo, t2, dst_stats);
   }
 
   // AttentionBlock (unet.py:223-269) + QKVAttention (:272-340).  The qkv projection writes q row-major and k / v
@@ -588,9 +566,7 @@ struct K22UNet : GraphPlan {   // dtype: arithmetic type of the MFMA kernels (K2
     Act a; a.s0 = s_ATT; a.C0 = C; a.H = in.H; a.W = in.W;
     // proj_out + residual; its epilogue also delivers the GroupNorm partial sums the next ResBlock needs
     Tuned* tp = op_gemm(ops, a, B * T, C, pfx + ".proj_out", &in, dst, 0, IG_OUT_ROWMAJOR, dst_stats);
-    Act out; out.s0 = dst; out.C0 = C; out.H = in.H; out.W = in.W;
-    if (tp->want_stats) { out.p0 = tp; out.st0 = dst_stats; }
-    return out;
+    return produced(dst, C, in.H, in.W, tp, dst_stats);
   }
 
   bool has_attn(int ds) const {
@@ -606,7 +582,6 @@ struct K22UNet : GraphPlan {   // dtype: arithmetic type of the MFMA kernels (K2
     if (nB > 8) return k22_set_error(K22_EINVAL, "unet: batch (2*bs) must be <= 8 per engine call");
     begin_plan();
     B = nB; H = nH; W = nW;
-    gn_links.clear();
     ops.clear(); cond_ops.clear(); hint_ops.clear(); s_ctxkv.clear(); frag_jobs.clear(); frag_done = false; n_attn = 0;
     cond_set = false; hint_set = false;
     loop.drop();
@@ -1032,7 +1007,6 @@ int k22_unet_create(const K22UNetConfig* cfg, const K22Weight* weights, int n_we
   K22UNet* u = new K22UNet();
   u->cfg = *cfg; u->set_dtype(cfg->dtype); u->sdt = k22_storage_dtype(cfg->dtype);
   u->stream_frag = env_flag("K22_STREAM", 1);     // 0 = no fragment-major weight copies, no weight-streaming kernel
-  u->fuse_gn = env_flag("K22_FUSE_GN", 0);        // 0 = every GroupNorm through the stand-alone gn_apply kernel
   u->fuse_skip = env_flag("K22_FUSE_SKIP", 1);    // 0 = 1x1 skip connections as separate GEMMs
   u->hoist_time = env_flag("K22_HOIST_TIME", 1);  // 0 (measurement only) = k22_unet_sample_loop keeps the per-step time-embedding / FiLM launches
   const char* xp = getenv("K22_X2_PLAN");         // K22_F16X2 only: which of the top level's convolutions run with two MFMAs (K22UNet::x2_plan)

@@ -545,7 +545,7 @@ int igemm_resolve(const IgemmParams& p, int dtype, IgemmLaunch* out) {
       L.depth = conv3_halo_ring(ph, bm);
       if (want >= 2 && want < L.depth) L.depth = want == 5 ? 4 : want;   // shallower ring on request (instantiated: 2, 3, 4, 6; halo3: 2, 3, 4)
       const bool split = k22_is_split(dtype);
-      if (conv3_algo_fuses_gn(L.algo)) {
+      if (L.algo == IG_ALGO_SPEC || L.algo == IG_ALGO_SPEC_PIPE) {
         // x3 and fp32 at BM = 256: two fragment sets of 8 registers per fragment do not fit beside 128 accumulators: compiler-scheduled consumers
         L.family = IG_FAM_SPEC;
         L.pipe = (L.algo == IG_ALGO_SPEC_PIPE && !(bm == 256 && (dtype == K22_F16X3 || dtype == K22_F32))) ? 1 : 0;
@@ -634,8 +634,6 @@ int igemm_resolve(const IgemmParams& p, int dtype, IgemmLaunch* out) {
   }
   if (!stream) {
     if (p.res_f32 && !generic) return k22_set_error(K22_EINVAL, "igemm: fp32 residual is not supported by the halo kernel");
-    if (p.gn_coeff != nullptr && !conv3_algo_fuses_gn(L.algo))
-      return k22_set_error(K22_EINVAL, "igemm: the fused GroupNorm-apply input needs the specialised halo kernel (algo 11 / 12)");
     if (p.S0 != nullptr && generic) return k22_set_error(K22_EINVAL, "igemm: the fused 1x1 skip connection needs the halo kernel");
     if (p.stats != nullptr && L.splitk == 1 && generic)
       return k22_set_error(K22_EINVAL, "igemm: GroupNorm partial sums requested from a configuration that cannot produce them");
