@@ -199,6 +199,12 @@ int k22_unet_sample_loop_keep(K22UNet* u, float* x, float* x_tmp, const float* t
                               const int* table_rows, int n_steps, float guidance, float clamp_lo, float clamp_hi, int pct_index,
                               double pct_gamma, void* scratch, const float* keep_init, const float* keep_noise, const float* keep_mask,
                               const float* keep_coef, int use_graph, void* stream);
+/* The threshold group of the sampler steps of k22_unet_sample_loop and k22_unet_sample_loop_keep (pct_group of k22_sampler_step_groups):
+ * rows of the cond half that share the percentile of their first row.  0, the default, is the whole batch from element 0 - the loop as it
+ * has always run.  The loop entries read it when they build their steps and check it there against the planned B (it must divide B / 2
+ * into at most 64 groups; K22_EINVAL from the loop entry otherwise, which leaves the handle and its captured loop as they were).  It is a
+ * word of the captured loop's key: another value re-captures, the same value replays.  K22_EINVAL here for a null handle and rows < 0. */
+int k22_unet_set_threshold_group(K22UNet* u, int rows);
 /* The whole classifier-free-guided DDIM or PLMS loop - generate_img's default sampler and its documented alternative - as ONE hipGraph
  * replay (kandinsky2/kandinsky2_1_model.py:222-233, the non-p_sampler model_fn, driving kandinsky2/model/samplers.py:206-331 for
  * kind = K22_LOOP_DDIM and samplers.py:475-637 for kind = K22_LOOP_PLMS): per step  UNet([x_half | x_half], t) -> k22_ddim_step or
@@ -335,6 +341,17 @@ int k22_sampler_step(const float* x, const float* model_out, const float* noise,
                      const float* mask, const float* table, int step_index, float guidance, int use_cfg,
                      float clamp_lo, float clamp_hi, int pct_index, double pct_gamma, void* scratch,
                      float* x_out, float* x0_out, int N, int HW, void* stream);
+/* k22_sampler_step with the dynamic threshold taken per GROUP of rows: several prompts packed into one CFG batch, each clamped by the
+ * percentile of its own image, as separate reference calls would clamp them.  half = use_cfg ? N / 2 : N.  Group j is rows
+ * j * pct_group .. (j + 1) * pct_group - 1 of the cond half together with their uncond partners: s_j = max(percentile_99.5(|x0[j * pct_group]|), 1),
+ * the order statistics and the float32 lerp of k22_sampler_step on that row, and every row n with (n % half) / pct_group == j is clamped to
+ * +-s_j and divided by it.  The half / pct_group selects run as one launch, a workgroup each; s_j is float j of the scratch (floats
+ * half / pct_group .. 63 are not written; the size of the scratch is unchanged).  pct_group == half is k22_sampler_step itself: the same
+ * kernels, the same bits.  K22_EINVAL (with a k22_last_error text, nothing launched) for pct_group < 1, a pct_group that does not divide
+ * half, more than 64 groups, and whatever k22_sampler_step refuses. */
+int k22_sampler_step_groups(const float* x, const float* model_out, const float* noise, const float* init_img, const float* mask,
+                            const float* table, int step_index, float guidance, int use_cfg, float clamp_lo, float clamp_hi, int pct_index,
+                            double pct_gamma, int pct_group, void* scratch, float* x_out, float* x0_out, int N, int HW, void* stream);
 
 /* ---- individual kernels (unit-parity surface; the engine calls the same launchers) -------------
  * dtype-typed buffers are bf16, fp16 or fp32 according to `dtype`.  Layouts: see the headers in kandinsky-2_amd/csrc. */

@@ -160,6 +160,8 @@ SIGNATURES = {
     "k22_plms_step": (_I, [_P, _P, _P, _P, _P, _I, _P, _F, _I, _P, _P, _P, _I, _I, _P]),
     "k22_sampler_scratch_bytes": (_Z, [_I, _I]),
     "k22_sampler_step": (_I, [_P, _P, _P, _P, _P, _P, _I, _F, _I, _F, _F, _I, _D, _P, _P, _P, _I, _I, _P]),
+    "k22_sampler_step_groups": (_I, [_P, _P, _P, _P, _P, _P, _I, _F, _I, _F, _F, _I, _D, _I, _P, _P, _P, _I, _I, _P]),
+    "k22_unet_set_threshold_group": (_I, [_P, _I]),
     "k22_gemm": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _L, _L, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "k22_x3_pack": (_I, [_P, _P, _L, _F, _P]),
     "k22_conv3x3": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),

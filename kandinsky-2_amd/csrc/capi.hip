@@ -530,11 +530,12 @@ int k22_plms_step(const float* x, const float* model_out, const float* eps_hist1
 
 size_t k22_sampler_scratch_bytes(int N, int HW) { return (size_t)N * 4 * HW * sizeof(float) + 256; }
 
-int k22_sampler_step(const float* x, const float* model_out, const float* noise, const float* init_img,
-                     const float* mask, const float* table, int step_index, float guidance, int use_cfg,
-                     float clamp_lo, float clamp_hi, int pct_index, double pct_gamma, void* scratch,
-                     float* x_out, float* x0_out, int N, int HW, void* stream) {
+// pct_group 0: k22_sampler_step - one threshold group, the whole cond half (launch_sampler_step)
+static int sampler_step_groups(const float* x, const float* model_out, const float* noise, const float* init_img, const float* mask,
+                               const float* table, int step_index, float guidance, int use_cfg, float clamp_lo, float clamp_hi, int pct_index,
+                               double pct_gamma, int pct_group, void* scratch, float* x_out, float* x0_out, int N, int HW, void* stream) {
   SamplerParams p = {};
+  p.pct_group = pct_group;
   p.x = x; p.model_out = model_out; p.noise = noise; p.init_img = init_img; p.mask = mask; p.table = table;
   p.step = nullptr; p.step_host = step_index; p.guidance = guidance; p.clamp_lo = clamp_lo; p.clamp_hi = clamp_hi;
   p.use_cfg = use_cfg; p.n_lo = pct_index; p.gamma = pct_gamma;
@@ -543,6 +544,22 @@ int k22_sampler_step(const float* x, const float* model_out, const float* noise,
   p.x_out = x_out; p.x0_out = x0_out; p.N = N; p.HW = HW;
   if (pct_index >= 4 * HW) return k22_set_error(K22_EINVAL, "sampler: percentile index out of range");
   return launch_sampler_step(p, reinterpret_cast<hipStream_t>(stream));
+}
+
+int k22_sampler_step(const float* x, const float* model_out, const float* noise, const float* init_img,
+                     const float* mask, const float* table, int step_index, float guidance, int use_cfg,
+                     float clamp_lo, float clamp_hi, int pct_index, double pct_gamma, void* scratch,
+                     float* x_out, float* x0_out, int N, int HW, void* stream) {
+  return sampler_step_groups(x, model_out, noise, init_img, mask, table, step_index, guidance, use_cfg, clamp_lo, clamp_hi, pct_index, pct_gamma, 0,
+                             scratch, x_out, x0_out, N, HW, stream);
+}
+
+int k22_sampler_step_groups(const float* x, const float* model_out, const float* noise, const float* init_img, const float* mask,
+                            const float* table, int step_index, float guidance, int use_cfg, float clamp_lo, float clamp_hi, int pct_index,
+                            double pct_gamma, int pct_group, void* scratch, float* x_out, float* x0_out, int N, int HW, void* stream) {
+  if (pct_group < 1) return k22_set_error(K22_EINVAL, "sampler_step_groups: pct_group must be >= 1");
+  return sampler_step_groups(x, model_out, noise, init_img, mask, table, step_index, guidance, use_cfg, clamp_lo, clamp_hi, pct_index, pct_gamma,
+                             pct_group, scratch, x_out, x0_out, N, HW, stream);
 }
 
 // ---- single-kernel entry points of the MoVQ helpers for the parity tests (include/k22.h); no product code calls them ---------------

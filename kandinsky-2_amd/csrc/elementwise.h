@@ -92,10 +92,11 @@ struct SamplerParams {
   int use_cfg;             // 1: eps = u + g (c - u) with halves [cond | uncond]; 0: eps as is
   int n_lo; double gamma;  // percentile order statistic index and interpolation weight; n_lo < 0: off
   float* x0_buf;           // scratch [N][4][HW]
-  float* s_buf;            // scratch [1]
+  float* s_buf;            // scratch [64]: one threshold per group
   float* x_out;            // [N][4][HW]
   float* x0_out;           // pred_xstart [N][4][HW] or null
   int N, HW;
+  int pct_group;           // threshold group: rows of the cond half that share the percentile of their first row (with their uncond partners); 0 = all
 };
 
 int launch_x3_pack(const float* in, void* out, int64_t n, float scale, hipStream_t s);

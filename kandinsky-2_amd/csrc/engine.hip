@@ -106,6 +106,9 @@ struct K22UNet : GraphPlan {   // dtype: arithmetic type of the MFMA kernels (K2
   // the whole denoising loop as ONE graph (any of the k22_unet_*_loop entries, unet_loop below): valid for exactly the buffers / scalars
   // it was captured with
   LoopCache loop;
+  // k22_unet_set_threshold_group: rows of the cond half per threshold group of the p_sampler loops (SamplerParams::pct_group); 0 = the whole
+  // batch from element 0.  A word of the captured loop's key.
+  int threshold_group = 0;
 
   // persistent slots
   Slot *s_xin, *s_img, *s_mask, *s_t, *s_out;
@@ -917,6 +920,9 @@ static int unet_sample_loop_body(K22UNet* u, float* x, float* x_tmp, const float
   auto own_fault = [&]() -> const char* {
     if (!x || !x_tmp || !timesteps || !noise_seq || !table || !table_rows || !scratch || n_steps < 1) return "null argument";
     if (pct_index >= 4 * u->H * u->W) return "percentile index out of range";
+    if (const int g = u->threshold_group) {
+      if (u->B % 2 == 0 && ((u->B / 2) % g || u->B / 2 / g > 64)) return "the threshold group (k22_unet_set_threshold_group) must divide B / 2 into at most 64 groups";
+    }
     return nullptr;
   };
   auto step = [&](int k, float* cur, float* nxt, auto&, hipStream_t s) -> int {
@@ -924,7 +930,7 @@ static int unet_sample_loop_body(K22UNet* u, float* x, float* x_tmp, const float
     SamplerParams p = {};
     p.x = cur; p.model_out = u->model_out(); p.noise = noise_seq + (size_t)k * B * 4 * HW; p.init_img = init_img; p.mask = mask;
     p.table = table; p.step = nullptr; p.step_host = table_rows[k]; p.guidance = guidance; p.clamp_lo = clamp_lo; p.clamp_hi = clamp_hi;
-    p.use_cfg = 1; p.n_lo = pct_index; p.gamma = pct_gamma;
+    p.use_cfg = 1; p.n_lo = pct_index; p.gamma = pct_gamma; p.pct_group = u->threshold_group;
     p.s_buf = reinterpret_cast<float*>(scratch); p.x0_buf = reinterpret_cast<float*>(scratch) + 64;
     p.x_out = nxt; p.x0_out = nullptr; p.N = B; p.HW = HW;
     if (int rc = launch_sampler_step(p, s)) return rc;
@@ -933,7 +939,8 @@ static int unet_sample_loop_body(K22UNet* u, float* x, float* x_tmp, const float
   };
   auto key_tail = [&](std::vector<unsigned long long>& key) {
     key.insert(key.end(), {loop_key_ptr(noise_seq), loop_key_ptr(init_img), loop_key_ptr(mask), loop_key_ptr(table), loop_key_ptr(scratch),
-                           (unsigned long long)pct_index, loop_key_bits(guidance), loop_key_bits(clamp_lo), loop_key_bits(clamp_hi), loop_key_bits(pct_gamma)});
+                           (unsigned long long)pct_index, loop_key_bits(guidance), loop_key_bits(clamp_lo), loop_key_bits(clamp_hi), loop_key_bits(pct_gamma),
+                           (unsigned long long)u->threshold_group});
     for (int k = 0; k < n_steps; ++k) key.push_back((unsigned long long)table_rows[k]);
     if (!keep_init) return;
     // the three device operands and the bits of every coefficient baked into the keep-region nodes
@@ -1061,6 +1068,13 @@ int k22_unet_set_hint(K22UNet* u, const float* hint, void* stream) {
   if (int rc = copy_d2d(u->ptr(u->s_hintin), hint, per * 4, st)) return rc;
   for (auto& op : u->hint_ops) { int rc = op(st); if (rc) return rc; }
   u->hint_set = true;
+  return K22_OK;
+}
+
+int k22_unet_set_threshold_group(K22UNet* u, int rows) {
+  if (!u) return k22_set_error(K22_EINVAL, "unet_set_threshold_group: null handle");
+  if (rows < 0) return k22_set_error(K22_EINVAL, "unet_set_threshold_group: rows must be >= 0 (0 = the whole batch)");
+  u->threshold_group = rows;
   return K22_OK;
 }
 

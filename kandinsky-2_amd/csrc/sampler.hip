@@ -54,7 +54,7 @@ __global__ __launch_bounds__(256) void sampler_x0_kernel(SamplerParams p) {
 }
 
 // pass 2: s = max(percentile_99.5(|x0[0]|), 1) — exact order statistics by radix select.
-// One 1024-thread workgroup.  |x0| is clamped, so the high key bytes collapse into two or three histogram
+// One 1024-thread workgroup per threshold group (one group unless the caller packs several prompts into the batch).  |x0| is clamped, so the high key bytes collapse into two or three histogram
 // bins: lanes of a wave that hit the same bin are combined with ballots and ONE LDS atomic per distinct bin
 // (a plain atomic per element serialises ~n same-address updates per pass).
 __device__ __forceinline__ void hist_add_aggregated(int* hist, bool valid, uint32_t bin) {
@@ -147,19 +147,28 @@ __device__ __forceinline__ uint32_t radix_select(const float* v, const uint32_t*
   return prefix;
 }
 
-template <int KPT>
+// GROUPS: one workgroup per threshold group (launch_sampler_step): workgroup j selects over row j * pct_group of x0_buf - the first row of
+// the j-th group of the cond half - and writes s_buf[j].  The groups run on different CUs at once.  GROUPS == false is the one-group launch:
+// row 0, s_buf[0], the code it has always been.
+template <int KPT, bool GROUPS>
 __global__ __launch_bounds__(1024) void sampler_threshold_kernel(SamplerParams p) {
   __shared__ int hist[K22_RS_BINS];
   __shared__ uint32_t bc[2];
   __shared__ unsigned int succ_cnt[2];  // [0] = #keys <= a, [1] = min key > a
   const int n = 4 * p.HW;
+  const float* v = p.x0_buf;
+  float* s_out = p.s_buf;
+  if constexpr (GROUPS) {
+    v += (size_t)blockIdx.x * p.pct_group * n;
+    s_out += blockIdx.x;
+  }
   const int k_hi = p.n_lo + 1 < n ? p.n_lo + 1 : n - 1;
   uint32_t keys[KPT > 0 ? KPT : 1];
   if constexpr (KPT > 0) {
 #pragma unroll
     for (int j = 0; j < KPT; ++j) {
       const int i = j * 1024 + (int)threadIdx.x;
-      keys[j] = i < n ? __float_as_uint(fabsf(p.x0_buf[i])) : 0xffffffffu;
+      keys[j] = i < n ? __float_as_uint(fabsf(v[i])) : 0xffffffffu;
     }
   }
   // Round 6: the order statistic wanted is a HIGH percentile (99.5 %), and the first radix pass - every key through the ballot-aggregated
@@ -202,7 +211,7 @@ __global__ __launch_bounds__(1024) void sampler_threshold_kernel(SamplerParams p
       __syncthreads();
     }
   }
-  const uint32_t ka = radix_select<KPT>(p.x0_buf, keys, n, k_sel, hist, bc, floor_key);
+  const uint32_t ka = radix_select<KPT>(v, keys, n, k_sel, hist, bc, floor_key);
   // the next order statistic: a itself if enough keys are <= a, else the smallest key above a
   if (threadIdx.x == 0) { succ_cnt[0] = 0u; succ_cnt[1] = 0xffffffffu; }
   __syncthreads();
@@ -217,7 +226,7 @@ __global__ __launch_bounds__(1024) void sampler_threshold_kernel(SamplerParams p
     }
   } else {
     for (int i = threadIdx.x; i < n; i += blockDim.x) {
-      const uint32_t key = __float_as_uint(fabsf(p.x0_buf[i]));
+      const uint32_t key = __float_as_uint(fabsf(v[i]));
       if (key <= ka) ++cnt;
       else mn = key < mn ? key : mn;
     }
@@ -247,19 +256,24 @@ __global__ __launch_bounds__(1024) void sampler_threshold_kernel(SamplerParams p
       const float du = d * u;
       r = b - du;
     }
-    p.s_buf[0] = r > 1.f ? r : 1.f;
+    s_out[0] = r > 1.f ? r : 1.f;
   }
 }
 
 // pass 3: threshold, posterior mean, learned-range variance, ancestral noise.
+// GROUPS (launched with the threshold on only): row n is clamped and divided by the s of its own group, s_buf[(n % half) / pct_group] - a
+// cond row and its uncond partner share one.  GROUPS == false: s_buf[0] for every row, the code it has always been.
+template <bool GROUPS>
 __global__ __launch_bounds__(256) void sampler_final_kernel(SamplerParams p) {
   const float* tr = step_row(p);
   const float c1 = tr[2], c2 = tr[3], min_log = tr[4], max_log = tr[5], nonzero = tr[6];
-  const float s = (p.n_lo >= 0) ? p.s_buf[0] : 0.f;
+  float s = (p.n_lo >= 0) ? p.s_buf[0] : 0.f;
+  const int half = p.use_cfg ? p.N / 2 : p.N;
   const int64_t total = (int64_t)p.N * 4 * p.HW;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
     const int pix = (int)(i % p.HW);
     const int c = (int)((i / p.HW) % 4), n = (int)(i / (4 * (int64_t)p.HW));
+    if constexpr (GROUPS) s = p.s_buf[(n % half) / p.pct_group];
     float x0 = p.x0_buf[i];
     if (p.n_lo >= 0) x0 = fminf(fmaxf(x0, -s), s) / s;
     const float mean = __fadd_rn(__fmul_rn(c1, x0), __fmul_rn(c2, p.x[i]));
@@ -472,10 +486,23 @@ int launch_ddim_step(const float* x, const float* model_out, const float* noise,
 // advances the device step counter (one thread); used when a whole step is replayed as a graph.
 __global__ void step_advance_kernel(int* step, int delta) { *step += delta; }
 
-int launch_sampler_step(const SamplerParams& p, hipStream_t s) {
-  if (p.N <= 0 || p.HW <= 0) return k22_set_error(K22_EINVAL, "sampler: empty batch");
-  if (p.use_cfg && (p.N & 1)) return k22_set_error(K22_EINVAL, "sampler: CFG needs an even batch [cond | uncond]");
-  if ((p.mask == nullptr) != (p.init_img == nullptr)) return k22_set_error(K22_EINVAL, "sampler: init_img and mask go together");
+template <int KPT>
+static void launch_threshold(const SamplerParams& p, int groups, hipStream_t s) {
+  if (groups > 1) hipLaunchKernelGGL((sampler_threshold_kernel<KPT, true>), dim3(groups), dim3(1024), 0, s, p);
+  else hipLaunchKernelGGL((sampler_threshold_kernel<KPT, false>), dim3(1), dim3(1024), 0, s, p);
+}
+
+// pct_group: rows of the cond half per threshold group (0 = all of them).  One group launches the kernels the step has always launched.
+int launch_sampler_step(const SamplerParams& p0, hipStream_t s) {
+  if (p0.N <= 0 || p0.HW <= 0) return k22_set_error(K22_EINVAL, "sampler: empty batch");
+  if (p0.use_cfg && (p0.N & 1)) return k22_set_error(K22_EINVAL, "sampler: CFG needs an even batch [cond | uncond]");
+  if ((p0.mask == nullptr) != (p0.init_img == nullptr)) return k22_set_error(K22_EINVAL, "sampler: init_img and mask go together");
+  const int half = p0.use_cfg ? p0.N / 2 : p0.N;
+  SamplerParams p = p0;
+  if (p.pct_group == 0) p.pct_group = half;
+  if (p.pct_group < 1 || half % p.pct_group) return k22_set_error(K22_EINVAL, "sampler: pct_group must be >= 1 and divide the cond half of the batch");
+  if (half / p.pct_group > 64) return k22_set_error(K22_EINVAL, "sampler: more than 64 threshold groups (s_buf holds 64 floats)");
+  const int groups = p.n_lo >= 0 ? half / p.pct_group : 1;
   const int64_t total = (int64_t)p.N * 4 * p.HW;
   int nb = (int)((total + 255) / 256);
   if (nb > 2048) nb = 2048;
@@ -483,14 +510,15 @@ int launch_sampler_step(const SamplerParams& p, hipStream_t s) {
   K22_CHECK_LAUNCH();
   if (p.n_lo >= 0) {
     const int kpt = (4 * p.HW + 1023) / 1024;   // keys per thread of the one 1024-thread workgroup
-    if (kpt <= 4) hipLaunchKernelGGL(sampler_threshold_kernel<4>, dim3(1), dim3(1024), 0, s, p);
-    else if (kpt <= 16) hipLaunchKernelGGL(sampler_threshold_kernel<16>, dim3(1), dim3(1024), 0, s, p);
-    else if (kpt <= 36) hipLaunchKernelGGL(sampler_threshold_kernel<36>, dim3(1), dim3(1024), 0, s, p);
-    else if (kpt <= 64) hipLaunchKernelGGL(sampler_threshold_kernel<64>, dim3(1), dim3(1024), 0, s, p);
-    else hipLaunchKernelGGL(sampler_threshold_kernel<0>, dim3(1), dim3(1024), 0, s, p);
+    if (kpt <= 4) launch_threshold<4>(p, groups, s);
+    else if (kpt <= 16) launch_threshold<16>(p, groups, s);
+    else if (kpt <= 36) launch_threshold<36>(p, groups, s);
+    else if (kpt <= 64) launch_threshold<64>(p, groups, s);
+    else launch_threshold<0>(p, groups, s);
     K22_CHECK_LAUNCH();
   }
-  hipLaunchKernelGGL(sampler_final_kernel, dim3(nb), dim3(256), 0, s, p);
+  if (groups > 1) hipLaunchKernelGGL(sampler_final_kernel<true>, dim3(nb), dim3(256), 0, s, p);
+  else hipLaunchKernelGGL(sampler_final_kernel<false>, dim3(nb), dim3(256), 0, s, p);
   K22_CHECK_LAUNCH();
   return K22_OK;
 }

@@ -188,7 +188,8 @@ class SpacedDiffusionHIP:
                       denoised_fn=None, model_kwargs: Optional[dict] = None, device=None, progress: bool = False,
                       init_step: Optional[int] = None, *, guidance_scale: Optional[float] = None,
                       noise_seq: Optional[torch.Tensor] = None, init_img: Optional[torch.Tensor] = None,
-                      img_mask: Optional[torch.Tensor] = None, return_pred_xstart: bool = False, whole_loop_graph: bool = False):
+                      img_mask: Optional[torch.Tensor] = None, return_pred_xstart: bool = False, whole_loop_graph: bool = False,
+                      threshold_group: Optional[int] = None):
         """GaussianDiffusion.p_sample_loop (gaussian_diffusion.py:384-425) with the reference's positional / keyword set, on
         the GPU without a host round trip per step.  Two ways to call it:
 
@@ -205,6 +206,10 @@ class SpacedDiffusionHIP:
 
         `shape` = (2*bs, 4, h, w) with halves [cond | uncond].  noise_seq[k] (optional, [n_iters, *shape]) replaces
         randn_like at the k-th executed step (parity tests inject the reference's noise).
+
+        threshold_group=g (several prompts packed into one batch, g rows each): the dynamic threshold of rows j g .. (j + 1) g - 1 of the cond
+        half and of their uncond partners is the percentile of row j g, what a reference call for that prompt alone takes from ITS element
+        0 (k22_sampler_step_groups).  None: the reference's one call - element 0 decides for the whole batch.
         """
         N, Cc, H, W = shape
         if Cc != 4 or N % 2:
@@ -225,6 +230,10 @@ class SpacedDiffusionHIP:
         ts = torch.from_numpy(self.model_timesteps()).to(dev)
         ts_rows = ts[:, None].expand(-1, N).contiguous()  # [T][N]
         pct = percentile_index(4 * H * W) if clip_denoised else (-1, 0.0)
+        group = sampling.threshold_group(threshold_group, N, fused)
+        if group is not None and getattr(model, "chains", 1) == 2:
+            raise ValueError("threshold_group: the two-chain mode (chains=2) splits the batch between two engines and thresholds it as one group")
+        grouped = {} if group is None else {"group": group}                # None: the calls below are the calls they have always been
         if fused:
             if denoised_fn is not None:
                 raise ValueError("fused call: denoised_fn is implied (clamp +-2 and the init_img / img_mask blend)")
@@ -249,14 +258,15 @@ class SpacedDiffusionHIP:
         ts_exec = ts_rows[torch.as_tensor(indices, dtype=torch.long, device=dev)].contiguous()      # timesteps, like the schedule rows, in execution order
         if fused and whole_loop_graph and hasattr(model, "sample_loop") and not return_pred_xstart and not progress and len(indices) > 0:
             # the whole loop as ONE hipGraph replay
-            return model.sample_loop(x, ts_exec, nzs, table, indices, guidance_scale, (lo, hi), pct, init_img=init, img_mask=mask, **model_kwargs)
+            return model.sample_loop(x, ts_exec, nzs, table, indices, guidance_scale, (lo, hi), pct, init_img=init, img_mask=mask,
+                                     **({} if group is None else {"threshold_group": group}), **model_kwargs)
         model_call = (sampling.fused_call if fused else _model_fn_call)(model, ts_exec, **model_kwargs)
         if progress:
             from tqdm.auto import tqdm
             indices = tqdm(indices)
         x, x0 = sampling.step_loop(model_call, x, indices, nzs, torch.empty_like(x) if return_pred_xstart else None, sampling.sampler_step,
                                    table=table, guidance=guidance_scale if fused else 1.0, use_cfg=fused, clamp=(lo, hi), pct=pct, init=init,
-                                   mask=mask, scratch=sampling.sampler_scratch(x))
+                                   mask=mask, scratch=sampling.sampler_scratch(x), **grouped)
         return (x, x0) if return_pred_xstart else x
 
 

@@ -87,6 +87,34 @@ def prepare_image(image, w=512, h=512) -> torch.Tensor:
     return torch.from_numpy(np.transpose(arr, [2, 0, 1])).unsqueeze(0)
 
 
+# ---- several prompts in ONE CFG batch: the row layout, pure functions (tests/test_prompt_pack_cpu.py) -------------------------------------
+def cfg_pack(per_prompt, batch_size: int, dim: int = 0) -> torch.Tensor:
+    """n per-prompt CFG tensors, each [cond rows | uncond rows] = 2 batch_size long in `dim`, -> one tensor 2 n batch_size long in `dim`:
+    [cond rows of prompt 0, 1, ... | uncond rows of prompt 0, 1, ...].  Row k batch_size + r of the cond half and its partner n batch_size
+    further on belong to prompt k: the pairing of the sampler kernels (row i with row i + half) holds for every prompt."""
+    per_prompt = list(per_prompt)
+    for t in per_prompt:
+        if t.shape[dim] != 2 * batch_size:
+            raise ValueError(f"cfg_pack: every tensor holds 2 * batch_size = {2 * batch_size} rows in dim {dim}; got {tuple(t.shape)}")
+    return torch.cat([t.narrow(dim, 0, batch_size) for t in per_prompt] + [t.narrow(dim, batch_size, batch_size) for t in per_prompt], dim)
+
+
+def cfg_unpack(packed: torch.Tensor, n: int, batch_size: int, dim: int = 0) -> list:
+    """cfg_pack's inverse: the n per-prompt [cond rows | uncond rows] tensors"""
+    if packed.shape[dim] != 2 * n * batch_size:
+        raise ValueError(f"cfg_unpack: {2 * n * batch_size} rows expected in dim {dim}; got {tuple(packed.shape)}")
+    return [torch.cat([packed.narrow(dim, k * batch_size, batch_size), packed.narrow(dim, (n + k) * batch_size, batch_size)], dim) for k in range(n)]
+
+
+def prompts_per_call(want: int, batch_size: int, negative_decoder_prompt: str = "") -> int:
+    """How many prompts one prior call (prior_group) or one denoising call (pack) of generate_text2img_many takes: `want`, clipped to what a
+    CFG batch of at most 8 rows holds at this batch_size, at least 1; and 1 with a negative decoder prompt, whose unconditional image
+    embedding takes a prior call per prompt."""
+    if negative_decoder_prompt != "":
+        return 1
+    return max(1, min(int(want), 4 // max(1, batch_size)))
+
+
 class SeededConditioner:
     """Deterministic stand-in for the conditioning encoders: N(0,1) embeddings seeded by a hash of the prompt."""
 
@@ -265,18 +293,34 @@ class Kandinsky2_1HIP:
                      init_img=None, img_mask=None, h=512, w=512, sampler="ddim_sampler", num_steps=50,
                      noise_seq: Optional[torch.Tensor] = None, output_type: str = "pil", *, text_embs=None, decode: bool = True):
         """text_embs = (full_emb, pooled_emb) computed by the caller (generate_text2img_many computes them beside the prior, on its stream);
-        decode=False returns the final latents [batch_size, 4, h/8, w/8] and leaves the MoVQ decode to the caller."""
+        decode=False returns the final latents [batch_size, 4, h/8, w/8] and leaves the MoVQ decode to the caller.
+        prompt may be a list or tuple of n strings: n prompts in ONE CFG batch of 2 n batch_size rows in cfg_pack's order (img_prompt, noise,
+        noise_seq and text_embs in that order too); the result holds n batch_size images, prompt after prompt.  Every row of the UNet is
+        computed for itself, and p_sampler takes its dynamic threshold per prompt (threshold_group=batch_size): each prompt gets what a call
+        of its own gets, to the rounding of the other tile shapes a larger batch runs.  A str is the reference's call."""
         new_h, new_w = self.get_new_h_w(h, w)
-        full_batch_size = batch_size * 2
+        packed = isinstance(prompt, (list, tuple))
+        n_prompts = len(prompt) if packed else 1
+        if packed and (n_prompts < 1 or not all(isinstance(p, str) for p in prompt)):
+            raise ValueError("prompt must be a string or a non-empty list / tuple of strings")
+        rows = n_prompts * batch_size                   # images of the call: the cond half of the CFG batch
+        full_batch_size = rows * 2
         if full_batch_size > 8:
             # The engine plans CFG batches of at most 8.  A larger batch cannot simply be split here: the reference's dynamic
             # threshold scales the WHOLE batch by the percentile of its element 0 (gaussian_diffusion.py:288-292), so chunks
             # would not reproduce one reference call.  Independent calls of <= 4 images (one per GPU stream / rank,
             # kandinsky2_amd.parallel.shard_range) are the supported way to a large batch.
             raise ValueError("batch_size must be <= 4 per call (CFG batch <= 8); shard larger batches over calls / ranks")
+        if packed and self.task_type == "inpainting":
+            raise ValueError("a list of prompts needs the text2img task (one init image and mask serve an inpainting call)")
         model_kwargs = {}
+        if text_embs is None and packed:
+            per_prompt = [self.encode_text(p, batch_size) for p in prompt]
+            text_embs = tuple(cfg_pack([e[k] for e in per_prompt], batch_size) for k in (0, 1))
         model_kwargs["full_emb"], model_kwargs["pooled_emb"] = self.encode_text(prompt, batch_size) if text_embs is None else text_embs
         model_kwargs["image_emb"] = img_prompt.to(self.device).float()
+        if packed and model_kwargs["image_emb"].shape[0] != full_batch_size:
+            raise ValueError(f"img_prompt must hold {full_batch_size} rows [cond rows of every prompt | uncond rows of every prompt]")
         self._last_image_emb = model_kwargs["image_emb"]
         if self.task_type == "inpainting":
             init_img = init_img.to(self.device).float()
@@ -292,14 +336,14 @@ class Kandinsky2_1HIP:
             samples = diffusion.p_sample_loop(
                 self.model, (full_batch_size, 4, new_h, new_w), device=self.device, noise=noise, model_kwargs=model_kwargs,
                 init_step=init_step, guidance_scale=guidance_scale, init_img=init_img, img_mask=img_mask, noise_seq=noise_seq,
-                whole_loop_graph=self.whole_loop_graph)[:batch_size]
+                whole_loop_graph=self.whole_loop_graph, **({"threshold_group": batch_size} if packed else {}))[:rows]
         elif sampler in ("ddim_sampler", "plms_sampler", "dpm_sampler"):
             # dpm_sampler: DPM-Solver++ 2M on the log-SNR grid (not in the reference; for generations of ~20 model calls)
             cls = {"ddim_sampler": DDIMSamplerHIP, "plms_sampler": PLMSSamplerHIP, "dpm_sampler": DPMSolverSamplerHIP}[sampler]
             samples, _ = cls(self.model, diffusion, guidance_scale).sample(
-                num_steps, batch_size * 2, (4, new_h, new_w), conditioning=model_kwargs, x_T=noise, init_step=init_step, device=self.device,
+                num_steps, full_batch_size, (4, new_h, new_w), conditioning=model_kwargs, x_T=noise, init_step=init_step, device=self.device,
                 whole_loop_graph=self.whole_loop_graph)
-            samples = samples[:batch_size]
+            samples = samples[:rows]
         else:
             raise ValueError("Only ddim_sampler and plms_sampler is available")
         self.model.del_cache()
@@ -316,7 +360,8 @@ class Kandinsky2_1HIP:
     @torch.no_grad()
     def generate_text2img_many(self, prompts, num_steps=100, batch_size=1, guidance_scale=7, h=512, w=512, sampler="ddim_sampler",
                                prior_cf_scale=4, prior_steps="25", negative_prior_prompt="", negative_decoder_prompt="", *,
-                               noises=None, noise_seqs=None, prior_noises=None, prior_noise_seqs=None, output_type="pil", prior_group: int = 1):
+                               noises=None, noise_seqs=None, prior_noises=None, prior_noise_seqs=None, output_type="pil", prior_group: int = 1,
+                               pack: int = 1):
         """generate_text2img for a LIST of prompts -> list of results, each equal to what generate_text2img(prompt, ...) returns for the same
         noise.  The three engines of a generation (conditioning + prior | denoise loop | MoVQ decode) are independent between prompts, so they
         run as a pipeline on three streams of the device: while the UNet denoises prompt i, the prior (a weight stream that leaves the matrix
@@ -326,7 +371,12 @@ class Kandinsky2_1HIP:
         prior_group > 1: the diffusion prior samples the embeddings of up to prior_group prompts in ONE call (its batch = 2 * batch_size *
         group <= 8): the prior is a weight stream - 2 GB per forward whatever the batch - so a group of four costs about what one prompt
         costs.  Every row of the prior is computed independently of the other rows, but a larger batch runs other GEMM tile shapes (other
-        fp32 summation orders): results then equal the per-prompt calls to rounding, not bit for bit (the default, 1, does)."""
+        fp32 summation orders): results then equal the per-prompt calls to rounding, not bit for bit (the default, 1, does).
+        pack > 1: up to `pack` consecutive prompts (pack * batch_size <= 4, clipped like prior_group) share ONE denoising call, a CFG batch of
+        2 * pack * batch_size rows (generate_img with a list of prompts), one prior call (the grouping above, with group = pack) and one MoVQ
+        decode; the three streams then pipeline packs instead of prompts.  The 3x3 convolutions fill the machine better at a CFG batch of 8
+        than at 2.  p_sampler thresholds every prompt by its own image, so a packed prompt gets what its own call gets - to rounding, for
+        the reason given for the prior.  The default, 1, is the path described first."""
         prompts = list(prompts)
         n = len(prompts)
         pick = lambda lst, i: None if lst is None else lst[i]          # noqa: E731
@@ -338,9 +388,10 @@ class Kandinsky2_1HIP:
         s_dec.wait_stream(cur)
         _, diffusion = self._diffusion(sampler, num_steps)
 
-        group = max(1, min(int(prior_group), 4 // max(1, batch_size)))
-        if negative_decoder_prompt != "":
-            group = 1                     # (the negative decoder prompt takes a prior call of its own: kept per prompt)
+        # (a negative decoder prompt takes a prior call of its own per prompt: no group and no pack then)
+        pack = prompts_per_call(pack, batch_size, negative_decoder_prompt)
+        group = pack if pack > 1 else prompts_per_call(prior_group, batch_size, negative_decoder_prompt)
+        units = [list(range(i0, min(i0 + pack, n))) for i0 in range(0, n, pack)]      # the prompts of every denoising call
         grouped = {}                      # prompt index -> image embedding rows computed by its group's prior call
 
         def prior_for_group(i0):
@@ -359,9 +410,13 @@ class Kandinsky2_1HIP:
             for k, i in enumerate(idx):
                 grouped[i] = emb[k * bs:(k + 1) * bs]
 
-        def stage_a(i):
+        def stage_a(idx):
+            i = idx[0]
             with torch.cuda.stream(s_prior):
-                if group > 1:
+                if pack > 1:
+                    prior_for_group(i)          # group == pack: exactly the prompts of idx
+                    emb = torch.cat([grouped.pop(j) for j in idx] + [self.create_zero_img_emb(batch_size=batch_size * len(idx))], dim=0).to(self.device)
+                elif group > 1:
                     if i not in grouped:
                         prior_for_group(i)
                     emb = torch.cat([grouped.pop(i), self.create_zero_img_emb(batch_size=batch_size)], dim=0).to(self.device)
@@ -369,21 +424,31 @@ class Kandinsky2_1HIP:
                     emb = self._image_embs(prompts[i], batch_size, prior_cf_scale, prior_steps, negative_prior_prompt, negative_decoder_prompt,
                                            noise=pick(prior_noises, i), noise_seq=pick(prior_noise_seqs, i))
                 txt = self.encode_text(prompts[i], batch_size)
+                if pack > 1:
+                    per_prompt = [txt] + [self.encode_text(prompts[j], batch_size) for j in idx[1:]]
+                    txt = tuple(cfg_pack([e[k] for e in per_prompt], batch_size) for k in (0, 1))
                 ev = torch.cuda.Event()
                 ev.record(s_prior)
             return emb, txt, ev
 
-        results, pending = [], stage_a(0) if n else None
-        for i in range(n):
+        def packed_noise(lst, idx, dim):
+            """the per-prompt noise of a denoising call: prompt idx[0]'s own, or for a pack [cond rows of all | uncond rows of all] in `dim`"""
+            if lst is None or pack == 1:
+                return pick(lst, idx[0])
+            return cfg_pack([lst[j] for j in idx], batch_size, dim)
+
+        results, pending = [], stage_a(units[0]) if n else None
+        for u, idx in enumerate(units):
             emb, txt, ev = pending
             cur.wait_event(ev)
             for t in (emb,) + tuple(txt):
                 if torch.is_tensor(t):
                     t.record_stream(cur)
-            pending = stage_a(i + 1) if i + 1 < n else None          # enqueued BEFORE this prompt's denoise loop: it overlaps it
-            lat = self.generate_img(prompt=prompts[i], img_prompt=emb, batch_size=batch_size, guidance_scale=guidance_scale, h=h, w=w,
-                                    sampler=sampler, num_steps=num_steps, diffusion=diffusion, noise=pick(noises, i), noise_seq=pick(noise_seqs, i),
-                                    output_type=output_type, text_embs=txt, decode=False)
+            pending = stage_a(units[u + 1]) if u + 1 < len(units) else None          # enqueued BEFORE this prompt's denoise loop: it overlaps it
+            lat = self.generate_img(prompt=[prompts[j] for j in idx] if pack > 1 else prompts[idx[0]], img_prompt=emb, batch_size=batch_size,
+                                    guidance_scale=guidance_scale, h=h, w=w, sampler=sampler, num_steps=num_steps, diffusion=diffusion,
+                                    noise=packed_noise(noises, idx, 0), noise_seq=packed_noise(noise_seqs, idx, 1), output_type=output_type,
+                                    text_embs=txt, decode=False)
             ev_u = torch.cuda.Event()
             ev_u.record(cur)
             with torch.cuda.stream(s_dec):
@@ -394,6 +459,8 @@ class Kandinsky2_1HIP:
         cur.wait_stream(s_prior)
         for r in results:
             r.record_stream(cur)
+        if pack > 1:                                            # one decoded tensor per pack -> one per prompt
+            results = [r_p for r in results for r_p in r.split(batch_size)]
         return [process_images(r, output_type) if output_type != "tensor" else r for r in results]
 
     def _image_embs(self, prompt, batch_size, prior_cf_scale, prior_steps, negative_prior_prompt, negative_decoder_prompt, **prior_noise):

@@ -191,12 +191,28 @@ def sampler_scratch(x: torch.Tensor) -> torch.Tensor:
 
 
 # ---- the three launches ----------------------------------------------------------------------------------------------------------------
-def sampler_step(x, model_out, noise, row, x_out, x0_out, *, table, guidance, use_cfg, clamp, pct, init, mask, scratch):
-    """One k22_sampler_step launch: row `row` of the [T,8] `table`; x0_out may be None."""
-    _lib.check(_lib.lib().k22_sampler_step(
-        x.data_ptr(), model_out.data_ptr(), noise.data_ptr(), _lib.ptr(init), _lib.ptr(mask), table.data_ptr(), int(row), float(guidance),
-        int(use_cfg), float(clamp[0]), float(clamp[1]), int(pct[0]), float(pct[1]), scratch.data_ptr(), x_out.data_ptr(), _lib.ptr(x0_out),
-        x.shape[0], x.shape[2] * x.shape[3], _lib.current_stream()))
+def threshold_group(group, N: int, use_cfg=True):
+    """p_sampler's threshold group checked against a batch of N rows -> None (one group: the call as it has always been) or the int that
+    k22_sampler_step_groups / k22_unet_set_threshold_group take.  group: rows of the cond half that share the 99.5th percentile of their
+    first row - batch_size where several prompts are packed into one CFG batch - or None.  No GPU is touched."""
+    half = N // 2 if use_cfg else N
+    if group is None:
+        return None
+    g = int(group)
+    if g != group or g < 1 or half % g or half // g > 64:
+        raise ValueError(f"threshold_group must be an int >= 1 that divides the cond half of the batch ({half} rows) into at most 64 groups; got {group!r}")
+    return None if g == half else g
+
+
+def sampler_step(x, model_out, noise, row, x_out, x0_out, *, table, guidance, use_cfg, clamp, pct, init, mask, scratch, group=None):
+    """One k22_sampler_step launch: row `row` of the [T,8] `table`; x0_out may be None.  group (threshold_group's int): k22_sampler_step_groups."""
+    head = (x.data_ptr(), model_out.data_ptr(), noise.data_ptr(), _lib.ptr(init), _lib.ptr(mask), table.data_ptr(), int(row), float(guidance),
+            int(use_cfg), float(clamp[0]), float(clamp[1]), int(pct[0]), float(pct[1]))
+    tail = (scratch.data_ptr(), x_out.data_ptr(), _lib.ptr(x0_out), x.shape[0], x.shape[2] * x.shape[3], _lib.current_stream())
+    if group is None:
+        _lib.check(_lib.lib().k22_sampler_step(*head, *tail))
+    else:
+        _lib.check(_lib.lib().k22_sampler_step_groups(*head, int(group), *tail))
 
 
 def ddim_step(x, model_out, noise, row, x_out, x0_out, *, guidance):

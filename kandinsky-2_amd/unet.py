@@ -318,10 +318,14 @@ class Text2ImUNetHIP(NativeModule):
         return results(bufs)
 
     def _ddpm_loop(self, owned, x, ts_rows, noise_seq, table, table_rows, guidance_scale, clamp, pct, cond, inpaint, init_img=None, img_mask=None,
-                   keep=None):
+                   keep=None, threshold_group=None):
         """sample_loop of both UNets behind their checks: k22_unet_sample_loop_keep, which with no keep IS k22_unet_sample_loop (one body, one
-        loop key), or step_loop with sampler_step and, with a keep, keep_region on the freshly written latent."""
+        loop key), or step_loop with sampler_step and, with a keep, keep_region on the freshly written latent.  threshold_group: the handle's
+        k22_unet_set_threshold_group, set before every native call (None = 0, the whole batch: a value never outlives the call it was given to)."""
         B, _, H, W = x.shape
+        group = sampling.threshold_group(threshold_group, B)
+        if group is not None and self._chained(B):
+            raise ValueError("sample_loop: threshold_group needs one chain (two chains split the batch between their engines)")
         n, rows, tshape, g = len(table_rows), [int(r) for r in table_rows], tuple(table.shape), float(guidance_scale)
         clip, pct = (float(clamp[0]), float(clamp[1])), (int(pct[0]), float(pct[1]))
         ii = None if init_img is None else init_img.float().expand(B, 4, H, W)
@@ -338,6 +342,7 @@ class Text2ImUNetHIP(NativeModule):
                                       mask=None if mm is None else mm.contiguous(), scratch=sampling.sampler_scratch(xc))[0]
 
         def native(b, kp, *tail):
+            _lib.check(_lib.lib().k22_unet_set_threshold_group(self._handle, group or 0))
             return _lib.lib().k22_unet_sample_loop_keep(
                 self._handle, b["x"].data_ptr(), b["tmp"].data_ptr(), b["ts"].data_ptr(), b["noise"].data_ptr(), _lib.ptr(b["init"]), _lib.ptr(b["mask"]),
                 _lib.ptr(b["img"]), _lib.ptr(b["msk"]), b["table"].data_ptr(), (C.c_int * n)(*rows), n, g, clip[0], clip[1], pct[0], pct[1],
@@ -370,16 +375,18 @@ class Text2ImUNetHIP(NativeModule):
 
     @torch.no_grad()
     def sample_loop(self, x, ts_rows, noise_seq, table, table_rows, guidance_scale, clamp, pct, *, full_emb=None, pooled_emb=None,
-                    image_emb=None, inpaint_image=None, inpaint_mask=None, init_img=None, img_mask=None):
+                    image_emb=None, inpaint_image=None, inpaint_mask=None, init_img=None, img_mask=None, threshold_group=None):
         """The whole guided p_sampler loop as ONE hipGraph replay (k22_unet_sample_loop); returns the final latent [N,4,h,w].
         x [N,4,h,w] = x_T; ts_rows [n_steps, N] and noise_seq [n_steps, N,4,h,w] in execution order; table [T,8] + table_rows (host ints):
-        the schedule row of every step.  Owned operand buffers, replay and the two-chain route: _run_loop."""
+        the schedule row of every step.  threshold_group: rows of the cond half per dynamic-threshold group (sampling.threshold_group; None:
+        the whole batch from element 0).  Owned operand buffers, replay and the two-chain route: _run_loop."""
         B, H, W = self._loop_x("sample_loop", x)
         n_steps = len(table_rows)
         if tuple(ts_rows.shape) != (n_steps, B) or tuple(noise_seq.shape) != (n_steps, B, 4, H, W):
             raise ValueError("sample_loop: ts_rows must be [n_steps, N] and noise_seq [n_steps, N, 4, h, w]")
         return self._ddpm_loop("_loop_bufs", x, ts_rows, noise_seq, table, table_rows, guidance_scale, clamp, pct,
-                               dict(full_emb=full_emb, pooled_emb=pooled_emb, image_emb=image_emb), (inpaint_image, inpaint_mask), init_img, img_mask)
+                               dict(full_emb=full_emb, pooled_emb=pooled_emb, image_emb=image_emb), (inpaint_image, inpaint_mask), init_img, img_mask,
+                               threshold_group=threshold_group)
 
     @torch.no_grad()
     def ddim_loop(self, kind, x, ts_rows, table, guidance_scale, noise_seq=None, *, full_emb=None, pooled_emb=None, image_emb=None,
