@@ -624,3 +624,44 @@ def igemm_candidates(t, dtype, has_frag=0):
     assert n <= cap
     tup = lambda c: tuple(getattr(c, f) for f in CFG_FIELDS)
     return [tup(out[i]) for i in range(n)], [tup(res[i]) for i in range(n)], tup(fixed)
+
+
+# ---- engine-level evidence: the tuning report of an engine, the tile table as text (tests/test_engine_switches_gpu.py) ------------------
+ReportLine = collections.namedtuple("ReportLine", "taps M N K H W stats algo bm bn splitk stages count")
+
+
+def report_lines(report):
+    """the lines of tuning_report_text (csrc/tuning.h) without their time column: the problem, the configuration that runs it (algo by
+    igemm_algo_name) and how many ops of the plan share the line"""
+    out = []
+    for ln in report.splitlines()[1:]:
+        if not ln.strip():
+            continue
+        prob, cfg, tail = (part.split() for part in ln.split("|"))
+        assert len(prob) == 7 and len(cfg) == 5 and len(tail) == 2 and tail[1].startswith("x"), ln
+        out.append(ReportLine(*(int(v) for v in prob), cfg[0], *(int(v) for v in cfg[1:]), int(tail[1][1:])))
+    return out
+
+
+def report_problems(report, taps):
+    """{(M, N, K, H, W)} of the report's lines with that many taps"""
+    return {(r.M, r.N, r.K, r.H, r.W) for r in report_lines(report) if r.taps == taps}
+
+
+def tile_table_text_lines(path):
+    """the data lines of a tile-table file as text, in the order read_tile_table returns them"""
+    with open(path) as f:
+        return [ln for ln in f if not ln.startswith("#") and ln.strip()]
+
+
+def tile_table_text_with_cfg(text_line, cfg):
+    """the table line with its configuration columns (algo bm bn splitk stages) replaced, key and time kept"""
+    cols = text_line.split()
+    assert len(cols) == 16 and len(cfg) == 5, text_line
+    return " ".join(cols[:10] + [str(int(v)) for v in cfg] + cols[15:]) + "\n"
+
+
+def host_refusal(err):
+    """is the RuntimeError of _lib.check a refusal on the host (K22_EINVAL / K22_ENOMEM: nothing was launched)?  Anything else - a failed
+    launch, a device fault - must end the session (tests/test_igemm_candidates_gpu.py)"""
+    return str(err).startswith(("k22 error -1:", "k22 error -3:"))
