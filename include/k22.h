@@ -54,7 +54,6 @@ extern "C" {
 int k22_version(void);
 /* Build flavour of this library: bit mask of K22_BUILD_*.  0 = the shipped form. */
 #define K22_BUILD_PACKED_FP32 1     /* built with NOPK=0: packed-fp32 VALU instructions present - do NOT overlap two handles on one device */
-#define K22_BUILD_DEBUG_VARIANTS 2  /* measurement-only kernel variants compiled in (K22_DEBUG_VARIANTS / K22_STREAM_DEBUG / K22_SKINNY_DEBUG) */
 int k22_build_flags(void);
 const char* k22_last_error(void);
 /* Tuning knobs.  PROCESS-WIDE MUTABLE STATE, NOT RE-ENTRANT: these exist for the kernel-level test / measurement surface (k22_gemm,
@@ -69,7 +68,7 @@ const char* k22_last_error(void);
  * Knobs: "igemm_stages" = 2..4 LDS-DMA pipeline depth (-1 default; with "gemm_algo" = 10: 2 = two workgroups per CU at BM = 128, 3 / 4 = the
  * specialised, pipelined gemm8_spec_kernel for the 16-bit types and its two-per-CU form - same bits as the lock-step kernel);
  * "igemm_xcd_remap" = 0/1 XCD-aware workgroup renumbering; "conv_algo" = 0 auto, 1 generic implicit GEMM,
- * 2 LDS-resident halo kernel for the 3x3 convolutions (3-7: its variants, see conv3_halo.hip; 8-9: measurement only);
+ * 2 LDS-resident halo kernel for the 3x3 convolutions (3, 6, 7, 11, 12: its variants, see conv3_halo.hip / conv3_spec.hip; 8, 9, 13, 14 are reserved numbers that no kernel answers to: auto);
  * "gemm_algo" = 0 generic implicit-GEMM kernel, 10 = 8-wave BM x 128 tile kernel where it applies;
  * "conv_algo" / "gemm_algo" = 20: the weight-streaming small-M kernel (stream_gemm.hip; bm = 160 / 288 picks 5 / 9 m-blocks
  * per workgroup, needs the fp32 partial buffer also for splitk == 1);
@@ -450,11 +449,6 @@ int k22_igemm_candidates(const K22IgemmProblem* pr, K22IgemmCfg* out, int capaci
  * is an error (K22_EINVAL), never a quiet run of another kernel.  With want_stats the GroupNorm partial sums land in ops->stats as in
  * k22_conv3x3_gnstats: image b owns rows [b * rpi, (b + 1) * rpi), *rows_per_image receives rpi (0 without want_stats). */
 int k22_igemm_cfg(const K22IgemmProblem* pr, const K22IgemmOperands* ops, int* rows_per_image, void* stream);
-/* Developer tool: runs the 256-row bf16 halo kernel once with s_memtime stamps; trace = device u64 [2][1024][4]
- * (wave 0 / wave 5 of workgroup 0; per tap: before the counted vmcnt wait, after it, after the barrier, after the last
- * MFMA was issued).  tools/conv_trace.py prints the per-phase cycle budget. */
-int k22_debug_conv_trace(const void* x_padded, const void* Wp, const float* bias, void* out, int B, int H, int W, int Cin, int Cout,
-                         int Npad, unsigned long long* trace, void* stream);
 int k22_groupnorm(const void* x0, const void* x1, int C0, int C1, int B, int H, int W, const float* gamma,
                   const float* beta, const float* film, long film_ld, float eps, int act, int mode, int pad,
                   void* scratch, void* out, int dtype, void* stream);

@@ -173,7 +173,6 @@ SIGNATURES = {
     "k22_igemm_cfg_accepted": (_I, [C.POINTER(K22IgemmProblem)]),
     "k22_igemm_cfg": (_I, [C.POINTER(K22IgemmProblem), C.POINTER(K22IgemmOperands), C.POINTER(_I), _P]),
     "k22_igemm_candidates": (_I, [C.POINTER(K22IgemmProblem), C.POINTER(K22IgemmCfg), _I, C.POINTER(K22IgemmCfg), C.POINTER(K22IgemmCfg)]),
-    "k22_debug_conv_trace": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "k22_groupnorm": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _L, _F, _I, _I, _I, _P, _P, _I, _P]),
     "k22_groupnorm_scratch_bytes": (_Z, [_I, _I]),
     "k22_attention": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),

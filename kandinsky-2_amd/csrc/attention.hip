@@ -70,9 +70,7 @@ __device__ __forceinline__ void att_store_out(const AttentionParams& p, const f3
       att_store4(orow, db * 32 + 8 * g + 4 * h, x3, [&](int j) { return o[db][4 * g + j] * inv; });
 }
 
-// DBG (K22_ATT_PROBE builds only, wrong results; 32 = attention_pipe_kernel without its sched_group_barrier pins): 1 = the K / V^T tiles are staged once (no barriers, stores or global loads inside the loop),
-// 2 = no v_exp (p = the fma result), 4 = no S MFMAs, 8 = no PV MFMAs, 16 = no max / rescale.  tools/micro/attn_probe.hip
-template <typename TS, int DBG = 0>
+template <typename TS>
 __global__ __launch_bounds__(256, 2) void attention_kernel(AttentionParams p) {
   using T = typename AttC<TS>::type;          // arithmetic / LDS type
   constexpr bool MIX = AttC<TS>::MIX;         // fp32 tensors in memory, fp16 tiles and MFMAs (xh_t)
@@ -138,12 +136,10 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(AttentionParams p) {
 
   K22_ATT_GLOAD(0);
   for (int kt = 0; kt < nkt; ++kt) {
-    if (!(DBG & 1) || kt == 0) {
     __syncthreads();  // every wave finished reading the previous tile
     K22_ATT_LSTORE();
     __syncthreads();
     K22_ATT_GLOAD(kt + 1 < nkt ? kt + 1 : nkt - 1);
-    }
 
     f32x16_t s[2];
 #pragma unroll
@@ -154,8 +150,7 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(AttentionParams p) {
       for (int a = 0; a < 4; ++a) {
         Frag<T> kf;
         ld_frag(kf, Ks + (a / KSTEPS) * 8192, kb * 32 + l31, a % KSTEPS, h);
-        if constexpr (DBG & 4) { if constexpr (sizeof(T) == 2) { s[kb][a] += __uint_as_float(kf.v.x); s[kb][a + 4] += __uint_as_float(qf[a].v.y); } }
-        else mma_atom(s[kb], kf, qf[a]);
+        mma_atom(s[kb], kf, qf[a]);
       }
 
     // ---- online softmax, lane-local: p = exp2(s*c - m*c) with c = scale*log2(e) folded into ONE fma per
@@ -181,7 +176,6 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(AttentionParams p) {
     for (int r = 4; r < 16; ++r) mq[r & 3] = max3f(mq[r & 3], s[0][r], s[1][r]);
     float mloc = max2f(max3f(mq[0], mq[1], mq[2]), mq[3]);
     mloc = max2f(mloc, __shfl_xor(mloc, 32, 64));
-    if constexpr (DBG & 16) mloc = s[0][0];
     if (__any(mloc > m_run)) {
       const float m_new = max2f(m_run, mloc);
       const float alpha = exp2_t<T>((m_run - m_new) * cexp);
@@ -197,8 +191,8 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(AttentionParams p) {
     for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
       for (int r = 0; r < 16; r += 2) {
-        const float e0 = (DBG & 2) ? fmaf(s[kb][r], cexp, -mc) : exp2_t<T>(fmaf(s[kb][r], cexp, -mc));
-        const float e1 = (DBG & 2) ? fmaf(s[kb][r + 1], cexp, -mc) : exp2_t<T>(fmaf(s[kb][r + 1], cexp, -mc));
+        const float e0 = exp2_t<T>(fmaf(s[kb][r], cexp, -mc));
+        const float e1 = exp2_t<T>(fmaf(s[kb][r + 1], cexp, -mc));
         pv[kb][r] = e0;
         pv[kb][r + 1] = e1;
         lsum2 += f32x2_t{e0, e1};
@@ -213,8 +207,7 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(AttentionParams p) {
       for (int db = 0; db < 2; ++db) {
         Frag<T> vf;
         ld_frag_split(vf, Vs, db * 32 + l31, a, h);
-        if constexpr (DBG & 8) { if constexpr (sizeof(T) == 2) { o[db][a] += __uint_as_float(vf.v.x); o[db][a + 4] += __uint_as_float(pf.v.y); } }
-        else mma_atom(o[db], vf, pf);
+        mma_atom(o[db], vf, pf);
       }
     }
   }
@@ -239,7 +232,7 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(AttentionParams p) {
 }
 
 // ---- attention_pipe_kernel (round 6): the same arithmetic for the UNet's unmasked 16-bit attention, SOFTWARE-PIPELINED ----------------------
-// What tools/micro/attn_probe.hip measured on attention_kernel at T = 2304 (12 heads, batch 2; profiles/r06_attention.txt): with ONE
+// What ablated forms of attention_kernel (since removed from the source) measured at T = 2304 (12 heads, batch 2; profiles/r06_attention.txt): with ONE
 // workgroup per CU (one wave per SIMD) a 64-key tile takes ~2600 cycles of which the matrix pipe is busy 512 - 27 % of it is the two barriers
 // + tile stores of the single-buffered staging, 15 % the 32 v_exp_f32 (~12 cycles each), 15 % the max chain with its ds_bpermute round trip
 // and rescale branch, and the MFMAs of a tile are strictly serial with its softmax (S -> max -> exp -> P V); a second workgroup on the CU
@@ -265,7 +258,7 @@ __device__ __forceinline__ float xhalf_max(float v) {
 #endif
 }
 
-template <typename TS, int DBG = 0>
+template <typename TS>
 __global__ __launch_bounds__(256, 2) void attention_pipe_kernel(AttentionParams p) {
   using T = typename AttC<TS>::type;
   constexpr bool MIX = AttC<TS>::MIX;
@@ -285,7 +278,7 @@ __global__ __launch_bounds__(256, 2) void attention_pipe_kernel(AttentionParams 
   const int nqb = (p.T + 127) / 128;
   const int nblk = (int)gridDim.x;
   int L = (int)blockIdx.x;
-  if (!(DBG & 64)) { const int q8 = nblk >> 3, r8 = nblk & 7, x8 = L & 7; L = (x8 < r8 ? x8 * (q8 + 1) : r8 * (q8 + 1) + (x8 - r8) * q8) + (L >> 3); }
+  { const int q8 = nblk >> 3, r8 = nblk & 7, x8 = L & 7; L = (x8 < r8 ? x8 * (q8 + 1) : r8 * (q8 + 1) + (x8 - r8) * q8) + (L >> 3); }
   const int pair = L / nqb, qb = L - pair * nqb;
   const int b = pair / p.H, hd = pair - b * p.H;
   K22_ATT_PROLOGUE(qb);
@@ -334,10 +327,7 @@ __global__ __launch_bounds__(256, 2) void attention_pipe_kernel(AttentionParams 
   {                                                                                                      \
     _Pragma("unroll") for (int kb = 0; kb < 2; ++kb) {                                                   \
       _Pragma("unroll") for (int r = 0; r < 16; ++r) SC[kb][r] = 0.f;                                    \
-      _Pragma("unroll") for (int a = 0; a < 4; ++a) {                                                    \
-        if constexpr (DBG & 4) { SC[kb][a] += __uint_as_float(KF[kb * 4 + a].v.x); SC[kb][a + 4] += __uint_as_float(qf[a].v.y); } \
-        else mma_atom(SC[kb], KF[kb * 4 + a], qf[a]);                                                    \
-      }                                                                                                  \
+      _Pragma("unroll") for (int a = 0; a < 4; ++a) mma_atom(SC[kb], KF[kb * 4 + a], qf[a]);             \
     }                                                                                                    \
   }
 
@@ -367,13 +357,11 @@ __global__ __launch_bounds__(256, 2) void attention_pipe_kernel(AttentionParams 
   // one tile: SC = its scores (complete), SN = the next tile's (issued here); PAR = kt & 1 (compile time)
 #define K22_AP_TILE(SC, SN, PAR, KT)                                                                     \
   {                                                                                                      \
-    if constexpr (!(DBG & 1)) {                                                                          \
     __syncthreads();   /* K tile kt + 1 / V^T tile kt visible; every wave is done with K tile kt and V^T tile kt - 1 */ \
     K22_AP_KSTORE(Kb + (PAR) * 8192);          /* K tile kt + 2 */                                       \
     K22_AP_VSTORE(Vb + (1 - (PAR)) * 8192);    /* V^T tile kt + 1 */                                     \
     K22_AP_KLOAD((KT) + 3);                                                                              \
     K22_AP_VLOAD((KT) + 2);                                                                              \
-    }                                                                                                    \
     if ((KT) == nkt - 1 && (p.Tk & 63)) {      /* the one partial tile */                                \
       _Pragma("unroll") for (int kb = 0; kb < 2; ++kb)                                                   \
         _Pragma("unroll") for (int r = 0; r < 16; ++r)                                                   \
@@ -394,17 +382,15 @@ __global__ __launch_bounds__(256, 2) void attention_pipe_kernel(AttentionParams 
     _Pragma("unroll") for (int r = 4; r < 16; ++r) mq[r & 3] = __builtin_fmaxf(__builtin_fmaxf(mq[r & 3], SC[0][r]), SC[1][r]); \
     const float mloc = xhalf_max(__builtin_fmaxf(__builtin_fmaxf(__builtin_fmaxf(mq[0], mq[1]), mq[2]), mq[3])); \
     const float m_old = m_run;                                                                           \
-    m_run = (DBG & 16) ? SC[0][0] : __builtin_fmaxf(m_run, mloc);                                        \
+    m_run = __builtin_fmaxf(m_run, mloc);                                                                \
     const float mc = m_run * cexp;                                                                       \
     _Pragma("unroll") for (int kb = 0; kb < 2; ++kb)                                                     \
       _Pragma("unroll") for (int r = 0; r < 16; ++r)                                                     \
-        SC[kb][r] = (DBG & 2) ? fmaf(SC[kb][r], cexp, -mc) : __builtin_amdgcn_exp2f(fmaf(SC[kb][r], cexp, -mc)); \
-    if constexpr (!(DBG & 32)) {                                                                         \
+        SC[kb][r] = __builtin_amdgcn_exp2f(fmaf(SC[kb][r], cexp, -mc));                                  \
     __builtin_amdgcn_sched_group_barrier(0x002, 30, 0);                                                  \
     _Pragma("unroll") for (int i_ = 0; i_ < 8; ++i_) {                                                   \
       __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                                 \
       __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);                                                 \
-    }                                                                                                    \
     }                                                                                                    \
     /* everything above belongs in front of the rescale branch (the compiler would otherwise sink the v_exp block behind it) */        \
     asm volatile("" : "+v"(SC[0]), "+v"(SC[1]), "+v"(SN[0]), "+v"(SN[1]));                               \
@@ -421,21 +407,16 @@ __global__ __launch_bounds__(256, 2) void attention_pipe_kernel(AttentionParams 
       float pv_[8];                                                                                      \
       _Pragma("unroll") for (int j = 0; j < 8; ++j) pv_[j] = SC[a >> 1][8 * (a & 1) + j];                \
       make_pfrag(pf, pv_);                                                                               \
-      _Pragma("unroll") for (int db = 0; db < 2; ++db) {                                                 \
-        if constexpr (DBG & 8) { o[db][a] += __uint_as_float(vf_[a * 2 + db].v.x); o[db][a + 4] += __uint_as_float(pf.v.y); } \
-        else mma_atom(o[db], vf_[a * 2 + db], pf);                                                       \
-      }                                                                                                  \
+      _Pragma("unroll") for (int db = 0; db < 2; ++db) mma_atom(o[db], vf_[a * 2 + db], pf);             \
     }                                                                                                    \
     float lsa = 0.f, lsb = 0.f;                                                                          \
     _Pragma("unroll") for (int kb = 0; kb < 2; ++kb)                                                     \
       _Pragma("unroll") for (int r = 0; r < 16; r += 2) { lsa += SC[kb][r]; lsb += SC[kb][r + 1]; }      \
     l_run += lsa + lsb;                                                                                  \
-    if constexpr (!(DBG & 32)) {                                                                         \
     __builtin_amdgcn_sched_group_barrier(0x002, 6, 0);                                                   \
     _Pragma("unroll") for (int i_ = 0; i_ < 8; ++i_) {                                                   \
       __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                                 \
       __builtin_amdgcn_sched_group_barrier(0x002, 6, 0);                                                 \
-    }                                                                                                    \
     }                                                                                                    \
     __builtin_amdgcn_sched_barrier(0);                                                                   \
   }

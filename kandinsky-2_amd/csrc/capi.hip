@@ -27,9 +27,6 @@ int k22_build_flags(void) {
 #ifndef K22_NOPK
   f |= K22_BUILD_PACKED_FP32;
 #endif
-#if defined(K22_DEBUG_VARIANTS) || defined(K22_STREAM_DEBUG) || defined(K22_SKINNY_DEBUG)
-  f |= K22_BUILD_DEBUG_VARIANTS;
-#endif
   return f;
 }
 
@@ -47,19 +44,11 @@ const char* k22_last_error(void) { return g_err; }
 // given to k22_debug_set_stream_frag ride along with every LATER kernel-level test entry of this file (k22_gemm, k22_conv3x3*,
 // k22_qkv_project_stream) until they are reset to NULL.  The engines own their copies themselves (engine.hip); nothing in the product
 // path reads these globals.
-#ifdef K22_STREAM_DEBUG
-static unsigned long long* g_dbg_trace = nullptr;
-extern "C" int k22_debug_set_stream_trace(unsigned long long* t) { g_dbg_trace = t; return K22_OK; }
-#define K22_DBG_TRACE(p) (p).st_trace = g_dbg_trace
-#else
-#define K22_DBG_TRACE(p) (void)0
-#endif
 static const void* g_dbg_wfrag = nullptr;
 static const void* g_dbg_wsfrag = nullptr;
 static void* g_dbg_scratch = nullptr;      // "repack on every call" mode for the parity tests (their helpers pack the weights themselves)
 static size_t g_dbg_scratch_bytes = 0;
 static int dbg_frag(IgemmParams& p, int dtype, hipStream_t st) {
-  K22_DBG_TRACE(p);
   p.Wfrag = g_dbg_wfrag; p.Wsfrag = g_dbg_wsfrag;
   if (g_dbg_wfrag || !g_dbg_scratch || dtype == K22_F32 || (p.taps != 1 && p.taps != 9) || p.Kc % 64 || p.Npad % 64) return K22_OK;
   const size_t n1 = stream_frag_bytes(p.Npad, p.taps, p.Kc, dtype);
@@ -374,14 +363,6 @@ int k22_igemm_cfg(const K22IgemmProblem* pr, const K22IgemmOperands* ops, int* r
   return launch_igemm(q, d.dtype, reinterpret_cast<hipStream_t>(stream));
 }
 
-int k22_debug_conv_trace(const void* x_padded, const void* Wp, const float* bias, void* out, int B, int H, int W, int Cin, int Cout,
-                         int Npad, unsigned long long* trace, void* stream) {
-  IgemmParams p = igemm_conv3_problem(B, H, W, Cin, Cout);
-  p.A0 = x_padded; p.Wp = Wp; p.bias = bias; p.out = out;
-  p.Npad = Npad; p.splitk = 1; p.trace = trace;
-  return launch_conv3_halo_trace(p, K22_BF16, reinterpret_cast<hipStream_t>(stream));
-}
-
 size_t k22_groupnorm_scratch_bytes(int B, int C) {
   return (size_t)B * 128 * C * 2 * sizeof(float) + (size_t)B * C * 2 * sizeof(float) + 512;
 }
@@ -462,7 +443,6 @@ int k22_skinny_gemm(const void* Afrag, const void* Wfrag, const float* bias, voi
   SkinnyParams q = {};
   q.Af = Afrag; q.Wf = Wfrag; q.bias = bias; q.out = out; q.partial = partial; q.M = M; q.N = N; q.Npad = Npad; q.K = K; q.MA = (M + 31) / 32;
   q.splitk = splitk > 0 ? splitk : 1; q.epi = epi; q.act = act; q.ldo = ldo;
-  q.trace = reinterpret_cast<unsigned long long*>(g_dbg_scratch);   // K22_SKINNY_DEBUG builds: stamps go to the debug scratch (k22_debug_set_stream_scratch)
   return launch_skinny(q, dtype, mt, nb, reinterpret_cast<hipStream_t>(stream));
 }
 int k22_finish_ln(const float* partial, int splitk, const float* bias, float* x, long ldx, const float* gain, const float* beta, void* yfrag,

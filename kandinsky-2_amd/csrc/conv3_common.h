@@ -318,9 +318,6 @@ template <bool GASM, bool WEIGHT> __device__ __forceinline__ void halo_dma16(con
 // tile are compile-time functions of the tap
 #define K22_TAPS_9(M, ...) M(0, __VA_ARGS__) M(1, __VA_ARGS__) M(2, __VA_ARGS__) M(3, __VA_ARGS__) M(4, __VA_ARGS__) M(5, __VA_ARGS__) M(6, __VA_ARGS__) M(7, __VA_ARGS__) M(8, __VA_ARGS__)
 #define K22_TAPS_4(M, ...) M(0, __VA_ARGS__) M(1, __VA_ARGS__) M(2, __VA_ARGS__) M(3, __VA_ARGS__)
-// A kernel may stand statements at four points of a tap: K22_TAP_HOOK(0 .. 3, TAP) = before the counted wait, behind it, behind the
-// barrier, behind the tap body (conv3_halo_kernel's TRACE stamps)
-#define K22_TAP_HOOK(N, TAP)
 // The loaders' half of a tap, for loader wave LW of NWL in a TAPS-tap filter (weights [n][tap][Kc]) with an NBST-deep weight ring behind
 // the two halo buffers: the counted vmcnt wait for this tap's weight tile (VMEM queue of a wave per tap: [weight tile NBST-1 taps ahead,
 // B_SLOTS loads] then [PPT halo pieces, taps 0 .. TAPS-NBST]: at most the B_SLOTS * (NBST-2) younger weight loads and the halo pieces issued
@@ -329,13 +326,10 @@ template <bool GASM, bool WEIGHT> __device__ __forceinline__ void halo_dma16(con
 // `fill` and the next PPT pieces of the next slab's halo (K22_ISSUE_A) into the halo buffer at LDS location ANEXT; RING = the LDS
 // location of the weight ring (pasted as written: its sum with the slot offset is one expression).
 // Needs s, sn, fill, B_BYTES, B_SLOTS, NBST, p.
-#define K22_TAP_FRONT(TAP, TAPS, LW, NWL, PPT, WAITS, LOADS, ANEXT, RING)                                  \
-  K22_TAP_HOOK(0, TAP)                                                                                     \
-  if (WAITS) wait_vmcnt<B_SLOTS * (NBST - 2) + (PPT) * halo_count<TAPS, NBST>(TAP)>();                     \
-  K22_TAP_HOOK(1, TAP)                                                                                     \
+#define K22_TAP_FRONT(TAP, TAPS, LW, NWL, PPT, ANEXT, RING)                                                \
+  wait_vmcnt<B_SLOTS * (NBST - 2) + (PPT) * halo_count<TAPS, NBST>(TAP)>();                                \
   raw_barrier();                                                                                           \
-  K22_TAP_HOOK(2, TAP)                                                                                     \
-  if (LOADS) {                                                                                             \
+  {                                                                                                        \
     constexpr int ta_ = ((TAP) + NBST - 1) % (TAPS);                                                       \
     const int sa_ = ((TAP) + NBST - 1 >= (TAPS)) ? sn : s;                                                 \
     K22_ISSUE_B(LW, NWL, ta_ * p.Kc + sa_ * BK, RING + fill * B_BYTES);                                    \
@@ -361,31 +355,27 @@ template <bool GASM, bool WEIGHT> __device__ __forceinline__ void halo_dma16(con
   }                                                                                                        \
   __VA_ARGS__                                                                                              \
   K22_READS_DONE();                                                                                        \
-  K22_TAP_HOOK(3, TAP)                                                                                     \
   cur = (cur + 1 == NBST) ? 0 : cur + 1;
 // One tap of a lock-step kernel: every wave loads, then multiplies
-#define K22_LOCKSTEP_TAP(TAP, TAPS, PPT, INLOOP, ...)                                                      \
+#define K22_LOCKSTEP_TAP(TAP, TAPS, PPT, ...)                                                              \
   {                                                                                                        \
-    K22_TAP_FRONT(TAP, TAPS, wave, NW, PPT, INLOOP, INLOOP, Anext, Bst)                                    \
+    K22_TAP_FRONT(TAP, TAPS, wave, NW, PPT, Anext, Bst)                                                    \
     K22_TAP_COMPUTE(TAP, TAPS, __VA_ARGS__)                                                                \
     fill = (fill + 1 == NBST) ? 0 : fill + 1;                                                              \
   }
 // The K loop of a lock-step kernel over slabs [s0, s1): prologue = the whole halo of the first slab (A_SLOTS pieces per wave), then the
-// weight tiles of taps 0 .. NBST-2; then TAPS taps per slab, the halo double-buffered across slabs.  LOADER: this wave issues LDS-DMA;
-// INLOOP: also inside the tap loop.
-#define K22_LOCKSTEP_LOOP(TAPS, A_SLOTS, PPT, LOADER, INLOOP, BODY)                                        \
+// weight tiles of taps 0 .. NBST-2; then TAPS taps per slab, the halo double-buffered across slabs.  Every wave issues LDS-DMA.
+#define K22_LOCKSTEP_LOOP(TAPS, A_SLOTS, PPT, BODY)                                                        \
   if (s0 < s1) {                                                                                           \
-    if (LOADER) {                                                                                          \
-      _Pragma("unroll") for (int q = 0; q < (A_SLOTS); ++q) K22_ISSUE_A(wave, NW, q, s0, smem);            \
-      _Pragma("unroll") for (int t = 0; t < NBST - 1; ++t) K22_ISSUE_B(wave, NW, t * p.Kc + s0 * BK, Bst + t * B_BYTES); \
-    }                                                                                                      \
+    _Pragma("unroll") for (int q = 0; q < (A_SLOTS); ++q) K22_ISSUE_A(wave, NW, q, s0, smem);              \
+    _Pragma("unroll") for (int t = 0; t < NBST - 1; ++t) K22_ISSUE_B(wave, NW, t * p.Kc + s0 * BK, Bst + t * B_BYTES); \
     int cur = 0;               /* ring slot of the current tap's weights */                                \
     int fill = NBST - 1;       /* ring slot the tile NBST-1 taps ahead goes into */                        \
     for (int s = s0; s < s1; ++s) {                                                                        \
       char* const Acur = smem + ((s - s0) & 1) * A_BYTES;                                                  \
       char* const Anext = smem + (((s - s0) & 1) ^ 1) * A_BYTES;                                           \
       const int sn = s + 1 < s1 ? s + 1 : s1 - 1;  /* past-the-end loads re-read the last slab (uniform counting) */ \
-      K22_TAPS_##TAPS(K22_LOCKSTEP_TAP, TAPS, PPT, INLOOP, BODY)                                           \
+      K22_TAPS_##TAPS(K22_LOCKSTEP_TAP, TAPS, PPT, BODY)                                                   \
     }                                                                                                      \
   }
 

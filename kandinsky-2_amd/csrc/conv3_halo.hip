@@ -23,41 +23,38 @@
 //     (sum, sum of squares) of the STORED values for the next GroupNorm (deterministic, no atomics)
 //   * split-K over channel slabs for the low-resolution levels (fp32 partials, finished by splitk_reduce)
 //   * variants selected by p.algo (measured in DESIGN.md section 9): 2 = this kernel; 7 = its LDS-DMA issued from inline asm
-//     (exact lgkmcnt for the fragment reads; the tuner's usual pick); 6 = 7 + explicit fragment pipeline; 3 = conv3_halo3 below;
-//     8 / 9 = measurement only.  gemm8_kernel (plain GEMM on the same frame, qkv / proj_out) is in gemm8.hip; both share the epilogue
+//     (exact lgkmcnt for the fragment reads; the tuner's usual pick); 6 = 7 + explicit fragment pipeline; 3 = conv3_halo3 below.
+//     gemm8_kernel (plain GEMM on the same frame, qkv / proj_out) is in gemm8.hip; both share the epilogue
 //     (halo_tail, conv3_common.h)
 //   * optional fused 1x1 skip_connection of the ResBlock (out += x . Ws^T): a second, plain-GEMM K loop over the
 //     block input's channels (A rows = the tile's own pixels, no halo) that accumulates into the same registers,
 //     so the skip tensor is never written, re-read or launched separately
 #include "conv3_common.h"
 
-// LW = number of waves that issue the LDS-DMA: 8 (every wave loads its share right after the barrier: 3 pieces per wave per tap).  (A
-// 4-loader form - p.algo 5 - measured 2-5 % slower in round 1 and was deleted in round 5; the parameter stays for the index arithmetic.)
+// Every wave issues its share of the LDS-DMA right after the barrier: 3 pieces per wave per tap.  (A 4-loader form - p.algo 5 - measured
+// 2-5 % slower in round 1 and was deleted in round 5.)
 // PIPE: explicit fragment pipeline across the per-tap barrier.  The fragments of k-step ks+1 are read from LDS BEFORE
 // the MFMAs of k-step ks are issued (two register sets), and the last k-step of a tap is multiplied after the NEXT
 // tap's barrier, where it covers the LDS-DMA issue and the first fragment reads of that tap: a wave never parks on
 // lgkmcnt with an empty matrix pipe behind it (the compiler's own schedule reads one MFMA ahead of the use).
-template <typename T, int BM, int NBST, bool TRACE = false, int LW = 8, int MODE = 0>
+template <typename T, int BM, int NBST, int MODE = 0>
 __global__ __launch_bounds__(512) void conv3_halo_kernel(const IgemmParams p) {
   constexpr bool PIPE = MODE == 1;      // explicit fragment pipeline (above)
   constexpr bool GASM = MODE == 1 || MODE == 2;  // LDS-DMA from inline asm (glds16_asm): exact lgkmcnt(N) for the fragment reads
-  constexpr bool DBG_NOLOAD = MODE == 3;  // measurement only (wrong results): no LDS-DMA inside the tap loop
-  constexpr bool DBG_NOMMA = MODE == 4;   // measurement only (wrong results): fragments are read but not multiplied
   using TR = TT<T>;
   constexpr int BK = TR::BK, EPC = TR::EPC, KSTEPS = TR::KSTEPS;
-  constexpr int BN = HALO_BN, NW = LW, WM = 4, WN = 2;
+  constexpr int BN = HALO_BN, NW = HALO_NW, WM = 4, WN = 2;
   constexpr int MI = BM / (WM * 32), NI = BN / (WN * 32);
-  constexpr int B_SLOTS = BN / 8 / NW;  // weight LDS-DMA instructions per loader wave per tap
+  constexpr int B_SLOTS = BN / 8 / NW;  // weight LDS-DMA instructions per wave per tap
   constexpr int B_BYTES = BN * 128;
-  constexpr int APT = HALO_NW / LW;     // halo pieces per loader wave per tap
-  constexpr int A_SLOTS = (10 - NBST) * APT;  // taps 0 .. 9-NBST issue APT halo pieces per loader wave
+  constexpr int APT = 1;                // halo pieces per wave per tap
+  constexpr int A_SLOTS = (10 - NBST) * APT;  // taps 0 .. 9-NBST issue APT halo pieces per wave
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
   const int h = lane >> 5, l31 = lane & 31;
-  const bool loader = LW == HALO_NW || wave < LW;   // wave-uniform
 
   const int W2 = p.W + 2;
   const int VR = p.H * W2;                     // virtual output rows per image
@@ -99,45 +96,11 @@ __global__ __launch_bounds__(512) void conv3_halo_kernel(const IgemmParams p) {
   for (int ni = 0; ni < NI; ++ni) brow[ni] = (wn * (BN / WN) + ni * 32 + l31) * 128;
   const int bsw = (l31 >> 1) & 7;  // (row >> 1) & 7 with row = multiple of 32 + l31
   const unsigned lds0 = halo_lds_base(smem);
-  int trace_it = 0;
-  (void)trace_it;
-
-  // TRACE: s_memtime stamps around the wait, the barrier and the tap body (launch_conv3_halo_trace below)
-#undef K22_TAP_HOOK
-#define K22_TAP_HOOK(N, TAP) K22_HALO_TRACE_##N
-#define K22_HALO_TRACE_0                                                                                   \
-  unsigned long long tr0_ = 0, tr1_ = 0, tr2_ = 0;                                                         \
-  if constexpr (TRACE) tr0_ = __builtin_amdgcn_s_memtime();
-#define K22_HALO_TRACE_1 if constexpr (TRACE) tr1_ = __builtin_amdgcn_s_memtime();
-#define K22_HALO_TRACE_2 if constexpr (TRACE) tr2_ = __builtin_amdgcn_s_memtime();
-#define K22_HALO_TRACE_3                                                                                   \
-  if constexpr (TRACE) {                                                                                   \
-    /* stamp after the last MFMA has been ISSUED (issue blocks while the pipe is busy) */                  \
-    asm volatile("" ::"v"(acc[0][0][0]), "v"(acc[MI - 1][NI - 1][15]));                                    \
-    const unsigned long long tr3_ = __builtin_amdgcn_s_memtime();                                          \
-    if (blockIdx.x == 0 && (wave == 0 || wave == 5) && lane == 0 && p.trace != nullptr) {                  \
-      unsigned long long* o_ = p.trace + ((size_t)(wave ? 1 : 0) * 4096 + (size_t)trace_it * 4);           \
-      if (trace_it < 1024) { o_[0] = tr0_; o_[1] = tr1_; o_[2] = tr2_; o_[3] = tr3_; }                      \
-    }                                                                                                      \
-    ++trace_it;                                                                                            \
-  }
-  // DBG_NOMMA: the fragments are read and kept alive, nothing is multiplied
 #define K22_HALO_BODY                                                                                      \
   if constexpr (PIPE) K22_TAP_PIPE(FragA<T>, Frag<T>, arow[mi], asw[mi], Bcur + brow[ni], bsw, K22_PIPE_LOCKSTEP) \
-  else if constexpr (DBG_NOMMA) {                                                                          \
-    _Pragma("unroll") for (int ks = 0; ks < KSTEPS; ++ks) {                                                \
-      FragA<T> a[MI];                                                                                      \
-      Frag<T> b[NI];                                                                                       \
-      _Pragma("unroll") for (int mi = 0; mi < MI; ++mi) ld_frag_at(a[mi], arow[mi], asw[mi], ks, h);       \
-      _Pragma("unroll") for (int ni = 0; ni < NI; ++ni) ld_frag_at(b[ni], Bcur + brow[ni], bsw, ks, h);    \
-      _Pragma("unroll") for (int mi = 0; mi < MI; ++mi) asm volatile("" ::"v"(a[mi].v));                   \
-      _Pragma("unroll") for (int ni = 0; ni < NI; ++ni) asm volatile("" ::"v"(b[ni].v));                   \
-    }                                                                                                      \
-  } else { K22_TAP_PLAIN(FragA<T>, Frag<T>, ld_frag_at, arow[mi], asw[mi], Bcur + brow[ni], bsw) }
-  K22_LOCKSTEP_LOOP(9, A_SLOTS, APT, loader, loader && !DBG_NOLOAD, K22_HALO_BODY)
+  else { K22_TAP_PLAIN(FragA<T>, Frag<T>, ld_frag_at, arow[mi], asw[mi], Bcur + brow[ni], bsw) }
+  K22_LOCKSTEP_LOOP(9, A_SLOTS, APT, K22_HALO_BODY)
 #undef K22_HALO_BODY
-#undef K22_TAP_HOOK
-#define K22_TAP_HOOK(N, TAP)
   if constexpr (PIPE) { K22_MMA_ALL(pb, pa) }
   halo_tail<T, BM>(p, acc, smem, bx, bz, img, v0, n0);
 }
@@ -342,34 +305,11 @@ int conv3_halo_tiles_per_image(const IgemmParams& p, int bm) { return halo_tiles
 size_t conv3_halo_lds_bytes(const IgemmParams& p, int bm, int depth) { return p.algo == IG_ALGO_HALO3 ? halo3_smem_bytes(p, bm, depth) : halo_smem_bytes(p, bm, depth); }
 
 // conv3_halo_kernel in form MODE at (L.bm, L.depth)
-template <typename T, int MODE, bool HAS128 = true>
+template <typename T, int MODE>
 static int launch_halo_mode(const IgemmParams& p, const IgemmLaunch& L, hipStream_t stream) {
-  auto depth = [&](auto bm) {
-    return halo_with_depth<2, 3, 4, 6>(L.depth, [&](auto d) { return halo_run<conv3_halo_kernel<T, decltype(bm)::value, decltype(d)::value, false, 8, MODE>>(p, L, stream); });
-  };
-  if constexpr (!HAS128) return depth(std::integral_constant<int, 256>{});
-  else return halo_with_bm(L.bm, depth);
-}
-
-// developer tool: conv3_halo_kernel<bf16, 256, NBST> with per-tap s_memtime stamps (wave 0 and wave 5 of block 0):
-// trace[w][tap][4] = (before the counted vmcnt wait, after it, after the barrier, after the last MFMA was issued)
-int launch_conv3_halo_trace(const IgemmParams& p, int dtype, hipStream_t stream) {
-  if (dtype != K22_BF16 || !conv3_halo_supported(p, dtype, 256) || p.trace == nullptr) return k22_set_error(K22_EINVAL, "conv3_halo_trace: bf16, BM = 256 only");
-  const int nbst = halo_pick_nbst(p, 256) >= 4 ? 4 : 2;
-  const size_t smem = halo_smem_bytes(p, 256, nbst);
-  IgemmParams q = p;
-  q.splitk = 1; q.xcd_remap = 1;
-  const int B = p.M / (p.H * p.W);
-  const int nblocks = B * halo_tiles_per_image(p, 256) * ((p.N + HALO_BN - 1) / HALO_BN);
-  if (nbst == 4) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3_halo_kernel<bf16_t, 256, 4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    hipLaunchKernelGGL((conv3_halo_kernel<bf16_t, 256, 4, true>), dim3(nblocks), dim3(512), smem, stream, q);
-  } else {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3_halo_kernel<bf16_t, 256, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    hipLaunchKernelGGL((conv3_halo_kernel<bf16_t, 256, 2, true>), dim3(nblocks), dim3(512), smem, stream, q);
-  }
-  K22_CHECK_LAUNCH();
-  return K22_OK;
+  return halo_with_bm(L.bm, [&](auto bm) {
+    return halo_with_depth<2, 3, 4, 6>(L.depth, [&](auto d) { return halo_run<conv3_halo_kernel<T, decltype(bm)::value, decltype(d)::value, MODE>>(p, L, stream); });
+  });
 }
 
 // Launches the lock-step kernel the resolved launch names (the split-K reduction, if any, is the caller's: launch_igemm): conv3_halo3_kernel, or
@@ -386,12 +326,6 @@ int launch_conv3_halo(const IgemmParams& p, int dtype, const IgemmLaunch& L, hip
         });
       if (L.pipe == 0) return launch_halo_mode<T, 0>(p, L, stream);
       if (L.pipe == 1) return launch_halo_mode<T, 1>(p, L, stream);
-#ifdef K22_DEBUG_VARIANTS   // measurement-only variants (wrong results), bf16 at BM = 256: 3 = no LDS-DMA in the loop, 4 = no MFMA
-      if constexpr (std::is_same<T, bf16_t>::value) {
-        if (L.pipe == 3) return launch_halo_mode<T, 3, false>(p, L, stream);
-        if (L.pipe == 4) return launch_halo_mode<T, 4, false>(p, L, stream);
-      }
-#endif
     }
     return launch_halo_mode<T, 2>(p, L, stream);
   });

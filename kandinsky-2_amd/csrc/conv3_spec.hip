@@ -24,8 +24,8 @@
 // convolutions of one step): 4.09 ms against 4.51 ms for the best lock-step variant at BM = 256, 4.43 against 4.77 at
 // BM = 128; the specialisation alone (algo 11, compiler-scheduled consumers) is +-0 - it is the interleaved pipeline that the
 // one-owner matrix pipe makes worthwhile.
-// DBG (measurement only, wrong results): 1 (algo 13) = the producers issue nothing inside the tap loop - what is left is
-// the consumers' speed limit under the same barriers; 2 (algo 14) = the LDS-DMA is issued but never waited for.  At 96x96
+// What the loads cost (measured with two wrong-result forms that have since left the source: producers that issue nothing inside the tap
+// loop - the consumers' speed limit under the same barriers - and LDS-DMA that is issued but never waited for).  At 96x96
 // 768->768, same box: 1.08 PFLOP/s complete, 1.22 without the waits, 1.39 without the loads - half of what the loads cost
 // there is the ONE tap a tile has to land in (2-slot ring: the LDS holds the double-buffered halo), half is contention;
 // where four slots fit (48x48) the waits cost nothing and the contention is the same 12-14 %.  Staging the weight tiles
@@ -36,7 +36,7 @@
 // GroupNorm, FiLM and SiLU to the raw tensor as it landed in the LDS: bit-identical to gn_apply + this kernel, 21 % slower per step
 // (profiles/r04_gn_fused_negative.txt).
 // ================================================================================================================
-template <typename T, int BM, int NBST, bool PIPE = false, int DBG = 0>
+template <typename T, int BM, int NBST, bool PIPE = false>
 __global__ __launch_bounds__(512) void conv3_halo_spec_kernel(const IgemmParams p) {
   using TR = TT<T>;
   constexpr int BK = TR::BK, EPC = TR::EPC, KSTEPS = TR::KSTEPS;
@@ -75,19 +75,18 @@ __global__ __launch_bounds__(512) void conv3_halo_spec_kernel(const IgemmParams 
   halo_zero_acc(acc);
 
   char* const Bst = smem + 2 * A_BYTES;
-  // The producers' K loop: per tap the loaders' half (K22_TAP_FRONT; WAITS / LOADS: the DBG forms leave one out), then the rotation of the
-  // ring slot
-#define K22_PRODUCER_TAP(TAP, WAITS, LOADS)                                                                \
+  // The producers' K loop: per tap the loaders' half (K22_TAP_FRONT), then the rotation of the ring slot
+#define K22_PRODUCER_TAP(TAP, ...)                                                                         \
   {                                                                                                        \
-    K22_TAP_FRONT(TAP, 9, lw, NWL, APT, WAITS, LOADS, lds0 + (unsigned)anext_off, lds0 + 2 * A_BYTES)      \
+    K22_TAP_FRONT(TAP, 9, lw, NWL, APT, lds0 + (unsigned)anext_off, lds0 + 2 * A_BYTES)                    \
     fill = (fill + 1 == NBST) ? 0 : fill + 1;                                                              \
   }
-#define K22_PRODUCER_LOOP(WAITS, LOADS)                                                                    \
+#define K22_PRODUCER_LOOP()                                                                                \
   int fill = NBST - 1;                                                                                     \
   for (int s = s0; s < s1; ++s) {                                                                          \
     const int anext_off = (((s - s0) & 1) ^ 1) * A_BYTES;                                                  \
     const int sn = s + 1 < s1 ? s + 1 : s1 - 1;   /* past-the-end loads re-read the last slab (uniform counting) */ \
-    K22_TAPS_9(K22_PRODUCER_TAP, WAITS, LOADS)                                                             \
+    K22_TAPS_9(K22_PRODUCER_TAP, )                                                                         \
   }
 #undef K22_LDS_ADDR
 #undef K22_LDS_PTR
@@ -107,7 +106,7 @@ __global__ __launch_bounds__(512) void conv3_halo_spec_kernel(const IgemmParams 
       for (int q = 0; q < A_SLOTS; ++q) K22_ISSUE_A(lw, NWL, q, s0, lds0);
 #pragma unroll
       for (int t = 0; t < NBST - 1; ++t) K22_ISSUE_B(lw, NWL, t * p.Kc + s0 * BK, lds0 + 2 * A_BYTES + t * B_BYTES);
-      K22_PRODUCER_LOOP(DBG == 0, DBG != 1)
+      K22_PRODUCER_LOOP()
     } else {
       // ---------------------------------------- consumers: fragments + MFMA only --------------------------------------
       const int wm = STRIP ? 0 : wave >> 1, wn = STRIP ? wave : wave & 1;
@@ -164,12 +163,6 @@ static int launch_spec_depth(const IgemmParams& p, const IgemmLaunch& L, hipStre
 int launch_conv3_halo_spec(const IgemmParams& p, int dtype, const IgemmLaunch& L, hipStream_t stream) {
   return k22_with_dtype(dtype, [&](auto tag) {
     using T = typename decltype(tag)::type;
-#ifdef K22_DEBUG_VARIANTS   // measurement-only forms of the pipelined kernel (wrong results), bf16 at BM = 256: DBG 1 = no LDS-DMA inside the tap loop, 2 = LDS-DMA issued but never waited for
-    if constexpr (std::is_same<T, bf16_t>::value) {
-      if (L.dbg == 1) return halo_with_depth<2, 4>(L.depth, [&](auto d) { return halo_run<conv3_halo_spec_kernel<T, 256, decltype(d)::value, true, 1>>(p, L, stream); });
-      if (L.dbg == 2) return halo_with_depth<2, 4>(L.depth, [&](auto d) { return halo_run<conv3_halo_spec_kernel<T, 256, decltype(d)::value, true, 2>>(p, L, stream); });
-    }
-#endif
     // the 224-row tile: 16-bit types, pipelined form (112 accumulators beside two sets of 7 + 1 fragments of 4 registers; the wider
     // fragments of the other types do not fit).  conv3_halo_supported says the same; a launch that names it otherwise is refused.
     constexpr bool pipe224 = std::is_same<T, bf16_t>::value || std::is_same<T, f16_t>::value;

@@ -89,7 +89,7 @@ __global__ __launch_bounds__(512) void conv3_up2_kernel(const IgemmParams p) {
 #define K22_UP2_BODY                                                                                       \
   if constexpr (PIPE) K22_TAP_PIPE(FragA<T>, Frag<T>, arow[mi], asw[mi], Bcur + brow[ni], bsw, K22_PIPE_LOCKSTEP) \
   else { K22_TAP_PLAIN(FragA<T>, Frag<T>, ld_frag_at, arow[mi], asw[mi], Bcur + brow[ni], bsw) }
-  K22_LOCKSTEP_LOOP(4, UP2_ASLOTS, HPT, true, true, K22_UP2_BODY)
+  K22_LOCKSTEP_LOOP(4, UP2_ASLOTS, HPT, K22_UP2_BODY)
 #undef K22_UP2_BODY
   if constexpr (PIPE) { K22_MMA_ALL(pb, pa) }
   halo_tail<T, BM, false, false, true>(p, acc, smem, (img * 4 + ph) * TPI + tile, bz, img, v0, n0, ph);

@@ -451,10 +451,7 @@ void igemm_set_default_stages(int v) { g_opts.stages = (v >= 2 && v <= 4) ? v : 
 void igemm_set_xcd_remap(int v) { g_opts.xcd_remap = v ? 1 : 0; }
 void igemm_set_gemm_algo(int v) { g_opts.gemm_algo = (v == IG_ALGO_GEMM8 || v == IG_ALGO_STREAM) ? v : 0; }
 void igemm_set_conv_algo(int v) {
-  bool ok = v == IG_ALGO_GENERIC || v == IG_ALGO_STREAM || v == IG_ALGO_UP2 || v == IG_ALGO_UP2_PIPE || (igemm_algo_is_halo(v) && !igemm_algo_is_debug(v));
-#ifdef K22_DEBUG_VARIANTS   // the measurement-only kernels (wrong results) are not reachable in a release build
-  ok = ok || igemm_algo_is_debug(v);
-#endif
+  const bool ok = v == IG_ALGO_GENERIC || v == IG_ALGO_STREAM || v == IG_ALGO_UP2 || v == IG_ALGO_UP2_PIPE || igemm_algo_is_halo(v);
   g_opts.conv_algo = ok ? v : 0;
 }
 
@@ -551,22 +548,9 @@ int igemm_resolve(const IgemmParams& p, int dtype, IgemmLaunch* out) {
         L.pipe = (L.algo == IG_ALGO_SPEC_PIPE && !(bm == 256 && (dtype == K22_F16X3 || dtype == K22_F32))) ? 1 : 0;
       } else if (split) {
         // split precision: one lock-step form (asm LDS-DMA) whichever of 2 / 6 / 7 was named
-        if (igemm_algo_is_debug(L.algo)) return k22_set_error(K22_EINVAL, "conv3_halo: no measurement-only variants in split precision");
         L.family = IG_FAM_HALO; L.pipe = 2;
       } else if (L.algo == IG_ALGO_HALO3) {
         L.family = IG_FAM_HALO3;
-      } else if (igemm_algo_is_debug(L.algo)) {
-#ifdef K22_DEBUG_VARIANTS   // measurement-only kernels (wrong results) are compiled only into a developer build: make EXTRA=-DK22_DEBUG_VARIANTS
-        if (L.algo == IG_ALGO_DBG_SPEC_NO_DMA || L.algo == IG_ALGO_DBG_SPEC_NO_WAIT) {
-          if (dtype != K22_BF16 || bm != 256) return k22_set_error(K22_EINVAL, "conv3_halo: the debug variants are bf16, BM = 256 only");
-          L.family = IG_FAM_SPEC; L.pipe = 1; L.dbg = L.algo == IG_ALGO_DBG_SPEC_NO_DMA ? 1 : 2; L.depth = L.depth == 2 ? 2 : 4;
-        } else {
-          if (dtype != K22_BF16 || bm != 256) return k22_set_error(K22_EINVAL, "conv3_halo: debug variants are bf16, BM = 256 only");
-          L.family = IG_FAM_HALO; L.pipe = L.algo == IG_ALGO_DBG_NO_DMA ? 3 : 4;
-        }
-#else
-        return k22_set_error(K22_EINVAL, "conv3_halo: measurement-only variants need a -DK22_DEBUG_VARIANTS build");
-#endif
       } else {
         L.family = IG_FAM_HALO;
         L.pipe = L.algo == IG_ALGO_HALO_PIPE ? 1 : (L.algo == IG_ALGO_HALO_ASM ? 2 : 0);

@@ -14,7 +14,6 @@ struct SkinnyParams {
   float* partial;
   int M, N, Npad, K, MA;
   int splitk, epi, act, ldo;
-  unsigned long long* trace;   // K22_SKINNY_DEBUG builds only: 8 stamps per workgroup (s_memrealtime, 100 MHz)
 };
 
 struct FinishLnParams {

@@ -38,13 +38,11 @@ __device__ __forceinline__ int64_t afrag_off(int m, int k, int MA) {
   return ((((int64_t)(k >> 6) * MA + (m >> 5)) * 4 + ((k >> 4) & 3)) * 64 + (m & 31) + 32 * ((k >> 3) & 1)) * 8 + (k & 7);
 }
 
-template <typename T, int MT, int NB, int D, int DBG = 0>
+template <typename T, int MT, int NB, int D>
 __global__ __launch_bounds__(256, 1) void skinny_kernel(const SkinnyParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, h = lane >> 5;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  unsigned long long ts[8];
-  if (DBG & 32) { for (int i = 0; i < 8; ++i) ts[i] = 0; ts[0] = __builtin_amdgcn_s_memrealtime(); }
   const int nchunks = p.K >> 6;
   const int mtiles = (p.MA + MT - 1) / MT;
   const int ntiles = p.Npad / (32 * NB);
@@ -89,15 +87,14 @@ __global__ __launch_bounds__(256, 1) void skinny_kernel(const SkinnyParams p) {
     const T* apc = ap + (int64_t)c * a_cstride;
     const T* wpc = wp + (int64_t)c * 2048;
 #pragma unroll
-    for (int j = 0; j < NB; ++j) if (!(DBG & 4) || c == c0) b[j].v = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(wpc + j * w_jstride));
+    for (int j = 0; j < NB; ++j) b[j].v = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(wpc + j * w_jstride));
 #pragma unroll
-    for (int i = 0; i < MT; ++i) if (!(DBG & 2) || c == c0) a[i].v = *reinterpret_cast<const u32x4_t*>(apc + aoff[i]);
+    for (int i = 0; i < MT; ++i) a[i].v = *reinterpret_cast<const u32x4_t*>(apc + aoff[i]);
   };
   if (c0 < c1) {
 #pragma unroll
     for (int d = 0; d < D; ++d) load(c0 + d, ar[d], wr[d]);
     int c = c0;
-    if (DBG & 32) { asm volatile("s_waitcnt vmcnt(%0)" ::"n"((D - 1) * (MT + NB)) : "memory"); ts[1] = __builtin_amdgcn_s_memrealtime(); }
     // steady state: no branch inside, and the refill of a ring slot stays BEHIND the MFMAs that read it (sched_barrier): hoisted above
     // them the compiler renames the slot and ends every pass over the ring with a full vmcnt(0) drain
     for (; c + D <= c1; c += D) {
@@ -106,10 +103,7 @@ __global__ __launch_bounds__(256, 1) void skinny_kernel(const SkinnyParams p) {
 #pragma unroll
         for (int i = 0; i < MT; ++i)
 #pragma unroll
-          for (int j = 0; j < NB; ++j) {
-            if (DBG & 1) acc[i][j][0] += __builtin_bit_cast(float, wr[u][j].v[0] ^ ar[u][i].v[0]);   // measurement only: no MFMA
-            else mma_atom(acc[i][j], wr[u][j], ar[u][i]);   // C^T: rows = weight rows n, columns = token rows m
-          }
+          for (int j = 0; j < NB; ++j) mma_atom(acc[i][j], wr[u][j], ar[u][i]);   // C^T: rows = weight rows n, columns = token rows m
         __builtin_amdgcn_sched_barrier(0);
         load(c + u + D, ar[u], wr[u]);
         __builtin_amdgcn_sched_barrier(0);
@@ -127,7 +121,6 @@ __global__ __launch_bounds__(256, 1) void skinny_kernel(const SkinnyParams p) {
     }
   }
 
-  if (DBG & 32) { asm volatile("s_nop 0" ::: "memory"); ts[2] = __builtin_amdgcn_s_memrealtime(); }
   // ---- fold the four k-steps in a fixed order: wave q ends up with accumulator registers 4q .. 4q+3 of every atom = weight rows
   // 8q + 4h + {0..3} of token column l31 -------------------------------------------------------------------------------------------
   constexpr int NAT = MT * NB;
@@ -150,7 +143,6 @@ __global__ __launch_bounds__(256, 1) void skinny_kernel(const SkinnyParams p) {
       }
     }
     __syncthreads();
-    if ((DBG & 32) && g0 == 0) ts[3] = __builtin_amdgcn_s_memrealtime();
 #pragma unroll
     for (int ga = 0; ga < GA; ++ga) {
       const int at = g0 + ga;
@@ -186,12 +178,6 @@ __global__ __launch_bounds__(256, 1) void skinny_kernel(const SkinnyParams p) {
       else *reinterpret_cast<uint2*>(out + afrag_off(m, n, p.MA)) = o;   // SK_EPI_AFRAG: the consumer's K index is this launch's n
     }
     if (g0 + GA < NAT) __syncthreads();   // the scratch is rewritten by the next pass
-  }
-  if ((DBG & 32) && p.trace != nullptr) {
-    ts[4] = __builtin_amdgcn_s_memrealtime();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    ts[5] = __builtin_amdgcn_s_memrealtime();
-    if (tid == 0) { unsigned xcc; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc)); ts[6] = xcc; for (int i = 0; i < 8; ++i) p.trace[(int64_t)blockIdx.x * 8 + i] = ts[i]; }
   }
 }
 
@@ -283,35 +269,20 @@ __global__ __launch_bounds__(256) void afrag_pack_kernel(const T* __restrict__ A
   }
 }
 
-template <typename T, int MT, int NB, int D, int DBG = 0>
+template <typename T, int MT, int NB, int D>
 int launch_skinny_cfg(const SkinnyParams& p, hipStream_t st) {
   static LdsAttrGuard guard;
   constexpr int NATL = MT * NB;
   constexpr int lds = (NATL < 8 ? NATL : (NATL % 6 == 0 ? 6 : (NATL % 8 == 0 ? 8 : NATL))) * 16 * 1024;
-  if (int rc = k22_ensure_lds_attr(guard, reinterpret_cast<const void*>(&skinny_kernel<T, MT, NB, D, DBG>), lds, __FILE__, __LINE__)) return rc;
+  if (int rc = k22_ensure_lds_attr(guard, reinterpret_cast<const void*>(&skinny_kernel<T, MT, NB, D>), lds, __FILE__, __LINE__)) return rc;
   const int mtiles = (p.MA + MT - 1) / MT, ntiles = p.Npad / (32 * NB);
-  hipLaunchKernelGGL((skinny_kernel<T, MT, NB, D, DBG>), dim3(mtiles * ntiles * p.splitk), dim3(256), lds, st, p);
+  hipLaunchKernelGGL((skinny_kernel<T, MT, NB, D>), dim3(mtiles * ntiles * p.splitk), dim3(256), lds, st, p);
   K22_CHECK_LAUNCH();
   return K22_OK;
 }
 
 template <typename T>
 int launch_skinny_typed(const SkinnyParams& p, int mt, int nb, hipStream_t st) {
-#ifdef K22_SKINNY_DEBUG   // measurement-only variants (wrong results): K22_SK_DBG bits 1 = no MFMA, 2 = A loaded once, 4 = W loaded once; 8: ring depth 12; 16: depth 4
-  if (const char* e = getenv("K22_SK_DBG")) {
-    const int d = atoi(e);
-    if (mt == 3 && nb == 2) {
-      if (d == 1) return launch_skinny_cfg<T, 3, 2, 8, 1>(p, st);
-      if (d == 2) return launch_skinny_cfg<T, 3, 2, 8, 2>(p, st);
-      if (d == 4) return launch_skinny_cfg<T, 3, 2, 8, 4>(p, st);
-      if (d == 6) return launch_skinny_cfg<T, 3, 2, 8, 6>(p, st);
-      if (d == 7) return launch_skinny_cfg<T, 3, 2, 8, 7>(p, st);
-      if (d == 8) return launch_skinny_cfg<T, 3, 2, 12, 0>(p, st);
-      if (d == 16) return launch_skinny_cfg<T, 3, 2, 4, 0>(p, st);
-      if (d == 32) return launch_skinny_cfg<T, 3, 2, 8, 32>(p, st);
-    }
-  }
-#endif
   if (mt == 6 && nb == 1) return launch_skinny_cfg<T, 6, 1, 6>(p, st);
   if (mt == 3 && nb == 2) return launch_skinny_cfg<T, 3, 2, 8>(p, st);
   if (mt == 3 && nb == 4) return launch_skinny_cfg<T, 3, 4, 8>(p, st);

@@ -23,7 +23,6 @@
 //     emits the GroupNorm partial sums - the same epilogue arithmetic, in the same order, as every other split-K launch.
 // bf16 / fp16 storage only (the K split maps the four 16-wide MFMA k-steps of a 128-byte row to the four waves).
 #include "kernels.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -44,16 +43,14 @@ template <int MB, int TAPS> struct StreamCfg {
 //   plane row r, channel c  =  c < K0 ? a0[r * ld0 + c] : a1[r * ld1 + c - K0]      (r < PR; rows are clamped to PR - 1)
 //   item (slab s, tap t): lane's A fragment of m-block i = plane row prow[i] + (t / 3) * W2 + t % 3, channels 64 s + 16 w + 8 h ..
 //                         lane's B fragment of n-block j = wl{j}[t * wtap + 64 s .. +8]
-template <typename T, int MB, int NB, int TAPS, int DBG, bool FRAG>
+template <typename T, int MB, int NB, int TAPS, bool FRAG>
 __device__ __forceinline__ void stream_phase(f32x16_t (&acc)[MB][NB], char* smem, const int buf_bytes,
                                              const T* __restrict__ a0, const int64_t ld0, const int K0,
                                              const T* __restrict__ a1, const int64_t ld1, const int PR,
                                              const int (&prow)[MB], const int W2,
                                              const T* __restrict__ wl0, const T* __restrict__ wl1, const int64_t wtap,
-                                             const int s0, const int s1, const int w, const int tid,
-                                             unsigned long long* ts = nullptr) {
+                                             const int s0, const int s1, const int w, const int tid) {
   using C = StreamCfg<MB, TAPS>;
-  int nts = 2;
   const int nslab = s1 - s0;
   if (nslab <= 0) return;   // uniform over the workgroup
   const int nstage = (nslab + C::G - 1) / C::G;
@@ -113,7 +110,6 @@ __device__ __forceinline__ void stream_phase(f32x16_t (&acc)[MB][NB], char* smem
   for (int d = 0; d < C::D; ++d) load_b(d, breg[d]);
   fill_store(0);
   __syncthreads();
-  if (DBG & 8) ts[1] = __builtin_readcyclecounter();   // first slab in the LDS
   int cur = 0;
   for (int st = 0; st < nstage; st += C::SPI) {
 #pragma unroll
@@ -129,10 +125,7 @@ __device__ __forceinline__ void stream_phase(f32x16_t (&acc)[MB][NB], char* smem
           const int shift = TAPS == 9 ? (tap / 3) * W2 + (tap % 3) : 0;
           const char* sub = abuf + g * sub_bytes;
 #pragma unroll
-          for (int i = 0; i < MB; ++i) {
-            if ((DBG & 4) && (k | stage | i) != 0) f[i] = f[0];   // measurement only: one LDS read per phase
-            else ld_frag(f[i], sub, prow[i] + shift, w, h);
-          }
+          for (int i = 0; i < MB; ++i) ld_frag(f[i], sub, prow[i] + shift, w, h);
         };
         read_a(0, a[0]);
         __builtin_amdgcn_sched_barrier(0);     // the first item's reads issue back to back (their own region), not one per MFMA pair
@@ -143,13 +136,10 @@ __device__ __forceinline__ void stream_phase(f32x16_t (&acc)[MB][NB], char* smem
 #pragma unroll
           for (int i = 0; i < MB; ++i)
 #pragma unroll
-            for (int j = 0; j < NB; ++j) {
-              if (DBG & 1) acc[i][j][0] += __builtin_bit_cast(float, breg[d][j].v[0] ^ a[k & 1][i].v[0]);   // measurement only: no MFMA
-              else mma_atom(acc[i][j], breg[d][j], a[k & 1][i]);   // C^T: rows = weight rows (channels), columns = pixels
-            }
+            for (int j = 0; j < NB; ++j) mma_atom(acc[i][j], breg[d][j], a[k & 1][i]);   // C^T: rows = weight rows (channels), columns = pixels
           // one fragment read of the NEXT item behind every NB MFMAs of this one (0x008 = MFMA, 0x100 = DS read): left to itself the
           // scheduler keeps two fragment registers and puts a full LDS round trip in front of every pair of MFMAs
-          if (k + 1 < C::SITEMS && (DBG & 7) == 0) {
+          if (k + 1 < C::SITEMS) {
 #pragma unroll
             for (int i = 0; i < MB; ++i) {
               __builtin_amdgcn_sched_group_barrier(0x008, NB, 0);
@@ -159,35 +149,27 @@ __device__ __forceinline__ void stream_phase(f32x16_t (&acc)[MB][NB], char* smem
           // TAPS == 9 (one stage = the whole ring): slot k is refilled as soon as item k's MFMAs are issued, so the next stage's first
           // fragments have a whole stage of MFMA time to arrive; refilled in bulk after the stage they were an exposed HBM round trip
           // per slab (stage < nstage always holds here: SPI == 1)
-          if (C::SPI == 1 && !(DBG & 2)) load_b(stage * C::SITEMS + k + C::D, breg[d]);
+          if (C::SPI == 1) load_b(stage * C::SITEMS + k + C::D, breg[d]);
           __builtin_amdgcn_sched_barrier(0);   // one item = one scheduling region: nothing of item k+1's MFMAs moves up into this one
         }
       }
       if (C::SPI != 1) {
 #pragma unroll
         for (int k = 0; k < C::SITEMS; ++k)
-          if (!(DBG & 2)) load_b(stage * C::SITEMS + k + C::D, breg[u * C::SITEMS + k]);   // DBG 2 (measurement only): the ring is never refilled
+          load_b(stage * C::SITEMS + k + C::D, breg[u * C::SITEMS + k]);
       }
       fill_store(cur ^ 1);
       __syncthreads();
-      if ((DBG & 8) && nts < 11) ts[nts++] = __builtin_readcyclecounter();
       cur ^= 1;
     }
   }
 }
 
-template <typename T, int MB, int NB, int DBG, bool FRAG>
+template <typename T, int MB, int NB, bool FRAG>
 __global__ __launch_bounds__(256) void stream_kernel(const IgemmParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, h = lane >> 5;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  unsigned long long ts[16];
-  if (DBG & 8) {
-#pragma unroll
-    for (int i = 0; i < 16; ++i) ts[i] = 0;
-    ts[0] = __builtin_readcyclecounter();
-    ts[11] = __builtin_amdgcn_s_memrealtime();   // 100 MHz wall clock: places the workgroups of a launch on one time axis
-  }
 
   constexpr int NT = 32 * NB;
   const int n_tiles = p.Npad / NT;
@@ -237,7 +219,7 @@ __global__ __launch_bounds__(256) void stream_kernel(const IgemmParams p) {
         const int y = px / p.W, x = px - y * p.W;
         prow[i] = y * W2 + x;
       }
-      stream_phase<T, MB, NB, 9, DBG, FRAG>(acc, smem, p.st_buf, plane, p.Kc, p.Kc, plane, p.Kc, PR, prow, W2, wl0, wl1, p.Kc, s0, s1, w, tid, ts);
+      stream_phase<T, MB, NB, 9, FRAG>(acc, smem, p.st_buf, plane, p.Kc, p.Kc, plane, p.Kc, PR, prow, W2, wl0, wl1, p.Kc, s0, s1, w, tid);
     } else {
 #pragma unroll
       for (int i = 0; i < MB; ++i) {
@@ -246,7 +228,7 @@ __global__ __launch_bounds__(256) void stream_kernel(const IgemmParams p) {
       }
       const T* a0 = reinterpret_cast<const T*>(p.A0) + (int64_t)m0 * p.lda0;
       const T* a1 = p.A1 ? reinterpret_cast<const T*>(p.A1) + (int64_t)m0 * p.lda1 : a0;
-      stream_phase<T, MB, NB, 1, DBG, FRAG>(acc, smem, p.st_buf, a0, p.lda0, p.K0, a1, p.lda1, rows, prow, 0, wl0, wl1, 0, s0, s1, w, tid);
+      stream_phase<T, MB, NB, 1, FRAG>(acc, smem, p.st_buf, a0, p.lda0, p.K0, a1, p.lda1, rows, prow, 0, wl0, wl1, 0, s0, s1, w, tid);
     }
   }
   // ---- fused 1x1 skip_connection: a second K phase over the unpadded rows of [S0 | S1] --------------------------------
@@ -270,13 +252,12 @@ __global__ __launch_bounds__(256) void stream_kernel(const IgemmParams p) {
     }
     const T* a0 = reinterpret_cast<const T*>(p.S0) + (int64_t)m0 * p.SK0;
     const T* a1 = p.S1 ? reinterpret_cast<const T*>(p.S1) + (int64_t)m0 * p.SK1 : a0;
-    stream_phase<T, MB, NB, 1, DBG, FRAG>(acc, smem, p.st_buf, a0, p.SK0, p.SK0, a1, p.SK1, rows, prow, 0, wl0, wl1, 0, s0, s1, w, tid);
+    stream_phase<T, MB, NB, 1, FRAG>(acc, smem, p.st_buf, a0, p.SK0, p.SK0, a1, p.SK1, rows, prow, 0, wl0, wl1, 0, s0, s1, w, tid);
   }
 
   // ---- fold the four K quarters (fixed order: wave 0 + 1 + 2 + 3) and write the workgroup's fp32 partial tile ------------
   // accumulator registers 4q .. 4q+3 of a 32x32 block = channels 8q + 4h + {0..3} of pixel l31: wave q keeps those, the
   // other three park theirs in the LDS (one float4 per lane: conflict-free), one n-block per pass.
-  if (DBG & 8) ts[12] = __builtin_readcyclecounter();
   f32x4_t* scr = reinterpret_cast<f32x4_t*>(smem);
   float* part = p.partial + (int64_t)bz * p.M * p.N;
 #pragma unroll
@@ -318,18 +299,6 @@ __global__ __launch_bounds__(256) void stream_kernel(const IgemmParams p) {
       }
     }
     if (j + 1 < NB) __syncthreads();
-  }
-  if ((DBG & 8) && p.st_trace != nullptr) {
-    __builtin_amdgcn_s_waitcnt(0);   // partial stores issued and (vmcnt) acknowledged
-    ts[13] = __builtin_readcyclecounter();
-    if (tid == 0) {
-      unsigned long long* o = p.st_trace + (int64_t)blockIdx.x * 16;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) o[i] = ts[i];
-      unsigned xcc;
-      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-      o[14] = xcc; o[15] = __builtin_amdgcn_s_memrealtime();
-    }
   }
 }
 
@@ -388,10 +357,10 @@ size_t stream_lds_bytes(const IgemmParams& p, int mb) {
   return stream_geom(p, mb, &g) ? (size_t)g.smem : 0;
 }
 
-template <typename T, int MB, int NB, int DBG, bool FRAG>
+template <typename T, int MB, int NB, bool FRAG>
 static int run_stream(const IgemmParams& q, const IgemmLaunch& L, hipStream_t stream) {
   static LdsAttrGuard guard;
-  const int rc = launch_lds_kernel(stream_kernel<T, MB, NB, DBG, FRAG>, guard, L.grid, L.block, L.lds, 160 * 1024, stream, q);
+  const int rc = launch_lds_kernel(stream_kernel<T, MB, NB, FRAG>, guard, L.grid, L.block, L.lds, 160 * 1024, stream, q);
   if (rc == K22_OK) g_stream_launches.fetch_add(1, std::memory_order_relaxed);
   return rc;
 }
@@ -409,25 +378,8 @@ int launch_stream(const IgemmParams& p, int dtype, const IgemmLaunch& L, hipStre
   return k22_with_dtype(dtype, [&](auto tag) {
     using T = typename decltype(tag)::type;
     if constexpr (sizeof(T) == 2) {
-#ifdef K22_STREAM_DEBUG
-      // measurement-only variants: K22_STREAM_DBG bits 1 = no MFMA, 2 = weight ring never refilled, 4 = one LDS read per phase (all three: wrong
-      // results), 8 = cycle stamps of every workgroup into p.st_trace (results intact)
-      if (const char* e = getenv("K22_STREAM_DBG")) {
-        const int dbg = atoi(e);
-        if (frag && mb == 5) {
-          if (dbg == 1) return run_stream<T, 5, 2, 1, true>(q, L, stream);
-          if (dbg == 2) return run_stream<T, 5, 2, 2, true>(q, L, stream);
-          if (dbg == 4) return run_stream<T, 5, 2, 4, true>(q, L, stream);
-          if (dbg == 8) return run_stream<T, 5, 2, 8, true>(q, L, stream);
-          if (dbg == 9) return run_stream<T, 5, 2, 9, true>(q, L, stream);
-          if (dbg == 10) return run_stream<T, 5, 2, 10, true>(q, L, stream);
-          if (dbg == 12) return run_stream<T, 5, 2, 12, true>(q, L, stream);
-        }
-        if (frag && mb == 9 && dbg == 8) return run_stream<T, 9, 1, 8, true>(q, L, stream);
-      }
-#endif
-      if (mb == 5) return frag ? run_stream<T, 5, 2, 0, true>(q, L, stream) : run_stream<T, 5, 2, 0, false>(q, L, stream);
-      return frag ? run_stream<T, 9, 1, 0, true>(q, L, stream) : run_stream<T, 9, 1, 0, false>(q, L, stream);
+      if (mb == 5) return frag ? run_stream<T, 5, 2, true>(q, L, stream) : run_stream<T, 5, 2, false>(q, L, stream);
+      return frag ? run_stream<T, 9, 1, true>(q, L, stream) : run_stream<T, 9, 1, false>(q, L, stream);
     } else {
       return k22_set_error(K22_EINVAL, "stream: bad dtype");
     }

@@ -15,8 +15,6 @@ TESTS = os.path.join(ROOT, "tests")
 DEVELOPER_ONLY = {
     "K22_X2_OWN_LINES": "tools/make_tile_table.py --x2-only: no x3 fall-back, so that the asymmetric split's own table lines get measured",
     "K22_PRIOR_QKV_SPLIT": "split-K of the skinny c_qkv, measurement knob (profiles/r06_skinny.txt: 1 is the measured best and the default)",
-    "K22_SK_DBG": "skinny.hip: prints the launch geometry",
-    "K22_STREAM_DBG": "measurement-only variants of the streaming kernel, compiled only with EXTRA=-DK22_STREAM_DEBUG (wrong results by design)",
     "K22_SKINNY_CFG": 'skinny.hip: "mt,nb" measurement override of the fixed tile rule',
     "K22_DBG_LDS_PAD": "tools/lds_victim_probe.py: LDS padding of the two-stream probe",
     "K22_LIB_PATH": "_lib.py: another build of the library (A/B of two builds)",

@@ -69,6 +69,41 @@ def test_acceptance_entry_tells_a_foreign_configuration_from_a_generated_one():
     assert _lib.lib().k22_igemm_cfg_accepted(C.byref(bad)) == _lib.lib().k22_igemm_cfg_accepted(None) == -1
 
 
+@pytest.mark.parametrize("algo", [8, 9, 13, 14])
+def test_reserved_algorithm_numbers_name_no_kernel(algo, tmp_path):
+    """8, 9, 13 and 14 once named measurement-only kernels; the numbers stay reserved (IgemmAlgo, kernels.h).  For a 3x3 problem the table
+    knows - bf16, 768 -> 768 at 96x96, batch 4 - none of them is a configuration this build generates, the launch entry refuses them on the
+    host, and as a "conv_algo" option they mean "auto": the problem's table line and the fixed choice are what they were"""
+    import ctypes as C
+    L = _lib.lib()
+    t = next(t for t in hp.read_tile_table() if (t.dtype, t.taps, t.M, t.N, t.Kc, t.K0, t.H, t.W) == (BF16, 9, 4 * 96 * 96, 768, 768, 768, 96, 96))
+    assert hp.tile_accepted(t) == 1
+    assert hp.tile_accepted(t._replace(algo=algo, bm=256)) == 0
+    pr, ops = hp.tile_problem(t._replace(algo=algo, bm=256)), _lib.K22IgemmOperands()
+    assert L.k22_igemm_cfg(C.byref(pr), C.byref(ops), None, None) == -1 and b"does not generate" in L.k22_last_error()
+
+    def state(name):
+        path = str(tmp_path / name)
+        assert L.k22_tile_table_save(path.encode()) > 0
+        key = [str(int(v)) for v in (t.dtype, t.taps, t.M, t.N, t.Kc, t.K0, t.H, t.W)]
+        lines = [ln for ln in hp.tile_table_text_lines(path) if ln.split()[:8] == key]
+        fixed = _lib.K22IgemmCfg()
+        auto = hp.tile_problem(t._replace(algo=0, bm=0, bn=0, splitk=0, stages=0))
+        assert L.k22_igemm_candidates(C.byref(auto), None, 0, None, C.byref(fixed)) > 0
+        return lines, (fixed.algo, fixed.bm, fixed.bn, fixed.splitk, fixed.stages)
+
+    before = state("before.txt")
+    assert len(before[0]) >= 1 and before[1][0] != 0
+    try:
+        assert L.k22_set_option(b"conv_algo", algo) == 0
+        during = state("during.txt")                    # the option reads as "auto": the fixed choice does not move
+        assert L.k22_set_option(b"conv_algo", 0) == 0
+        assert during == before and state("after.txt") == before
+        assert hp.tile_accepted(t) == 1
+    finally:
+        L.k22_set_option(b"conv_algo", 0)
+
+
 def test_launch_entry_refuses_what_the_acceptance_entry_rejects():
     """k22_igemm_cfg checks the configuration and the operands on the host before it touches the device: a configuration this build does
     not generate is an error, never a quiet run of another kernel"""

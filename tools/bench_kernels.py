@@ -83,9 +83,9 @@ def main():
     for c in a.configs.split(","):
         if c == "auto":
             cfgs.append((0, 0, 0, 0, False))
-        elif c[0] in "hgklpaxystuvmf":   # h256 / h128x2 : halo kernel (g = 64-byte-row variant), BM, split-K; m160x5 = streaming kernel (f160x5: fragment-major weights)
+        elif c[0] in "hgklpastmf":   # h256 / h128x2 : halo kernel (g = 64-byte-row variant), BM, split-K; m160x5 = streaming kernel (f160x5: fragment-major weights)
             parts = c[1:].split("x")
-            cfgs.append((int(parts[0]), 0, int(parts[1]) if len(parts) > 1 else 0, {"h": 2, "g": 3, "k": 4, "l": 5, "p": 6, "a": 7, "x": 8, "y": 9, "s": 11, "t": 12, "u": 13, "v": 14, "m": 20, "f": 20}[c[0]], c[0] == "f"))
+            cfgs.append((int(parts[0]), 0, int(parts[1]) if len(parts) > 1 else 0, {"h": 2, "g": 3, "k": 4, "l": 5, "p": 6, "a": 7, "s": 11, "t": 12, "m": 20, "f": 20}[c[0]], c[0] == "f"))
         else:                            # 128x64x8 : generic implicit GEMM
             parts = c.split("x")
             cfgs.append((int(parts[0]), int(parts[1]), int(parts[2]) if len(parts) > 2 else 1, 1, False))

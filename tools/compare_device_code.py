@@ -8,10 +8,14 @@ code bytes or descriptor bytes differ; only names and bytes are compared (which 
 of a descriptor (kernel_code_entry_byte_offset: the distance from the descriptor to the code inside its file) say where the
 linker put the two, not what the kernel is, and move whenever a neighbour in the file does: they are left out.
 
-usage: compare_device_code.py DIR_A DIR_B [--readelf /opt/rocm/llvm/bin/llvm-readelf]
+A change that removes a template parameter changes the mangled names: --rename-a 'REGEX=REPLACEMENT' (repeatable; re.sub on every kernel
+name of DIR_A, in the order given) states the pairing rule on the command line.
+
+usage: compare_device_code.py DIR_A DIR_B [--readelf /opt/rocm/llvm/bin/llvm-readelf] [--rename-a REGEX=REPL ...] [--all]
 """
 import argparse
 import pathlib
+import re
 import subprocess
 import sys
 
@@ -48,8 +52,21 @@ def main():
     ap.add_argument("dir_a")
     ap.add_argument("dir_b")
     ap.add_argument("--readelf", default="/opt/rocm/llvm/bin/llvm-readelf")
+    ap.add_argument("--rename-a", action="append", default=[], metavar="REGEX=REPL")
+    ap.add_argument("--all", action="store_true", help="print every name of a list, not the first 20")
     a = ap.parse_args()
     ka, kb = kernels(a.dir_a, a.readelf), kernels(a.dir_b, a.readelf)
+    renamed = {}
+    for name, blobs in ka.items():
+        new = name
+        for rule in a.rename_a:
+            pat, _, repl = rule.partition("=")
+            new = re.sub(pat, repl, new)
+        assert new not in renamed, "two kernels of A renamed to " + new
+        renamed[new] = blobs
+    if a.rename_a:
+        print(f"renamed in A: {sum(1 for n in renamed if n not in ka)}")
+    ka = renamed
     only_a, only_b = sorted(set(ka) - set(kb)), sorted(set(kb) - set(ka))
     code = [n for n in sorted(set(ka) & set(kb)) if ka[n][0] != kb[n][0]]
     desc = [n for n in sorted(set(ka) & set(kb)) if ka[n][1] != kb[n][1]]
@@ -57,7 +74,7 @@ def main():
     print(f"code bytes compared: {sum(len(v[0]) for v in ka.values())} / {sum(len(v[0]) for v in kb.values())}")
     for title, names in (("only in A", only_a), ("only in B", only_b), ("code differs", code), ("descriptor differs", desc)):
         print(f"{title}: {len(names)}")
-        for n in names[:20]:
+        for n in names if a.all else names[:20]:
             print("   ", n)
     return 1 if (only_a or only_b or code or desc) else 0
 

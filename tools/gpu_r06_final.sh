@@ -47,5 +47,4 @@ room 150 && { bash tools/gpu_pmc_mfma.sh ${TAG}_mfma > gpurun_out/pmc_${TAG}_mfm
 room 60 && run_cfg "--head 2.2"
 room 60 && run_cfg "--controlnet --bs 2"
 room 120 && { bash tools/gpu_pmc_mfma.sh ${TAG}_mfma_f16x2 "--dtype f16x2" > gpurun_out/pmc_${TAG}_mfma_f16x2.log 2>&1; head -14 gpurun_out/pmc_${TAG}_mfma_f16x2_summary.txt | cut -c1-170; }
-room 30 && { timeout 120 tools/micro/attn_probe > gpurun_out/attn_probe_$TAG.txt 2>&1; grep -E "workgroups|shipped|pipe_kernel|differ" gpurun_out/attn_probe_$TAG.txt | head -16; }
 echo "[done t=$SECONDS s]"
