@@ -9,6 +9,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 typedef unsigned short bf16_t;  // bf16 storage type
 typedef _Float16 f16_t;         // fp16 storage type (IEEE binary16)
@@ -268,6 +269,41 @@ template <bool RAW, typename T, typename F> __device__ __forceinline__ void ld_f
     ld_frag(f, tile, r, ks, h);
   }
 }
+// ld_frag_at / ld_frag_at_a are THE SAME LOADER as ld_frag / ld_frag_a in another address spelling: ld_frag names the row by tile + row
+// index r, ld_frag_at by row pointer rowp = tile + r * 128 and swizzle key sw = (r >> 1) & 7, which the kernels on the 8-wave frame
+// compute once per tap for all k-steps.  Both stay: with ld_frag written as ld_frag_at(f, tile + r * 128, (r >> 1) & 7, ks, h) hipcc
+// folds the address arithmetic differently and 82 kernels change code (profiles/shared_helpers_device_code.txt).
+__device__ __forceinline__ void ld_frag_at(Frag<bf16_t>& f, const char* rowp, int sw, int ks, int h) {
+  f.v = *reinterpret_cast<const u32x4_t*>(rowp + (((2 * ks + h) ^ sw) << 4));
+}
+__device__ __forceinline__ void ld_frag_at(Frag<f16_t>& f, const char* rowp, int sw, int ks, int h) {
+  f.v = *reinterpret_cast<const u32x4_t*>(rowp + (((2 * ks + h) ^ sw) << 4));
+}
+__device__ __forceinline__ void ld_frag_at(Frag<float>& f, const char* rowp, int sw, int ks, int h) {
+  const float4 a = *reinterpret_cast<const float4*>(rowp + (((4 * ks + 2 * h) ^ sw) << 4));
+  const float4 b = *reinterpret_cast<const float4*>(rowp + (((4 * ks + 2 * h + 1) ^ sw) << 4));
+  f.v[0] = a.x; f.v[1] = a.y; f.v[2] = a.z; f.v[3] = a.w;
+  f.v[4] = b.x; f.v[5] = b.y; f.v[6] = b.z; f.v[7] = b.w;
+}
+__device__ __forceinline__ void ld_frag_at(Frag<x3_t>& f, const char* rowp, int sw, int ks, int h) {
+  x3_frag_from_chunks(f, *reinterpret_cast<const u32x4_t*>(rowp + (((4 * ks + 2 * h) ^ sw) << 4)),
+                      *reinterpret_cast<const u32x4_t*>(rowp + (((4 * ks + 2 * h + 1) ^ sw) << 4)));
+}
+__device__ __forceinline__ void ld_frag_at(Frag<x2_t>& f, const char* rowp, int sw, int ks, int h) {
+  x3_frag_from_chunks(f, *reinterpret_cast<const u32x4_t*>(rowp + (((4 * ks + 2 * h) ^ sw) << 4)),
+                      *reinterpret_cast<const u32x4_t*>(rowp + (((4 * ks + 2 * h + 1) ^ sw) << 4)));
+}
+__device__ __forceinline__ void ld_frag_at(FragHi& f, const char* rowp, int sw, int ks, int h) {
+  f.hi = *reinterpret_cast<const u32x4_t*>(rowp + (((4 * ks + 2 * h) ^ sw) << 4));
+}
+template <bool RAW, typename T, typename F> __device__ __forceinline__ void ld_frag_at_a(F& f, const char* rowp, int sw, int ks, int h) {
+  if constexpr (RAW && is_x3<T>::value) {
+    x3_frag_from_f32(f, *reinterpret_cast<const float4*>(rowp + (((4 * ks + 2 * h) ^ sw) << 4)),
+                     *reinterpret_cast<const float4*>(rowp + (((4 * ks + 2 * h + 1) ^ sw) << 4)));
+  } else {
+    ld_frag_at(f, rowp, sw, ks, h);
+  }
+}
 
 // acc(32x32, C layout: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)) += A(32x16) * B(16x32)
 // A fragment: row = lane&31; B fragment: col = lane&31; both hold K = 8*(lane>>5) + j.
@@ -310,6 +346,49 @@ __device__ __forceinline__ void raw_barrier() {
   asm volatile("" ::: "memory");
 }
 
+// counted wait for the LDS-DMA / global loads of this wave: at most N stay in flight
+template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+
+// ---- the block map and K split the conv / GEMM kernels share ---------------------------------------------------------------------
+// Logical block index of hardware block `bid` (XCD = bid % 8): XCD x gets the contiguous range
+// [start_x, start_x + count_x) of logical indices, in dispatch order.  Bijective for any nblocks.
+__device__ __forceinline__ int xcd_remap(int bid, int nblocks) {
+  const int q = nblocks >> 3, r = nblocks & 7, x = bid & 7;
+  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
+}
+constexpr int TILE_GM = 8;        // m-tiles per group of the block map
+// block -> (k-split bz, m-tile bx, n-tile by) of a (gx m-tiles) x (gy n-tiles) x splitk grid: XCD remap (on request), k-split outermost,
+// then groups of TILE_GM m-tiles that walk the n-tiles together
+__device__ __forceinline__ void tile_block_map(int remap, int gx, int gy, int& bz, int& bx, int& by) {
+  constexpr int GM = TILE_GM;
+  int L = remap ? xcd_remap(blockIdx.x, gridDim.x) : (int)blockIdx.x;
+  const int per_z = gx * gy;
+  bz = L / per_z;
+  L -= bz * per_z;
+  const int grp = L / (GM * gy);
+  const int first_m = grp * GM;
+  const int gsz = gx - first_m < GM ? gx - first_m : GM;
+  const int lin = L - grp * GM * gy;
+  bx = first_m + lin % gsz;
+  by = lin / gsz;
+}
+// K tiles (slabs) [s0, s1) of k-split bz out of n
+__device__ __forceinline__ void splitk_range(int splitk, int n, int bz, int& s0, int& s1) {
+  s0 = 0;
+  s1 = n;
+  if (splitk > 1) {
+    const int per = (n + splitk - 1) / splitk;
+    s0 = bz * per;
+    s1 = s0 + per < n ? s0 + per : n;
+  }
+}
+// ACC[MI_][NI_] = 0.  A macro: as a function template over a reference to the array it moved code in igemm_kernel<64 x 64>, skinny_kernel and
+// stream_kernel (profiles/shared_helpers_device_code.txt)
+#define K22_ZERO_ACC(ACC, MI_, NI_)                                                                        \
+  _Pragma("unroll") for (int mi_ = 0; mi_ < (MI_); ++mi_)                                                  \
+    _Pragma("unroll") for (int ni_ = 0; ni_ < (NI_); ++ni_)                                                \
+      _Pragma("unroll") for (int r_ = 0; r_ < 16; ++r_) ACC[mi_][ni_][r_] = 0.f;
+
 // ---- 64-lane reductions --------------------------------------------------------------
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -321,6 +400,41 @@ __device__ __forceinline__ float wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
+
+// ---- row vectors: W = 4 or 8 consecutive channels of one row, as floats in registers -------------------------------------------
+// store_row rounds to the stored type T (the split types store fp32); load_row_f32 widens; stored<T>(v) = v as it will be read back
+// (the GroupNorm statistics are those of the stored tensor).
+template <typename T, int W> __device__ __forceinline__ void store_row(T* dst, const float* v) {
+  static_assert(W == 4 || W == 8, "row vectors are 4 or 8 wide");
+  if constexpr (is_x3<T>::value) {
+    store_row<float, W>(reinterpret_cast<float*>(dst), v);
+  } else if constexpr (sizeof(T) == 4) {
+#pragma unroll
+    for (int i = 0; i < W; i += 4) *reinterpret_cast<float4*>(dst + i) = make_float4(v[i], v[i + 1], v[i + 2], v[i + 3]);
+  } else {
+    typename std::conditional<W == 4, uint2, uint4>::type w;
+#pragma unroll
+    for (int i = 0; i < W / 2; ++i) (&w.x)[i] = pack2<T>(v[2 * i], v[2 * i + 1]);
+    *reinterpret_cast<decltype(w)*>(dst) = w;
+  }
+}
+template <typename T, int W> __device__ __forceinline__ void load_row_f32(const T* src, float* v) {
+  static_assert(W == 4 || W == 8, "row vectors are 4 or 8 wide");
+  if constexpr (is_x3<T>::value) {
+    load_row_f32<float, W>(reinterpret_cast<const float*>(src), v);
+  } else if constexpr (sizeof(T) == 4) {
+#pragma unroll
+    for (int i = 0; i < W; i += 4) {
+      const float4 r = *reinterpret_cast<const float4*>(src + i);
+      v[i] = r.x; v[i + 1] = r.y; v[i + 2] = r.z; v[i + 3] = r.w;
+    }
+  } else {
+    const auto r = *reinterpret_cast<const typename std::conditional<W == 4, uint2, uint4>::type*>(src);
+    unpack2<T>(r.x, v[0], v[1]); unpack2<T>(r.y, v[2], v[3]);   // (written out: as a loop over (&r.x)[i] it moved gn_stats_kernel's code)
+    if constexpr (W == 8) { unpack2<T>(r.z, v[4], v[5]); unpack2<T>(r.w, v[6], v[7]); }
+  }
+}
+template <typename T> __device__ __forceinline__ float stored(float v) { return to_f32(from_f32<T>(v)); }
 
 // ---- vector load/store of 8 (bf16) / 4 (f32) elements = 16 bytes -----------------------
 template <typename T> struct Vec16;

@@ -1,104 +1,14 @@
 // k22 - shared by the LDS-resident-halo convolution kernels (conv3_halo.hip: lock-step kernels; conv3_up2.hip; gemm8.hip; conv3_spec.hip:
-// the producer / consumer specialised kernel): fragment loaders, the LDS-DMA helper, the one definition
-// of the 8-wave frame (block map, slab range, loader offsets and issues), of the tap body and of the tap step, the common epilogue
-// halo_tail, and the LDS budget and launch dispatch every launcher and kernel agrees on.
+// the producer / consumer specialised kernel): the LDS-DMA helper, the one definition
+// of the 8-wave frame (loader offsets and issues), of the tap body and of the tap step, the common epilogue
+// halo_tail, and the LDS budget and launch dispatch every launcher and kernel agrees on.  What these kernels share with the other conv / GEMM
+// kernels - fragment loaders, counted vmcnt wait, block map, split-K range, accumulator zeroing, row vectors - is in common.h, the q/k/v
+// scatter in kernels.h.
 #pragma once
 #include "kernels.h"
 #include <stdlib.h>
 
 namespace {
-
-template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
-__device__ __forceinline__ void ld_frag_at(Frag<bf16_t>& f, const char* rowp, int sw, int ks, int h) {
-  f.v = *reinterpret_cast<const u32x4_t*>(rowp + (((2 * ks + h) ^ sw) << 4));
-}
-__device__ __forceinline__ void ld_frag_at(Frag<f16_t>& f, const char* rowp, int sw, int ks, int h) {
-  f.v = *reinterpret_cast<const u32x4_t*>(rowp + (((2 * ks + h) ^ sw) << 4));
-}
-__device__ __forceinline__ void ld_frag_at(Frag<float>& f, const char* rowp, int sw, int ks, int h) {
-  const float4 a = *reinterpret_cast<const float4*>(rowp + (((4 * ks + 2 * h) ^ sw) << 4));
-  const float4 b = *reinterpret_cast<const float4*>(rowp + (((4 * ks + 2 * h + 1) ^ sw) << 4));
-  f.v[0] = a.x; f.v[1] = a.y; f.v[2] = a.z; f.v[3] = a.w;
-  f.v[4] = b.x; f.v[5] = b.y; f.v[6] = b.z; f.v[7] = b.w;
-}
-
-// split precision: the operand is in x3 chunks (weights; activations written by gn_apply / the attention epilogue)
-__device__ __forceinline__ void ld_frag_at(Frag<x3_t>& f, const char* rowp, int sw, int ks, int h) {
-  x3_frag_from_chunks(f, *reinterpret_cast<const u32x4_t*>(rowp + (((4 * ks + 2 * h) ^ sw) << 4)),
-                      *reinterpret_cast<const u32x4_t*>(rowp + (((4 * ks + 2 * h + 1) ^ sw) << 4)));
-}
-__device__ __forceinline__ void ld_frag_at(Frag<x2_t>& f, const char* rowp, int sw, int ks, int h) {
-  x3_frag_from_chunks(f, *reinterpret_cast<const u32x4_t*>(rowp + (((4 * ks + 2 * h) ^ sw) << 4)),
-                      *reinterpret_cast<const u32x4_t*>(rowp + (((4 * ks + 2 * h + 1) ^ sw) << 4)));
-}
-// asymmetric split, activation operand: the hi piece of the group (one conflict-free ds_read_b128)
-__device__ __forceinline__ void ld_frag_at(FragHi& f, const char* rowp, int sw, int ks, int h) {
-  f.hi = *reinterpret_cast<const u32x4_t*>(rowp + (((4 * ks + 2 * h) ^ sw) << 4));
-}
-// RAW operands (split arithmetics only): plain fp32 rows in the LDS, split while they are read; every other type = ld_frag_at
-template <bool RAW, typename T, typename F> __device__ __forceinline__ void ld_frag_at_a(F& f, const char* rowp, int sw, int ks, int h) {
-  if constexpr (RAW && is_x3<T>::value) {
-    x3_frag_from_f32(f, *reinterpret_cast<const float4*>(rowp + (((4 * ks + 2 * h) ^ sw) << 4)),
-                     *reinterpret_cast<const float4*>(rowp + (((4 * ks + 2 * h + 1) ^ sw) << 4)));
-  } else {
-    ld_frag_at(f, rowp, sw, ks, h);
-  }
-}
-
-template <typename T> __device__ __forceinline__ void store8(T* dst, const float* v);
-template <> __device__ __forceinline__ void store8<bf16_t>(bf16_t* dst, const float* v) {
-  uint4 w;
-  w.x = pack2_bf16(v[0], v[1]);
-  w.y = pack2_bf16(v[2], v[3]);
-  w.z = pack2_bf16(v[4], v[5]);
-  w.w = pack2_bf16(v[6], v[7]);
-  *reinterpret_cast<uint4*>(dst) = w;
-}
-template <> __device__ __forceinline__ void store8<f16_t>(f16_t* dst, const float* v) {
-  uint4 w;
-  w.x = pack2_f16(v[0], v[1]);
-  w.y = pack2_f16(v[2], v[3]);
-  w.z = pack2_f16(v[4], v[5]);
-  w.w = pack2_f16(v[6], v[7]);
-  *reinterpret_cast<uint4*>(dst) = w;
-}
-template <> __device__ __forceinline__ void store8<float>(float* dst, const float* v) {
-  *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[1], v[2], v[3]);
-  *reinterpret_cast<float4*>(dst + 4) = make_float4(v[4], v[5], v[6], v[7]);
-}
-template <> __device__ __forceinline__ void store8<x3_t>(x3_t* dst, const float* v) { store8<float>(reinterpret_cast<float*>(dst), v); }
-template <> __device__ __forceinline__ void store8<x2_t>(x2_t* dst, const float* v) { store8<float>(reinterpret_cast<float*>(dst), v); }
-template <typename T> __device__ __forceinline__ void load8f(const T* src, float* v);
-template <> __device__ __forceinline__ void load8f<bf16_t>(const bf16_t* src, float* v) {
-  const uint4 r = *reinterpret_cast<const uint4*>(src);
-  v[0] = __uint_as_float(r.x << 16); v[1] = __uint_as_float(r.x & 0xffff0000u);
-  v[2] = __uint_as_float(r.y << 16); v[3] = __uint_as_float(r.y & 0xffff0000u);
-  v[4] = __uint_as_float(r.z << 16); v[5] = __uint_as_float(r.z & 0xffff0000u);
-  v[6] = __uint_as_float(r.w << 16); v[7] = __uint_as_float(r.w & 0xffff0000u);
-}
-template <> __device__ __forceinline__ void load8f<f16_t>(const f16_t* src, float* v) {
-  const uint4 r = *reinterpret_cast<const uint4*>(src);
-  unpack2_f16(r.x, v[0], v[1]); unpack2_f16(r.y, v[2], v[3]); unpack2_f16(r.z, v[4], v[5]); unpack2_f16(r.w, v[6], v[7]);
-}
-template <> __device__ __forceinline__ void load8f<float>(const float* src, float* v) {
-  const float4 a = *reinterpret_cast<const float4*>(src), b = *reinterpret_cast<const float4*>(src + 4);
-  v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-}
-template <> __device__ __forceinline__ void load8f<x3_t>(const x3_t* src, float* v) { load8f<float>(reinterpret_cast<const float*>(src), v); }
-template <> __device__ __forceinline__ void load8f<x2_t>(const x2_t* src, float* v) { load8f<float>(reinterpret_cast<const float*>(src), v); }
-// value as it will be read back from memory (the GroupNorm statistics are those of the stored tensor)
-template <typename T> __device__ __forceinline__ float stored(float v);
-template <> __device__ __forceinline__ float stored<bf16_t>(float v) { return bf16_to_f32(f32_to_bf16(v)); }
-template <> __device__ __forceinline__ float stored<f16_t>(float v) { return (float)(f16_t)v; }
-template <> __device__ __forceinline__ float stored<float>(float v) { return v; }
-template <> __device__ __forceinline__ float stored<x3_t>(float v) { return v; }
-template <> __device__ __forceinline__ float stored<x2_t>(float v) { return v; }
-
-__device__ __forceinline__ int xcd_remap_h(int bid, int nblocks) {
-  const int q = nblocks >> 3, r = nblocks & 7, x = bid & 7;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-}
 
 // LDS-DMA issued from inline asm: 16 bytes per lane from `g` to LDS byte address `lds_dst` (wave-uniform) + 16*lane.
 // hipcc books a __builtin_amdgcn_global_load_lds as a FLAT access pending on BOTH counters, and because the counted
@@ -125,7 +35,6 @@ __device__ __forceinline__ void glds16w_asm(const void* g, unsigned lds_dst) {
 
 constexpr int HALO_BN = 128;
 constexpr int HALO_NW = 8;        // waves per workgroup
-constexpr int HALO_GM = 8;        // m-tiles per group of the block map
 
 // Each iteration issues [weight tile NBST-1 taps ahead (2 loads)] THEN [the halo pieces of this tap]: the halo piece is the
 // youngest entry of the VMEM queue, so the counted wait for the weight tile can leave it in flight — it gets two
@@ -145,38 +54,6 @@ template <int TAPS> constexpr int halo_tap_dy(int t) { return TAPS == 9 ? t / 3 
 template <int TAPS> constexpr int halo_tap_dx(int t) { return TAPS == 9 ? t % 3 : t & 1; }
 
 // ---- the frame: 512 threads = 8 waves own one BM x 128 tile of a (gx m-tiles) x (gy n-tiles) x splitk grid -------------------
-// block -> (k-split bz, m-tile bx, n-tile by): XCD remap, then groups of HALO_GM m-tiles that walk the n-tiles together
-__device__ __forceinline__ void halo_block_map(const IgemmParams& p, int gx, int gy, int& bz, int& bx, int& by) {
-  constexpr int GM = HALO_GM;
-  int L = p.xcd_remap ? xcd_remap_h(blockIdx.x, gridDim.x) : (int)blockIdx.x;
-  const int per_z = gx * gy;
-  bz = L / per_z;
-  L -= bz * per_z;
-  const int grp = L / (GM * gy);
-  const int first_m = grp * GM;
-  const int gsz = gx - first_m < GM ? gx - first_m : GM;
-  const int lin = L - grp * GM * gy;
-  bx = first_m + lin % gsz;
-  by = lin / gsz;
-}
-// K slabs [s0, s1) of k-split bz
-__device__ __forceinline__ void halo_slab_range(const IgemmParams& p, int nslab, int bz, int& s0, int& s1) {
-  s0 = 0;
-  s1 = nslab;
-  if (p.splitk > 1) {
-    const int per = (nslab + p.splitk - 1) / p.splitk;
-    s0 = bz * per;
-    s1 = s0 + per < nslab ? s0 + per : nslab;
-  }
-}
-template <int MI, int NI> __device__ __forceinline__ void halo_zero_acc(f32x16_t (&acc)[MI][NI]) {
-#pragma unroll
-  for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
-}
 // LDS byte address of the dynamic shared segment (wave-uniform), for the asm LDS-DMA path
 __device__ __forceinline__ unsigned halo_lds_base(char* smem) {
   return __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) char*)smem);
@@ -607,30 +484,18 @@ __device__ __forceinline__ void halo_tail(const IgemmParams& p, f32x16_t (&acc)[
     for (int e = 0; e < 8; ++e) val[e] += bias8[e];
     if (res != nullptr) {
       float rv[8];
-      load8f<T>(res + m * p.ldr + n, rv);
+      load_row_f32<T, 8>(res + m * p.ldr + n, rv);
 #pragma unroll
       for (int e = 0; e < 8; ++e) val[e] += rv[e];
     }
 #pragma unroll
     for (int e = 0; e < 8; ++e) val[e] = apply_act(val[e], p.act);
     if (PLAIN && p.out_mode == IG_OUT_QKV) {
-      // columns [q | k | v] x [heads][64]: q row-major, k behind the context keys of K_all, v transposed into V^T_all
-      const int C = p.N / 3, heads = C >> 6;
-      const int which = n / C, c = n - which * C;
-      const int head = c >> 6, d = c & 63;
-      if (which == 0) {
-        store8<T>(reinterpret_cast<T*>(p.out) + m * p.ldo + c, val);
-      } else if (which == 1) {
-        store8<T>(reinterpret_cast<T*>(p.kall) + ((int64_t)(img * heads + head) * p.att_Tkp + p.att_S + v) * 64 + d, val);
-      } else {
-        T* vt = reinterpret_cast<T*>(p.vtall) + ((int64_t)(img * heads + head) * 64 + d) * p.att_Tkp + p.att_S + v;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) vt[(int64_t)e * p.att_Tkp] = from_f32<T>(val[e]);
-      }
+      K22_QKV_SCATTER(T, 8, val, m, img, v, n)
       continue;
     }
-    if (p.out_mode == IG_OUT_ROWMAJOR) store8<T>(reinterpret_cast<T*>(p.out) + m * p.ldo + n, val);
-    else store8<float>(reinterpret_cast<float*>(p.out) + m * p.ldo + n, val);
+    if (p.out_mode == IG_OUT_ROWMAJOR) store_row<T, 8>(reinterpret_cast<T*>(p.out) + m * p.ldo + n, val);
+    else store_row<float, 8>(reinterpret_cast<float*>(p.out) + m * p.ldo + n, val);
     if (p.stats != nullptr) {
 #pragma unroll
       for (int e = 0; e < 8; ++e) {

@@ -66,7 +66,7 @@ __global__ __launch_bounds__(512) void conv3_halo_kernel(const IgemmParams p) {
   const int B = p.M / (p.H * p.W);
 
   int bz, bx, by;
-  halo_block_map(p, B * TPI, (p.N + BN - 1) / BN, bz, bx, by);
+  tile_block_map(p.xcd_remap, B * TPI, (p.N + BN - 1) / BN, bz, bx, by);
   const int img = bx / TPI, v0 = (bx - img * TPI) * BM;
   const int n0 = by * BN;
 
@@ -76,10 +76,10 @@ __global__ __launch_bounds__(512) void conv3_halo_kernel(const IgemmParams p) {
   K22_PIECE_OFFSETS(aoff, A_SLOTS, wave, NW, v0, NP, 8)
   K22_ROW_OFFSETS(boff, B_SLOTS, wave, NW, n0, p.Npad - 1, n * 9 * p.Kc)
   int s0, s1;
-  halo_slab_range(p, p.Kc / BK, bz, s0, s1);
+  splitk_range(p.splitk, p.Kc / BK, bz, s0, s1);
 
   f32x16_t acc[MI][NI];
-  halo_zero_acc(acc);
+  K22_ZERO_ACC(acc, MI, NI)
   FragA<T> pa[MI];          // PIPE: fragments read but not yet multiplied (zero = a no-op group before the first tap)
   Frag<T> pb[NI];
   if constexpr (PIPE) {
@@ -157,7 +157,7 @@ __global__ __launch_bounds__(512) void conv3_halo3_kernel(const IgemmParams p) {
   const int B = p.M / (p.H * p.W);
 
   int bz, bx, by;
-  halo_block_map(p, B * TPI, (p.N + BN - 1) / BN, bz, bx, by);
+  tile_block_map(p.xcd_remap, B * TPI, (p.N + BN - 1) / BN, bz, bx, by);
   const int img = bx / TPI, v0 = (bx - img * TPI) * BM;
   const int n0 = by * BN;
 
@@ -175,10 +175,10 @@ __global__ __launch_bounds__(512) void conv3_halo3_kernel(const IgemmParams p) {
     boff = n * 9 * p.Kc + ((lane & 3) ^ ((row >> 2) & 3)) * EPC;
   }
   int h0, h1;
-  halo_slab_range(p, p.Kc / EPH, bz, h0, h1);
+  splitk_range(p.splitk, p.Kc / EPH, bz, h0, h1);
 
   f32x16_t acc[MI][NI];
-  halo_zero_acc(acc);
+  K22_ZERO_ACC(acc, MI, NI)
 
   char* const Bring = smem + 2 * A_BYTES;
   const int abase = wm * (BM / WM) + l31;

@@ -65,14 +65,14 @@ __global__ __launch_bounds__(512) void conv3_halo_spec_kernel(const IgemmParams 
   const int B = p.M / (p.H * p.W);
 
   int bz, bx, by;
-  halo_block_map(p, B * TPI, (p.N + BN - 1) / BN, bz, bx, by);
+  tile_block_map(p.xcd_remap, B * TPI, (p.N + BN - 1) / BN, bz, bx, by);
   const int img = bx / TPI, v0 = (bx - img * TPI) * BM;
   const int n0 = by * BN;
   int s0, s1;
-  halo_slab_range(p, p.Kc / BK, bz, s0, s1);
+  splitk_range(p.splitk, p.Kc / BK, bz, s0, s1);
 
   f32x16_t acc[MI][NI];
-  halo_zero_acc(acc);
+  K22_ZERO_ACC(acc, MI, NI)
 
   char* const Bst = smem + 2 * A_BYTES;
   // The producers' K loop: per tap the loaders' half (K22_TAP_FRONT), then the rotation of the ring slot

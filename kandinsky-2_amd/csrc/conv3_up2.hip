@@ -54,7 +54,7 @@ __global__ __launch_bounds__(512) void conv3_up2_kernel(const IgemmParams p) {
 
   // block -> (m-tile, n-tile x phase, k-split): the phase is the fastest part of the n index
   int bz, bx, byp;
-  halo_block_map(p, B * TPI, ((p.N + BN - 1) / BN) * 4, bz, bx, byp);
+  tile_block_map(p.xcd_remap, B * TPI, ((p.N + BN - 1) / BN) * 4, bz, bx, byp);
   const int ph = byp & 3, by = byp >> 2;
   const int img = bx / TPI, tile = bx - img * TPI, v0 = tile * BM;
   const int n0 = by * BN;
@@ -66,10 +66,10 @@ __global__ __launch_bounds__(512) void conv3_up2_kernel(const IgemmParams p) {
   K22_PIECE_OFFSETS(aoff, UP2_ASLOTS, wave, NW, base, NP, 8)
   K22_ROW_OFFSETS(boff, B_SLOTS, wave, NW, n0, p.Npad - 1, (ph * p.Npad + n) * 4 * p.Kc)
   int s0, s1;
-  halo_slab_range(p, p.Kc / BK, bz, s0, s1);
+  splitk_range(p.splitk, p.Kc / BK, bz, s0, s1);
 
   f32x16_t acc[MI][NI];
-  halo_zero_acc(acc);
+  K22_ZERO_ACC(acc, MI, NI)
   FragA<T> pa[MI];          // PIPE: fragments read but not yet multiplied (zero = a no-op group before the first tap)
   Frag<T> pb[NI];
   if constexpr (PIPE) {

@@ -11,25 +11,9 @@
 #include "kernels.h"
 #include "elementwise.h"
 
-// ------------------------------------------------------------------------------------------
-// 4-element loads (one GroupNorm group never splits a 4-channel vector: C % 128 == 0)
-// ------------------------------------------------------------------------------------------
-__device__ __forceinline__ void load4(const bf16_t* p, float* f) {
-  const uint2 r = *reinterpret_cast<const uint2*>(p);
-  f[0] = __uint_as_float(r.x << 16); f[1] = __uint_as_float(r.x & 0xffff0000u);
-  f[2] = __uint_as_float(r.y << 16); f[3] = __uint_as_float(r.y & 0xffff0000u);
-}
-__device__ __forceinline__ void load4(const f16_t* p, float* f) {
-  const uint2 r = *reinterpret_cast<const uint2*>(p);
-  unpack2_f16(r.x, f[0], f[1]); unpack2_f16(r.y, f[2], f[3]);
-}
-__device__ __forceinline__ void load4(const float* p, float* f) {
-  const float4 r = *reinterpret_cast<const float4*>(p);
-  f[0] = r.x; f[1] = r.y; f[2] = r.z; f[3] = r.w;
-}
-
 // ---- GroupNorm pass 1 (stand-alone form): per (batch, pixel-range) partial sums of x and x^2 per CHANNEL ----
-// grid (nsplit, B), 256 threads. Threads own fixed 4-channel vectors so the sums stay in registers; pixels of
+// grid (nsplit, B), 256 threads. Threads own fixed 4-channel vectors (one GroupNorm group never splits one: C % 128 == 0) so the sums
+// stay in registers; pixels of
 // the block's range are walked with every wave reading whole contiguous NHWC rows.  (Tensors produced by the
 // 3x3 convolutions arrive with these sums already computed by the conv epilogue; this kernel serves the rest.)
 template <typename T>
@@ -63,7 +47,7 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(GnStatsParams p) {
       for (; pix + 7 * PL < pix1; pix += 8 * PL) {
         float f[8][4];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) load4(src + (int64_t)(pix + u * PL) * ld, f[u]);
+        for (int u = 0; u < 8; ++u) load_row_f32<T, 4>(src + (int64_t)(pix + u * PL) * ld, f[u]);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           sum[j][k] += ((f[0][k] + f[1][k]) + (f[2][k] + f[3][k])) + ((f[4][k] + f[5][k]) + (f[6][k] + f[7][k]));
@@ -73,7 +57,7 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(GnStatsParams p) {
       }
       for (; pix < pix1; pix += PL) {
         float f[4];
-        load4(src + (int64_t)pix * ld, f);
+        load_row_f32<T, 4>(src + (int64_t)pix * ld, f);
 #pragma unroll
         for (int k = 0; k < 4; ++k) { sum[j][k] += f[k]; sq[j][k] += f[k] * f[k]; }
       }

@@ -44,7 +44,7 @@ __global__ __launch_bounds__(512) void gemm8_kernel(const IgemmParams p) {
   const int TPI = (HW + BM - 1) / BM;
   const int B = p.M / HW;
   int bz, bx, by;
-  halo_block_map(p, B * TPI, (p.N + BN - 1) / BN, bz, bx, by);
+  tile_block_map(p.xcd_remap, B * TPI, (p.N + BN - 1) / BN, bz, bx, by);
   const int img = bx / TPI, v0 = (bx - img * TPI) * BM;
   const int n0 = by * BN;
 
@@ -54,10 +54,10 @@ __global__ __launch_bounds__(512) void gemm8_kernel(const IgemmParams p) {
   K22_ROW_OFFSETS(aoff, A_SLOTS, wave, NW, v0, HW - 1, n * (int)p.lda0)   // rows past the image re-read its last pixel; they are never stored
   K22_ROW_OFFSETS(boff, B_SLOTS, wave, NW, n0, p.Npad - 1, n * p.Kc)
   int s0, s1;
-  halo_slab_range(p, p.Kc / BK, bz, s0, s1);
+  splitk_range(p.splitk, p.Kc / BK, bz, s0, s1);
 
   f32x16_t acc[MI][NI];
-  halo_zero_acc(acc);
+  K22_ZERO_ACC(acc, MI, NI)
 
   const unsigned lds0 = halo_lds_base(smem);
   int arow[MI], brow[NI];
@@ -117,14 +117,14 @@ __global__ __launch_bounds__(512) void gemm8_spec_kernel(const IgemmParams p) {
   const int TPI = (HW + BM - 1) / BM;
   const int B = p.M / HW;
   int bz, bx, by;
-  halo_block_map(p, B * TPI, (p.N + BN - 1) / BN, bz, bx, by);
+  tile_block_map(p.xcd_remap, B * TPI, (p.N + BN - 1) / BN, bz, bx, by);
   const int img = bx / TPI, v0 = (bx - img * TPI) * BM;
   const int n0 = by * BN;
   int s0, s1;
-  halo_slab_range(p, p.Kc / BK, bz, s0, s1);
+  splitk_range(p.splitk, p.Kc / BK, bz, s0, s1);
 
   f32x16_t acc[MI][NI];
-  halo_zero_acc(acc);
+  K22_ZERO_ACC(acc, MI, NI)
 
   if (s0 < s1) {
     if (producer) {

@@ -25,56 +25,63 @@
 //     that XCD's L2 (hardware places block b on XCD b % 8): every weight byte is pulled from
 //     HBM/Infinity-Fabric by one XCD, pixels by the few XCDs that hold their m-tile group.
 //   * fp32 accumulate; epilogue fuses bias, residual add and activation, or writes fp32 split-K
-//     partials that splitk_reduce_kernel finishes.
+//     partials that splitk_reduce_kernel finishes.  The epilogue arithmetic of the kernel and of the two finishes is one text (K22_EPI_*
+//     below); block map, split-K range, row vectors and the counted vmcnt wait are common.h's, the q/k/v scatter kernels.h's.
 #include "kernels.h"
 #include <stdlib.h>
 #include <type_traits>
 
-template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
-// 4 consecutive output channels of one pixel
-template <typename T> __device__ __forceinline__ void store4(T* dst, const float* v);
-template <> __device__ __forceinline__ void store4<bf16_t>(bf16_t* dst, const float* v) {
-  uint2 w;
-  w.x = pack2_bf16(v[0], v[1]);
-  w.y = pack2_bf16(v[2], v[3]);
-  *reinterpret_cast<uint2*>(dst) = w;
-}
-template <> __device__ __forceinline__ void store4<f16_t>(f16_t* dst, const float* v) {
-  uint2 w;
-  w.x = pack2_f16(v[0], v[1]);
-  w.y = pack2_f16(v[2], v[3]);
-  *reinterpret_cast<uint2*>(dst) = w;
-}
-template <> __device__ __forceinline__ void store4<float>(float* dst, const float* v) {
-  *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[1], v[2], v[3]);
-}
-template <> __device__ __forceinline__ void store4<x3_t>(x3_t* dst, const float* v) { store4<float>(reinterpret_cast<float*>(dst), v); }
-template <> __device__ __forceinline__ void store4<x2_t>(x2_t* dst, const float* v) { store4<float>(reinterpret_cast<float*>(dst), v); }
-template <typename T> __device__ __forceinline__ void load4f(const T* src, float* v);
-template <> __device__ __forceinline__ void load4f<bf16_t>(const bf16_t* src, float* v) {
-  const uint2 r = *reinterpret_cast<const uint2*>(src);
-  v[0] = __uint_as_float(r.x << 16); v[1] = __uint_as_float(r.x & 0xffff0000u);
-  v[2] = __uint_as_float(r.y << 16); v[3] = __uint_as_float(r.y & 0xffff0000u);
-}
-template <> __device__ __forceinline__ void load4f<f16_t>(const f16_t* src, float* v) {
-  const uint2 r = *reinterpret_cast<const uint2*>(src);
-  unpack2_f16(r.x, v[0], v[1]); unpack2_f16(r.y, v[2], v[3]);
-}
-template <> __device__ __forceinline__ void load4f<float>(const float* src, float* v) {
-  const float4 r = *reinterpret_cast<const float4*>(src);
-  v[0] = r.x; v[1] = r.y; v[2] = r.z; v[3] = r.w;
-}
-
-template <> __device__ __forceinline__ void load4f<x3_t>(const x3_t* src, float* v) { load4f<float>(reinterpret_cast<const float*>(src), v); }
-template <> __device__ __forceinline__ void load4f<x2_t>(const x2_t* src, float* v) { load4f<float>(reinterpret_cast<const float*>(src), v); }
-
-// Logical block index of hardware block `bid` (XCD = bid % 8): XCD x gets the contiguous range
-// [start_x, start_x + count_x) of logical indices, in dispatch order.  Bijective for any nblocks.
-__device__ __forceinline__ int xcd_remap(int bid, int nblocks) {
-  const int q = nblocks >> 3, r = nblocks & 7, x = bid & 7;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-}
+// ---- the epilogue arithmetic of igemm_kernel and the two split-K finishes, once --------------------------------------------------------
+// Macros, not functions: through function templates the same text moved the code of every kernel of this file (block order, branch
+// polarity; profiles/shared_helpers_device_code.txt).  Names they take from the kernel: T, p, res (p.residual as const T*).
+// V[0..3] = channels COL .. COL + 3 of row ROW: + bias (+ bias2 under BIAS2: the finishes only - igemm_resolve refuses a fused skip on the generic
+// kernel) + residual (T, or fp32 under p.res_f32), then the activation
+#define K22_EPI_FINISH4(BIAS2, V, ROW, COL)                                                                \
+  {                                                                                                        \
+    if (p.bias != nullptr) {                                                                               \
+      const float4 bv = *reinterpret_cast<const float4*>(p.bias + (COL));                                  \
+      V[0] += bv.x; V[1] += bv.y; V[2] += bv.z; V[3] += bv.w;                                              \
+    }                                                                                                      \
+    if constexpr (BIAS2) {                                                                                 \
+      if (p.bias2 != nullptr) {                                                                            \
+        const float4 bv = *reinterpret_cast<const float4*>(p.bias2 + (COL));                               \
+        V[0] += bv.x; V[1] += bv.y; V[2] += bv.z; V[3] += bv.w;                                            \
+      }                                                                                                    \
+    }                                                                                                      \
+    if (res != nullptr) {                                                                                  \
+      float rv[4];                                                                                         \
+      if (p.res_f32) load_row_f32<float, 4>(reinterpret_cast<const float*>(p.residual) + (int64_t)(ROW) * p.ldr + (COL), rv); \
+      else load_row_f32<T, 4>(res + (int64_t)(ROW) * p.ldr + (COL), rv);                                   \
+      _Pragma("unroll") for (int e = 0; e < 4; ++e) V[e] += rv[e];                                         \
+    }                                                                                                      \
+    _Pragma("unroll") for (int e = 0; e < 4; ++e) V[e] = apply_act(V[e], p.act);                           \
+  }
+// the same four values to where p.out_mode puts them: row-major T, row-major fp32 or the q/k/v scatter - or else (IG_OUT_NCHW_F32) the
+// statement that follows, which each kernel spells from the index arithmetic it already has
+#define K22_EPI_STORE4_OR_ELSE(V, ROW, COL)                                                                \
+  if (p.out_mode == IG_OUT_ROWMAJOR) {                                                                     \
+    store_row<T, 4>(reinterpret_cast<T*>(p.out) + (int64_t)(ROW) * p.ldo + (COL), V);                      \
+  } else if (p.out_mode == IG_OUT_ROWMAJOR_F32) {                                                          \
+    store_row<float, 4>(reinterpret_cast<float*>(p.out) + (int64_t)(ROW) * p.ldo + (COL), V);              \
+  } else if (p.out_mode == IG_OUT_QKV) {                                                                   \
+    K22_QKV_SCATTER(T, 4, V, ROW, (ROW) / p.att_T, (ROW) - img_ * p.att_T, COL)                            \
+  } else
+// one element U at (ROW, COL) (the ragged tails: N, ldo or ldr not a multiple of 4; no q/k/v mode there), NCHW as above
+#define K22_EPI_FINISH1(BIAS2, U, ROW, COL)                                                                \
+  {                                                                                                        \
+    if (p.bias != nullptr) U += p.bias[COL];                                                               \
+    if constexpr (BIAS2) {                                                                                 \
+      if (p.bias2 != nullptr) U += p.bias2[COL];                                                           \
+    }                                                                                                      \
+    if (res != nullptr) U += p.res_f32 ? reinterpret_cast<const float*>(p.residual)[(int64_t)(ROW) * p.ldr + COL] : to_f32(res[(int64_t)(ROW) * p.ldr + COL]); \
+    U = apply_act(U, p.act);                                                                               \
+  }
+#define K22_EPI_STORE1_OR_ELSE(U, ROW, COL)                                                                \
+  if (p.out_mode == IG_OUT_ROWMAJOR) {                                                                     \
+    reinterpret_cast<T*>(p.out)[(int64_t)(ROW) * p.ldo + COL] = from_f32<T>(U);                            \
+  } else if (p.out_mode == IG_OUT_ROWMAJOR_F32) {                                                          \
+    reinterpret_cast<float*>(p.out)[(int64_t)(ROW) * p.ldo + COL] = U;                                     \
+  } else
 
 // ARAW (K22_F16X3 only): the A operand is plain fp32 rows, split into fp16 halves while its fragments are read (p.a_raw).
 template <typename T, int BM, int BN, int STAGES, bool ARAW = false>
@@ -84,24 +91,14 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmParams p) {
   constexpr int MI = BM / 64, NI = BN / 64;     // 32x32 atoms per wave along M / N
   constexpr int A_CH = BM / 32, B_CH = BN / 32, CH = A_CH + B_CH;  // LDS-DMA instructions per wave per K tile
   constexpr int A_BYTES = BM * 128, B_BYTES = BN * 128, BUF = A_BYTES + B_BYTES;
-  constexpr int GM = 8;                         // m-tiles per rasterisation group
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
 
-  // ---- block -> (m-tile, n-tile, k-split): groups of GM m-tiles x all n-tiles, k-split outermost ----
-  const int gx = (p.M + BM - 1) / BM, gy = (p.N + BN - 1) / BN;
-  int L = p.xcd_remap ? xcd_remap(blockIdx.x, gridDim.x) : (int)blockIdx.x;
-  const int per_z = gx * gy;
-  const int bz = L / per_z;
-  L -= bz * per_z;
-  const int grp = L / (GM * gy);
-  const int first_m = grp * GM;
-  const int gsz = gx - first_m < GM ? gx - first_m : GM;
-  const int lin = L - grp * GM * gy;
-  const int bx = first_m + lin % gsz, by = lin / gsz;
+  int bz, bx, by;
+  tile_block_map(p.xcd_remap, (p.M + BM - 1) / BM, (p.N + BN - 1) / BN, bz, bx, by);
   const int m0 = bx * BM, n0 = by * BN;
 
   const bool conv = (p.taps == 9);
@@ -137,20 +134,11 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmParams p) {
   }
   const int kt_per_tap = p.Kc / BK;
   const int nkt = p.taps * kt_per_tap;
-  int kt0 = 0, kt1 = nkt;
-  if (p.splitk > 1) {
-    const int per = (nkt + p.splitk - 1) / p.splitk;
-    kt0 = bz * per;
-    kt1 = kt0 + per < nkt ? kt0 + per : nkt;
-  }
+  int kt0, kt1;
+  splitk_range(p.splitk, nkt, bz, kt0, kt1);
 
   f32x16_t acc[MI][NI];
-#pragma unroll
-  for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
+  K22_ZERO_ACC(acc, MI, NI)
   const int h = lane >> 5, l31 = lane & 31;
   const int64_t lck = lchunk * EPC;
   const int wave_row0 = wave * 8;  // rows [8*wave + 32*i, +8) of a tile are filled by this wave's i-th DMA
@@ -243,38 +231,8 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmParams p) {
           continue;
         }
         if (vec_ok) {
-          if (p.bias != nullptr) {
-            const float4 bv = *reinterpret_cast<const float4*>(p.bias + n);
-            v[0] += bv.x; v[1] += bv.y; v[2] += bv.z; v[3] += bv.w;
-          }
-          if (res != nullptr) {
-            float rv[4];
-            if (p.res_f32) load4f<float>(reinterpret_cast<const float*>(p.residual) + (int64_t)m * p.ldr + n, rv);
-            else load4f<T>(res + (int64_t)m * p.ldr + n, rv);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] += rv[e];
-          }
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = apply_act(v[e], p.act);
-          if (p.out_mode == IG_OUT_ROWMAJOR) {
-            store4<T>(reinterpret_cast<T*>(p.out) + (int64_t)m * p.ldo + n, v);
-          } else if (p.out_mode == IG_OUT_ROWMAJOR_F32) {
-            store4<float>(reinterpret_cast<float*>(p.out) + (int64_t)m * p.ldo + n, v);
-          } else if (p.out_mode == IG_OUT_QKV) {
-            const int C = p.N / 3, heads = C >> 6;
-            const int which = n / C, c = n - which * C;
-            const int head = c >> 6, d = c & 63;
-            const int b = m / p.att_T, t = m - b * p.att_T;
-            if (which == 0) {
-              store4<T>(reinterpret_cast<T*>(p.out) + (int64_t)m * p.ldo + c, v);
-            } else if (which == 1) {
-              store4<T>(reinterpret_cast<T*>(p.kall) + ((int64_t)(b * heads + head) * p.att_Tkp + p.att_S + t) * 64 + d, v);
-            } else {
-              T* vt = reinterpret_cast<T*>(p.vtall) + ((int64_t)(b * heads + head) * 64 + d) * p.att_Tkp + p.att_S + t;
-#pragma unroll
-              for (int e = 0; e < 4; ++e) vt[(int64_t)e * p.att_Tkp] = from_f32<T>(v[e]);
-            }
-          } else {
+          K22_EPI_FINISH4(false, v, m, n)
+          K22_EPI_STORE4_OR_ELSE(v, m, n) {
             const int64_t hw = (int64_t)p.H * p.W;
 #pragma unroll
             for (int e = 0; e < 4; ++e) reinterpret_cast<float*>(p.out)[nchw_base + (int64_t)(n + e) * hw] = v[e];
@@ -284,16 +242,8 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmParams p) {
           for (int e = 0; e < 4; ++e) {
             if (n + e >= p.N) continue;
             float u = v[e];
-            if (p.bias != nullptr) u += p.bias[n + e];
-            if (res != nullptr) u += p.res_f32 ? reinterpret_cast<const float*>(p.residual)[(int64_t)m * p.ldr + n + e] : to_f32(res[(int64_t)m * p.ldr + n + e]);
-            u = apply_act(u, p.act);
-            if (p.out_mode == IG_OUT_ROWMAJOR) {
-              reinterpret_cast<T*>(p.out)[(int64_t)m * p.ldo + n + e] = from_f32<T>(u);
-            } else if (p.out_mode == IG_OUT_ROWMAJOR_F32) {
-              reinterpret_cast<float*>(p.out)[(int64_t)m * p.ldo + n + e] = u;
-            } else {
-              reinterpret_cast<float*>(p.out)[nchw_base + (int64_t)(n + e) * p.H * p.W] = u;
-            }
+            K22_EPI_FINISH1(false, u, m, n + e)
+            K22_EPI_STORE1_OR_ELSE(u, m, n + e) reinterpret_cast<float*>(p.out)[nchw_base + (int64_t)(n + e) * p.H * p.W] = u;
           }
         }
       }
@@ -316,43 +266,8 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const IgemmParams p)
         a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
       }
       float v[4] = {a.x, a.y, a.z, a.w};
-      if (p.bias != nullptr) {
-        const float4 bv = *reinterpret_cast<const float4*>(p.bias + n);
-        v[0] += bv.x; v[1] += bv.y; v[2] += bv.z; v[3] += bv.w;
-      }
-      if (p.bias2 != nullptr) {
-        const float4 bv = *reinterpret_cast<const float4*>(p.bias2 + n);
-        v[0] += bv.x; v[1] += bv.y; v[2] += bv.z; v[3] += bv.w;
-      }
-      if (res != nullptr) {
-        float rv[4];
-        if (p.res_f32) load4f<float>(reinterpret_cast<const float*>(p.residual) + (int64_t)m * p.ldr + n, rv);
-        else load4f<T>(res + (int64_t)m * p.ldr + n, rv);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] += rv[e];
-      }
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = apply_act(v[e], p.act);
-      if (p.out_mode == IG_OUT_ROWMAJOR) {
-        store4<T>(reinterpret_cast<T*>(p.out) + (int64_t)m * p.ldo + n, v);
-      } else if (p.out_mode == IG_OUT_ROWMAJOR_F32) {
-        store4<float>(reinterpret_cast<float*>(p.out) + (int64_t)m * p.ldo + n, v);
-      } else if (p.out_mode == IG_OUT_QKV) {
-        // same destinations as igemm_kernel's epilogue: q row-major, k / v^T behind the context keys of the attention operands
-        const int C = p.N / 3, heads = C >> 6;
-        const int which = n / C, c = n - which * C;
-        const int head = c >> 6, d = c & 63;
-        const int b = m / p.att_T, t = m - b * p.att_T;
-        if (which == 0) {
-          store4<T>(reinterpret_cast<T*>(p.out) + (int64_t)m * p.ldo + c, v);
-        } else if (which == 1) {
-          store4<T>(reinterpret_cast<T*>(p.kall) + ((int64_t)(b * heads + head) * p.att_Tkp + p.att_S + t) * 64 + d, v);
-        } else {
-          T* vt = reinterpret_cast<T*>(p.vtall) + ((int64_t)(b * heads + head) * 64 + d) * p.att_Tkp + p.att_S + t;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) vt[(int64_t)e * p.att_Tkp] = from_f32<T>(v[e]);
-        }
-      } else {
+      K22_EPI_FINISH4(true, v, m, n)
+      K22_EPI_STORE4_OR_ELSE(v, m, n) {
         const int hw = p.H * p.W;
         const int b = m / hw, rem = m - b * hw;
 #pragma unroll
@@ -365,15 +280,8 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const IgemmParams p)
     const int m = (int)(i / p.N), n = (int)(i - (int64_t)m * p.N);
     float v = 0.f;
     for (int s = 0; s < p.splitk; ++s) v += p.partial[(int64_t)s * total + i];
-    if (p.bias != nullptr) v += p.bias[n];
-    if (p.bias2 != nullptr) v += p.bias2[n];
-    if (res != nullptr) v += p.res_f32 ? reinterpret_cast<const float*>(p.residual)[(int64_t)m * p.ldr + n] : to_f32(res[(int64_t)m * p.ldr + n]);
-    v = apply_act(v, p.act);
-    if (p.out_mode == IG_OUT_ROWMAJOR) {
-      reinterpret_cast<T*>(p.out)[(int64_t)m * p.ldo + n] = from_f32<T>(v);
-    } else if (p.out_mode == IG_OUT_ROWMAJOR_F32) {
-      reinterpret_cast<float*>(p.out)[(int64_t)m * p.ldo + n] = v;
-    } else {
+    K22_EPI_FINISH1(true, v, m, n)
+    K22_EPI_STORE1_OR_ELSE(v, m, n) {
       const int hw = p.H * p.W;
       const int b = m / hw, rem = m - b * hw;
       reinterpret_cast<float*>(p.out)[((int64_t)b * p.N + n) * hw + rem] = v;
@@ -403,29 +311,13 @@ __global__ __launch_bounds__(256) void splitk_reduce_rows_kernel(const IgemmPara
       a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
     }
     v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-    if (p.bias != nullptr) {
-      const float4 b = *reinterpret_cast<const float4*>(p.bias + n);
-      v[0] += b.x; v[1] += b.y; v[2] += b.z; v[3] += b.w;
-    }
-    if (p.bias2 != nullptr) {
-      const float4 b = *reinterpret_cast<const float4*>(p.bias2 + n);
-      v[0] += b.x; v[1] += b.y; v[2] += b.z; v[3] += b.w;
-    }
-    if (res != nullptr) {
-      float rv[4];
-      if (p.res_f32) load4f<float>(reinterpret_cast<const float*>(p.residual) + (int64_t)m * p.ldr + n, rv);
-      else load4f<T>(res + (int64_t)m * p.ldr + n, rv);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] += rv[e];
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = apply_act(v[e], p.act);
+    K22_EPI_FINISH4(true, v, m, n)
     if (p.out_mode == IG_OUT_ROWMAJOR) {
-      store4<T>(reinterpret_cast<T*>(p.out) + (int64_t)m * p.ldo + n, v);
+      store_row<T, 4>(reinterpret_cast<T*>(p.out) + (int64_t)m * p.ldo + n, v);
 #pragma unroll
       for (int e = 0; e < 4; ++e) v[e] = to_f32(from_f32<T>(v[e]));
     } else {
-      store4<float>(reinterpret_cast<float*>(p.out) + (int64_t)m * p.ldo + n, v);
+      store_row<float, 4>(reinterpret_cast<float*>(p.out) + (int64_t)m * p.ldo + n, v);
     }
   }
   if (p.stats == nullptr) return;

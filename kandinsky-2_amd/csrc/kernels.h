@@ -90,6 +90,27 @@ struct IgemmParams {
 // kernel argument, copied by value into every launch: the layout is what the kernels were compiled against
 static_assert(sizeof(IgemmParams) == 272 && std::is_trivially_copyable<IgemmParams>::value, "IgemmParams layout");
 
+// IG_OUT_QKV: where W (4 or 8) consecutive columns COL.. of row ROW = token TOK of image IMG go (values V[W], rounded to T; p = the problem).
+// Columns are [q | k | v] x [heads][64]: q row-major, k behind the context keys of K_all, v transposed into V^T_all.  The one text of
+// these addresses (igemm_kernel, splitk_reduce_kernel, halo_tail); a macro: as a function it moved the code of the first two.
+// IMG and TOK are evaluated once, behind the column split and in this order (the expression TOK may name img_): the order of the two
+// divisions is part of what hipcc's output follows.
+#define K22_QKV_SCATTER(T, W, V, ROW, IMG, TOK, COL)                                                       \
+  {                                                                                                        \
+    const int C = p.N / 3, heads = C >> 6;                                                                 \
+    const int which = (COL) / C, c = (COL) - which * C;                                                    \
+    const int head = c >> 6, d = c & 63;                                                                   \
+    const int img_ = (IMG), tok_ = (TOK);                                                                  \
+    if (which == 0) {                                                                                      \
+      store_row<T, W>(reinterpret_cast<T*>(p.out) + (int64_t)(ROW) * p.ldo + c, V);                        \
+    } else if (which == 1) {                                                                               \
+      store_row<T, W>(reinterpret_cast<T*>(p.kall) + ((int64_t)(img_ * heads + head) * p.att_Tkp + p.att_S + tok_) * 64 + d, V); \
+    } else {                                                                                               \
+      T* vt = reinterpret_cast<T*>(p.vtall) + ((int64_t)(img_ * heads + head) * 64 + d) * p.att_Tkp + p.att_S + tok_; \
+      _Pragma("unroll") for (int e = 0; e < (W); ++e) vt[(int64_t)e * p.att_Tkp] = from_f32<T>(V[e]);      \
+    }                                                                                                      \
+  }
+
 // The kernel variants.  The numbers are ABI: K22IgemmProblem.algo, the "conv_algo" / "gemm_algo" options and the tile table use them.
 // 8, 9, 13 and 14 are RESERVED: they named measurement-only forms (wrong results by design) that have left the source; no kernel answers to
 // them (tuned_is_candidate refuses them, "conv_algo" maps them to auto) and the numbers are not to be given out again.

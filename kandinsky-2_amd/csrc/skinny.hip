@@ -28,11 +28,6 @@
 
 namespace {
 
-__device__ __forceinline__ int xcd_remap_sk(int bid, int nblocks) {
-  const int q = nblocks >> 3, r = nblocks & 7, x = bid & 7;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-}
-
 // element offset of (row m, column k) in an A-fragment tensor with MA m-atoms
 __device__ __forceinline__ int64_t afrag_off(int m, int k, int MA) {
   return ((((int64_t)(k >> 6) * MA + (m >> 5)) * 4 + ((k >> 4) & 3)) * 64 + (m & 31) + 32 * ((k >> 3) & 1)) * 8 + (k & 7);
@@ -46,7 +41,7 @@ __global__ __launch_bounds__(256, 1) void skinny_kernel(const SkinnyParams p) {
   const int nchunks = p.K >> 6;
   const int mtiles = (p.MA + MT - 1) / MT;
   const int ntiles = p.Npad / (32 * NB);
-  int L = xcd_remap_sk(blockIdx.x, gridDim.x);
+  int L = xcd_remap(blockIdx.x, gridDim.x);
   const int mt = L % mtiles;
   L /= mtiles;
   const int nt = L % ntiles, z = L / ntiles;
@@ -65,12 +60,7 @@ __global__ __launch_bounds__(256, 1) void skinny_kernel(const SkinnyParams p) {
   for (int i = 0; i < MT; ++i) aoff[i] = (a0 + i < p.MA ? i : p.MA - 1 - a0) * 2048;   // atoms past the operand re-read its last one (results dropped)
 
   f32x16_t acc[MT][NB];
-#pragma unroll
-  for (int i = 0; i < MT; ++i)
-#pragma unroll
-    for (int j = 0; j < NB; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  K22_ZERO_ACC(acc, MT, NB)
   // this wave's bias values (weight rows 8 w + 4 h + {0..3} of every n-atom), fetched now: in the epilogue the load would be an exposed miss
   float4 bv[NB];
 #pragma unroll

@@ -26,11 +26,6 @@
 
 namespace {
 
-__device__ __forceinline__ int xcd_remap_stream(int bid, int nblocks) {
-  const int q = nblocks >> 3, r = nblocks & 7, x = bid & 7;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-}
-
 template <int MB, int TAPS> struct StreamCfg {
   static constexpr int G = (TAPS == 1 && MB <= 5) ? 2 : 1;   // 64-channel slabs per LDS stage
   static constexpr int SITEMS = G * TAPS;                      // (slab, tap) items per stage
@@ -173,7 +168,7 @@ __global__ __launch_bounds__(256) void stream_kernel(const IgemmParams p) {
 
   constexpr int NT = 32 * NB;
   const int n_tiles = p.Npad / NT;
-  int L = p.xcd_remap ? xcd_remap_stream(blockIdx.x, gridDim.x) : (int)blockIdx.x;
+  int L = p.xcd_remap ? xcd_remap(blockIdx.x, gridDim.x) : (int)blockIdx.x;
   const int mt = L % p.st_mtiles;
   L /= p.st_mtiles;
   const int nt = L % n_tiles, bz = L / n_tiles;
@@ -186,12 +181,7 @@ __global__ __launch_bounds__(256) void stream_kernel(const IgemmParams p) {
   const T* __restrict__ Wp = reinterpret_cast<const T*>(p.Wp);
 
   f32x16_t acc[MB][NB];
-#pragma unroll
-  for (int i = 0; i < MB; ++i)
-#pragma unroll
-    for (int j = 0; j < NB; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  K22_ZERO_ACC(acc, MB, NB)
 
   // ---- main phase --------------------------------------------------------------------------------------------
   {
